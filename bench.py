@@ -4,16 +4,28 @@
 mask_ratio 0.75, bf16 MFMA operands / fp32 accumulate, batch 2000 per GPU (BASELINE.json configs[1]; SURVEY 8d "2a").
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full               # + roofline, per-kernel times, HBM budget, CPU baseline
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + what the last timed step computed, as DIR/*.npy
     python bench.py --config configs/vitb16_dec512.yaml --batch 512      # another configs/*.yaml model; the default line is unchanged
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-One JSON line on rank 0.  `value` is whole-job images/s with inputs resident in HBM (K steps, barrier + synchronize on
-both sides, max over ranks).  `roofline` prices the dominant kernel class (the bf16 MFMA Linear GEMM, forward + dgrad
+One JSON line on rank 0.  `value` is whole-job images/s with inputs resident in HBM (K = --steps timed steps after
+--warmup untimed ones, barrier + synchronize on both sides, max over ranks); `ms_per_step` is the wall time of one timed
+step.  A plain run does only that.  With --full it also reports what takes runs or passes of its own:
+`roofline` prices the dominant kernel class (the bf16 MFMA Linear GEMM, forward + dgrad
 launches) from HIP events recorded on the launch stream around every launch, in a second pass over the same K steps
 (the ~860 events per step cost ~5 % and would otherwise distort `value`): `bound` is the roof the class's flop per
 algorithmic byte falls under (hbm below the 312 flop/B ridge), `frac` the fraction of that roof, `frac_mfma` and
-`frac_hbm` both; `traffic` is the HBM bytes per launch of that kernel from the newest committed rocprofv3 PMC passes.  `cpu_baseline` times the CPU oracle (the torch fp32 restatement of the
+`frac_hbm` both; `traffic` is the HBM bytes per launch of that kernel from the newest committed rocprofv3 PMC passes.
+`kernels` splits the same pass by kernel class, `hbm_budget` is the algorithmic HBM bytes of one step.  `cpu_baseline` times the CPU oracle (the torch fp32 restatement of the
 reference path) on the host cores, rank 0 / N=1 only, on a bounded sample (ViT-S/8, batch 64).
+
+--dump-outputs DIR writes, right after the timed steps (before any --full pass), what the last timed step left to its
+caller, in float32: `loss.npy` (the step's mean loss), `params.npy` (the trainable fp32 parameters after AdamW),
+`grads.npy` (the step's gradient buffer as the optimizer left it) and, for I-JEPA, `target_params.npy` (the EMA target
+encoder).  An array of more than DUMP_SAMPLE elements is replaced by a fixed sample of DUMP_SAMPLE of them (positions
+drawn from a generator seeded with 0, ascending), so the files stay under 64 MB in all.  Inputs, weights and masks are
+seeded: the same arguments give the same inputs on every run, and two builds can be compared file for file.
 """
 from __future__ import annotations
 
@@ -72,6 +84,7 @@ def _pmc_file():
 
 
 PMC_FILE = _pmc_file()
+DUMP_SAMPLE = 4 << 20   # elements kept of a larger --dump-outputs array (16 MiB in float32; at most 3 such arrays)
 NT_KERNEL = "gemm_nt3_kernel"   # the dominant kernel class: Linear forward + dgrad launches (k_gemm_nt3.hip)
 
 
@@ -183,6 +196,19 @@ def jepa_cpu_baseline(general, encoder, predictor, label: str, batch: int = 32, 
             "sample": f"oracle.jepa train_step fp32 'highest', {label}, batch {batch}, 1 warm-up + {steps} timed steps, median"}
 
 
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy in float32 for every array; one of more than DUMP_SAMPLE elements is sampled at fixed positions."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1).float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t[idx.to(t.device)]
+        np.save(out / f"{name}.npy", t.cpu().numpy())
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -190,8 +216,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (weak scaling); default 2000 (BASELINE configs[1])")
     ap.add_argument("--config", default=None, help="a configs/*.yaml model instead of the default ViT-S/8 + dec 192x2x6 workload")
-    ap.add_argument("--no-kernel-timers", action="store_true", help="skip the second, event-instrumented pass (no roofline object)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the event-instrumented second pass (roofline, kernels), hbm_budget and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-kernel-timers", action="store_true", help="with --full: skip the second, event-instrumented pass (no roofline object)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--backend", default="nccl", help="collective backend: nccl (= RCCL, the measured path) or gloo (rehearsal of the N > 1 control flow)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0 (with --backend gloo on a one-GPU box)")
     args = ap.parse_args()
@@ -289,10 +319,16 @@ def main() -> None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:   # before the --full pass below steps the model on
+        n = model.flat_grads.numel()
+        arrays = {"loss": loss, "params": model.flat_params[:n], "grads": model.flat_grads}
+        if predictor:
+            arrays["target_params"] = model.target_arena[:n]
+        dump_outputs(args.dump_outputs, arrays)
 
     # Per-kernel-class HIP events (two per launch, ~860 per step) cost ~5 % of the step, so `value` comes from the
     # un-instrumented region above and the roofline from a second pass over the SAME K steps with the events on.
-    timers = not args.no_kernel_timers
+    timers = args.full and not args.no_kernel_timers
     kernels, timed_ms = {}, None
     if timers:
         model.engine.timers_reset()
@@ -353,9 +389,9 @@ def main() -> None:
                                   "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["ms"] > 0 and v["flops"] > 0 else None,
                                   "gbs": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 else None}
                               for n, v in kernels.items()}
-        if not predictor:
+        if args.full and not predictor:
             out["hbm_budget"] = hbm_budget(general, encoder, decoder, B, default_workload=(not args.config and B == 2000))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = (jepa_cpu_baseline(general, encoder, predictor, label, batch=32 if img <= 96 else 4) if predictor
                                    else cpu_baseline(general, encoder, decoder, label, batch=64 if img <= 96 else 8))
         print(json.dumps(out), flush=True)

@@ -33,6 +33,17 @@ def weights(cfg, seed=73):
     return params, target
 
 
+def steps64(params, target, cfg, images, ctx, tgt):
+    """Two whole steps on float64 copies.  The key third of every qkv bias has a gradient that is zero up to rounding (the
+    softmax ignores a shift), and AdamW's first step turns that rounding into a move of up to ~lr whose sign follows the
+    host's summation order; in float32 the norms after the steps differ by ~1e-5 between hosts and thread counts, in
+    float64 by ~1e-15."""
+    p2, t2, state = {k: v.double() for k, v in params.items()}, {k: v.double() for k, v in target.items()}, {}
+    for step in (1, 2):
+        J.train_step(p2, t2, cfg, state, images.double(), ctx, tgt, 1e-3, step, 0.99)
+    return p2, t2
+
+
 def case(B, seed, loss):
     cfg = J.JEPAConfig(**{**CFG.__dict__, "loss": loss})
     params, target = weights(cfg)
@@ -43,10 +54,8 @@ def case(B, seed, loss):
            "grad_norms": torch.stack([g.norm() for g in grads.values()])}
     for n in PINNED_GRADS:
         out["grad/" + n] = grads[n]
-    # two whole steps (AdamW unclipped + EMA) at a fixed learning rate and momentum
-    p2, t2, state = {k: v.clone() for k, v in params.items()}, {k: v.clone() for k, v in target.items()}, {}
-    for step in (1, 2):
-        J.train_step(p2, t2, cfg, state, images, ctx, tgt, 1e-3, step, 0.99)
+    # two whole steps (AdamW unclipped + EMA) at a fixed learning rate and momentum, in float64 (see steps64)
+    p2, t2 = steps64(params, target, cfg, images, ctx, tgt)
     out["param_norms_after_2_steps"] = torch.stack([p2[n].norm() for n in J.trainable_names(cfg)])
     out["target_norms_after_2_steps"] = torch.stack([t2[n].norm() for n in J.ema_names(cfg)])
     return out

@@ -9,9 +9,9 @@ TAG=${1:-}
 if [ -n "$TAG" ]; then shift; OUT=$ROOT/gpurun_out/evidence_$TAG; else OUT=$ROOT/gpurun_out/evidence; fi
 ARGS=$(echo "$*" | sed "s#configs/#$ROOT/configs/#g")   # rocprofv3 runs from /tmp: absolute config path
 rm -rf $OUT; mkdir -p $OUT
-python bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err
+python bench.py $ARGS --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py $ARGS --steps 5 --warmup 2 --no-cpu-baseline > $OUT/stats.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py $ARGS --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/stats.log 2>&1
 timeout -k 10 500 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $ROOT/bench.py $ARGS --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timers > $OUT/pmc_fetch.log 2>&1
 timeout -k 10 500 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $ROOT/bench.py $ARGS --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timers > $OUT/pmc_write.log 2>&1
 cd $ROOT
