@@ -237,6 +237,54 @@ int mae_engine_adamw_range(mae_engine_t* e, float* params, const float* grads, f
                            float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, const float* stats,
                            int64_t lo, int64_t count, void* stream);
 
+/* Downstream classifier (additive in ABI v4): ViTClassifier + ViTClassifierTrainModule of the reference
+ * (src/models/classifier.py:47-57, src/training/classifier.py:75-171), i.e. the encoder over EVERY token (timm
+ * forward_features, scripts/training/train_mae.py:143), pooled = feats[:, 0] (MAE_POOL_CLS) or feats.mean(dim=1) over all
+ * L = 1 + num_patches rows (MAE_POOL_MEAN), logits = pooled @ W.T + b, loss = F.cross_entropy(logits, labels) (batch mean),
+ * correct = sum(logits.argmax(1) == labels) (first index among equal maxima).
+ *   head: the head's own fp32 buffer, W (num_classes, embed_dim) row-major then b (num_classes) -- not part of the arena;
+ *   labels: (batch) int64 in [0, num_classes); a label outside that range is never read through: that batch's loss is NaN
+ *           (and so are the gradients of its row);
+ *   num_classes in [2, 128]; logits (batch, num_classes) fp32, loss_out (1) fp32, correct_out (1) int32 -- each may be NULL.
+ *   workspace: mae_engine_classifier_workspace_bytes(batch, num_classes) bytes (it is also a valid workspace of
+ *              mae_engine_workspace_bytes(batch, L) layout: the classifier overwrites the saved activations of any forward).
+ * mae_engine_classifier_forward: inference (no activation is saved for a backward); labels may be NULL when loss_out and
+ *   correct_out are.
+ * mae_engine_classifier_loss_and_grads: forward + loss + backward over the trainable set
+ *   train_blocks = -1 : encoder frozen (linear probe, freeze_encoder()): only head_grads is written;
+ *   train_blocks = n  : blocks[depth-n:] and the final norm (unfreeze_last_layers(n), :139-171): their gradients land in
+ *                       `grads` (the arena-shaped trainable-range buffer) at their usual offsets; nothing else of `grads` is
+ *                       written and no block below depth-n runs;
+ *   train_embed = 1   : n = depth only -- also cls_token, patch_embed.proj.* (in `grads`) and pos_embed, whose gradient
+ *                       goes to pos_grad (L * embed_dim floats, it lies outside the trainable range) (unfreeze_encoder(), :134).
+ *   head_grads: dW then db, same layout as head.  grad_scale multiplies every gradient (not the loss). */
+enum { MAE_POOL_CLS = 0, MAE_POOL_MEAN = 1 };
+int64_t mae_engine_classifier_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t num_classes);
+int mae_engine_classifier_forward(mae_engine_t* e, const float* params, const void* wcache, const float* head, const void* images,
+                                  int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes,
+                                  void* workspace, int64_t workspace_bytes, float* logits, float* loss_out, int32_t* correct_out,
+                                  void* stream);
+int mae_engine_classifier_loss_and_grads(mae_engine_t* e, const float* params, const void* wcache, const float* head,
+                                         const void* images, int32_t image_dtype, const int64_t* labels, int32_t batch,
+                                         int32_t pool, int32_t num_classes, int32_t train_blocks, int32_t train_embed,
+                                         float grad_scale, void* workspace, int64_t workspace_bytes, float* grads,
+                                         float* head_grads, float* pos_grad, float* logits, float* loss_out,
+                                         int32_t* correct_out, void* stream);
+/* The classifier's optimizer (Lightning gradient_clip_val = 1.0 + one-group torch AdamW over the requires_grad tensors,
+ * scripts/training/train_mae.py:213, src/training/classifier.py:106-108) over buffers that are not the arena's trainable range:
+ *   mae_engine_grad_sumsq_buffer       : sumsq_io[0] = (accumulate ? sumsq_io[0] : 0) + sum of grads[0 .. count)^2
+ *                                        (sumsq_io holds 2 floats; [1] is a temporary); count a multiple of 4;
+ *   mae_engine_adamw_buffer            : the AdamW of mae_engine_adamw_range (same device code, gradients scaled by stats[1])
+ *                                        on a plain buffer (the head, pos_embed); count a multiple of 4;
+ *   mae_engine_refresh_transposed_range: the transposed bf16 operand copies of the matrices inside [lo, lo+count) of the
+ *                                        arena (mae_engine_adamw_range already wrote the straight copies of that range). */
+int mae_engine_grad_sumsq_buffer(mae_engine_t* e, const float* grads, int64_t count, int32_t accumulate, float* sumsq_io,
+                                 float* scratch, void* stream);
+int mae_engine_adamw_buffer(mae_engine_t* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t count,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, const float* stats,
+                            void* stream);
+int mae_engine_refresh_transposed_range(mae_engine_t* e, const float* params, void* wcache, int64_t lo, int64_t count, void* stream);
+
 /* mae_engine_optimizer_step with the EMA update of the target encoder fused into the AdamW sweep:
  * target[0 .. encoder_grad_elems) = m * target + (1 - m) * params_new (+ the bf16 operand copy in target_wcache).
  * max_norm = +inf disables clipping (I-JEPA trains unclipped). */
@@ -273,6 +321,16 @@ int mae_add_layernorm_fwd(const float* x, const void* branch, float* x_out, cons
 int mae_layernorm_bwd(const void* dy, int32_t dy_dtype, const float* x, const int32_t* row_map, const float* gamma,
                       const float* mean, const float* rstd, int64_t rows, int32_t dim, int32_t accumulate,
                       float* dx_io, void* dx_copy, float* dgamma, float* dbeta, float* partial, void* stream);
+
+/* The classifier head alone (what mae_engine_classifier_* run after the encoder): feats (batch, seq_len, dim) in dtype,
+ * head / labels / logits / loss_out / correct_out / head_grads as there.  d_feats (dtype, may be NULL): MAE_POOL_CLS ->
+ * (batch, dim), the gradient of feats[:, 0] (every other row's gradient is zero); MAE_POOL_MEAN -> (batch, seq_len, dim).
+ * scratch: mae_classifier_head_scratch_bytes(batch, num_classes, dim) bytes, 256-byte aligned. */
+int64_t mae_classifier_head_scratch_bytes(int32_t batch, int32_t num_classes, int32_t dim);
+int mae_classifier_head(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t pool,
+                        const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
+                        float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
+                        int64_t scratch_bytes, void* stream);
 
 /* Epilogues of the GEMM family. */
 enum {

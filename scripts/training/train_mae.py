@@ -1,0 +1,148 @@
+"""Supervised fine-tuning / linear probing of the classifier on the MI355X engine (the reference's
+scripts/training/train_mae.py, without Lightning): same flags, YAML keys and output tree
+``outputs/train/<suffix>/{checkpoints/{best,last}.ckpt, logs/metrics.jsonl, config.yaml, <logging.model_path>}``.
+
+    python -m scripts.training.train_mae --config configs/mae.yaml --encoder_ckpt outputs/pretrain/mae_pretrain/checkpoints/last.ckpt
+
+Model branches as the reference (:85-161): --classifier_ckpt (weights only, fresh optimizer), --encoder_ckpt (encoder
+weights found by prefix), or the random-init baseline.  Freeze precedence (:167-176): train.unfreeze_last_layers, then
+train.freeze_encoder.  Each epoch: the native fused step over the training split, a no-grad validation pass, the
+per-epoch LR, one metrics line; best.ckpt on a new maximum of val_acc, last.ckpt every epoch.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+from pathlib import Path
+
+import torch
+import yaml
+
+from ssrl_vit_mae_jepa_amd.classifier import ViTClassifierTrainModule, encoder_mae, load_encoder_weights
+from ssrl_vit_mae_jepa_amd.data import get_train_batches
+
+SEED = 73
+PREFIXES = ("model.encoder.", "encoder.", "module.encoder.")
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description="Fine-tune / linear-probe the ViT classifier")
+    parser.add_argument("--config", type=str, default="configs/mae.yaml")
+    parser.add_argument("--encoder_ckpt", type=str, default=None, help="Path to a pretrained MAE checkpoint (encoder weights)")
+    parser.add_argument("--classifier_ckpt", type=str, default=None, help="Path to a full classifier checkpoint")
+    parser.add_argument("--output_dir_suffix", type=str, default="mae_finetune", help="Suffix for the output directory")
+    # additions (not in the reference): bounded runs
+    parser.add_argument("--max_epochs", type=int, default=None)
+    parser.add_argument("--max_steps_per_epoch", type=int, default=None)
+    parser.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic labeled images instead of STL-10")
+    return parser.parse_args(argv)
+
+
+def model_config(cfg: dict) -> dict:
+    m = cfg["model"]
+    return dict(m, general=dict(m["general"], engine_precision=cfg.get("engine", {}).get("precision", "bf16")))
+
+
+def load_state(path: str) -> dict:
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    return ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
+
+
+def build_module(cfg: dict, encoder_ckpt=None, classifier_ckpt=None) -> ViTClassifierTrainModule:
+    model_cfg, train_cfg = model_config(cfg), cfg["train"]
+    if classifier_ckpt:
+        print(f"Loading full classifier checkpoint: {classifier_ckpt}")
+        module = ViTClassifierTrainModule(pretrained_encoder=encoder_mae(model_cfg).encoder.vit, model_cfg=model_cfg, training_cfg=train_cfg)
+        state = load_state(classifier_ckpt)
+        if not any(k.startswith("model.") for k in state):
+            state = {"model." + k: v for k, v in state.items()}  # a bare module.model.state_dict() (.pt)
+        module.load_state_dict(state, strict=False)
+    elif encoder_ckpt:
+        print(f"Loading pretrained encoder: {encoder_ckpt}")
+        mae = encoder_mae(model_cfg)
+        state = load_state(encoder_ckpt)
+        if not any(k.startswith(p) for p in PREFIXES for k in state):
+            raise ValueError("Could not find encoder weights in checkpoint. Expected keys starting with one of: " + ", ".join(PREFIXES))
+        missing, unexpected = load_encoder_weights(mae, state)
+        print(f"Loaded encoder weights ({len(missing)} missing, {len(unexpected)} unexpected)")
+        module = ViTClassifierTrainModule(pretrained_encoder=mae.encoder.vit, model_cfg=model_cfg, training_cfg=train_cfg)
+    else:
+        print("Baseline: random-initialized VisionTransformer (no MAE)")
+        module = ViTClassifierTrainModule(pretrained_encoder=None, model_cfg=model_cfg, training_cfg=train_cfg)
+    if train_cfg.get("unfreeze_last_layers", None) is not None:
+        module.unfreeze_last_layers(int(train_cfg["unfreeze_last_layers"]))
+    elif train_cfg.get("freeze_encoder", True):
+        module.freeze_encoder()
+    else:
+        module.unfreeze_encoder()
+    return module
+
+
+def save(path: Path, obj) -> None:
+    tmp = path.with_suffix(path.suffix + ".tmp")
+    torch.save(obj, tmp)
+    os.replace(tmp, path)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    with open(args.config, "r") as f:
+        cfg = yaml.safe_load(f)
+    if not torch.cuda.is_available():
+        raise SystemExit("train_mae: the MI355X engine has no CPU fallback")
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(SEED)
+    train_cfg, log_cfg = cfg["train"], cfg["logging"]
+    output_dir = Path(log_cfg["output_dir_base"]) / "train" / args.output_dir_suffix
+    ckpt_dir = output_dir / "checkpoints"
+    ckpt_dir.mkdir(parents=True, exist_ok=True)
+    (output_dir / "logs").mkdir(exist_ok=True)
+    with open(output_dir / "config.yaml", "w") as f_out:
+        yaml.safe_dump(cfg, f_out)
+
+    train_batches, val_batches = get_train_batches(cfg, dev, synthetic_images=args.synthetic_images, seed=SEED)
+    module = build_module(cfg, args.encoder_ckpt, args.classifier_ckpt).to(dev)
+    total = int(train_cfg["total_epochs"]) if args.max_epochs is None else min(int(train_cfg["total_epochs"]), args.max_epochs)
+    best_acc, log_path = -1.0, output_dir / "logs" / "metrics.jsonl"
+    for epoch in range(total):
+        module.current_epoch = epoch
+        lr = module.current_lr(epoch)
+        t0, seen = time.perf_counter(), 0
+        sums = torch.zeros(2, dtype=torch.float64, device=dev)  # [sum of batch-mean loss * rows, correct]
+        for step, (imgs, labels) in enumerate(train_batches(epoch)):
+            if args.max_steps_per_epoch is not None and step >= args.max_steps_per_epoch:
+                break
+            loss, correct = module.fused_training_step(imgs, labels, lr=lr)
+            sums[0] += loss[0].double() * imgs.shape[0]
+            sums[1] += correct[0].double()
+            seen += imgs.shape[0]
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        val = torch.zeros(2, dtype=torch.float64, device=dev)
+        n_val = 0
+        with torch.no_grad():
+            for imgs, labels in val_batches():
+                _l, loss, correct = module.model.evaluate(imgs, labels, logits=False)
+                val[0] += loss[0].double() * imgs.shape[0]
+                val[1] += correct[0].double()
+                n_val += imgs.shape[0]
+        rec = dict(epoch=epoch, train_loss=float(sums[0]) / max(1, seen), train_acc=float(sums[1]) / max(1, seen),
+                   val_loss=float(val[0]) / max(1, n_val), val_acc=float(val[1]) / max(1, n_val), lr=lr, images_per_s=seen / dt)
+        with open(log_path, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+        print(json.dumps(rec))
+        ckpt = module.checkpoint(epoch)
+        ckpt["val_acc"] = rec["val_acc"]
+        if rec["val_acc"] > best_acc:
+            best_acc = rec["val_acc"]
+            save(ckpt_dir / "best.ckpt", ckpt)
+        save(ckpt_dir / "last.ckpt", ckpt)
+    model_path = output_dir / log_cfg["model_path"]
+    torch.save({k: v.detach().cpu() for k, v in module.model.state_dict().items()}, model_path)
+    print(f"Training complete; model weights saved to: {model_path}; best checkpoint: {ckpt_dir / 'best.ckpt'}")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,448 @@
+"""The downstream classifier of the reference (``src/models/classifier.py``, ``src/training/classifier.py``) on the engine.
+
+``ViTClassifier`` wraps the engine's encoder node (``mae.encoder.vit``, what ``scripts/training/train_mae.py:143`` hands
+the reference's classifier) and a ``ClassificationHead`` whose ``weight`` / ``bias`` live in one flat fp32 buffer (W then
+b, the layout the C ABI reads).  ``ViTClassifierTrainModule`` keeps the reference's keys, defaults, freeze methods and
+logged names, and adds the native step: one call for forward + pooled head + cross-entropy + a backward that stops where
+the trainable blocks end, then clip_grad_norm_(1.0) + one-group AdamW over exactly the tensors whose ``requires_grad``
+is set (Lightning ``gradient_clip_val=1.0``, scripts/training/train_mae.py:213; src/training/classifier.py:106-108).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Any, Dict, List, Optional, Tuple
+
+import torch
+from torch import nn
+
+from . import _lib
+from ._lib import check, lib
+from .mae import MaskedAutoencoder, _ptr, _stream, _ViT
+from .training import lr_lambda
+
+POOLS = {"cls": _lib.POOL_CLS, "mean": _lib.POOL_MEAN}
+MAX_CLASSES = 128
+
+
+def _pad4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+class ClassificationHead(nn.Module):
+    """src/models/classifier.py:10-22: ``.classification`` = Linear(input_dim, output_dim), initialised as nn.Linear is.
+    Its weight and bias are views into ``flat`` (W then b, padded to a multiple of 4 floats)."""
+
+    def __init__(self, input_dim: int, output_dim: int) -> None:
+        super().__init__()
+        self.input_dim, self.output_dim = int(input_dim), int(output_dim)
+        self.classification = nn.Linear(self.input_dim, self.output_dim)
+        self.flat = torch.zeros(_pad4(self.output_dim * self.input_dim + self.output_dim), dtype=torch.float32)
+        self._reflatten(self.flat.device)
+
+    @property
+    def numel(self) -> int:
+        return self.output_dim * self.input_dim + self.output_dim
+
+    @torch.no_grad()
+    def _reflatten(self, device: torch.device) -> None:
+        w, b = self.classification.weight, self.classification.bias
+        nw = w.numel()
+        if self.flat.device != device:
+            self.flat = torch.zeros(self.flat.numel(), dtype=torch.float32, device=device)
+        for p, lo, n in ((w, 0, nw), (b, nw, b.numel())):
+            view = self.flat[lo:lo + n].view(p.shape)
+            if p.data.data_ptr() != view.data_ptr():
+                view.copy_(p.data.to(device=device, dtype=torch.float32))
+                p.data = view
+                p.grad = None
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn)
+        self._reflatten(self.classification.weight.device)
+        return self
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.classification(x)
+
+
+class ViTClassifier(nn.Module):
+    """src/models/classifier.py:25-57 over the engine: ``encoder`` is the engine's ``_ViT`` node, ``head`` the linear head,
+    ``pool_type`` "cls" or "mean".  ``forward`` is an inference call (the training route is the native step of
+    ``ViTClassifierTrainModule``)."""
+
+    def __init__(self, pretrained_encoder: _ViT, num_classes: int = 10, head_cfg: Optional[Dict[str, Any]] = None):
+        super().__init__()
+        if not isinstance(pretrained_encoder, _ViT):
+            raise TypeError("ViTClassifier needs the engine's encoder node (MaskedAutoencoder(...).encoder.vit)")
+        head_cfg = head_cfg or {}
+        embed_dim = int(head_cfg.get("embed_dim", pretrained_encoder.embed_dim))
+        if embed_dim != pretrained_encoder.embed_dim:
+            raise ValueError(f"head embed_dim {embed_dim} != encoder width {pretrained_encoder.embed_dim}")
+        pool_type = head_cfg.get("pool", "cls")
+        if pool_type not in POOLS:
+            raise ValueError(f"pool must be 'cls' or 'mean', got {pool_type!r}")
+        if not 2 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError(f"num_classes must be in [2, {MAX_CLASSES}], got {num_classes}")
+        self.encoder = pretrained_encoder
+        self.pool_type = pool_type
+        self.num_classes = int(num_classes)
+        self.head = ClassificationHead(input_dim=embed_dim, output_dim=self.num_classes)
+
+    @property
+    def mae(self) -> MaskedAutoencoder:
+        return self.encoder._owner()
+
+    def _apply(self, fn, recurse=True):
+        # the encoder's tensors are views into the MAE's arena: move them through their owner, which re-flattens them
+        self.mae._apply(fn)
+        self.head._apply(fn)
+        return self
+
+    def workspace(self, batch: int) -> torch.Tensor:
+        """The owner's workspace grown to the classifier's size.  It is shared with the MAE's forwards, so every saved
+        activation of an earlier call is invalidated: a pending hand-off backward refuses to run."""
+        m = self.mae
+        need = lib.mae_engine_classifier_workspace_bytes(m.engine.handle, batch, self.num_classes)
+        if need < 0:
+            raise ValueError(f"bad batch {batch} / num_classes {self.num_classes}")
+        if m._workspace is None or m._workspace.numel() < need or m._workspace.device != m.flat_params.device:
+            m._workspace = None
+            m._workspace = torch.empty(need, dtype=torch.uint8, device=m.flat_params.device)
+        m._gen_enc += 1; m._gen_dec += 1
+        m._plan = None
+        return m._workspace
+
+    def _guard(self) -> None:
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("ViTClassifier.forward() is an inference call on the MI355X engine and records no autograd graph; "
+                               "train through ViTClassifierTrainModule.loss_and_grads()/fused_training_step(), or wrap the call "
+                               "in torch.no_grad()")
+
+    def evaluate(self, images: torch.Tensor, labels: Optional[torch.Tensor] = None, logits: bool = True):
+        """Native forward: returns (logits or None, loss or None, correct count or None), device tensors."""
+        m = self.mae
+        dev = m._require_cuda()
+        images = m._check_images(images)
+        B = images.shape[0]
+        out = torch.empty(B, self.num_classes, dtype=torch.float32, device=dev) if logits else None
+        loss = correct = None
+        if labels is not None:
+            labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+            loss = torch.empty(1, dtype=torch.float32, device=dev)
+            correct = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = self.workspace(B)
+        check(lib.mae_engine_classifier_forward(m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(self.head.flat), _ptr(images),
+                                                m._img_dt(images), _ptr(labels), B, POOLS[self.pool_type], self.num_classes, _ptr(ws), ws.numel(),
+                                                _ptr(out), _ptr(loss), _ptr(correct), _stream(dev)))
+        return out, loss, correct
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        self._guard()
+        return self.evaluate(x)[0]
+
+
+def _group_of(name: str) -> str:
+    if name.startswith("blocks."):
+        return "blocks." + name.split(".")[1]
+    if name.startswith("norm."):
+        return "norm"
+    return "embed"  # cls_token, pos_embed, patch_embed.proj.*
+
+
+class ViTClassifierTrainModule(nn.Module):
+    """src/training/classifier.py:16-171 without Lightning, plus the native fused step."""
+
+    def __init__(self, pretrained_encoder: Optional[_ViT] = None, model_cfg: Optional[Dict[str, Any]] = None,
+                 training_cfg: Optional[Dict[str, Any]] = None, num_classes: int = 10):
+        super().__init__()
+        self.model_cfg = model_cfg or {}
+        self.training_cfg = training_cfg or {}
+        self.hparams = {"model_cfg": self.model_cfg, "training_cfg": self.training_cfg, "num_classes": num_classes}
+        self.learning_rate = float(self.training_cfg.get("learning_rate", 3e-4))
+        self.weight_decay = float(self.training_cfg.get("weight_decay", 0.05))
+        self.warmup_epochs = int(self.training_cfg.get("warmup_epochs", 5))
+        self.total_epochs = int(self.training_cfg.get("total_epochs", 100))
+        self.freeze_encoder_flag = self.training_cfg.get("freeze_encoder", True)
+        self.num_classes = num_classes
+        self.gradient_clip_val = 1.0
+        self.current_epoch = 0
+        self.logged: Dict[str, Any] = {}
+        encoder = pretrained_encoder if pretrained_encoder is not None else build_baseline_encoder(self.model_cfg)
+        self.model = ViTClassifier(pretrained_encoder=encoder, num_classes=self.num_classes, head_cfg=self.model_cfg.get("head", {}))
+        self._opt: Dict[str, torch.Tensor] = {}
+        self._opt_steps = 0
+        self._pos_grad: Optional[torch.Tensor] = None
+        self._head_grad: Optional[torch.Tensor] = None
+        if self.freeze_encoder_flag:
+            self.freeze_encoder()
+        else:
+            self.unfreeze_encoder()
+
+    # ---- reference surface ---------------------------------------------------------------------
+    def forward(self, x: torch.Tensor):
+        return self.model(x)
+
+    def log(self, name: str, value, **_kw) -> None:
+        self.logged[name] = value  # device tensors stay on device: no host sync in the step
+
+    def freeze_encoder(self):
+        for name, param in self.model.named_parameters():
+            if "head" not in name:
+                param.requires_grad = False
+
+    def unfreeze_encoder(self):
+        for param in self.model.parameters():
+            param.requires_grad = True
+
+    def unfreeze_last_layers(self, n_layers: int):
+        encoder = self.model.encoder
+        blocks = encoder.blocks
+        total = len(blocks)
+        if n_layers < 0 or n_layers > total:
+            raise ValueError(f"n_layers must be between 0 and {total}, got {n_layers}")
+        for param in encoder.parameters():
+            param.requires_grad = False
+        for block in blocks[total - n_layers:]:
+            for param in block.parameters():
+                param.requires_grad = True
+        if hasattr(encoder, "norm"):
+            for param in encoder.norm.parameters():
+                param.requires_grad = True
+        for param in self.model.head.parameters():
+            param.requires_grad = True
+
+    def current_lr(self, epoch: Optional[int] = None) -> float:
+        """LambdaLR per epoch over learning_rate (src/training/classifier.py:113-119); no batch-size scaling."""
+        return self.learning_rate * lr_lambda(self.current_epoch if epoch is None else epoch, self.warmup_epochs, self.total_epochs)
+
+    def _eval_step(self, batch, prefix: str):
+        imgs, labels = batch
+        with torch.no_grad():
+            _logits, loss, correct = self.model.evaluate(imgs, labels, logits=False)
+        self.log(f"{prefix}_loss", loss[0])
+        self.log(f"{prefix}_acc", correct[0].float() / imgs.shape[0])
+        return loss[0]
+
+    def training_step(self, batch, batch_idx):
+        """Loss + gradients of the trainable set (native); ``optimizer_step`` applies them."""
+        imgs, labels = batch
+        loss, correct = self.loss_and_grads(imgs, labels)
+        self.log("train_loss", loss[0])
+        self.log("train_acc", correct[0].float() / imgs.shape[0])
+        return loss[0]
+
+    def validation_step(self, batch, batch_idx):
+        return self._eval_step(batch, "val")
+
+    def test_step(self, batch, batch_idx):
+        return self._eval_step(batch, "test")
+
+    # ---- trainable set ---------------------------------------------------------------------------
+    def train_mode(self) -> Tuple[int, int]:
+        """(train_blocks, train_embed) of the C ABI from the requires_grad flags; a pattern the native backward cannot
+        express raises ValueError naming the tensors (it never trains another set than the flags describe)."""
+        enc = self.model.encoder
+        depth = len(enc.blocks)
+        groups: Dict[str, List[Tuple[str, bool]]] = {}
+        for name, p in enc.named_parameters():
+            groups.setdefault(_group_of(name), []).append((name, p.requires_grad))
+        head_frozen = [f"head.{n}" for n, p in self.model.head.named_parameters() if not p.requires_grad]
+        if head_frozen:
+            raise ValueError(f"the classifier head is always trained; frozen: {head_frozen}")
+        state = {}
+        for g, items in groups.items():
+            flags = {f for _n, f in items}
+            if len(flags) > 1:
+                raise ValueError(f"encoder group {g} is partly trainable: {[('encoder.' + n, f) for n, f in items]}")
+            state[g] = flags.pop()
+        blocks = [state[f"blocks.{i}"] for i in range(depth)]
+        n = 0
+        while n < depth and blocks[depth - 1 - n]:
+            n += 1
+        if any(blocks[: depth - n]):
+            bad = [f"encoder.blocks.{i}" for i in range(depth - n) if blocks[i]]
+            raise ValueError(f"trainable blocks must be a suffix of the encoder: {bad} train while encoder.blocks.{depth - n - 1} is frozen")
+        if not state["norm"]:
+            if n or state["embed"]:
+                raise ValueError("encoder.norm.* is frozen while earlier encoder tensors train: not a trainable suffix")
+            return -1, 0
+        if state["embed"]:
+            if n != depth:
+                raise ValueError(f"encoder embedding tensors (cls_token, pos_embed, patch_embed.proj.*) train while "
+                                 f"encoder.blocks.{depth - n - 1} is frozen")
+            return depth, 1
+        return n, 0
+
+    def _arena_range(self, train_blocks: int, train_embed: int) -> Tuple[int, int]:
+        m = self.model.mae
+        hi = lib.mae_engine_encoder_grad_elems(m.engine.handle)
+        if train_blocks < 0:
+            return hi, hi
+        if train_embed:
+            return 0, hi
+        depth = len(self.model.encoder.blocks)
+        first = f"encoder.vit.blocks.{depth - train_blocks}.norm1.weight" if train_blocks else "encoder.vit.norm.weight"
+        return m._offsets[first][1], hi
+
+    # ---- native step -------------------------------------------------------------------------------
+    def _grad_buffers(self):
+        m = self.model.mae
+        dev = m.flat_params.device
+        if self._head_grad is None or self._head_grad.device != dev:
+            self._head_grad = torch.zeros(self.model.head.flat.numel(), dtype=torch.float32, device=dev)
+            self._pos_grad = torch.zeros(m.sequence_length * m._dims["embed_dim"], dtype=torch.float32, device=dev)
+        return self._head_grad, self._pos_grad
+
+    @property
+    def head_grads(self) -> torch.Tensor:
+        return self._grad_buffers()[0]
+
+    @property
+    def pos_grads(self) -> torch.Tensor:
+        return self._grad_buffers()[1]
+
+    def loss_and_grads(self, images: torch.Tensor, labels: torch.Tensor, grad_scale: float = 1.0,
+                       logits_out: Optional[torch.Tensor] = None):
+        """Forward + cross-entropy + backward of the trainable set in one native call.  Gradients land in
+        ``model.mae.flat_grads`` (blocks / norm / embeddings, at their arena offsets; frozen rows are not written),
+        ``head_grads`` (W then b) and ``pos_grads``.  Returns device tensors (loss[1], correct[1]); no host sync."""
+        tb, te = self.train_mode()
+        clf, m = self.model, self.model.mae
+        dev = m._require_cuda()
+        images = m._check_images(images)
+        B = images.shape[0]
+        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+        if labels.shape != (B,):
+            raise ValueError(f"labels must be ({B},), got {tuple(labels.shape)}")
+        head_g, pos_g = self._grad_buffers()
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        correct = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = clf.workspace(B)
+        check(lib.mae_engine_classifier_loss_and_grads(
+            m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(clf.head.flat), _ptr(images), m._img_dt(images), _ptr(labels),
+            B, POOLS[clf.pool_type], clf.num_classes, tb, te, float(grad_scale), _ptr(ws), ws.numel(), _ptr(m.flat_grads), _ptr(head_g),
+            _ptr(pos_g), _ptr(logits_out), _ptr(loss), _ptr(correct), _stream(dev)))
+        self._last_mode = (tb, te)
+        return loss, correct
+
+    def _state(self, key: str, n: int, dev) -> torch.Tensor:
+        t = self._opt.get(key)
+        if t is None or t.device != dev or t.numel() != n:
+            t = self._opt[key] = torch.zeros(n, dtype=torch.float32, device=dev)
+        return t
+
+    def optimizer_step(self, lr: Optional[float] = None) -> torch.Tensor:
+        """clip_grad_norm_(gradient_clip_val) over the trainable set, then AdamW(betas (0.9, 0.999), eps 1e-8,
+        weight_decay) on it, then the bf16 operand copies of the updated matrices.  Returns the device [norm, coef]."""
+        tb, te = getattr(self, "_last_mode", None) or self.train_mode()
+        clf, m = self.model, self.model.mae
+        dev = m._require_cuda()
+        h = m.engine.handle
+        head_g, pos_g = self._grad_buffers()
+        lo, hi = self._arena_range(tb, te)
+        n_arena = m.engine.trainable_elems
+        stats = self._state("stats", 8, dev)
+        sums = self._state("sumsq", 4, dev)
+        scratch = m._scratch_f32()
+        self._opt_steps += 1
+        step = self._opt_steps
+        lr = float(self.current_lr() if lr is None else lr)
+        hyper = (lr, 0.9, 0.999, 1e-8, float(self.weight_decay), step)
+        s = _stream(dev)
+        if hi > lo:
+            check(lib.mae_engine_grad_sumsq_range(h, _ptr(m.flat_grads), lo, hi - lo, _ptr(sums), _ptr(scratch), s))
+        check(lib.mae_engine_grad_sumsq_buffer(h, _ptr(head_g), head_g.numel(), int(hi > lo), _ptr(sums), _ptr(scratch), s))
+        if te:
+            check(lib.mae_engine_grad_sumsq_buffer(h, _ptr(pos_g), pos_g.numel(), 1, _ptr(sums), _ptr(scratch), s))
+        check(lib.mae_engine_clip_from_sumsq(h, _ptr(sums), float(self.gradient_clip_val), _ptr(stats), s))
+        if hi > lo:
+            ea, eq = self._state("arena_m", n_arena, dev), self._state("arena_v", n_arena, dev)
+            check(lib.mae_engine_adamw_range(h, _ptr(m.flat_params), _ptr(m.flat_grads), _ptr(ea), _ptr(eq), _ptr(m._weights()), *hyper[:5],
+                                             step, _ptr(stats), lo, hi - lo, s))
+        check(lib.mae_engine_adamw_buffer(h, _ptr(clf.head.flat), _ptr(head_g), _ptr(self._state("head_m", head_g.numel(), dev)),
+                                          _ptr(self._state("head_v", head_g.numel(), dev)), head_g.numel(), *hyper[:5], step, _ptr(stats), s))
+        if te:
+            _n, pos_off, pos_n, _s, _f = m._offsets["encoder.vit.pos_embed"]
+            check(lib.mae_engine_adamw_buffer(h, _ptr(m.flat_params[pos_off:pos_off + pos_n]), _ptr(pos_g), _ptr(self._state("pos_m", pos_n, dev)),
+                                              _ptr(self._state("pos_v", pos_n, dev)), pos_n, *hyper[:5], step, _ptr(stats), s))
+        if hi > lo:
+            check(lib.mae_engine_refresh_transposed_range(h, _ptr(m.flat_params), _ptr(m._weights()), lo, hi - lo, s))
+        m.mark_weights_fresh()
+        return stats[:2]
+
+    def fused_training_step(self, images: torch.Tensor, labels: torch.Tensor, lr: Optional[float] = None):
+        """training_step + clip + AdamW, all native; returns device (loss, correct)."""
+        loss, correct = self.loss_and_grads(images, labels)
+        self.optimizer_step(lr)
+        self.log("train_loss", loss[0])
+        self.log("train_acc", correct[0].float() / images.shape[0])
+        return loss, correct
+
+    # ---- checkpoints -------------------------------------------------------------------------------
+    def checkpoint(self, epoch: int = 0, global_step: int = 0) -> Dict[str, Any]:
+        """Lightning-shaped: state_dict keys model.encoder.<timm name> / model.head.classification.*."""
+        return {"epoch": epoch, "global_step": global_step,
+                "state_dict": {k: v.detach().cpu().clone() for k, v in self.state_dict().items()},
+                "hyper_parameters": dict(self.hparams)}
+
+
+def encoder_mae(model_cfg: Dict[str, Any]) -> MaskedAutoencoder:
+    """An engine MAE whose encoder is the classifier's; the decoder (unused here) is the smallest valid one unless the
+    config names it."""
+    g = dict(model_cfg.get("general", {}))
+    e = dict(model_cfg.get("encoder", {}))
+    d = model_cfg.get("decoder") or {}
+    if "engine_precision" not in g and "engine" in model_cfg:
+        g["engine_precision"] = model_cfg["engine"].get("precision", "bf16")
+    if not d:
+        d = dict(decoder_embed_dim=int(e.get("embed_dim", 384)), decoder_depth=1, decoder_num_heads=int(e.get("num_heads", 6)))
+    return MaskedAutoencoder(g, e, d)
+
+
+@torch.no_grad()
+def build_baseline_encoder(model_cfg: Dict[str, Any], seed: Optional[int] = None) -> _ViT:
+    """The reference's randomly initialised timm VisionTransformer (src/training/classifier.py:46-56), initialised as
+    timm 1.0.21 ``VisionTransformer.init_weights('')`` does: Linear weights trunc_normal(std .02) with zero bias,
+    LayerNorm 1 / 0, pos_embed trunc_normal(std .02) (trainable), cls_token normal(std 1e-6), and the patch Conv2d at
+    PyTorch's default init (kaiming_uniform(a=sqrt 5) weight, uniform(+-1/sqrt(fan_in)) bias)."""
+    mae = encoder_mae(model_cfg)
+    g = torch.Generator().manual_seed(seed) if seed is not None else None
+    vit = mae.encoder.vit
+    for name, p in vit.named_parameters():
+        if name == "pos_embed":
+            p.copy_(_trunc_normal(p.shape, 0.02, g))
+        elif name == "cls_token":
+            p.copy_(torch.randn(p.shape, generator=g) * 1e-6)
+        elif name.startswith("patch_embed.proj."):
+            fan_in = int(torch.tensor(vit.patch_embed.proj.weight.shape[1:]).prod())
+            bound = 1.0 / math.sqrt(fan_in)  # kaiming_uniform(a=sqrt(5)) on the weight gives the same bound
+            p.copy_((torch.rand(p.shape, generator=g) * 2 - 1) * bound)
+        elif name.startswith("norm") or ".norm" in name:
+            p.fill_(1.0 if name.endswith("weight") else 0.0)
+        elif name.endswith("weight"):
+            p.copy_(_trunc_normal(p.shape, 0.02, g))
+        else:
+            p.zero_()
+    vit.pos_embed.requires_grad = True
+    return vit
+
+
+def _trunc_normal(shape, std: float, g: Optional[torch.Generator]) -> torch.Tensor:
+    """torch.nn.init.trunc_normal_(std=std, a=-2, b=2) (timm's call: the cut is at +-2 absolute, i.e. +-100 sigma here)."""
+    t = torch.empty(shape)
+    torch.nn.init.trunc_normal_(t, std=std, a=-2.0, b=2.0, generator=g)
+    return t
+
+
+def load_encoder_weights(mae: MaskedAutoencoder, state: Dict[str, torch.Tensor]) -> Tuple[List[str], List[str]]:
+    """scripts/training/train_mae.py:111-135: strip the first of ``model.encoder.`` / ``encoder.`` / ``module.encoder.``
+    that matches and load into ``mae.encoder`` with strict=False; returns (missing, unexpected)."""
+    for pfx in ("model.encoder.", "encoder.", "module.encoder."):
+        sub = {k[len(pfx):]: v for k, v in state.items() if k.startswith(pfx)}
+        if sub:
+            break
+    else:
+        sub = dict(state)
+    res = mae.encoder.load_state_dict(sub, strict=False)
+    return list(res.missing_keys), list(res.unexpected_keys)

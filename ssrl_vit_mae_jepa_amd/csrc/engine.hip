@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
+#include <cstdint>
 #include "kernels.h"
 
 namespace mae {
@@ -686,7 +687,8 @@ extern "C" int64_t mae_engine_wcache_bytes(const mae_engine_t* e) {
   return round_up(2 * (e->trainable_elems + e->trans_elems), 256);
 }
 
-static int refresh_transposed(mae_engine* e, const float* params, void* wcache, hipStream_t s) {
+// transposed bf16 copies of the matrices that lie inside the arena range [lo, hi)
+static int refresh_transposed(mae_engine* e, const float* params, void* wcache, hipStream_t s, int64_t lo = 0, int64_t hi = INT64_MAX) {
   bf16* tbase = reinterpret_cast<bf16*>(wcache) + e->trainable_elems;
   TransposeTable tab;
   auto flush = [&]() -> int {
@@ -698,7 +700,7 @@ static int refresh_transposed(mae_engine* e, const float* params, void* wcache, 
   };
   tab.tile_begin[0] = 0;
   for (const auto& pi : e->params) {
-    if (!(pi.flags & MAE_PARAM_MATRIX) || pi.t_off < 0) continue;
+    if (!(pi.flags & MAE_PARAM_MATRIX) || pi.t_off < 0 || pi.offset < lo || pi.offset + pi.numel > hi) continue;
     const int rows = (int)pi.shape[0], cols = (int)(pi.numel / pi.shape[0]);
     const int i = tab.n++;
     tab.src_off[i] = pi.offset; tab.dst_off[i] = pi.t_off; tab.rows[i] = rows; tab.cols[i] = cols;
@@ -1041,6 +1043,162 @@ extern "C" int mae_engine_optimizer_step_ema(mae_engine_t* e, float* params, flo
   MAE_REQUIRE(ema_momentum >= 0.f && ema_momentum <= 1.f, "mae_engine_optimizer_step_ema: momentum %g outside [0, 1]", (double)ema_momentum);
   return optimizer_step_impl(e, params, grads, exp_avg, exp_avg_sq, wcache, lr, beta1, beta2, eps, weight_decay, max_norm, step, stats_out,
                              scratch, target_params, target_wcache, ema_momentum, stream);
+}
+
+// =====================================================================================================
+// Downstream classifier (src/models/classifier.py:47-57, src/training/classifier.py:75-171): the encoder over every token,
+// the pooled head + cross-entropy (k_classifier.hip) and a backward that stops where the trainable suffix ends.
+//   train_blocks = -1: linear probe -- the forward saves nothing for a backward, only the head gets gradients;
+//   train_blocks = n : final LayerNorm + blocks[depth-n:] (unfreeze_last_layers(n)); nothing below them runs;
+//   train_embed  = 1 : (n = depth only) also cls_token, the patch projection and pos_embed (unfreeze_encoder()).
+// =====================================================================================================
+namespace mae {
+
+struct ClsPlan {
+  Plan pl;  // the full-sequence plan (num_keep = L) at offset 0; the classifier's own buffers follow it
+  int64_t pooled, dlogits, row_loss, row_correct, dpooled, mean_c, rstd_c, cls_rows, head_partial, head_sum, pos_partial, total;
+};
+
+static ClsPlan make_cls_plan(const mae_engine* e, int B, int C) {
+  ClsPlan cp;
+  cp.pl = make_plan(e, B, e->L);
+  int64_t off = round_up(cp.pl.total, 256);
+  auto take = [&](int64_t bytes) { const int64_t o = off; off += round_up(std::max<int64_t>(bytes, 4), 256); return o; };
+  const int64_t D = e->D;
+  cp.pooled = take(B * D * 4);
+  cp.dlogits = take((int64_t)B * C * 4);
+  cp.row_loss = take((int64_t)B * 4);
+  cp.row_correct = take((int64_t)B * 4);
+  cp.dpooled = take(B * D * 4);
+  cp.mean_c = take((int64_t)B * 4);
+  cp.rstd_c = take((int64_t)B * 4);
+  cp.cls_rows = take((int64_t)B * 4);
+  cp.head_partial = take(classifier_wgrad_partial_floats(B, C, e->D) * 4);
+  cp.head_sum = take(round_up((int64_t)C * D + C, 4) * 4);
+  cp.pos_partial = take((int64_t)full_grad_split_slices(B, e->L, e->D) * e->L * D * 4);
+  cp.total = off;
+  return cp;
+}
+
+static int classifier_impl(mae_engine* e, const float* params, const void* wcache, const float* head, const void* images, int32_t image_dtype,
+                           const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes, int32_t train_blocks, int32_t train_embed,
+                           float grad_scale, void* workspace, int64_t workspace_bytes, float* grads, float* head_grads, float* pos_grad,
+                           float* logits, float* loss_out, int32_t* correct_out, void* stream, const char* who) {
+  Plan pl;
+  MAE_TRY(check_call(e, params, wcache, batch, e ? e->L : 1, workspace, workspace_bytes, &pl, who));
+  MAE_REQUIRE(head && images, "%s: null head/images", who);
+  MAE_TRY(check_image_dtype(image_dtype, who));
+  MAE_REQUIRE(num_classes >= 2 && num_classes <= HEAD_MAX_CLASSES, "%s: num_classes = %d outside [2, %d]", who, num_classes, HEAD_MAX_CLASSES);
+  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN, "%s: pool must be MAE_POOL_CLS or MAE_POOL_MEAN (got %d)", who, pool);
+  const ClsPlan cp = make_cls_plan(e, batch, num_classes);
+  MAE_REQUIRE(workspace_bytes >= cp.total, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)cp.total);
+  const bool train = head_grads != nullptr;
+  if (train) {
+    MAE_REQUIRE(labels && loss_out, "%s: training needs labels and loss_out", who);
+    MAE_REQUIRE(train_blocks >= -1 && train_blocks <= e->depth, "%s: train_blocks = %d outside [-1, %d]", who, train_blocks, e->depth);
+    MAE_REQUIRE(train_embed == 0 || (train_embed == 1 && train_blocks == e->depth),
+                "%s: train_embed = 1 needs train_blocks = depth (%d), got %d", who, e->depth, train_blocks);
+    MAE_REQUIRE(train_blocks < 0 || grads, "%s: train_blocks >= 0 needs the gradient arena", who);
+    MAE_REQUIRE(!train_embed || pos_grad, "%s: train_embed needs the pos_embed gradient buffer", who);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  Ctx c{e, params, (const char*)wcache, grads, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  const bool enc_bwd = train && train_blocks >= 0;
+  c.fwd_only = !enc_bwd;  // the linear probe and evaluation save no GELU derivative
+  const int B = batch, L = e->L, D = e->D, C = num_classes;
+  MAE_TRY(launch_iota_rows(c.buf<int32_t>(pl.keep32), B, L, s));
+  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
+  const bool cls = pool == MAE_POOL_CLS;
+  void* dfeat = enc_bwd ? (cls ? c.buf<>(cp.dpooled) : c.buf<>(pl.d_ln)) : nullptr;
+  RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), (cls ? (double)B * D : (double)pl.Me * D) * c.as + (double)C * D * 4 + (enc_bwd && !cls ? (double)pl.Me * D * c.as : 0.0),
+      launch_classifier_head(c.buf<>(pl.enc_norm), e->act, B, L, D, pool, head, head + (int64_t)C * D, C, labels, grad_scale, logits,
+                             c.buf<float>(cp.row_loss), c.buf<int32_t>(cp.row_correct), loss_out, correct_out,
+                             train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat,
+                             c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c),
+                             enc_bwd && cls ? c.buf<int32_t>(cp.cls_rows) : nullptr, s));
+  if (!train) return 0;
+  RUN(TK_WGRAD, 2.0 * B * C * D, (double)B * (C + D) * 4, launch_classifier_head_wgrad(c.buf<float>(cp.dlogits), c.buf<float>(cp.pooled), B, C, D,
+                                                                                    c.buf<float>(cp.head_partial), c.buf<float>(cp.head_sum), head_grads, s));
+  if (!enc_bwd) return 0;
+  float* dres = c.buf<float>(pl.dres);
+  void* dres_c = c.buf<>(pl.dres_c);
+  backward_begin(c);
+  MAE_TRY(await_side(e, DEP_DRESC, s));
+  if (cls) {
+    // only the B class-token rows carry gradient: zero the rest of the residual gradient, then a row-mapped final LayerNorm backward
+    RUN(TK_DATA, 0, (pl.Me - B) * D * (4 + c.as), launch_zero_token_rows(pl.Me, L, D, e->act, dres, dres_c, s));
+    RUN(TK_LN_BWD, 0, (int64_t)B * D * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(cp.dpooled), e->act, c.buf<float>(pl.enc_x[e->depth]), c.buf<int32_t>(cp.cls_rows), c.P(e->i_norm_w), c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c), B, D, 0, dres, dres_c, c.Gp(e->i_norm_w), c.Gp(e->i_norm_b), ln_slot(c, pl), s, &e->ln_tab));
+  } else {
+    RUN(TK_LN_BWD, 0, pl.Me * D * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(pl.d_ln), e->act, c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), pl.Me, D, 0, dres, dres_c, c.Gp(e->i_norm_w), c.Gp(e->i_norm_b), ln_slot(c, pl), s, &e->ln_tab));
+  }
+  for (int i = e->depth - 1; i >= e->depth - train_blocks; --i)  // the trainable suffix only: the sweep stops below blocks[depth-n]
+    MAE_TRY(block_backward(c, pl, e->enc[i], pl.enc[i], pl.Me, D, e->H, B, L, pl.enc_x[i]));
+  if (train_embed) {
+    // token assembly: d pos_embed, d cls_token and the patch rows from one read of dres, then the patch projection
+    RUN(TK_DATA, 0, pl.Me * D * (4 + c.as), launch_full_grad_split(dres, B, L, D, e->act, c.buf<>(pl.dtok), pos_grad, c.Gp(e->i_cls), c.buf<float>(cp.pos_partial), s));
+    MAE_TRY(wgrad(c, pl, c.buf<>(pl.dtok), c.buf<>(pl.patchA), pl.Me, D, e->P, e->i_patch_w, e->i_patch_b, DEP_MISC));
+  }
+  return backward_end(c);
+}
+
+}  // namespace mae
+
+extern "C" int64_t mae_engine_classifier_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t num_classes) {
+  if (!e || batch <= 0 || num_classes < 2 || num_classes > HEAD_MAX_CLASSES) return -1;
+  return make_cls_plan(e, batch, num_classes).total;
+}
+
+extern "C" int mae_engine_classifier_forward(mae_engine_t* e, const float* params, const void* wcache, const float* head, const void* images,
+                                             int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes,
+                                             void* workspace, int64_t workspace_bytes, float* logits, float* loss_out, int32_t* correct_out,
+                                             void* stream) {
+  MAE_REQUIRE(labels || (!loss_out && !correct_out), "mae_engine_classifier_forward: loss / correct count need labels");
+  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, -1, 0, 1.f, workspace, workspace_bytes,
+                         nullptr, nullptr, nullptr, logits, loss_out, correct_out, stream, "mae_engine_classifier_forward");
+}
+
+extern "C" int mae_engine_classifier_loss_and_grads(mae_engine_t* e, const float* params, const void* wcache, const float* head,
+                                                    const void* images, int32_t image_dtype, const int64_t* labels, int32_t batch,
+                                                    int32_t pool, int32_t num_classes, int32_t train_blocks, int32_t train_embed,
+                                                    float grad_scale, void* workspace, int64_t workspace_bytes, float* grads,
+                                                    float* head_grads, float* pos_grad, float* logits, float* loss_out,
+                                                    int32_t* correct_out, void* stream) {
+  MAE_REQUIRE(head_grads, "mae_engine_classifier_loss_and_grads: null head_grads");
+  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
+                         workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
+                         "mae_engine_classifier_loss_and_grads");
+}
+
+extern "C" int mae_engine_grad_sumsq_buffer(mae_engine_t* e, const float* grads, int64_t count, int32_t accumulate, float* sumsq_io,
+                                            float* scratch, void* stream) {
+  MAE_REQUIRE(e && grads && sumsq_io && scratch, "mae_engine_grad_sumsq_buffer: null argument");
+  MAE_REQUIRE(count >= 0 && count % 4 == 0, "mae_engine_grad_sumsq_buffer: count %lld is not a multiple of 4", (long long)count);
+  if (accumulate) return launch_grad_sumsq_accumulate(grads, count, sumsq_io, scratch, (hipStream_t)stream);
+  return launch_grad_sumsq(grads, count, sumsq_io, scratch, (hipStream_t)stream);
+}
+
+extern "C" int mae_engine_adamw_buffer(mae_engine_t* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t count,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, const float* stats,
+                                       void* stream) {
+  MAE_REQUIRE(e && params && grads && exp_avg && exp_avg_sq && stats, "mae_engine_adamw_buffer: null argument");
+  MAE_REQUIRE(step >= 1, "mae_engine_adamw_buffer: step is 1-based");
+  MAE_REQUIRE(count >= 0 && count % 4 == 0, "mae_engine_adamw_buffer: count %lld is not a multiple of 4", (long long)count);
+  if (count == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
+  const float bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));
+  RUN(TK_OPTIM, 0, count * 28, launch_adamw(params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2, eps, weight_decay, bc1, bc2, stats, nullptr, s));
+  return 0;
+}
+
+extern "C" int mae_engine_refresh_transposed_range(mae_engine_t* e, const float* params, void* wcache, int64_t lo, int64_t count, void* stream) {
+  MAE_REQUIRE(e && params, "mae_engine_refresh_transposed_range: null argument");
+  MAE_REQUIRE(lo >= 0 && count >= 0 && lo + count <= e->trainable_elems, "mae_engine_refresh_transposed_range: range outside the trainable elements");
+  if (e->act != MAE_BF16) return 0;
+  MAE_REQUIRE(wcache, "mae_engine_refresh_transposed_range: null weight cache");
+  hipStream_t s = (hipStream_t)stream;
+  RUN(TK_OPTIM, 0, 0, refresh_transposed(e, params, wcache, s, lo, lo + count));
+  return 0;
 }
 
 extern "C" int mae_engine_timers_enable(mae_engine_t* e, int32_t on) {

@@ -1,0 +1,334 @@
+// Downstream classifier: pooled linear head + cross-entropy (forward and backward) and the full-sequence embedding
+// gradient.  Reference: src/models/classifier.py:47-57 (pool + head), src/training/classifier.py:75-105 (F.cross_entropy,
+// accuracy), src/training/classifier.py:134 (unfreeze_encoder: cls_token, pos_embed and the patch projection train too).
+//
+// bf16 engine rounding points (each one a GEMM operand of the head, fp32 accumulation everywhere):
+//   (1) the pooled feature vector  -- with "mean" the rows are the engine's bf16 LayerNorm outputs, summed in fp32, then rounded;
+//   (2) the head weight W          -- rounded as it is read (the head's fp32 buffer has no bf16 copy);
+//   (3) d_logits                   -- rounded before dW, db and d_pooled are formed from it.
+// The feature gradient leaves in the activation dtype (the input of the final LayerNorm backward), as every other dy does.
+#include "kernels.h"
+
+namespace mae {
+
+template <class T> __device__ __forceinline__ float head_round(float x) { return x; }
+template <> __device__ __forceinline__ float head_round<bf16>(float x) { return (float)(bf16)x; }
+
+__global__ void iota_rows_kernel(int32_t* __restrict__ keep, int64_t n, int L) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) keep[i] = (int)(i % L);
+}
+
+int launch_iota_rows(int32_t* keep32, int B, int L, hipStream_t s) {
+  const int64_t n = (int64_t)B * L;
+  MAE_REQUIRE(keep32 && n > 0 && n < (1ll << 31), "iota_rows: bad arguments");
+  hipLaunchKernelGGL(iota_rows_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, keep32, n, L);
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
+
+// One block per image.  Thread t owns feature columns [4t, 4t+4) (t < D/4); wave w owns classes w, w+4, ...
+template <class T>
+__global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restrict__ feats, int L, int D, int pool,
+                                                              const float* __restrict__ W, const float* __restrict__ bias, int C,
+                                                              const int64_t* __restrict__ labels, float grad_scale, int B,
+                                                              float* __restrict__ logits_out, float* __restrict__ row_loss,
+                                                              int32_t* __restrict__ row_correct, float* __restrict__ pooled_out,
+                                                              float* __restrict__ dlogits_out, T* __restrict__ dfeat_out,
+                                                              const float* __restrict__ mean_all, const float* __restrict__ rstd_all,
+                                                              float* __restrict__ mean_c, float* __restrict__ rstd_c,
+                                                              int32_t* __restrict__ cls_rows) {
+  __shared__ __attribute__((aligned(16))) float sp[1024];
+  __shared__ float sl[HEAD_MAX_CLASSES], sdl[HEAD_MAX_CLASSES], sstat[2];
+  __shared__ int sy;
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int D4 = D / 4;
+  const int64_t row0 = (int64_t)b * L;
+  // pooled features: feats[:, 0] or feats.mean(dim=1) over all L rows (class token included)
+  if (t < D4) {
+    f32x4 v;
+    if (pool == MAE_POOL_CLS) {
+      v = load4(feats + row0 * D + 4 * t);
+    } else {
+      v = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < L; ++j) v += load4(feats + (row0 + j) * D + 4 * t);
+      v = v / (float)L;
+    }
+    for (int i = 0; i < 4; ++i) sp[4 * t + i] = head_round<T>(v[i]);  // rounding point (1)
+  }
+  __syncthreads();
+  // logits = pooled @ W.T + b
+  for (int c = wave; c < C; c += 4) {
+    float acc = 0.f;
+    for (int q = lane; q < D4; q += 64) {
+      const f32x4 w = load4(W + (int64_t)c * D + 4 * q);
+      for (int i = 0; i < 4; ++i) acc += head_round<T>(w[i]) * sp[4 * q + i];  // rounding point (2)
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) sl[c] = acc + bias[c];
+  }
+  __syncthreads();
+  if (t == 0) {
+    // max-subtracted log-sum-exp; argmax keeps the first index among equal maxima (torch.argmax)
+    float mx = sl[0];
+    int am = 0;
+    for (int c = 1; c < C; ++c)
+      if (sl[c] > mx) { mx = sl[c]; am = c; }
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(sl[c] - mx);
+    const float lse = mx + logf(se);
+    const int64_t y = labels ? labels[b] : -1;
+    const bool valid = y >= 0 && y < C;   // an out-of-range label is never used as an index: its row's loss is NaN
+    sy = valid ? (int)y : -1;
+    sstat[0] = lse;
+    row_loss[b] = valid ? lse - sl[y] : __builtin_nanf("");
+    row_correct[b] = (valid && am == (int)y) ? 1 : 0;
+    if (cls_rows) {  // compact statistics of the class-token rows for the row-mapped final LayerNorm backward
+      cls_rows[b] = (int32_t)row0;
+      mean_c[b] = mean_all[row0];
+      rstd_c[b] = rstd_all[row0];
+    }
+  }
+  __syncthreads();
+  if (logits_out)
+    for (int c = t; c < C; c += 256) logits_out[(int64_t)b * C + c] = sl[c];
+  if (!dlogits_out) return;
+  // d_logits = (softmax - onehot(y)) * grad_scale / B
+  const float lse = sstat[0];
+  const int y = sy;
+  for (int c = t; c < C; c += 256) {
+    float g = (expf(sl[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale / (float)B;
+    if (y < 0) g = __builtin_nanf("");
+    g = head_round<T>(g);  // rounding point (3)
+    sdl[c] = g;
+    dlogits_out[(int64_t)b * C + c] = g;
+  }
+  if (t < D4) store4(pooled_out + (int64_t)b * D + 4 * t, f32x4{sp[4 * t], sp[4 * t + 1], sp[4 * t + 2], sp[4 * t + 3]});
+  if (!dfeat_out) return;
+  __syncthreads();
+  // d_pooled = d_logits . W  ->  cls: row 0 of the image only (compact, row-mapped by the caller); mean: d_pooled / L on every row
+  if (t < D4) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < C; ++c) {
+      const f32x4 w = load4(W + (int64_t)c * D + 4 * t);
+      const f32x4 wr = {head_round<T>(w[0]), head_round<T>(w[1]), head_round<T>(w[2]), head_round<T>(w[3])};
+      acc += sdl[c] * wr;
+    }
+    if (pool == MAE_POOL_CLS) {
+      store4(dfeat_out + (int64_t)b * D + 4 * t, acc);
+    } else {
+      acc = acc / (float)L;
+      for (int j = 0; j < L; ++j) store4(dfeat_out + (row0 + j) * D + 4 * t, acc);
+    }
+  }
+}
+
+// loss = mean of the row losses, correct = count of correct rows: one block, fixed summation order
+__global__ void __launch_bounds__(256) classifier_reduce_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ row_correct,
+                                                                int B, float* __restrict__ loss_out, int32_t* __restrict__ correct_out) {
+  __shared__ float sl[256];
+  __shared__ int sc[256];
+  const int t = threadIdx.x;
+  float l = 0.f;
+  int n = 0;
+  for (int b = t; b < B; b += 256) { l += row_loss[b]; n += row_correct[b]; }
+  sl[t] = l; sc[t] = n;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) { sl[t] += sl[t + w]; sc[t] += sc[t + w]; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (loss_out) loss_out[0] = sl[0] / (float)B;
+    if (correct_out) correct_out[0] = sc[0];
+  }
+}
+
+int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int pool, const float* W, const float* bias, int C,
+                           const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
+                           float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out,
+                           const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s) {
+  MAE_REQUIRE(feats && W && bias && row_loss && row_correct && B > 0 && L > 0, "classifier_head: bad arguments");
+  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "classifier_head: D = %d must be a multiple of 4 in [4, 1024]", D);
+  MAE_REQUIRE(C >= 2 && C <= HEAD_MAX_CLASSES, "classifier_head: num_classes = %d outside [2, %d]", C, HEAD_MAX_CLASSES);
+  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN, "classifier_head: pool must be MAE_POOL_CLS or MAE_POOL_MEAN");
+  MAE_REQUIRE(!dlogits_out || pooled_out, "classifier_head: the backward needs the pooled-feature buffer");
+  MAE_REQUIRE(!dfeat_out || dlogits_out, "classifier_head: the feature gradient needs d_logits");
+  MAE_REQUIRE(!cls_rows || (mean_all && rstd_all && mean_c && rstd_c), "classifier_head: class-row statistics need every buffer");
+#define HEAD(T) hipLaunchKernelGGL(classifier_head_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)feats, L, D, pool, W, bias, C, labels, grad_scale, B, \
+                                   logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out, mean_all, rstd_all, mean_c, rstd_c, cls_rows)
+  if (dt == MAE_BF16) HEAD(bf16); else HEAD(float);
+#undef HEAD
+  MAE_LAUNCH_CHECK();
+  if (loss_out || correct_out) {
+    hipLaunchKernelGGL(classifier_reduce_kernel, dim3(1), dim3(256), 0, s, row_loss, row_correct, B, loss_out, correct_out);
+    MAE_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// Head weight gradient: column j < C*D is dW[j / D][j % D], column C*D + c is db[c]; grid.y = batch slices.
+// partial[slice][j] = sum over the slice's rows in ascending order (launch_sum_partials then adds the slices in order).
+__global__ void __launch_bounds__(256) classifier_head_wgrad_kernel(const float* __restrict__ dlogits, const float* __restrict__ pooled,
+                                                                    int B, int C, int D, int ncols, int ncols_p,
+                                                                    float* __restrict__ partial) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= ncols_p) return;
+  const int S = gridDim.y, sl = blockIdx.y;
+  const int b0 = (int)((int64_t)B * sl / S), b1 = (int)((int64_t)B * (sl + 1) / S);
+  float acc = 0.f;
+  if (j < C * D) {
+    const int c = j / D, d = j - c * D;
+    for (int b = b0; b < b1; ++b) acc += dlogits[(int64_t)b * C + c] * pooled[(int64_t)b * D + d];
+  } else if (j < ncols) {
+    const int c = j - C * D;
+    for (int b = b0; b < b1; ++b) acc += dlogits[(int64_t)b * C + c];
+  }
+  partial[(int64_t)sl * ncols_p + j] = acc;
+}
+
+int64_t classifier_wgrad_partial_floats(int B, int C, int D) {
+  const int S = std::min(B, CLS_WGRAD_SLICES);
+  return (int64_t)S * round_up((int64_t)C * D + C, 4);
+}
+
+int launch_classifier_head_wgrad(const float* dlogits, const float* pooled, int B, int C, int D, float* partial, float* sum_out,
+                                 float* head_grads, hipStream_t s) {
+  MAE_REQUIRE(dlogits && pooled && partial && sum_out && head_grads && B > 0 && C > 0 && D > 0, "classifier_head_wgrad: bad arguments");
+  const int ncols = C * D + C, ncols_p = (int)round_up(ncols, 4);
+  const int S = std::min(B, CLS_WGRAD_SLICES);
+  hipLaunchKernelGGL(classifier_head_wgrad_kernel, dim3((unsigned)cdiv(ncols_p, 256), S), dim3(256), 0, s, dlogits, pooled, B, C, D, ncols, ncols_p, partial);
+  MAE_LAUNCH_CHECK();
+  MAE_TRY(launch_sum_partials(partial, S, ncols_p, sum_out, nullptr, ncols_p, s));
+  MAE_HIP(hipMemcpyAsync(head_grads, sum_out, (size_t)ncols * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// cls pooling: every row of dres / dres_c except the class-token row of each image is zero before the blocks' backward
+template <class T>
+__global__ void __launch_bounds__(256) zero_token_rows_kernel(int64_t rows, int L, int D4, float* __restrict__ dres, T* __restrict__ dres_c) {
+  const int lanes = D4 <= 64 ? 64 : 128;
+  const int rpb = 256 / lanes, sub = threadIdx.x / lanes, l = threadIdx.x % lanes;
+  for (int64_t row = (int64_t)blockIdx.x * rpb + sub; row < rows; row += (int64_t)gridDim.x * rpb) {
+    if (row % L == 0) continue;
+    for (int c = l; c < D4; c += lanes) {
+      store4(dres + row * (int64_t)D4 * 4 + c * 4, f32x4{0.f, 0.f, 0.f, 0.f});
+      store4(dres_c + row * (int64_t)D4 * 4 + c * 4, f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+  }
+}
+
+int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, void* dres_c, hipStream_t s) {
+  MAE_REQUIRE(dres && dres_c && rows > 0 && L > 0 && D % 4 == 0 && D <= 1024, "zero_token_rows: bad arguments");
+  const int rpb = D / 4 <= 64 ? 4 : 2;
+  const int grid = (int)std::min<int64_t>(cdiv(rows, rpb), 8192);
+  if (act == MAE_BF16)
+    hipLaunchKernelGGL(zero_token_rows_kernel<bf16>, dim3(grid), dim3(256), 0, s, rows, L, D / 4, dres, reinterpret_cast<bf16*>(dres_c));
+  else
+    hipLaunchKernelGGL(zero_token_rows_kernel<float>, dim3(grid), dim3(256), 0, s, rows, L, D / 4, dres, reinterpret_cast<float*>(dres_c));
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
+
+// Full-sequence embedding gradient in ONE pass over dres (B, L, D) fp32:
+//   dtok (act dtype) = dres with the class-token rows zeroed (the patch-projection weight gradient reads it),
+//   partial[slice][t][d] = sum of dres[b, t, d] over the slice's images in ascending order.
+// The slices' partials are then added in order: d pos_embed[t] = sum_b dres[b, t], and d cls_token = d pos_embed[0].
+// Thread (t, 4 columns) of slice s walks its images with four rows in flight.
+template <class T>
+__global__ void __launch_bounds__(256) full_grad_split_kernel(const float* __restrict__ dx, int B, int L, int D, T* __restrict__ dtok,
+                                                              float* __restrict__ partial) {
+  const int D4 = D / 4;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= L * D4) return;
+  const int t = q / D4, d = (q - t * D4) * 4;
+  const int S = gridDim.y, sl = blockIdx.y;
+  const int b0 = (int)((int64_t)B * sl / S), b1 = (int)((int64_t)B * (sl + 1) / S);
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = z;
+  constexpr int U = 4;
+  for (int bb = b0; bb < b1; bb += U) {
+    f32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t off = (((int64_t)(bb + u) * L + t) * D) + d;
+      v[u] = bb + u < b1 ? load4_nt(dx + off) : z;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (bb + u < b1) {
+        acc += v[u];
+        store4(dtok + (((int64_t)(bb + u) * L + t) * D) + d, t == 0 ? z : v[u]);
+      }
+    }
+  }
+  store4(partial + (int64_t)sl * L * D + (int64_t)t * D + d, acc);
+}
+
+int full_grad_split_slices(int B, int L, int D) {
+  const int per_slice = (int)cdiv((int64_t)L * (D / 4), 256);
+  return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)B, (int64_t)CLS_EMBED_SLICES, cdiv(2048, per_slice)}));
+}
+
+int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s) {
+  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && L > 0 && D % 4 == 0 && D <= 1024, "full_grad_split: bad arguments");
+  MAE_REQUIRE((int64_t)B * L < (1ll << 31), "full_grad_split: B * L < 2^31");
+  const int S = full_grad_split_slices(B, L, D);
+  const dim3 grid((unsigned)cdiv((int64_t)L * (D / 4), 256), S);
+  if (dt == MAE_BF16)
+    hipLaunchKernelGGL(full_grad_split_kernel<bf16>, grid, dim3(256), 0, s, dx, B, L, D, (bf16*)dtok, partial);
+  else
+    hipLaunchKernelGGL(full_grad_split_kernel<float>, grid, dim3(256), 0, s, dx, B, L, D, (float*)dtok, partial);
+  MAE_LAUNCH_CHECK();
+  MAE_TRY(launch_sum_partials(partial, S, L * D, dpos, nullptr, L * D, s));
+  MAE_HIP(hipMemcpyAsync(dcls, dpos, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// out[0] += out[1] (the buffer sum of squares folded into a running total)
+__global__ void add_slot_kernel(float* out) { out[0] += out[1]; }
+
+int launch_grad_sumsq_accumulate(const float* g, int64_t n, float* io, float* scratch, hipStream_t s) {
+  MAE_TRY(launch_grad_sumsq(g, n, io + 1, scratch, s));
+  hipLaunchKernelGGL(add_slot_kernel, dim3(1), dim3(1), 0, s, io);
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace mae
+
+// single-kernel entry (parity tests and reuse): the head's forward and backward on caller features
+extern "C" int64_t mae_classifier_head_scratch_bytes(int32_t batch, int32_t num_classes, int32_t dim) {
+  if (batch <= 0 || num_classes < 2 || num_classes > mae::HEAD_MAX_CLASSES || dim <= 0) return -1;
+  const int64_t B = batch, C = num_classes, D = dim;
+  auto seg = [](int64_t n) { return mae::round_up(n, 64); };  // every segment starts 256-byte aligned (vector loads)
+  return 4 * (seg(B * D) + seg(B * C) + 2 * seg(B) + seg(mae::classifier_wgrad_partial_floats(batch, num_classes, dim)) + seg(C * D + C));
+}
+
+extern "C" int mae_classifier_head(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t pool,
+                                   const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
+                                   float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
+                                   int64_t scratch_bytes, void* stream) {
+  using namespace mae;
+  MAE_REQUIRE(dtype == MAE_F32 || dtype == MAE_BF16, "mae_classifier_head: dtype must be MAE_F32 or MAE_BF16");
+  const int64_t need = mae_classifier_head_scratch_bytes(batch, num_classes, dim);
+  MAE_REQUIRE(need > 0 && scratch && scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0,
+              "mae_classifier_head: scratch must hold mae_classifier_head_scratch_bytes (%lld) bytes, 256-byte aligned", (long long)need);
+  MAE_REQUIRE(!d_feats || head_grads, "mae_classifier_head: d_feats needs head_grads");
+  MAE_REQUIRE(!head_grads || labels, "mae_classifier_head: gradients need labels");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t B = batch, C = num_classes, D = dim;
+  auto seg = [](int64_t n) { return round_up(n, 64); };
+  float* pooled = reinterpret_cast<float*>(scratch);
+  float* dlogits = pooled + seg(B * D);
+  float* row_loss = dlogits + seg(B * C);
+  int32_t* row_correct = reinterpret_cast<int32_t*>(row_loss + seg(B));
+  float* partial = row_loss + 2 * seg(B);
+  float* hsum = partial + seg(classifier_wgrad_partial_floats(batch, num_classes, dim));
+  MAE_TRY(launch_classifier_head(feats, dtype, batch, seq_len, dim, pool, head, head + C * D, num_classes, labels, grad_scale, logits, row_loss,
+                                 row_correct, loss_out, correct_out, head_grads ? pooled : nullptr, head_grads ? dlogits : nullptr, d_feats,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, s));
+  if (!head_grads) return 0;
+  return launch_classifier_head_wgrad(dlogits, pooled, batch, num_classes, dim, partial, hsum, head_grads, s);
+}
+

@@ -63,6 +63,33 @@ int launch_add_into(const float* src, void* dst, int dst_dt, int64_t n, hipStrea
 // out[c] = sum_{i<G} partial[i][c] in row order (deterministic); columns [0,split) go to out0, [split,C) to out1
 int launch_sum_partials(const float* partial, int G, int C, float* out0, float* out1, int split, hipStream_t s);
 
+// ---- k_classifier.hip: pooled linear head + cross-entropy, full-sequence embedding gradient ---------------------------------
+constexpr int HEAD_MAX_CLASSES = 128;   // classes held in LDS by the head kernel
+constexpr int CLS_WGRAD_SLICES = 64;    // batch slices of the head weight-gradient partials
+constexpr int CLS_EMBED_SLICES = 64;    // batch slices of the d pos_embed partials
+// keep[b*L + j] = j (every token of every image)
+int launch_iota_rows(int32_t* keep32, int B, int L, hipStream_t s);
+// one block per image: pooled = feats[b, 0] or mean over L rows; logits = pooled W^T + bias; row loss / correct flag;
+// with dlogits_out: d_logits (and pooled, both fp32, rounded at the bf16 points); with dfeat_out: cls -> (B, D) compact
+// d_pooled, mean -> (B*L, D) d_pooled / L; with cls_rows: class-row map and its LayerNorm statistics (compact).
+// loss_out = mean of the row losses, correct_out = number of correct rows (fixed-order reduction; either may be null)
+int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int pool, const float* W, const float* bias, int C,
+                           const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
+                           float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out,
+                           const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s);
+// head_grads[0 .. C*D) = dW, [C*D .. C*D+C) = db; partial >= classifier_wgrad_partial_floats, sum_out >= round_up(C*D+C, 4) floats
+int64_t classifier_wgrad_partial_floats(int B, int C, int D);
+int launch_classifier_head_wgrad(const float* dlogits, const float* pooled, int B, int C, int D, float* partial, float* sum_out,
+                                 float* head_grads, hipStream_t s);
+// zero every row of dres / dres_c (B*L rows) whose token index is not 0
+int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, void* dres_c, hipStream_t s);
+// one read of dx (B, L, D): dtok = dx with class rows zeroed, dpos (L*D) = sum over images, dcls (D) = dpos[0].
+// partial >= full_grad_split_slices(B, L, D) * L * D floats
+int full_grad_split_slices(int B, int L, int D);
+int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s);
+// io[0] += sum(g^2) (io[1] is a temporary)
+int launch_grad_sumsq_accumulate(const float* g, int64_t n, float* io, float* scratch, hipStream_t s);
+
 // ---- k_loss_optim.hip -----------------------------------------------------------------------------
 // loss[0] = mean((pred-target)^2); d_pred (dt, may be null) = grad_scale*2*(pred-target)/n.  scratch >= 1024+ floats
 int launch_mse(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,

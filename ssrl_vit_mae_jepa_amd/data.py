@@ -21,7 +21,8 @@ Without the dataset file (no network here) it serves seeded synthetic uniform[-1
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Callable, Iterator, Optional, Tuple
+import math
+from typing import Callable, Iterator, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -264,3 +265,105 @@ def get_pretrain_batches(cfg: dict, device: torch.device, synthetic_images: Opti
     train_batches.steps_per_epoch = (n_train + batch - 1) // batch
     train_batches.n_train = n_train
     return train_batches, val_batches
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Labeled STL-10 (fine-tuning / evaluation: src/data.py:109-176)
+# ---------------------------------------------------------------------------------------------------------------------
+STL10_DIR = Path("data") / "stl10_binary"
+
+
+def _load_stl10_labeled(split: str) -> Optional[Tuple[torch.Tensor, np.ndarray]]:
+    xp, yp = STL10_DIR / f"{split}_X.bin", STL10_DIR / f"{split}_y.bin"
+    if not (xp.exists() and yp.exists()):
+        return None
+    raw = np.fromfile(xp, dtype=np.uint8)
+    imgs = raw.reshape(-1, 3, 96, 96).transpose(0, 1, 3, 2)  # file stores each plane column-major
+    labels = np.fromfile(yp, dtype=np.uint8).astype(np.int64) - 1  # STL-10 labels 1..10 -> 0..9 (torchvision STL10)
+    return torch.from_numpy(np.ascontiguousarray(imgs)), labels
+
+
+def split_per_class(labels: np.ndarray, samples_per_class: int, seed: int = 73) -> Tuple[List[int], List[int]]:
+    """src/data.py:129-138: for each class in sorted order, its indices shuffled by a FRESH default_rng(seed); the first
+    samples_per_class go to train, the rest to validation (lists in that class-major order)."""
+    train_idx: List[int] = []
+    val_idx: List[int] = []
+    for c in np.unique(labels):
+        cls_idx = np.where(labels == c)[0]
+        np.random.default_rng(seed).shuffle(cls_idx)
+        train_idx.extend(cls_idx[:samples_per_class].tolist())
+        val_idx.extend(cls_idx[samples_per_class:].tolist())
+    return train_idx, val_idx
+
+
+def synthetic_labeled(n: int, num_classes: int = 10, seed: int = 73) -> Tuple[torch.Tensor, np.ndarray]:
+    """Seeded stand-in for a labeled split: balanced labels (i mod num_classes, shuffled) and uint8 images whose class is
+    recoverable from the pixels -- a class-dependent low-frequency grating (orientation and phase fixed per class, the
+    same in every split) plus seeded noise."""
+    g = torch.Generator().manual_seed(seed)
+    labels = (torch.arange(n) % num_classes)[torch.randperm(n, generator=g)]
+    yy, xx = torch.meshgrid(torch.arange(96, dtype=torch.float32), torch.arange(96, dtype=torch.float32), indexing="ij")
+    ang = torch.arange(num_classes, dtype=torch.float32) * (math.pi / num_classes)
+    freq = 2 * math.pi * 3 / 96
+    pat = torch.sin(freq * (xx[None] * torch.cos(ang)[:, None, None] + yy[None] * torch.sin(ang)[:, None, None]))  # (K, 96, 96)
+    chan = torch.tensor([1.0, -0.5, 0.25])[None, :, None, None]
+    base = 128 + 70 * pat[labels][:, None] * chan
+    imgs = (base + 25 * torch.randn(n, 3, 96, 96, generator=g)).clamp(0, 255).round().to(torch.uint8)
+    return imgs, labels.numpy().astype(np.int64)
+
+
+class LabeledBatches:
+    """(images uint8 on the device, labels int64 on the device) batches of a fixed index list; ``shuffle`` reorders the
+    list every epoch from a generator seeded with (seed, epoch) (DataLoader(shuffle=True)); no batch is dropped."""
+
+    def __init__(self, images: torch.Tensor, labels: torch.Tensor, idx: List[int], batch: int, shuffle: bool, seed: int):
+        self.images, self.labels = images, labels
+        self.idx = torch.as_tensor(idx, dtype=torch.int64, device=images.device)
+        self.batch, self.shuffle, self.seed = int(batch), shuffle, seed
+        self.n = len(idx)
+        self.steps_per_epoch = (self.n + self.batch - 1) // self.batch
+
+    def __call__(self, epoch: int = 0) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        order = self.idx
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed + 1000 + epoch)
+            order = order[torch.randperm(self.n, generator=g).to(order.device)]
+        for i in range(0, self.n, self.batch):
+            j = order[i:i + self.batch]
+            yield self.images[j].contiguous(), self.labels[j].contiguous()
+
+
+def get_train_batches(cfg: dict, device: torch.device, synthetic_images: Optional[int] = None, seed: int = 73):
+    """(train_batches(epoch), val_batches()) over the labeled STL-10 train split (``train_X.bin`` / ``train_y.bin``),
+    split per class as src/data.py:126-138 does.  Neither split is augmented: the reference assigns the eval transform to
+    ``val_dataset.dataset`` (src/data.py:139), which is the STL10 object BOTH subsets share, so its training images are only
+    normalised too; the same holds here (uint8 on the device, normalised inside the engine's pixel kernels).  Without the
+    files: ``synthetic_labeled`` images (default 5000), with samples_per_class capped at 80 % of a class."""
+    train_cfg = cfg["train"]
+    seed = int(cfg.get("seed", seed))
+    spc = int(train_cfg.get("samples_per_class", 400))
+    loaded = None if synthetic_images is not None else _load_stl10_labeled("train")
+    if loaded is None:
+        n = int(synthetic_images or 5000)
+        imgs, labels = synthetic_labeled(n, seed=seed)
+        spc = min(spc, int(0.8 * n / 10))
+    else:
+        imgs, labels = loaded
+    train_idx, val_idx = split_per_class(labels, spc, seed)
+    print(f"Using {spc} samples/class -> {len(train_idx)} train, {len(val_idx)} val")
+    images = imgs.to(device)
+    lab = torch.from_numpy(labels).to(device)
+    bs = int(train_cfg.get("batch_size", 64))
+    return (LabeledBatches(images, lab, train_idx, bs, True, seed), LabeledBatches(images, lab, val_idx, bs, False, seed))
+
+
+def get_test_batches(cfg: dict, device: torch.device, synthetic_images: Optional[int] = None, seed: int = 73) -> LabeledBatches:
+    """The labeled STL-10 test split (``test_X.bin`` / ``test_y.bin``) in file order (src/data.py:157-176); without the
+    files, ``synthetic_labeled`` images drawn with another seed than the training split's."""
+    loaded = None if synthetic_images is not None else _load_stl10_labeled("test")
+    if loaded is None:
+        imgs, labels = synthetic_labeled(int(synthetic_images or 2000), seed=int(cfg.get("seed", seed)) + 1)
+    else:
+        imgs, labels = loaded
+    bs = int(cfg.get("test", {}).get("batch_size", 64))
+    return LabeledBatches(imgs.to(device), torch.from_numpy(labels).to(device), list(range(len(labels))), bs, False, seed)

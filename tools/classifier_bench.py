@@ -1,0 +1,134 @@
+"""Throughput of the downstream classifier step (images/s), printed as one JSON document.
+
+For each model (the configs/mae.yaml encoder and ViT-S/8 of configs/vits8_dec192.yaml, B = 2000 by default):
+  * the native fused step (loss_and_grads + clip + AdamW) with the encoder frozen, unfreeze_last_layers(1) and fully unfrozen;
+  * the autograd hand-off (forward_features node + torch Linear head + F.cross_entropy + clip_grad_norm_ + torch AdamW)
+    in the last-1 and full modes, alternated with the fused step in the same process;
+  * the evaluation forward (no grad).
+Device events time `--steps` steps after `--warmup` steps; each number is the median of `--repeats` timed runs.
+
+    python tools/classifier_bench.py --batch 2000 --steps 10 --warmup 3 --out profiles/r04_classifier_bench.json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import torch
+import torch.nn.functional as F
+import yaml
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+from ssrl_vit_mae_jepa_amd.classifier import ViTClassifierTrainModule, encoder_mae  # noqa: E402
+
+
+def timed(fn, steps: int, warmup: int) -> float:
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def set_mode(mod, mode):
+    if mode == "frozen":
+        mod.freeze_encoder()
+    elif mode == "full":
+        mod.unfreeze_encoder()
+    else:
+        mod.unfreeze_last_layers(1)
+
+
+def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repeats: int, modes=("frozen", "last1", "full"),
+                handoff: bool = True) -> dict:
+    cfg = yaml.safe_load(cfg_path.read_text())
+    mc = dict(cfg["model"], general=dict(cfg["model"]["general"], engine_precision=cfg.get("engine", {}).get("precision", "bf16")))
+    dev = torch.device("cuda", 0)
+    mae = encoder_mae(mc)
+    mod = ViTClassifierTrainModule(pretrained_encoder=mae.encoder.vit, model_cfg=mc, training_cfg=dict(cfg.get("train", {}))).to(dev)
+    S = mc["general"]["image_size"]
+    g = torch.Generator(device=dev).manual_seed(0)
+    images = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, device=dev, generator=g)
+    labels = torch.randint(0, 10, (B,), device=dev, generator=g)
+    m = mod.model.mae
+    ws_bytes = int(mod.model.workspace(B).numel())
+    res = {"model": name, "config": str(cfg_path.relative_to(ROOT)), "batch": B, "precision": m.engine.precision,
+           "workspace_gib": ws_bytes / 2 ** 30, "ms": {}, "images_per_s": {}}
+
+    def fused():
+        mod.fused_training_step(images, labels, lr=1e-5)
+
+    def handoff_opt():
+        params = [p for p in mod.model.parameters() if p.requires_grad]
+        opt = torch.optim.AdamW(params, lr=1e-5, weight_decay=mod.weight_decay)
+
+        def step():
+            feats = mod.model.encoder.forward_features(images)
+            logits = F.linear(feats[:, 0], mod.model.head.classification.weight, mod.model.head.classification.bias)
+            loss = F.cross_entropy(logits, labels)
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(params, 1.0)
+            opt.step()
+            opt.zero_grad(set_to_none=True)
+        return step
+
+    def evaluate():
+        with torch.no_grad():
+            mod.model.evaluate(images, labels, logits=False)
+
+    runs = {}
+    for mode in modes:
+        set_mode(mod, mode)
+        cases = [(f"fused_{mode}", fused)]
+        if mode != "frozen" and handoff:
+            cases.append((f"handoff_{mode}", handoff_opt()))
+        for _r in range(repeats):  # alternated: fused, hand-off, fused, hand-off, ...
+            for key, fn in cases:
+                runs.setdefault(key, []).append(timed(fn, steps, warmup))
+    mod.freeze_encoder()
+    for _r in range(repeats):
+        runs.setdefault("eval_forward", []).append(timed(evaluate, steps, warmup))
+    for key, v in runs.items():
+        ms = statistics.median(v)
+        res["ms"][key] = ms
+        res["images_per_s"][key] = B / (ms / 1e3)
+    res["ms_all"] = runs
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--batch", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--models", default="yaml,vits8")
+    ap.add_argument("--modes", default="frozen,last1,full")
+    ap.add_argument("--no-handoff", action="store_true", help="fused steps only (e.g. under a kernel trace)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    torch.backends.cuda.matmul.allow_tf32 = False
+    cfgs = {"yaml": ROOT / "configs" / "mae.yaml", "vits8": ROOT / "configs" / "vits8_dec192.yaml"}
+    out = {"tool": "tools/classifier_bench.py", "argv": sys.argv[1:], "device": torch.cuda.get_device_name(0), "results": []}
+    for name in args.models.split(","):
+        out["results"].append(bench_model(name, cfgs[name], args.batch, args.steps, args.warmup, args.repeats,
+                                              tuple(args.modes.split(",")), not args.no_handoff))
+        torch.cuda.empty_cache()
+    text = json.dumps(out, indent=1)
+    print(text)
+    if args.out:
+        Path(args.out).write_text(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
