@@ -258,7 +258,7 @@ int mae_engine_adamw_range(mae_engine_t* e, float* params, const float* grads, f
  *   train_embed = 1   : n = depth only -- also cls_token, patch_embed.proj.* (in `grads`) and pos_embed, whose gradient
  *                       goes to pos_grad (L * embed_dim floats, it lies outside the trainable range) (unfreeze_encoder(), :134).
  *   head_grads: dW then db, same layout as head.  grad_scale multiplies every gradient (not the loss). */
-enum { MAE_POOL_CLS = 0, MAE_POOL_MEAN = 1 };
+enum { MAE_POOL_CLS = 0, MAE_POOL_MEAN = 1, MAE_POOL_MEAN_PATCHES = 2 /* features only: the classifier rejects it */ };
 int64_t mae_engine_classifier_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t num_classes);
 int mae_engine_classifier_forward(mae_engine_t* e, const float* params, const void* wcache, const float* head, const void* images,
                                   int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes,
@@ -284,6 +284,42 @@ int mae_engine_adamw_buffer(mae_engine_t* e, float* params, const float* grads, 
                             float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, const float* stats,
                             void* stream);
 int mae_engine_refresh_transposed_range(mae_engine_t* e, const float* params, void* wcache, int64_t lo, int64_t count, void* stream);
+
+/* Frozen-encoder features (additive in ABI v4; scripts/evaluation/visualize_representation.py:87-108 of the reference):
+ * the encoder forward over every image, nothing saved for a backward, then ONE fused step that does the last residual add,
+ * the final LayerNorm (encoder.vit.norm, eps 1e-6) in fp32, the pool and the optional normalisation, writing only
+ * feats (batch, embed_dim) fp32.
+ *   with_cls = 1: the sequence is [cls | patch 1..N] (timm forward_features, the classifier's sequence);
+ *   with_cls = 0: patch tokens 1..N only (what the I-JEPA encoders see);
+ *   params / wcache: any arena of the engine's layout (the I-JEPA EMA target arena included);
+ *   pool: MAE_POOL_CLS (row 0; with_cls = 1 only), MAE_POOL_MEAN (mean over every row of the sequence, the classifier's
+ *         mean), MAE_POOL_MEAN_PATCHES (mean over the patch rows: out[:, 1:].mean(1) with cls, every row without);
+ *   normalize: MAE_FEAT_NONE, or MAE_FEAT_L2 = f / (||f||_2 + 1e-8).
+ * embed_dim must be a multiple of 4 and at most 1024 (else both calls fail: -1 / an error, before any launch).
+ * Deterministic (fixed summation orders, no atomics).  workspace: mae_engine_features_workspace_bytes(batch, with_cls)
+ * bytes, 256-byte aligned; it overwrites the saved activations of any earlier forward that used the same buffer. */
+enum { MAE_FEAT_NONE = 0, MAE_FEAT_L2 = 1 };
+int64_t mae_engine_features_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls);
+int mae_engine_extract_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, void* workspace,
+                                int64_t workspace_bytes, float* feats, void* stream);
+
+/* Weighted k-NN probe on features (no reference counterpart; DINO's k-NN evaluation).
+ * mae_knn_topk: for every query row the k bank rows of highest fp32 dot product, sorted by similarity descending, then bank
+ *   index ascending; a NaN similarity is reported and sorted as -inf.  queries (num_queries, dim), bank (bank_size, dim) fp32,
+ *   16-byte aligned, may be the same buffer; dim a multiple of 4 in [4, 4096]; 1 <= k <= min(256, bank_size);
+ *   bank_size < 2^31.  The similarity of a pair is an fp32 fma chain in a fixed column order: it depends on the two rows
+ *   only (not on num_queries, bank_size or how the bank is split).  topk_sim / topk_idx (num_queries, k).
+ *   scratch: mae_knn_scratch_bytes(...) bytes, 256-byte aligned (-1 = arguments outside the limits).
+ * mae_knn_vote: scores[q][c] = sum over j < k of [bank_labels[topk_idx[q][j]] == c] * exp(topk_sim[q][j] / temperature),
+ *   summed in j order over the first k of k_stride columns; pred[q] = argmax (lowest class among equal scores).
+ *   num_classes in [2, 128]; temperature > 0; scores (num_queries, num_classes) may be NULL.  A label outside
+ *   [0, num_classes) is never used as an index: that query's scores are NaN and its pred is -1. */
+int64_t mae_knn_scratch_bytes(int64_t num_queries, int64_t bank_size, int32_t dim, int32_t k);
+int mae_knn_topk(const float* queries, int64_t num_queries, const float* bank, int64_t bank_size, int32_t dim, int32_t k,
+                 float* topk_sim, int64_t* topk_idx, void* scratch, int64_t scratch_bytes, void* stream);
+int mae_knn_vote(const float* topk_sim, const int64_t* topk_idx, int64_t num_queries, int32_t k_stride, int32_t k,
+                 const int64_t* bank_labels, int32_t num_classes, float temperature, float* scores, int64_t* pred, void* stream);
 
 /* mae_engine_optimizer_step with the EMA update of the target encoder fused into the AdamW sweep:
  * target[0 .. encoder_grad_elems) = m * target + (1 - m) * params_new (+ the bf16 operand copy in target_wcache).

@@ -17,7 +17,8 @@ LIB_PATH = Path(os.environ.get("MAE_HIP_LIB") or _HERE / "lib" / "libmae_hip.so"
 MAE_F32, MAE_BF16, MAE_U8 = 0, 1, 2
 PARAM_TRAINABLE, PARAM_FROZEN, PARAM_UNUSED, PARAM_MATRIX = 1, 2, 4, 8
 LOSS_MSE, LOSS_SMOOTH_L1 = 0, 1
-POOL_CLS, POOL_MEAN = 0, 1
+POOL_CLS, POOL_MEAN, POOL_MEAN_PATCHES = 0, 1, 2
+FEAT_NONE, FEAT_L2 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL, EPI_GELU_ACT = 0, 1, 2, 3, 4, 5, 6
 ABI_VERSION = 4
 
@@ -88,6 +89,11 @@ SIGNATURES = {
     "mae_engine_grad_sumsq_buffer": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "mae_engine_adamw_buffer": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _vp, _vp]),
     "mae_engine_refresh_transposed_range": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
+    "mae_engine_features_workspace_bytes": (_i64, [_vp, _i32, _i32]),
+    "mae_engine_extract_features": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "mae_knn_scratch_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "mae_knn_topk": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "mae_knn_vote": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _f32, _vp, _vp, _vp]),
     "mae_engine_optimizer_step_ema": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _vp, _vp, _vp, _vp, _f32, _vp]),
     "mae_engine_timers_enable": (C.c_int, [_vp, _i32]),
     "mae_engine_timer_count": (_i32, [_vp]),

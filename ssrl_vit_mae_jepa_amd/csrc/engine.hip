@@ -280,6 +280,7 @@ struct Ctx {
   int64_t as;
   void* const* ready = nullptr;  // hipEvent_t per gradient-ready point (entries may be null), or null
   bool fwd_only = false;         // no backward will follow (I-JEPA target encoder): the MLP saves no derivative
+  bool skip_final_norm = false;  // forward_encoder_impl stops after the last block: x_mid + branch_b is left for the caller
   const float* P(int i) const { return params + e->params[i].offset; }
   float* Gp(int i) const { return grads + e->params[i].offset; }
   // GEMM operand view of weight i: (out, in) row-major in the activation dtype
@@ -463,6 +464,7 @@ static int forward_encoder_impl(const Ctx& c, const Plan& pl, const void* images
   RUN(TK_DATA, 0, pl.Me * e->D * 12, launch_assemble_visible(c.buf<float>(pl.enc_x[0]), keep32, c.P(e->i_cls), c.P(e->i_pos), pl.Me, e->D, s));
   for (int i = 0; i < e->depth; ++i)
     MAE_TRY(block_forward(c, pl, e->enc[i], pl.enc[i], pl.Me, e->D, e->H, pl.B, pl.k, i ? pl.enc[i - 1].x_mid : 0, i > 0, pl.enc_x[i]));
+  if (c.skip_final_norm) return 0;
   RUN(TK_LN_FWD, 0, pl.Me * e->D * (8 + 2 * c.as), launch_layernorm_fwd(c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w), c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, c.act, c.buf<>(pl.enc_norm), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), s));
   if (x_encoded_out) {
     if (c.act == MAE_F32) MAE_HIP(hipMemcpyAsync(x_encoded_out, c.buf<>(pl.enc_norm), (size_t)pl.Me * e->D * 4, hipMemcpyDeviceToDevice, s));
@@ -1167,6 +1169,51 @@ extern "C" int mae_engine_classifier_loss_and_grads(mae_engine_t* e, const float
   return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
                          workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
                          "mae_engine_classifier_loss_and_grads");
+}
+
+// =====================================================================================================
+// Frozen-encoder features (scripts/evaluation/visualize_representation.py:87-108): the encoder over [cls | patches] or the
+// patches alone, forward only, with a token-sized decoder stub (the I-JEPA target phase's plan).  The encoder stops before
+// its final LayerNorm; k_representation.hip does that add + LayerNorm (fp32) + pool + L2 and writes only (batch, D).
+// =====================================================================================================
+extern "C" int64_t mae_engine_features_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls) {
+  if (!e || batch <= 0 || (with_cls != 0 && with_cls != 1) || e->D % 4 != 0 || e->D > 1024) return -1;  // the pool kernel's width limit
+  const int T = with_cls ? e->L : e->L - 1;
+  if ((int64_t)batch * e->L * std::max(3 * e->D, e->mlp * std::max(e->D, e->Dd)) >= (1ll << 40)) return -1;
+  return make_plan_ex(e, batch, T, 1, 1, 1).total;
+}
+
+extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                           int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, void* workspace,
+                                           int64_t workspace_bytes, float* feats, void* stream) {
+  const char* who = "mae_engine_extract_features";
+  MAE_REQUIRE(e, "%s: null engine", who);
+  MAE_REQUIRE(params && workspace && images && feats, "%s: null argument", who);
+  MAE_REQUIRE(e->act == MAE_F32 || wcache, "%s: bf16 engine needs the weight cache", who);
+  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+  MAE_REQUIRE(e->D % 4 == 0 && e->D <= 1024, "%s: embed_dim = %d must be a multiple of 4 and at most 1024", who, e->D);
+  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES, "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
+  MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
+  MAE_REQUIRE(normalize == MAE_FEAT_NONE || normalize == MAE_FEAT_L2, "%s: normalize must be MAE_FEAT_NONE or MAE_FEAT_L2 (got %d)", who, normalize);
+  MAE_TRY(check_image_dtype(image_dtype, who));
+  const int64_t need = mae_engine_features_workspace_bytes(e, batch, with_cls);
+  MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
+  MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
+  MAE_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)params & 15) == 0, "%s: workspace must be 256-byte aligned, params 16-byte", who);
+  const int T = with_cls ? e->L : e->L - 1;
+  const Plan pl = make_plan_ex(e, batch, T, 1, 1, 1);
+  hipStream_t s = (hipStream_t)stream;
+  Ctx c{e, params, (const char*)wcache, nullptr, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  c.fwd_only = true;
+  c.skip_final_norm = true;
+  if (with_cls) MAE_TRY(launch_iota_rows(c.buf<int32_t>(pl.keep32), batch, T, s));
+  else MAE_TRY(launch_iota_tokens(c.buf<int32_t>(pl.keep32), batch, T, s));
+  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
+  const int lo = pool == MAE_POOL_MEAN_PATCHES && with_cls ? 1 : 0, hi = pool == MAE_POOL_CLS ? 1 : T;
+  RUN(TK_LN_FWD, 0, (double)batch * (hi - lo) * e->D * (4 + c.as) + (double)batch * e->D * 4,
+      launch_features_pool(c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), e->act, c.P(e->i_norm_w), c.P(e->i_norm_b), 1e-6f,
+                           batch, T, e->D, lo, hi, normalize, feats, s));
+  return 0;
 }
 
 extern "C" int mae_engine_grad_sumsq_buffer(mae_engine_t* e, const float* grads, int64_t count, int32_t accumulate, float* sumsq_io,

@@ -90,6 +90,19 @@ int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* d
 // io[0] += sum(g^2) (io[1] is a temporary)
 int launch_grad_sumsq_accumulate(const float* g, int64_t n, float* io, float* scratch, hipStream_t s);
 
+// ---- k_representation.hip: frozen-encoder features and the k-NN probe -----------------------------------------------------
+// out[b] (fp32, D) = pool over rows [row_lo, row_hi) of LN(x_mid + branch) of image b (seq rows each), then f / (||f|| + 1e-8)
+// when normalize == MAE_FEAT_L2.  Reads only the pooled rows.
+int launch_features_pool(const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta, float eps, int B, int seq,
+                         int D, int row_lo, int row_hi, int normalize, float* out, hipStream_t s);
+// top-k of queries (Q, D) . bank (N, D)^T per query row: similarity descending, bank index ascending; -1 for bad arguments
+int knn_splits(int64_t Q, int64_t N, int k);
+int64_t knn_scratch_bytes(int64_t Q, int64_t N, int D, int k);
+int launch_knn_topk(const float* queries, int64_t Q, const float* bank, int64_t N, int D, int k, float* topk_sim, int64_t* topk_idx,
+                    void* scratch, int64_t scratch_bytes, hipStream_t s);
+int launch_knn_vote(const float* sim, const int64_t* idx, int64_t Q, int k_stride, int k, const int64_t* labels, int C, float T, float* scores,
+                    int64_t* pred, hipStream_t s);
+
 // ---- k_loss_optim.hip -----------------------------------------------------------------------------
 // loss[0] = mean((pred-target)^2); d_pred (dt, may be null) = grad_scale*2*(pred-target)/n.  scratch >= 1024+ floats
 int launch_mse(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,

@@ -237,6 +237,20 @@ class IJEPA(nn.Module):
         return (loss, h, pred) if return_aux else loss
 
     @torch.no_grad()
+    def extract_features(self, images: torch.Tensor, encoder: str = "target", pool: str = "mean", normalize: str = "none") -> torch.Tensor:
+        """Pooled features of the EMA target encoder (``encoder="target"``, what I-JEPA evaluates) or the context encoder:
+        (B, D) fp32 over the patch tokens, the only tokens the I-JEPA encoders were trained on.  pool "mean" (the only one:
+        there is no class token); normalize "none" | "l2"."""
+        if encoder not in ("target", "context"):
+            raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
+        if pool != "mean":
+            raise ValueError(f"I-JEPA encoders see no class token: pool must be 'mean', got {pool!r}")
+        net = self.net
+        if encoder == "target":
+            return net._extract(images, self.target_arena, self._target_weights(), pool, normalize, with_cls=False)
+        return net._extract(images, net.flat_params, net._weights(), pool, normalize, with_cls=False)
+
+    @torch.no_grad()
     def target_features(self, images: torch.Tensor, idx_target: torch.Tensor) -> torch.Tensor:
         """layer_norm(target_encoder(images))[target blocks]: (B, nblk, m, D) fp32 (no gradient, nothing else computed)."""
         net = self.net

@@ -96,6 +96,15 @@ class _ViT(_Node):
     def forward(self, images: torch.Tensor) -> torch.Tensor:
         return self.forward_features(images)
 
+    def extract_features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none", with_cls: bool = True) -> torch.Tensor:
+        """Pooled features of the frozen encoder: ``MaskedAutoencoder.extract_features``."""
+        return self._owner().extract_features(images, pool=pool, normalize=normalize, with_cls=with_cls)
+
+
+# extract_features pool names: "mean" averages the patch tokens (visualize_representation.py:94), "mean_all" every token (the classifier)
+FEATURE_POOLS = {"cls": _lib.POOL_CLS, "mean": _lib.POOL_MEAN_PATCHES, "mean_all": _lib.POOL_MEAN}
+FEATURE_NORMS = {"none": _lib.FEAT_NONE, "l2": _lib.FEAT_L2}
+
 
 class _Encoder(_Node):
     """lightly MaskedVisionTransformerTIMM surface used at src/models/mae.py:55."""
@@ -484,6 +493,40 @@ class MaskedAutoencoder(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._enc_params):
             return _EncoderFunction.apply(self, images, idx_keep, *self._enc_params)
         return self._run_encoder(images, idx_keep)
+
+    @torch.no_grad()
+    def extract_features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none", with_cls: bool = True) -> torch.Tensor:
+        """Pooled features of the encoder (scripts/evaluation/visualize_representation.py:87-108): (B, D) fp32, no autograd graph.
+        pool "cls" = the class-token row, "mean" = mean over the patch tokens, "mean_all" = mean over every token (the
+        classifier's "mean"); normalize "none" | "l2" (f / (||f|| + 1e-8)).  with_cls=False runs the encoder over the patch
+        tokens only, as the I-JEPA encoders see them ("cls" is then an error)."""
+        return self._extract(images, self._arena, self._weights(), pool, normalize, with_cls)
+
+    def _extract(self, images: torch.Tensor, params: torch.Tensor, wcache: Optional[torch.Tensor], pool: str, normalize: str,
+                 with_cls: bool) -> torch.Tensor:
+        if pool not in FEATURE_POOLS:
+            raise ValueError(f"pool must be one of {sorted(FEATURE_POOLS)}, got {pool!r}")
+        if normalize not in FEATURE_NORMS:
+            raise ValueError(f"normalize must be one of {sorted(FEATURE_NORMS)}, got {normalize!r}")
+        if pool == "cls" and not with_cls:
+            raise ValueError("pool='cls' needs the class token (with_cls=True)")
+        dev = self._require_cuda()
+        images = self._check_images(images.to(dev))
+        B = images.shape[0]
+        need = lib.mae_engine_features_workspace_bytes(self._engine.handle, B, int(bool(with_cls)))
+        if need < 0:
+            raise ValueError(f"bad batch {B}")
+        # the module's workspace is reused: whatever a pending backward saved in it is gone
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._plan = None
+        self._gen_enc += 1; self._gen_dec += 1
+        out = torch.empty(B, self._dims["embed_dim"], dtype=torch.float32, device=dev)
+        check(lib.mae_engine_extract_features(self._engine.handle, _ptr(params), _ptr(wcache), _ptr(images), self._img_dt(images), B,
+                                              int(bool(with_cls)), FEATURE_POOLS[pool], FEATURE_NORMS[normalize], _ptr(self._workspace),
+                                              self._workspace.numel(), _ptr(out), _stream(dev)))
+        return out
 
     def _run_decoder(self, x_encoded: torch.Tensor, idx_keep: torch.Tensor, idx_mask: torch.Tensor) -> torch.Tensor:
         dev = self._require_cuda()

@@ -1,0 +1,151 @@
+"""Timing of the representation-evaluation kernels, printed as one JSON document.
+
+  * feature extraction (mae_engine_extract_features) at B = 2000, bf16, pool cls and mean-over-patches, for the
+    configs/mae.yaml encoder and ViT-S/8 (configs/vits8_dec192.yaml), alternated in the same process with the classifier's
+    evaluation forward (mae_engine_classifier_forward), its yardstick;
+  * I-JEPA ViT-S/8 (configs/ijepa_vits8.yaml) target-encoder features, patch tokens only;
+  * mae_knn_topk at (Q, N, D, k) = (8000, 5000, 384, 20 / 200) and (8000, 100000, 384, 20), alternated with torch.mm +
+    torch.topk (a measurement-only baseline that materialises Q x N), with the achieved 2QND / t as a share of the
+    157.3 TF fp32-MFMA peak.
+Device events time `--steps` calls after `--warmup` calls; every number is the median of `--repeats` alternated runs.
+
+    python tools/representation_bench.py --out profiles/r05_representation_bench.json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import torch
+import yaml
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+from ssrl_vit_mae_jepa_amd.classifier import ViTClassifierTrainModule, encoder_mae  # noqa: E402
+from ssrl_vit_mae_jepa_amd.jepa import IJEPA  # noqa: E402
+from ssrl_vit_mae_jepa_amd.representation import knn_topk  # noqa: E402
+
+FP32_MFMA_PEAK_TF = 157.3
+
+
+def timed(fn, steps: int, warmup: int) -> float:
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def alternate(cases, steps, warmup, repeats):
+    runs = {}
+    for _r in range(repeats):
+        for key, fn in cases:
+            runs.setdefault(key, []).append(timed(fn, steps, warmup))
+    return {k: statistics.median(v) for k, v in runs.items()}, runs
+
+
+def model_cfg(cfg_path: Path) -> dict:
+    cfg = yaml.safe_load(cfg_path.read_text())
+    return dict(cfg["model"], general=dict(cfg["model"]["general"], engine_precision=cfg.get("engine", {}).get("precision", "bf16")))
+
+
+def bench_extraction(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repeats: int) -> dict:
+    mc = model_cfg(cfg_path)
+    dev = torch.device("cuda", 0)
+    mod = ViTClassifierTrainModule(pretrained_encoder=encoder_mae(mc).encoder.vit, model_cfg=mc, training_cfg={}).to(dev)
+    mod.freeze_encoder()
+    mae = mod.model.mae
+    S = mc["general"]["image_size"]
+    g = torch.Generator(device=dev).manual_seed(0)
+    images = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, device=dev, generator=g)
+
+    def evaluate():
+        with torch.no_grad():
+            mod.model.evaluate(images, None, logits=True)
+
+    cases = [("classifier_eval_forward", evaluate),
+             ("extract_cls", lambda: mae.extract_features(images, pool="cls")),
+             ("extract_mean_patches", lambda: mae.extract_features(images, pool="mean")),
+             ("extract_mean_patches_l2", lambda: mae.extract_features(images, pool="mean", normalize="l2"))]
+    ms, runs = alternate(cases, steps, warmup, repeats)
+    res = {"model": name, "config": str(cfg_path.relative_to(ROOT)), "batch": B, "precision": mae.engine.precision,
+           "ms": ms, "images_per_s": {k: B / (v / 1e3) for k, v in ms.items()}, "ms_all": runs}
+    del mod, mae
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_ijepa(B: int, steps: int, warmup: int, repeats: int) -> dict:
+    cfg_path = ROOT / "configs" / "ijepa_vits8.yaml"
+    mc = model_cfg(cfg_path)
+    dev = torch.device("cuda", 0)
+    model = IJEPA(mc["general"], mc["encoder"], mc["predictor"]).to(dev)
+    S = mc["general"]["image_size"]
+    images = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
+    ms, runs = alternate([("extract_target_mean", lambda: model.extract_features(images, encoder="target")),
+                          ("extract_context_mean", lambda: model.extract_features(images, encoder="context"))], steps, warmup, repeats)
+    res = {"model": "ijepa_vits8", "config": str(cfg_path.relative_to(ROOT)), "batch": B, "precision": model.net.engine.precision,
+           "ms": ms, "images_per_s": {k: B / (v / 1e3) for k, v in ms.items()}, "ms_all": runs}
+    del model
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_topk(Q: int, N: int, D: int, k: int, steps: int, warmup: int, repeats: int) -> dict:
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(2)
+    q = torch.nn.functional.normalize(torch.randn(Q, D, device=dev, generator=g), dim=1)
+    b = torch.nn.functional.normalize(torch.randn(N, D, device=dev, generator=g), dim=1)
+
+    def baseline():
+        torch.topk(torch.mm(q, b.T), k, dim=1)
+
+    ms, runs = alternate([("knn_topk", lambda: knn_topk(q, b, k)), ("torch_mm_topk", baseline)], steps, warmup, repeats)
+    flop = 2.0 * Q * N * D
+    res = {"Q": Q, "N": N, "D": D, "k": k, "ms": ms, "ms_all": runs,
+           "tflops": {key: flop / (v / 1e3) / 1e12 for key, v in ms.items()}}
+    res["share_of_fp32_mfma_peak"] = {key: t / FP32_MFMA_PEAK_TF for key, t in res["tflops"].items()}
+    del q, b
+    torch.cuda.empty_cache()
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--batch", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--parts", default="extract,ijepa,topk")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    torch.backends.cuda.matmul.allow_tf32 = False
+    parts = set(args.parts.split(","))
+    out = {"tool": "tools/representation_bench.py", "argv": sys.argv[1:] if argv is None else list(argv),
+           "device": torch.cuda.get_device_name(0), "extraction": [], "topk": []}
+    if "extract" in parts:
+        for name, path in (("yaml", ROOT / "configs" / "mae.yaml"), ("vits8", ROOT / "configs" / "vits8_dec192.yaml")):
+            out["extraction"].append(bench_extraction(name, path, args.batch, args.steps, args.warmup, args.repeats))
+    if "ijepa" in parts:
+        out["extraction"].append(bench_ijepa(args.batch, args.steps, args.warmup, args.repeats))
+    if "topk" in parts:
+        for shape in ((8000, 5000, 384, 20), (8000, 5000, 384, 200), (8000, 100_000, 384, 20)):
+            out["topk"].append(bench_topk(*shape, args.steps, args.warmup, args.repeats))
+    text = json.dumps(out, indent=1)
+    print(text)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
