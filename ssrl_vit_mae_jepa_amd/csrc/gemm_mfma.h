@@ -1,4 +1,4 @@
-// bf16 MFMA GEMM kernels (k_gemm_mfma.hip): entry points used by the dispatch in k_gemm.hip.
+// bf16 MFMA GEMM kernels (k_gemm_mfma.hip and the files named below): entry points used by the dispatch in k_gemm.hip.
 // Each returns MFMA_UNSUPPORTED when the shape is outside what the tiles assume; the caller then falls
 // back to the any-shape kernel.
 #pragma once
@@ -17,7 +17,7 @@ int mfma_linear_fwd_v2(const bf16* A, const bf16* W, int64_t M, int N, int K, co
 // round-3 K-loop on the same tiles (k_gemm_nt3.hip): NONE / GELU_GRAD / GELU_ACT / MUL epilogues, same shapes as v2
 int mfma_linear_fwd_v3(const bf16* A, const bf16* W, int64_t M, int N, int K, const Epi& epi, hipStream_t s);
 
-// dW[N,K] = dY[M,N]^T * A[M,K] (fp32, written)
+// weight gradient (k_gemm_tn.hip): dW[N,K] = dY[M,N]^T * A[M,K] (fp32, written)
 int64_t mfma_wgrad_scratch_bytes(int64_t M, int N, int K);
 // also db[N] = column sums of dY when db != null
 int mfma_linear_wgrad(const bf16* dY, const bf16* A, int64_t M, int N, int K, float* dW, float* db, void* slab, hipStream_t s);

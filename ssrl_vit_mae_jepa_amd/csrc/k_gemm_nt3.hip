@@ -26,7 +26,7 @@
 //   slices (880 ns in the probe, nothing in the kernel, and the summation order would depend on the column), an L2 prefetch of the NEXT tile's panel by 4-byte-per-lane DMAs (a whole tile ahead it thrashes
 //   L2 on the narrow-N shapes and costs as many tag lookups as half the pieces: 5-10 % slower), pieces spread over both halves of
 //   a step or issued by the two waves of a SIMD in different halves (2-5 % slower).
-#include "gemm_mfma.h"
+#include "gemm_dev.cuh"
 #include <cstdlib>
 #include <cstring>
 
@@ -34,7 +34,6 @@ namespace mae {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
 constexpr int BK3 = 64;
 // WM = waves along M (2 waves along N).  WM = 4: one 512-thread workgroup per CU (256- or 192-row tiles, all 160 KiB of LDS).
 // WM = 2: 256-thread workgroups, two per CU (128-row tiles, 80 KiB each): two independent wave groups share every SIMD, so one
@@ -151,41 +150,6 @@ __device__ __forceinline__ bf16x8 row_merge8(const bf16x8& keep, const bf16x8& f
   return __builtin_bit_cast(bf16x8, k);
 }
 
-// LDS-DMA pieces from inline asm (the compiler neither counts nor drains them: every wait below is ours).  M0 is written in
-// the statement that uses it.  Raw buffer addressing: byte offset = voff (per lane) + soff (scalar), range-checked against
-// the descriptor's num_records (out of range -> zeros, no fault).
-__device__ __forceinline__ void dma16(const i32x4& rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-// the same with the non-temporal cache policy (streamed-once rows: the lines are not kept in L2)
-__device__ __forceinline__ void dma16_nt(const i32x4& rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds" ::"s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma4(const i32x4& rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ i32x4 make_rsrc(const void* p, uint32_t bytes) {
-  const uint64_t a = (uint64_t)(uintptr_t)p;
-  return i32x4{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
-
-__device__ __forceinline__ int64_t xcd_remap3(int64_t bid, int64_t nb) {
-  const int64_t q = nb >> 3, r = nb & 7, xcd = bid & 7, loc = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-// Counted waits: vector-memory operations of a wave retire in issue order (LDS-DMA, loads and stores share one counter).
-// -DMAE_DBG_VMCNT0 drains every wait; tests/test_gpu_kernels.py compares the two builds bit for bit.
-template <int N>
-__device__ __forceinline__ void wait_vm3() {
-#ifdef MAE_DBG_VMCNT0
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#endif
-}
-
 template <int I0, int I1, int MI, int NI>
 __device__ __forceinline__ void mfma_range(f32x4 (&acc)[MI][NI], const bf16x8 (&a)[MI], const bf16x8 (&b)[NI]) {
 #pragma unroll
@@ -230,7 +194,7 @@ __global__ void __launch_bounds__((64 * Geo3<NI, MI, WM>::NWV), 2) gemm_nt3_kern
   constexpr int WROWS = 16 * MI;
   const int fr = lane & 15, fq = lane >> 4;
   const int G = gridDim.x, T = tiles_m * tiles_n;
-  const int vb = (int)xcd_remap3(blockIdx.x, G);
+  const int vb = (int)xcd_remap(blockIdx.x, G);
   const int ntile = (T - vb + G - 1) / G;
   const int nk = K / BK3;
   const uint32_t lds0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
@@ -459,7 +423,7 @@ __global__ void __launch_bounds__((64 * Geo3<NI, MI, WM>::NWV), 2) gemm_nt3_kern
   // next step's weight pieces first, the activation pieces of step + SA - 1 after them.  Phase 2: reads of half 1 beside the
   // MFMAs of half 0; the scalar bookkeeping of the next step sits in its shadow.
 #define NT3_STEP_TOP(NVM)                                                                                          \
-    wait_vm3<NVM>();                                                                                               \
+    wait_vm<NVM>();                                                                                                \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                             \
     __builtin_amdgcn_s_barrier();                                                                                  \
     __builtin_amdgcn_sched_barrier(0);                                                                             \

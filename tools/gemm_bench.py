@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the Linear GEMM kernels on the pretrain-step shapes (GPU box).  Interleaved A/B of the NT kernel
 variants in one process (MAE_GEMM_NT=v1|v2), random bf16 data, reports TFLOP/s and GB/s and checks the variants agree
-bit for bit.    python tools/gemm_bench.py [--rounds 5]"""
+bit for bit.    python tools/gemm_bench.py [--rounds 5]
+--wgrad does the same for the weight-gradient kernels (MAE_WGRAD=v1|v3r|v4|v4b), --wgrad-pair for the paired launch."""
 import argparse
 import os
 import sys
@@ -148,7 +149,7 @@ def main():
     ap.add_argument("--cold", action="store_true", help="evict the Infinity Cache before every timed launch (a 512 MiB fill), as inside a training step where the operand was written long before")
     ap.add_argument("--wgrad", action="store_true", help="time the weight-gradient GEMM (+ slab reduce) instead")
     ap.add_argument("--wgrad-pair", action="store_true", help="time the paired weight-gradient launch against the two launches it replaces")
-    ap.add_argument("--wgrad-variants", default="v2", help="comma list of MAE_WGRAD values to A/B (v1 | v2 | v2r | v3 | v3r)")
+    ap.add_argument("--wgrad-variants", default="v3r,v4,v4b", help="comma list of MAE_WGRAD values to A/B (v1 | v3r | v4 | v4b)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.wgrad_pair:
