@@ -1,5 +1,5 @@
-// Device helpers shared by the MFMA GEMM files (k_gemm_mfma.hip, k_gemm_mfma2.hip, k_gemm_nt3.hip, k_gemm_tn.hip): the block
-// remap, the counted wait, the transposed LDS read and the LDS-DMA issue forms.
+// Device helpers shared by the MFMA GEMM files (k_gemm_nt1.hip, k_gemm_nt2.hip, k_gemm_nt3.hip, k_gemm_tn.hip): the block
+// remap, the counted wait, the transposed LDS read, the LDS-DMA issue forms and the value pieces of the NT epilogues.
 #pragma once
 #include "gemm_mfma.h"
 
@@ -58,5 +58,53 @@ __device__ __forceinline__ i32x4 make_rsrc(const void* p, uint32_t bytes) {
   const uint64_t a = (uint64_t)(uintptr_t)p;
   return i32x4{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
 }
+
+// ---- pieces of the NT epilogues (k_gemm_nt1 / nt2 / nt3.hip).  The store forms are NOT here: they differ per kernel on purpose
+// (nt1 plain, nt2 non-temporal, nt3 buffer stores with a per-piece cache policy), each measured.
+
+// 8 consecutive outputs of one row as two f32x4: load (fp32 / bf16 side inputs), unpack and pack
+__device__ __forceinline__ void unpack8(const bf16x8& v, f32x4& a, f32x4& b) {
+  a = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+  b = f32x4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
+}
+__device__ __forceinline__ void ld8(const float* p, f32x4& a, f32x4& b) { a = load4(p); b = load4(p + 4); }
+__device__ __forceinline__ void ld8(const bf16* p, f32x4& a, f32x4& b) { unpack8(*reinterpret_cast<const bf16x8*>(p), a, b); }
+__device__ __forceinline__ bf16x8 pk8(const f32x4& a, const f32x4& b) {
+  return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
+}
+// the 16 bytes of the lane 8 places away inside its 16-lane row (DPP row_ror:8; lanes l and l ^ 8 swap)
+__device__ __forceinline__ bf16x8 row_swap8(const bf16x8& v) {
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_;
+  u32x4_ x = __builtin_bit_cast(u32x4_, v);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) x[i] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)x[i], 0x128, 0xf, 0xf, true);
+  return __builtin_bit_cast(bf16x8, x);
+}
+// v = the pre-activation as stored (rounded through the output type), a = fast GELU of it, g = its slope
+template <class TO>
+__device__ __forceinline__ void gelu_rounded(f32x4& v0, f32x4& v1, f32x4& a0, f32x4& a1, f32x4& g0, f32x4& g1) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    v0[r] = to_f(from_f<TO>(v0[r]));
+    v1[r] = to_f(from_f<TO>(v1[r]));
+  }
+  gelu_fast_pair(v0, a0, g0);
+  gelu_fast_pair(v1, a1, g1);
+}
+
+// After the MFMAs lane (fq, fr) holds, per 16x16 tile ni, 4 consecutive columns (4 fq ..) of row fr.  One v_permlane16_swap per
+// register pair (tiles 2j, 2j+1; lanes l <-> l+16) regroups that into 8 consecutive columns per lane: 16-byte bf16 stores, and
+// the 4 lanes of a row cover 64 contiguous bytes per store.  acc is f32x4[MI][NI].
+// A macro, not a function template: taking the accumulator array by reference changed the register allocation of 74 of the 84
+// gemm_nt3_kernel instantiations (instruction counts -76 .. +8) and of 64 of the 78 gemm_nt2_kernel ones; expanded in place the
+// three kernels compile to the instructions they had with the loop written out (profiles/r07_nt_refactor_isa.txt).
+#define MAE_REGROUP8(acc, MI, NI)                                                                                  \
+  _Pragma("unroll") for (int mi_ = 0; mi_ < (MI); ++mi_)                                                           \
+    _Pragma("unroll") for (int j_ = 0; j_ < (NI) / 2; ++j_)                                                        \
+      _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) {                                                           \
+        const auto sw_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[mi_][2 * j_][r_]), __float_as_uint(acc[mi_][2 * j_ + 1][r_]), false, false); \
+        acc[mi_][2 * j_][r_] = __uint_as_float(sw_[0]);                                                            \
+        acc[mi_][2 * j_ + 1][r_] = __uint_as_float(sw_[1]);                                                        \
+      }
 
 }  // namespace mae

@@ -1,11 +1,12 @@
 // GEMM family of the transformer blocks: Linear forward (NT), dgrad (NN), wgrad (TN) with fused epilogues.
 // This file holds (1) the exact-fp32 / any-layout tiled kernel used by the MAE_F32 parity path and as the
-// shape fallback, and (2) the dispatch to the bf16 MFMA kernels (k_gemm_mfma.hip) for the throughput path.
+// shape fallback, and (2) the dispatch to the bf16 MFMA kernels (k_gemm_nt1 / nt2 / nt3.hip, k_gemm_tn.hip) for the throughput path.
 // Reference behaviour: torch.nn.Linear inside timm Attention.qkv/.proj, Mlp.fc1/.fc2, lightly
 // decoder_embed/decoder_pred and the patch-embed conv viewed as a Linear over (c,py,px) patch vectors.
 #include "kernels.h"
 #include "gemm_mfma.h"
 #include <cstdlib>
+#include <cstring>
 
 namespace mae {
 
@@ -133,17 +134,37 @@ int num_cus() {
   return n;
 }
 
+bool prefer_bm192(int64_t M, int N, int margin_pct) {
+  static const int force = [] { const char* v = getenv("MAE_NT_BM"); return v ? atoi(v) : 0; }();
+  if (force == 192) return true;
+  if (force == 256) return false;
+  const int64_t t256 = cdiv(M, 256) * (N / 192), t192 = cdiv(M, 192) * (N / 192);
+  const int64_t c256 = cdiv(t256, num_cus()) * 256, c192 = cdiv(t192, num_cus()) * 192;
+  return c192 * 100 < c256 * margin_pct;
+}
+
+// MAE_GEMM_NT, read per call (tests and tools/gemm_bench.py flip it inside one process): the first NT kernel tried.  v1 pins the
+// per-tile kernel, v2 the 64-bit-pointer ring kernel, v3 is the default, v3w2 its two-workgroups-per-CU layouts.  Whole-string
+// match, anything else selects nothing (up to 59830e7 a prefix / substring was enough: "v1x" pinned v1, "v2w2" v2, "xw2" chose w2).
+struct NtSel { const char* text; int first; bool w2; };
+static const NtSel kNtSel[] = {{"v1", 1, false}, {"v2", 2, false}, {"v3", 3, false}, {"v3w2", 3, true}};
+static NtSel nt_sel() {
+  if (const char* v = getenv("MAE_GEMM_NT"))
+    for (const NtSel& n : kNtSel)
+      if (!strcmp(v, n.text)) return n;
+  return kNtSel[2];
+}
+
 int launch_linear_fwd(const void* A, const void* W, int64_t M, int N, int K, int dt, const Epi& e, hipStream_t s) {
   MAE_REQUIRE(A && W && M > 0 && N > 0 && K > 0, "linear_fwd: bad arguments");
   MAE_TRY(check_epi(e, dt, "linear_fwd"));
   if (dt == MAE_BF16) {
-    const char* var = getenv("MAE_GEMM_NT");  // "v1" pins the per-tile kernel, "v2" round 2's ring kernel (A/B runs in tools/gemm_bench.py)
-    const bool pin = var && var[0] == 'v' && (var[1] == '1' || var[1] == '2');
-    if (!pin) {   // round 3's K-loop (k_gemm_nt3.hip) wherever it applies; v2 keeps the epilogues the engine does not use
-      const int r3 = mfma_linear_fwd_v3((const bf16*)A, (const bf16*)W, M, N, K, e, s);
+    const NtSel sel = nt_sel();
+    if (sel.first == 3) {   // the production K-loop wherever it applies
+      const int r3 = mfma_linear_fwd_v3((const bf16*)A, (const bf16*)W, M, N, K, e, sel.w2, s);
       if (r3 != MFMA_UNSUPPORTED) return r3;
     }
-    if (!(var && var[0] == 'v' && var[1] == '1')) {
+    if (sel.first >= 2) {   // v2 keeps the epilogues the engine does not use
       const int r2 = mfma_linear_fwd_v2((const bf16*)A, (const bf16*)W, M, N, K, e, s);
       if (r2 != MFMA_UNSUPPORTED) return r2;
     }

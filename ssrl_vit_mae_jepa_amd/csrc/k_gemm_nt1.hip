@@ -1,11 +1,12 @@
-// bf16 MFMA GEMMs for gfx950 (v_mfma_f32_16x16x32_bf16, fp32 accumulate), fused epilogues.
+// Per-tile bf16 MFMA NT GEMM for gfx950 (v_mfma_f32_16x16x32_bf16, fp32 accumulate), fused epilogues: v1, the path of ragged and
+// tiny shapes.
 //
 //  gemm_nt_kernel   out[M,N] = A[M,K] * W[N,K]^T      Linear forward, and dgrad via the transposed weight copy.
 //                   Block tile 128 x (64|128) x 64, 4 waves (2x2), register-staged global->LDS with an XOR
 //                   swizzle (conflict-free ds_read_b128 fragments), double-buffered LDS, one barrier per K step.
 //                   Operands are passed to the MFMA swapped (W as A-operand) so every lane ends up with 4
 //                   consecutive output columns of one row: 8-byte (bf16) / 16-byte (fp32) epilogue stores.
-//  The weight gradients (dW = dY^T X) are in k_gemm_tn.hip, the persistent LDS-DMA NT kernels in k_gemm_mfma2.hip / k_gemm_nt3.hip.
+//  The weight gradients (dW = dY^T X) are in k_gemm_tn.hip, the persistent LDS-DMA NT kernels in k_gemm_nt2.hip / k_gemm_nt3.hip.
 //
 // M here is batch*tokens (72 000 .. 290 000), N/K are 192..1536: every GEMM is short-K and output-bound
 // (arithmetic intensity ~ the bf16 ridge), so the epilogue stores and the A-panel L2 reuse matter as much as the
@@ -15,15 +16,7 @@
 namespace mae {
 
 __device__ __forceinline__ void store8(float* p, const f32x4& a, const f32x4& b) { store4(p, a); store4(p + 4, b); }
-__device__ __forceinline__ void store8(bf16* p, const f32x4& a, const f32x4& b) {
-  *reinterpret_cast<bf16x8*>(p) = bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-}
-__device__ __forceinline__ void load8(const float* p, f32x4& a, f32x4& b) { a = load4(p); b = load4(p + 4); }
-__device__ __forceinline__ void load8(const bf16* p, f32x4& a, f32x4& b) {
-  const bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
-  a = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-  b = f32x4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
-}
+__device__ __forceinline__ void store8(bf16* p, const f32x4& a, const f32x4& b) { *reinterpret_cast<bf16x8*>(p) = pk8(a, b); }
 
 struct EpiArgs {
   const float* bias;
@@ -123,19 +116,8 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const bf16* __restrict_
     }
   }
 
-  // epilogue.  After the MFMAs lane (fq, fr) holds, per 16x16 tile ni, 4 consecutive columns (4 fq ..) of row fr.
-  // One v_permlane16_swap per register pair (tiles 2j, 2j+1; lanes l <-> l+16) regroups that into 8 consecutive
-  // columns per lane: 16-byte bf16 stores, and the 4 lanes of a row cover 64 contiguous bytes per store.
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int j = 0; j < NI / 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[mi][2 * j][r]), __float_as_uint(acc[mi][2 * j + 1][r]), false, false);
-        acc[mi][2 * j][r] = __uint_as_float(sw[0]);
-        acc[mi][2 * j + 1][r] = __uint_as_float(sw[1]);
-      }
+  // epilogue: 8 consecutive columns per lane (gemm_dev.cuh)
+  MAE_REGROUP8(acc, 4, NI)
   const int gb = (fq & 1) ? 3 + fq : fq;  // 4-column group of this lane inside a 32-column half: {0,4,2,6}[fq]
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
@@ -167,7 +149,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const bf16* __restrict_
         store8(reinterpret_cast<TO*>(ep.out) + o, v0, v1);
       } else if (MODE == MAE_EPI_DGELU) {
         f32x4 p0, p1;
-        load8(reinterpret_cast<const TO*>(ep.aux) + o, p0, p1);
+        ld8(reinterpret_cast<const TO*>(ep.aux) + o, p0, p1);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           v0[r] *= gelu_grad_fast(p0[r]);
@@ -193,7 +175,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const bf16* __restrict_
         store8(reinterpret_cast<TO*>(ep.out) + o, a0, a1);
       } else {  // MAE_EPI_MUL
         f32x4 p0, p1;
-        load8(reinterpret_cast<const TO*>(ep.aux) + o, p0, p1);
+        ld8(reinterpret_cast<const TO*>(ep.aux) + o, p0, p1);
         store8(reinterpret_cast<TO*>(ep.out) + o, v0 * p0, v1 * p1);
       }
     }
@@ -226,17 +208,9 @@ int mfma_linear_fwd(const bf16* A, const bf16* W, int64_t M, int N, int K, const
   if (K % 8 != 0 || N % 8 != 0 || K < 32 || N < 16 || M < 1) return MFMA_UNSUPPORTED;
   if ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)e.out | (uintptr_t)e.out2 | (uintptr_t)e.aux | (uintptr_t)e.bias) & 15) != 0)
     return MFMA_UNSUPPORTED;
-  const bool f32out = e.out_dt == MAE_F32;
-  switch (e.mode) {
-    case MAE_EPI_NONE: return f32out ? launch_nt_ni<MAE_EPI_NONE, float>(A, W, M, N, K, e, s) : launch_nt_ni<MAE_EPI_NONE, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_GELU: return f32out ? launch_nt_ni<MAE_EPI_GELU, float>(A, W, M, N, K, e, s) : launch_nt_ni<MAE_EPI_GELU, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_RESID: return f32out ? launch_nt_ni<MAE_EPI_RESID, float>(A, W, M, N, K, e, s) : MFMA_UNSUPPORTED;
-    case MAE_EPI_DGELU: return f32out ? launch_nt_ni<MAE_EPI_DGELU, float>(A, W, M, N, K, e, s) : launch_nt_ni<MAE_EPI_DGELU, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_GELU_GRAD: return f32out ? launch_nt_ni<MAE_EPI_GELU_GRAD, float>(A, W, M, N, K, e, s) : launch_nt_ni<MAE_EPI_GELU_GRAD, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_MUL: return f32out ? launch_nt_ni<MAE_EPI_MUL, float>(A, W, M, N, K, e, s) : launch_nt_ni<MAE_EPI_MUL, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_GELU_ACT: return f32out ? launch_nt_ni<MAE_EPI_GELU_ACT, float>(A, W, M, N, K, e, s) : launch_nt_ni<MAE_EPI_GELU_ACT, bf16>(A, W, M, N, K, e, s);
-    default: return MFMA_UNSUPPORTED;
-  }
+  return dispatch_epi<EpiAll>(e, [&](auto mode, auto to) {
+    return launch_nt_ni<decltype(mode)::value, typename decltype(to)::type>(A, W, M, N, K, e, s);
+  });
 }
 
 }  // namespace mae

@@ -1,6 +1,11 @@
 // Persistent bf16 MFMA NT GEMM for gfx950 with an LDS-DMA ring (v2 of gemm_nt_kernel).
 //
-//   out[M,N] = A[M,K] * W[N,K]^T (+bias) with the NONE / GELU epilogues, M = batch*tokens (huge), K = 192..1536.
+//   out[M,N] = A[M,K] * W[N,K]^T (+bias) with every Epi epilogue, M = batch*tokens (huge), K = 192..1536.
+//
+// Since gemm_nt3_kernel (k_gemm_nt3.hip) this kernel is off the training path: it serves the epilogues the engine does not issue
+// (GELU, RESID, DGELU, and GELU_GRAD / GELU_ACT / MUL with fp32 outputs) and, with its 64-bit pointers, it is the independent
+// reference the tests compare nt3's 32-bit buffer offsets with, bit for bit.  Its round-2 phase and epilogue ablation builds went
+// with that (results: profiles/r01_nt2_phase_ablation.txt, profiles/r02_nt2_epilogue_ablation.txt).
 //
 // Why: with K = 384 a 128x128 tile lives for only 6 K-steps, so a one-tile register prefetch leaves every CU waiting
 // on memory latency (v1 measured ~5 TB/s of L2->CU traffic, 0.3-0.7 PF).  Here one 512-thread workgroup per CU walks a
@@ -16,7 +21,6 @@
 //     epilogue needs no ordinary global load (hipcc drains the DMA queue with vmcnt(0) before using one).
 //   * blocks are XCD-remapped so the 32 CUs of an XCD work on adjacent tiles (shared A panels / W tiles in L2).
 #include "gemm_dev.cuh"
-#include <cstdlib>
 
 namespace mae {
 
@@ -41,38 +45,14 @@ struct Geo {
   static_assert((BM + BN) % 64 == 0, "DMA groups must divide evenly over the 8 waves");
 };
 
-__device__ __forceinline__ void ld8(const float* p, f32x4& a, f32x4& b) { a = load4(p); b = load4(p + 4); }
-__device__ __forceinline__ void unpack8(const bf16x8& v, f32x4& a, f32x4& b) {
-  a = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-  b = f32x4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
-}
-__device__ __forceinline__ void ld8(const bf16* p, f32x4& a, f32x4& b) { unpack8(*reinterpret_cast<const bf16x8*>(p), a, b); }
 // Outputs are written once and read by a LATER kernel: non-temporal stores stream them to HBM instead of parking the
 // lines in L2 until eviction, which both frees L2 for the A / W re-reads and spreads the write traffic over the tile loop
 // (measured: fc1 + GELU forward 220 -> 170 us, decoder fc1 332 -> 242 us).
 // (a per-launch runtime choice between the two store forms was tried: the uniform branch per store cost 1.1 ms per step)
-#ifdef MAE_DBG_EPI_PLAINSTORE
-template <class V> __device__ __forceinline__ void stream_store(V v, V* p) { *p = v; }
-#else
 template <class V> __device__ __forceinline__ void stream_store(V v, V* p) { __builtin_nontemporal_store(v, p); }
-#endif
-__device__ __forceinline__ void st8(float* p, const f32x4& a, const f32x4& b) {
+__device__ __forceinline__ void st8(float* p, const f32x4& a, const f32x4& b) {   // (bf16 outputs: whole-line stores in the kernel)
   stream_store(a, reinterpret_cast<f32x4*>(p));
   stream_store(b, reinterpret_cast<f32x4*>(p + 4));
-}
-__device__ __forceinline__ void st8(bf16* p, const f32x4& a, const f32x4& b) {
-  stream_store(bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]}, reinterpret_cast<bf16x8*>(p));
-}
-__device__ __forceinline__ bf16x8 pk8(const f32x4& a, const f32x4& b) {
-  return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-}
-// the 16 bytes of the lane 8 places away inside its 16-lane row (DPP row_ror:8; lanes l and l ^ 8 swap)
-__device__ __forceinline__ bf16x8 row_swap8(const bf16x8& v) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_;
-  u32x4_ x = __builtin_bit_cast(u32x4_, v);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)x[i], 0x128, 0xf, 0xf, true);
-  return __builtin_bit_cast(bf16x8, x);
 }
 // The counted waits (wait_vm<N>, gemm_dev.cuh) take E = the number of store instructions the compiler emits per wave and tile;
 // the MAE_DBG_VMCNT0 build checks that count.
@@ -128,9 +108,6 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
     if (HAS_BIAS) pbias = bias + n0 + lane;
   };
   auto issue = [&]() {
-#ifdef MAE_DBG_NO_DMA
-    return;
-#endif
     char* dst = smem + is_stage * STAGE + wave * (GPW * 1024);
     const int ko = is_k * BK2;
     glds16(p0 + ko, dst);
@@ -174,10 +151,6 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
     //      = the next AHEAD-1 steps' DMAs (+ the bias DMAs when that step opens a tile)
     //        (+ the previous tile's epilogue stores, when that tile was full so every store was issued)
     const bool after_epi = ct > 0 && prev_full && ck < AHEAD;
-#ifdef MAE_DBG_NO_DMA
-    if (false) {
-    } else
-#endif
     if (AHEAD == 2) {
       if (step + 1 >= nsteps) wait_vm<0>();
       else if (ck == nk - 1) wait_vm<GPW + NB>();   // the next step is a tile's first: it carried the bias DMAs
@@ -205,7 +178,6 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
     const char* a_base = smem + cs * STAGE + (wm * WROWS + fr) * 128;
     const char* b_base = smem + cs * STAGE + BM2 * 128 + (wn * (NI * 16) + fr) * 128;
     // fragments of both 32-deep halves are read up front, the DMA refill is issued between the two read bursts
-#ifndef MAE_DBG_NO_MFMA
     bf16x8 af[2][MI], bfr[2][NI];
     const int sw0 = ((0 + fq) ^ (fr & 7)) << 4, sw1 = ((4 + fq) ^ (fr & 7)) << 4;
 #pragma unroll
@@ -224,29 +196,15 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ks][ni], af[ks][mi], acc[mi][ni], 0, 0, 0);
-#else
-    if (step + AHEAD < nsteps) issue();
-#endif
     cs = cs == NSTAGE - 1 ? 0 : cs + 1;
 
     if (++ck == nk) {
-      // ---- epilogue of tile `ct`: regroup to 8 consecutive columns per lane (see gemm_nt_kernel), store
+      // ---- epilogue of tile `ct`: regroup to 8 consecutive columns per lane (gemm_dev.cuh), store
       const int t = vb + ct * G;
       const int64_t m0 = (int64_t)(t / tiles_n) * BM2;
       const int n0 = (t % tiles_n) * BN;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int j = 0; j < NI / 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[mi][2 * j][r]), __float_as_uint(acc[mi][2 * j + 1][r]), false, false);
-            acc[mi][2 * j][r] = __uint_as_float(sw[0]);
-            acc[mi][2 * j + 1][r] = __uint_as_float(sw[1]);
-          }
+      MAE_REGROUP8(acc, MI, NI)
       const float* sbias = reinterpret_cast<const float*>(smem + G_::BIAS_OFF + (ct & 1) * (BN * 4)) + wn * (NI * 16);
-#if !defined(MAE_DBG_NT_HALF_LINES) && !defined(MAE_DBG_NO_EPI) && !defined(MAE_DBG_EPI_NOGELU) && \
-    !defined(MAE_DBG_EPI_NOSTORE) && !defined(MAE_DBG_EPI_ONESTORE)
       if constexpr (sizeof(TO) == 2) {
         // bf16 outputs, WHOLE-LINE stores.  A lane holds 8 consecutive columns (16 B) of one row and the 4 lanes of a row 64 B:
         // written unit by unit, every store instruction covers 16 rows x half a line, and the other half of each line arrives
@@ -272,24 +230,14 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
             if (HAS_BIAS) { b0 = load4(sbias + nl); b1 = load4(sbias + nl + 4); }
             f32x4 v0 = acc[mi][2 * j] + b0, v1 = acc[mi][2 * j + 1] + b1;
             if (MODE == MAE_EPI_GELU || MODE == MAE_EPI_GELU_GRAD || MODE == MAE_EPI_GELU_ACT) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                v0[r] = to_f(from_f<TO>(v0[r]));
-                v1[r] = to_f(from_f<TO>(v1[r]));
-              }
               f32x4 a0, a1, g0, g1;
-              gelu_fast_pair(v0, a0, g0);
-              gelu_fast_pair(v1, a1, g1);
+              gelu_rounded<TO>(v0, v1, a0, a1, g0, g1);
               if (MODE == MAE_EPI_GELU) { pa[j] = pk8(v0, v1); pb[TWO ? j : 0] = pk8(a0, a1); }
               else if (MODE == MAE_EPI_GELU_GRAD) { pa[j] = pk8(g0, g1); pb[TWO ? j : 0] = pk8(a0, a1); }
               else pa[j] = pk8(a0, a1);
-            } else if (MODE == MAE_EPI_DGELU || MODE == MAE_EPI_MUL) {
+            } else if (PREF) {   // DGELU / MUL: the side input fetched during the last K-step
               f32x4 q0, q1;
-              if (PREF) unpack8(qa[PREF ? j : 0][PREF ? mi : 0], q0, q1);
-              else {
-                const int64_t mc = m < M ? m : M - 1;
-                ld8(reinterpret_cast<const TO*>(aux) + mc * N + colw + 32 * j, q0, q1);
-              }
+              unpack8(qa[PREF ? j : 0][PREF ? mi : 0], q0, q1);
               if (MODE == MAE_EPI_DGELU) { f32x4 a_, g_; gelu_fast_pair(q0, a_, g_); v0 *= g_; gelu_fast_pair(q1, a_, g_); v1 *= g_; }
               else { v0 *= q0; v1 *= q1; }
               pa[j] = pk8(v0, v1);
@@ -322,86 +270,42 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
             if (TWO) { store_single(out2, pb[0], 0); store_rows(out2, pb, TWO ? NJ - 2 : 0); }
           }
         }
-      } else
-#endif
+      } else {
+        // fp32 outputs only (bf16 ones took the branch above): PREF is false here, so the side input is read where it is used
 #pragma unroll
-      for (int j = 0; j < NI / 2; ++j) {
-        const int nl = 32 * j + 4 * gb;  // column inside the wave's NI*16
-        f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
-        if (HAS_BIAS) { b0 = load4(sbias + nl); b1 = load4(sbias + nl + 4); }
+        for (int j = 0; j < NI / 2; ++j) {
+          const int nl = 32 * j + 4 * gb;  // column inside the wave's NI*16
+          f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
+          if (HAS_BIAS) { b0 = load4(sbias + nl); b1 = load4(sbias + nl + 4); }
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          const int64_t m = m0 + wm * WROWS + mi * 16 + fr;
-#ifdef MAE_DBG_NO_EPI
-          if (m < M && acc[mi][2 * j][0] == 1.2345e30f) {
-#else
-          if (m < M) {
-#endif
-            const int64_t o = m * N + n0 + wn * (NI * 16) + nl;
-            f32x4 v0 = acc[mi][2 * j] + b0, v1 = acc[mi][2 * j + 1] + b1;
-            if (MODE == MAE_EPI_GELU) {
-              f32x4 a0, a1;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                v0[r] = to_f(from_f<TO>(v0[r]));
-                v1[r] = to_f(from_f<TO>(v1[r]));
+          for (int mi = 0; mi < MI; ++mi) {
+            const int64_t m = m0 + wm * WROWS + mi * 16 + fr;
+            if (m < M) {
+              const int64_t o = m * N + n0 + wn * (NI * 16) + nl;
+              f32x4 v0 = acc[mi][2 * j] + b0, v1 = acc[mi][2 * j + 1] + b1;
+              if (MODE == MAE_EPI_GELU || MODE == MAE_EPI_GELU_GRAD || MODE == MAE_EPI_GELU_ACT) {
+                f32x4 a0, a1, g0, g1;
+                gelu_rounded<TO>(v0, v1, a0, a1, g0, g1);
+                if (MODE == MAE_EPI_GELU) { st8(out + o, v0, v1); st8(out2 + o, a0, a1); }
+                else if (MODE == MAE_EPI_GELU_GRAD) { st8(out + o, g0, g1); st8(out2 + o, a0, a1); }
+                else st8(out + o, a0, a1);
+              } else if (MODE == MAE_EPI_RESID) {
+                v0 += load4(reinterpret_cast<const float*>(aux) + o);
+                v1 += load4(reinterpret_cast<const float*>(aux) + o + 4);
+                st8(out + o, v0, v1);
+              } else if (MODE == MAE_EPI_DGELU || MODE == MAE_EPI_MUL) {
+                f32x4 q0, q1;
+                ld8(reinterpret_cast<const TO*>(aux) + o, q0, q1);
+                if (MODE == MAE_EPI_DGELU) { f32x4 a_, g_; gelu_fast_pair(q0, a_, g_); v0 *= g_; gelu_fast_pair(q1, a_, g_); v1 *= g_; }
+                else { v0 *= q0; v1 *= q1; }
+                st8(out + o, v0, v1);
+              } else {
+                st8(out + o, v0, v1);
               }
-              { f32x4 g_; gelu_fast_pair(v0, a0, g_); gelu_fast_pair(v1, a1, g_); }
-              st8(out + o, v0, v1);
-              st8(out2 + o, a0, a1);
-            } else if (MODE == MAE_EPI_RESID) {
-              v0 += load4(reinterpret_cast<const float*>(aux) + o);
-              v1 += load4(reinterpret_cast<const float*>(aux) + o + 4);
-              st8(out + o, v0, v1);
-            } else if (MODE == MAE_EPI_DGELU) {
-              f32x4 q0, q1;
-              if (PREF) unpack8(qa[PREF ? j : 0][PREF ? mi : 0], q0, q1);
-              else ld8(reinterpret_cast<const TO*>(aux) + o, q0, q1);
-              { f32x4 a_, g_; gelu_fast_pair(q0, a_, g_); v0 *= g_; gelu_fast_pair(q1, a_, g_); v1 *= g_; }
-              st8(out + o, v0, v1);
-            } else if (MODE == MAE_EPI_GELU_GRAD) {
-              f32x4 a0, a1, g0, g1;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                v0[r] = to_f(from_f<TO>(v0[r]));
-                v1[r] = to_f(from_f<TO>(v1[r]));
-              }
-#if defined(MAE_DBG_EPI_NOGELU)   // epilogue ablation builds (tools/run_epi_ablation.sh): timing probes, wrong values
-              a0 = v0; a1 = v1; g0 = v0 * 0.5f; g1 = v1 * 0.5f;
-#else
-              gelu_fast_pair(v0, a0, g0);
-              gelu_fast_pair(v1, a1, g1);
-#endif
-#if defined(MAE_DBG_EPI_NOSTORE)
-              asm volatile("" ::"v"(g0), "v"(g1), "v"(a0), "v"(a1));
-#elif defined(MAE_DBG_EPI_ONESTORE)
-              asm volatile("" ::"v"(g0), "v"(g1));
-              st8(out2 + o, a0, a1);
-#else
-              st8(out + o, g0, g1);
-              st8(out2 + o, a0, a1);
-#endif
-            } else if (MODE == MAE_EPI_GELU_ACT) {
-              f32x4 a0, a1, g_;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                v0[r] = to_f(from_f<TO>(v0[r]));
-                v1[r] = to_f(from_f<TO>(v1[r]));
-              }
-              gelu_fast_pair(v0, a0, g_);
-              gelu_fast_pair(v1, a1, g_);
-              st8(out + o, a0, a1);
-            } else if (MODE == MAE_EPI_MUL) {
-              f32x4 q0, q1;
-              if (PREF) unpack8(qa[PREF ? j : 0][PREF ? mi : 0], q0, q1);
-              else ld8(reinterpret_cast<const TO*>(aux) + o, q0, q1);
-              st8(out + o, v0 * q0, v1 * q1);
-            } else {
-              st8(out + o, v0, v1);
             }
+            acc[mi][2 * j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            acc[mi][2 * j + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
           }
-          acc[mi][2 * j] = f32x4{0.f, 0.f, 0.f, 0.f};
-          acc[mi][2 * j + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
       }
       prev_full = m0 + BM2 <= M;
@@ -418,35 +322,15 @@ static int launch_nt2(const bf16* A, const bf16* W, int64_t M, int N, int K, con
   MAE_REQUIRE(T < (1ll << 30), "gemm: too many tiles");
   const int tiles_m = (int)cdiv(M, G_::BM), tiles_n = N / G_::BN;
   const int grid = (int)std::min<int64_t>(T, num_cus());  // one persistent workgroup per CU
-  if (e.bias) {
-    auto kern = gemm_nt2_kernel<MODE, TO, true, NI, MI>;
-    MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), G_::LDS, s, A, W, M, N, K, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, tiles_m, tiles_n);
-  } else {
-    auto kern = gemm_nt2_kernel<MODE, TO, false, NI, MI>;
-    MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), G_::LDS, s, A, W, M, N, K, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, tiles_m, tiles_n);
-  }
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
-// rounds of tiles on the 256 CUs x rows per tile = time proxy; the 192-row tile must win by a margin because it stages
-// 15 % more operand bytes per flop
-static bool prefer_bm192(int64_t M, int N) {
-  static const int force = [] { const char* v = getenv("MAE_NT_BM"); return v ? atoi(v) : 0; }();
-  if (force == 192) return true;
-  if (force == 256) return false;
-  const int64_t t256 = cdiv(M, 256) * (N / 192), t192 = cdiv(M, 192) * (N / 192);
-  const int64_t c256 = cdiv(t256, num_cus()) * 256, c192 = cdiv(t192, num_cus()) * 192;
-  return c192 * 100 < c256 * 95;  // measured: 192-row tiles win whenever they save a round (decoder fc2 130 vs 143 us, pred head 69 vs 79 us)
+  return launch_bias_pair(e.bias != nullptr, gemm_nt2_kernel<MODE, TO, true, NI, MI>, gemm_nt2_kernel<MODE, TO, false, NI, MI>, grid, 512, G_::LDS, s, A, W, M,
+                          N, K, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, tiles_m, tiles_n);
 }
 
 template <int MODE, class TO>
 static int launch_nt2_ni(const bf16* A, const bf16* W, int64_t M, int N, int K, const Epi& e, hipStream_t s) {
-  static const bool force_ni4 = [] { const char* v = getenv("MAE_NT_NI"); return v && atoi(v) == 4; }();
-  if (N % 192 == 0 && !(force_ni4 && N % 128 == 0)) {
-    if (prefer_bm192(M, N)) return launch_nt2<MODE, TO, 6, 3>(A, W, M, N, K, e, s);
+  if (N % 192 == 0) {
+    // measured: 192-row tiles win whenever they save a round (decoder fc2 130 vs 143 us, pred head 69 vs 79 us)
+    if (prefer_bm192(M, N, 95)) return launch_nt2<MODE, TO, 6, 3>(A, W, M, N, K, e, s);
     return launch_nt2<MODE, TO, 6, 4>(A, W, M, N, K, e, s);
   }
   return launch_nt2<MODE, TO, 4, 4>(A, W, M, N, K, e, s);
@@ -455,17 +339,9 @@ static int launch_nt2_ni(const bf16* A, const bf16* W, int64_t M, int N, int K, 
 int mfma_linear_fwd_v2(const bf16* A, const bf16* W, int64_t M, int N, int K, const Epi& e, hipStream_t s) {
   if (K % 64 != 0 || K < 192 || (N % 128 != 0 && N % 192 != 0) || M < 1) return MFMA_UNSUPPORTED;
   if ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)e.out | (uintptr_t)e.out2 | (uintptr_t)e.bias | (uintptr_t)e.aux) & 15) != 0) return MFMA_UNSUPPORTED;
-  const bool f32out = e.out_dt == MAE_F32;
-  switch (e.mode) {
-    case MAE_EPI_NONE: return f32out ? launch_nt2_ni<MAE_EPI_NONE, float>(A, W, M, N, K, e, s) : launch_nt2_ni<MAE_EPI_NONE, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_GELU: return f32out ? launch_nt2_ni<MAE_EPI_GELU, float>(A, W, M, N, K, e, s) : launch_nt2_ni<MAE_EPI_GELU, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_RESID: return f32out ? launch_nt2_ni<MAE_EPI_RESID, float>(A, W, M, N, K, e, s) : MFMA_UNSUPPORTED;
-    case MAE_EPI_DGELU: return f32out ? launch_nt2_ni<MAE_EPI_DGELU, float>(A, W, M, N, K, e, s) : launch_nt2_ni<MAE_EPI_DGELU, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_GELU_GRAD: return f32out ? launch_nt2_ni<MAE_EPI_GELU_GRAD, float>(A, W, M, N, K, e, s) : launch_nt2_ni<MAE_EPI_GELU_GRAD, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_MUL: return f32out ? launch_nt2_ni<MAE_EPI_MUL, float>(A, W, M, N, K, e, s) : launch_nt2_ni<MAE_EPI_MUL, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_GELU_ACT: return f32out ? launch_nt2_ni<MAE_EPI_GELU_ACT, float>(A, W, M, N, K, e, s) : launch_nt2_ni<MAE_EPI_GELU_ACT, bf16>(A, W, M, N, K, e, s);
-    default: return MFMA_UNSUPPORTED;
-  }
+  return dispatch_epi<EpiAll>(e, [&](auto mode, auto to) {
+    return launch_nt2_ni<decltype(mode)::value, typename decltype(to)::type>(A, W, M, N, K, e, s);
+  });
 }
 
 }  // namespace mae

@@ -28,7 +28,6 @@
 //   a step or issued by the two waves of a SIMD in different halves (2-5 % slower).
 #include "gemm_dev.cuh"
 #include <cstdlib>
-#include <cstring>
 
 namespace mae {
 
@@ -59,12 +58,6 @@ struct Geo3 {
   static_assert(SA >= 2 && LDS <= CAP && BM % (8 * NWV) == 0 && BN % (8 * NWV) == 0, "LDS budget / even deal of the pieces over the waves");
 };
 
-__device__ __forceinline__ void unpack8(const bf16x8& v, f32x4& a, f32x4& b) {
-  a = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-  b = f32x4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
-}
-__device__ __forceinline__ void ld8(const float* p, f32x4& a, f32x4& b) { a = load4(p); b = load4(p + 4); }
-__device__ __forceinline__ void ld8(const bf16* p, f32x4& a, f32x4& b) { unpack8(*reinterpret_cast<const bf16x8*>(p), a, b); }
 // Outputs are written once and read by a LATER kernel: non-temporal stores (see gemm_nt2_kernel).  -DMAE_NT3_STORE=1 / 2 / 3 build
 // the plain / sc1 / sc0 sc1 forms for A/B runs of the whole step (profiles/r03_nt3_kloop.txt).
 #ifndef MAE_NT3_STORE
@@ -107,18 +100,7 @@ __device__ __forceinline__ void st8(float* p, const f32x4& a, const f32x4& b) {
   part_store(b, reinterpret_cast<f32x4*>(p + 4));
 #endif
 }
-__device__ __forceinline__ bf16x8 pk8(const f32x4& a, const f32x4& b) {
-  return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-}
 __device__ __forceinline__ void st8(bf16* p, const f32x4& a, const f32x4& b) { stream_store(pk8(a, b), reinterpret_cast<bf16x8*>(p)); }
-// the 16 bytes of the lane 8 places away inside its 16-lane row (DPP row_ror:8; lanes l and l ^ 8 swap)
-__device__ __forceinline__ bf16x8 row_swap8(const bf16x8& v) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_;
-  u32x4_ x = __builtin_bit_cast(u32x4_, v);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)x[i], 0x128, 0xf, 0xf, true);
-  return __builtin_bit_cast(bf16x8, x);
-}
 
 // Epilogue stores and side-input loads go through raw buffer descriptors: the address is a per-lane 32-bit offset that never changes (row in the
 // wave tile x N + column) plus a SCALAR offset (tile, 16-row group, column group), rows past M fall outside the descriptor's range and are dropped
@@ -305,16 +287,7 @@ __global__ void __launch_bounds__((64 * Geo3<NI, MI, WM>::NWV), 2) gemm_nt3_kern
   const uint32_t vo_pair = ((uint32_t)(wm * WROWS + (fr & 7)) * (uint32_t)N + (uint32_t)(wn * (NI * 16) + 4 * gb + (fr < 8 ? 0 : 32))) * (uint32_t)sizeof(TO);
 
   auto epilogue = [&](int64_t m0, int n0, int strip) {
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[mi][2 * j][r]), __float_as_uint(acc[mi][2 * j + 1][r]), false, false);
-          acc[mi][2 * j][r] = __uint_as_float(sw[0]);
-          acc[mi][2 * j + 1][r] = __uint_as_float(sw[1]);
-        }
+    MAE_REGROUP8(acc, MI, NI)   // 8 consecutive columns per lane
     const float* sbias = G_::STRIP ? reinterpret_cast<const float*>(smem + G_::BIAS_OFF + strip * (BN * 4)) + wn * (NI * 16) : bias + n0 + wn * (NI * 16);
     constexpr uint32_t OSZ = sizeof(TO);
     const uint32_t rowb = (uint32_t)N * OSZ;                                        // bytes per output row
@@ -337,14 +310,8 @@ __global__ void __launch_bounds__((64 * Geo3<NI, MI, WM>::NWV), 2) gemm_nt3_kern
           f32x4 v0 = acc[mi][2 * j], v1 = acc[mi][2 * j + 1];
           if (HAS_BIAS) { v0 += b0; v1 += b1; }   // (without a bias no add at all: x + 0.0f is not an identity the compiler may drop)
           if (MODE == MAE_EPI_GELU_GRAD || MODE == MAE_EPI_GELU_ACT) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              v0[r] = to_f(from_f<TO>(v0[r]));
-              v1[r] = to_f(from_f<TO>(v1[r]));
-            }
             f32x4 a0, a1, g0, g1;
-            gelu_fast_pair(v0, a0, g0);
-            gelu_fast_pair(v1, a1, g1);
+            gelu_rounded<TO>(v0, v1, a0, a1, g0, g1);
             if (MODE == MAE_EPI_GELU_GRAD) { pa[j] = pk8(g0, g1); pb[TWO ? j : 0] = pk8(a0, a1); }
             else pa[j] = pk8(a0, a1);
           } else if (MODE == MAE_EPI_MUL) {
@@ -515,36 +482,12 @@ static int launch_nt3(const bf16* A, const bf16* W, int64_t M, int N, int K, con
   // MAE_NT3_ANT = largest tiles_n that gets the policy (0 = never; A/B)
   static const int ant_max = [] { const char* v = getenv("MAE_NT3_ANT"); return v ? atoi(v) : 1; }();
   const int a_nt = tiles_n <= ant_max ? 1 : 0;
-  if (e.bias) {
-    auto kern = gemm_nt3_kernel<MODE, TO, true, NI, MI, WM>;
-    MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * G_::NWV), G_::LDS, s, A, W, M, N, K, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, tiles_m, tiles_n, a_nt);
-  } else {
-    auto kern = gemm_nt3_kernel<MODE, TO, false, NI, MI, WM>;
-    MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * G_::NWV), G_::LDS, s, A, W, M, N, K, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, tiles_m, tiles_n, a_nt);
-  }
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
-// rounds of tiles on the CUs x rows per tile = time proxy; the 192-row tile must win by a margin: it stages 15 % more bytes per flop and, with two
-// waves across its 192 columns, stores a third of every row as half lines, which the eight-waves-along-M layout of the 256-row tile does not
-// (decoder launches, M = 290000, N = 192: 1152 against 1280 row-rounds, yet 117.6 us on 256-row tiles against 124.2 us; encoder N = 384:
-// 576 against 768 row-rounds, 86.0 against 99.4 us)
-static bool prefer_bm192_3(int64_t M, int N) {
-  static const int force = [] { const char* v = getenv("MAE_NT_BM"); return v ? atoi(v) : 0; }();
-  if (force == 192) return true;
-  if (force == 256) return false;
-  const int64_t t256 = cdiv(M, 256) * (N / 192), t192 = cdiv(M, 192) * (N / 192);
-  const int64_t c256 = cdiv(t256, num_cus()) * 256, c192 = cdiv(t192, num_cus()) * 192;
-  return c192 * 100 < c256 * 85;   // (95 and 85 measure the same in the step: 10.03 ms of NT GEMMs either way, ViT-B/16 21.83)
+  return launch_bias_pair(e.bias != nullptr, gemm_nt3_kernel<MODE, TO, true, NI, MI, WM>, gemm_nt3_kernel<MODE, TO, false, NI, MI, WM>, grid, 64 * G_::NWV, G_::LDS, s,
+                          A, W, M, N, K, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, tiles_m, tiles_n, a_nt);
 }
 
 template <int MODE, class TO>
-static int launch_nt3_ni(const bf16* A, const bf16* W, int64_t M, int N, int K, const Epi& e, hipStream_t s) {
-  const char* var = getenv("MAE_GEMM_NT");   // A/B: "v3w2" = two 4-wave workgroups per CU on 128-row tiles
-  const bool w2 = var && strstr(var, "w2") != nullptr;
+static int launch_nt3_ni(const bf16* A, const bf16* W, int64_t M, int N, int K, const Epi& e, bool w2, hipStream_t s) {   // w2: two 4-wave workgroups per CU on 128-row tiles (A/B)
   // Widths that are multiples of 256 take 192 x 256 tiles -- the 256 x 192 tile transposed: same staged bytes per flop and the same 24 MFMA tiles per
   // wave (48 x 128), but a wave then owns 128 columns = two whole 128-byte lines of every output row (no partial-line stores) and a row panel is
   // shared by N / 256 workgroups instead of N / 192.  gemm_bench: -4 ... -11 % on the fc1 / fc2-dgrad / 512- and 1024-wide launches, bit-identical;
@@ -554,7 +497,11 @@ static int launch_nt3_ni(const bf16* A, const bf16* W, int64_t M, int N, int K, 
   // (128 x 384 tiles -- wave tile 32 x 192, three whole lines per row, for 384 / 1152 -- stage 14 % more bytes per flop: +1.0 ms per step, not kept)
   if (N % 192 == 0) {
     if (w2) return launch_nt3<MODE, TO, 6, 4, 2>(A, W, M, N, K, e, s);
-    if (prefer_bm192_3(M, N)) return launch_nt3<MODE, TO, 6, 3, 4>(A, W, M, N, K, e, s);
+    // The 192-row tile must save 15 % of the row-rounds, not v2's 5 %: with two waves across its 192 columns it stores a third of every row as half
+    // lines, which the eight-waves-along-M layout of the 256-row tile does not (decoder launches, M = 290000, N = 192: 1152 against 1280 row-rounds,
+    // yet 117.6 us on 256-row tiles against 124.2 us; encoder N = 384: 576 against 768 row-rounds, 86.0 against 99.4 us).
+    // (95 and 85 measure the same in the step: 10.03 ms of NT GEMMs either way, ViT-B/16 21.83)
+    if (prefer_bm192(M, N, 85)) return launch_nt3<MODE, TO, 6, 3, 4>(A, W, M, N, K, e, s);
     // bf16 outputs: the 256 x 192 tile with EIGHT waves along M, each owning 32 whole rows (three full lines per row: no partial-line stores; 14 instead
     // of 10 fragment reads per half-step, which the LDS absorbs).  gemm_bench -1 ... -4 % on the 192- / 576- / 1152-wide launches, K = 4096 1278 -> 1285 TF/s,
     // step -0.02 ... -0.05 ms; fp32 outputs (two half-row stores per lane) lose 3 % and keep the 4 x 2 layout.  MAE_NT_WN1=0: 4 x 2 everywhere (A/B).
@@ -566,27 +513,30 @@ static int launch_nt3_ni(const bf16* A, const bf16* W, int64_t M, int N, int K, 
   return launch_nt3<MODE, TO, 4, 4, 4>(A, W, M, N, K, e, s);
 }
 
-int mfma_linear_fwd_v3(const bf16* A, const bf16* W, int64_t M, int N, int K, const Epi& e, hipStream_t s) {
+struct EpiV3 {   // what the engine's bf16 path issues
+  static constexpr bool ok(int mode, bool f32out) {
+    return mode == MAE_EPI_NONE || (!f32out && (mode == MAE_EPI_GELU_GRAD || mode == MAE_EPI_GELU_ACT || mode == MAE_EPI_MUL));
+  }
+};
+
+int mfma_linear_fwd_v3(const bf16* A, const bf16* W, int64_t M, int N, int K, const Epi& e, bool w2, hipStream_t s) {
   if (K % 64 != 0 || K < 192 || (N % 128 != 0 && N % 192 != 0) || M < 1) return MFMA_UNSUPPORTED;
   if ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)e.out | (uintptr_t)e.out2 | (uintptr_t)e.bias | (uintptr_t)e.aux) & 15) != 0) return MFMA_UNSUPPORTED;
   // 32-bit byte offsets inside the buffer descriptors (a tile may start up to 255 rows before the end and reach 256 rows past it)
   if ((uint64_t)(M + 512) * (uint64_t)K * 2u >= (1ull << 32) || (uint64_t)N * (uint64_t)K * 2u >= (1ull << 32)) return MFMA_UNSUPPORTED;
   if ((uint64_t)(M + 512) * (uint64_t)N * (e.out_dt == MAE_F32 ? 4u : 2u) >= (1ull << 32)) return MFMA_UNSUPPORTED;   // the epilogue's buffer offsets are 32-bit too
-  const bool f32out = e.out_dt == MAE_F32;
-  switch (e.mode) {
-    case MAE_EPI_NONE: {
+  return dispatch_epi<EpiV3>(e, [&](auto mode, auto to) {
+    constexpr int MODE = decltype(mode)::value;
+    using TO = typename decltype(to)::type;
+    if constexpr (MODE == MAE_EPI_NONE && sizeof(TO) == 2) {
       // bf16 outputs of at most 64 MB (MAE_NT_KEEP=<bytes>; 0 = never) are written with ordinary stores: they stay in the 256 MB memory-side cache for the
       // LayerNorm / attention kernel that reads them next (proj, fc2 and the dgrads of the 384-wide encoder: LayerNorm forward 1.81 -> 1.78 ms, backward
       // 2.54 -> 2.50 ms per step, the GEMMs unchanged; at 400 MB the GEMMs lose more than the readers win)
       static const int64_t keep = [] { const char* v = getenv("MAE_NT_KEEP"); return v ? atoll(v) : 64ll << 20; }();
-      if (!f32out && keep > 0 && M * (int64_t)N * 2 <= keep && N % 256 != 0) return launch_nt3_ni<77, bf16>(A, W, M, N, K, e, s);   // (the 192 x 256 tiles lose 0.6 % with it: ViT-B/16)
-      return f32out ? launch_nt3_ni<MAE_EPI_NONE, float>(A, W, M, N, K, e, s) : launch_nt3_ni<MAE_EPI_NONE, bf16>(A, W, M, N, K, e, s);
+      if (keep > 0 && M * (int64_t)N * 2 <= keep && N % 256 != 0) return launch_nt3_ni<77, bf16>(A, W, M, N, K, e, w2, s);   // (the 192 x 256 tiles lose 0.6 % with it: ViT-B/16)
     }
-    case MAE_EPI_GELU_GRAD: return f32out ? MFMA_UNSUPPORTED : launch_nt3_ni<MAE_EPI_GELU_GRAD, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_GELU_ACT: return f32out ? MFMA_UNSUPPORTED : launch_nt3_ni<MAE_EPI_GELU_ACT, bf16>(A, W, M, N, K, e, s);
-    case MAE_EPI_MUL: return f32out ? MFMA_UNSUPPORTED : launch_nt3_ni<MAE_EPI_MUL, bf16>(A, W, M, N, K, e, s);
-    default: return MFMA_UNSUPPORTED;
-  }
+    return launch_nt3_ni<MODE, TO>(A, W, M, N, K, e, w2, s);
+  });
 }
 
 }  // namespace mae

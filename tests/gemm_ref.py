@@ -263,7 +263,7 @@ class Knobs:
     def from_env(env=None) -> "Knobs":
         env = os.environ if env is None else env
         v = env.get("MAE_GEMM_NT")
-        return Knobs(w2=bool(v and "w2" in v), bm=int(env.get("MAE_NT_BM", 0)), wn1=int(env.get("MAE_NT_WN1", 1)),
+        return Knobs(w2=(v == "v3w2"), bm=int(env.get("MAE_NT_BM", 0)), wn1=int(env.get("MAE_NT_WN1", 1)),
                      n256=int(env.get("MAE_NT_N256", 1)), keep=int(env.get("MAE_NT_KEEP", 64 << 20)), ant_max=int(env.get("MAE_NT3_ANT", 1)))
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the Linear GEMM kernels on the pretrain-step shapes (GPU box).  Interleaved A/B of the NT kernel
-variants in one process (MAE_GEMM_NT=v1|v2), random bf16 data, reports TFLOP/s and GB/s and checks the variants agree
+variants in one process (MAE_GEMM_NT=v1|v2|v3|v3w2, --variants), random bf16 data, reports TFLOP/s and GB/s and checks the variants agree
 bit for bit.    python tools/gemm_bench.py [--rounds 5]
 --wgrad does the same for the weight-gradient kernels (MAE_WGRAD=v1|v3r|v4|v4b), --wgrad-pair for the paired launch."""
 import argparse
