@@ -12,15 +12,6 @@
 // Reference behaviour: F.scaled_dot_product_attention inside timm Attention.forward (no mask, no dropout).
 #include "gemm_mfma.h"
 
-#ifndef MAE_ATT_DMA_POLICY
-#define MAE_ATT_DMA_POLICY 0  // cache-policy bits of the staging DMAs (2 = nt)
-#endif
-#ifdef MAE_ATT_NT
-#define AT_ST store4_nt
-#else
-#define AT_ST store4
-#endif
-
 namespace mae {
 
 namespace {
@@ -35,21 +26,41 @@ struct AT {
   static constexpr int CPR = HD / 8;      // 16-byte chunks per row
 };
 
-// stage rows [0,T) of a (T, HD) matrix with global row stride gs (elements) into an LDS image, zero rows [T,Tp)
-template <int HD>
-__device__ __forceinline__ void stage_image(char* s, const bf16* g, int64_t gs, int T, int Tp) {
-  for (int c = threadIdx.x; c < Tp * AT<HD>::CPR; c += blockDim.x) {
-    const int row = c / AT<HD>::CPR, cc = c - row * AT<HD>::CPR;
-    uint4 v = uint4{0, 0, 0, 0};
-    if (row < T) v = *reinterpret_cast<const uint4*>(g + row * gs + cc * 8);
-    *reinterpret_cast<uint4*>(s + row * AT<HD>::RS + cc * 16) = v;
-  }
+// ---- LDS geometry: the ONE copy, used by the kernels (where the images start) and by the host (how much LDS a launch asks for).
+// Sequences of up to three 32-key chunks (the short unrolled variants) hold round_up(T, 16) rows per image instead of the chunk
+// loops' Tp = round_up(T, 32): a fourth encoder-backward workgroup fits a CU.  Their row reads clamp (rowfrag / trfrag below).
+__host__ __device__ constexpr bool attn_trims(int chunks) { return chunks >= 1 && chunks <= 3; }
+struct AttnImage { int rows, bytes; };  // bytes: a multiple of 1 KiB, the unit of the staging DMAs
+__host__ __device__ constexpr AttnImage attn_image(int T, int Tp, int row_stride, bool trim) {
+  const int rows = trim ? (T + 15) & ~15 : Tp;
+  return AttnImage{rows, (rows * row_stride + 1023) & ~1023};
+}
+// Where the pieces of a workgroup's dynamic LDS start and where they end, from `base`: the kernels pass the LDS pointer and take the
+// pieces, the host passes 0 and takes `end` as the size to ask for.
+// Forward: Q, K, V; FQ (the query tile's fragments come from global memory): K, V.
+template <class P> struct AttnFwdLds { P q, k, v, end; };
+template <bool FQ, class P>
+__host__ __device__ constexpr AttnFwdLds<P> attn_fwd_lds(P base, int img) {
+  const P k = FQ ? base : base + img, v = k + img;
+  return {base, k, v, v + img};
+}
+// Backward: Q, K, V, dO (PH = 0); K, V (PH = 1) or Q, dO (PH = 2); then Tp log-sum-exps and Tp D values (fp32).
+__host__ __device__ constexpr int past_floats(int p, int n) { return p + n * (int)sizeof(float); }
+__device__ __forceinline__ char* past_floats(char* p, int n) { return reinterpret_cast<char*>(reinterpret_cast<float*>(p) + n); }
+// (lse is a byte offset from q: handed out as a pointer it moves the schedule of attn_bwd_mfma_kernel<64, 1>)
+template <class P> struct AttnBwdLds { P q, k, v, d_o; int lse; P d, end; };
+template <int PH, class P>
+__host__ __device__ constexpr AttnBwdLds<P> attn_bwd_lds(P base, int img, int Tp) {
+  const P k = PH == 1 ? base : base + img, v = k + img, d_o = PH == 2 ? base + img : v + img;
+  const int lse = (PH == 0 ? 4 : 2) * img;
+  const P d = past_floats(base + lse, Tp);
+  return {base, k, v, d_o, lse, d, past_floats(d, Tp)};
 }
 
-// Same image filled by LDS-DMA (global_load_lds_dwordx4): every 16-byte slot of the padded image is one lane of one
-// DMA, all of a wave's DMAs are in flight together (the register-staged loop above serialises ~3 global round trips
-// per image).  Rows past T and the pad chunks read clamped (valid, finite) data: every use of them is multiplied by
-// an exactly-zero probability, so they only have to be finite.  img_bytes is a multiple of 1 KiB.
+// Rows [0,T) of a (T, HD) matrix with global row stride gs (elements) staged into an LDS image by LDS-DMA (global_load_lds_dwordx4):
+// every 16-byte slot of the padded image is one lane of one DMA, all of a wave's DMAs are in flight together (a register-staged
+// loop serialises ~3 global round trips per image).  Rows past T and the pad chunks read clamped (valid, finite) data: every use of
+// them is multiplied by an exactly-zero probability, so they only have to be finite.  img_bytes is a multiple of 1 KiB.
 template <int HD>
 __device__ __forceinline__ void stage_image_dma(char* s, int img_bytes, const bf16* g, int64_t gs, int T, int wave, int nwaves, int lane, int cprv) {
   constexpr int SPR = AT<HD>::RS / 16;  // 16-byte slots per padded row
@@ -59,7 +70,7 @@ __device__ __forceinline__ void stage_image_dma(char* s, int img_bytes, const bf
     row = row < T ? row : T - 1;
     c = c < cprv ? c : cprv - 1;
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + row * gs + c * 8),
-                                     (__attribute__((address_space(3))) void*)(s + blk * 1024), 16, 0, MAE_ATT_DMA_POLICY);
+                                     (__attribute__((address_space(3))) void*)(s + blk * 1024), 16, 0, 0);
   }
 }
 
@@ -81,6 +92,14 @@ template <int HD, bool CL>
 __device__ __forceinline__ bf16x8 rowfrag(const char* s, int row0, int ks, int lane, int rmax) {
   const int row = CL ? min(row0 + (lane & 15), rmax) : row0 + (lane & 15);
   return *reinterpret_cast<const bf16x8*>(s + row * AT<HD>::RS + (ks * 32 + 8 * (lane >> 4)) * 2);
+}
+
+// row fragment of the caller's own tile straight from global memory (rows past T clamp to T - 1: masked or multiplied by zero downstream)
+template <int HD>
+__device__ __forceinline__ bf16x8 rowfrag_global(const bf16* g, int64_t gs, int row0, int ks, int lane, int T) {
+  int row = row0 + (lane & 15);
+  row = row < T ? row : T - 1;
+  return *reinterpret_cast<const bf16x8*>(g + row * gs + ks * 32 + 8 * (lane >> 4));
 }
 
 // operand indexed by hd column (c0 + lane&15), elements = tokens j0 + 16h + 4*(lane>>4) + q, (h,q) = element>>2, &3
@@ -114,27 +133,70 @@ __device__ __forceinline__ float group_sum(float v) {
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 
-}  // namespace
+// ---- the pieces both kernels are made of.  A piece is a function where that leaves every kernel's instructions between its first and
+// last MFMA where they were, else a macro; profiles/r08_attention_refactor_isa.txt lists which form moved which kernels.
+// One 32-deep step of a product pair: the two 16-row tiles row0 and row0 + 16 of a 32-token chunk of image s against the held
+// fragment f (scores: K or Q rows against a q / k fragment; dP: V or dO rows against a dO / v fragment).
+template <int HD, bool CL>
+__device__ __forceinline__ void pair_mfma(const char* s, int row0, int ks, const bf16x8& f, f32x4& a0, f32x4& a1, int lane, int rmax) {
+  a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(s, row0, ks, lane, rmax), f, a0, 0, 0, 0);
+  a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(s, row0 + 16, ks, lane, rmax), f, a1, 0, 0, 0);
+}
 
-// NCH > 0: the number of 32-token chunks is a compile-time constant, the chunk loops are fully unrolled and the
-// compiler overlaps the MFMA / exp chains of different chunks (a runtime loop serialises them); NCH == 0: any length.
-// Every workgroup runs load (HBM) -> compute -> store, and the workgroups resident on the chip fall into step: all load,
-// then all compute (measured: the phases add up, e.g. decoder backward 155 us of staging + 330 us of compute = 483 us).
-// The first generation of workgroups is therefore started out of phase: the workgroup in residency slot r of its CU
-// (blockIdx / 256, one slot per CU filled first) waits r * stagger ticks of the 100 MHz wall clock before its loads.
-__device__ __forceinline__ void first_generation_stagger(int stagger, int gen1) {
-  if (stagger > 0 && (int)blockIdx.x >= 256 && (int)blockIdx.x < gen1) {
-    const uint64_t t0 = wall_clock64(), wait = (uint64_t)(blockIdx.x >> 8) * stagger;
-    while (wall_clock64() - t0 < wait) __builtin_amdgcn_s_sleep(4);
+// Keys past T of a score pair: the lane holds keys j0 + r (s0) and j0 + 16 + r (s1), j0 = 32 c + 4 g.  Only the last chunk of a sequence
+// holds such keys; the caller says which chunk that is (static when unrolled, else a wave-uniform test).
+#define ATT_MASK_TAIL(s0, s1, j0, T)                \
+  _Pragma("unroll") for (int r = 0; r < 4; ++r) {   \
+    if ((j0) + r >= (T)) (s0)[r] = -INFINITY;       \
+    if ((j0) + 16 + r >= (T)) (s1)[r] = -INFINITY;  \
   }
+
+// acc^T[d][.] += sum over the chunk's 32 tokens of img^T[d][j0 + kk] f[kk], for the NDT 16-wide tiles of the head dimension
+// (uses the kernel's HD, CL, lane and rmax)
+#define ATT_TR_ACC(s, j0, f, acc)                              \
+  _Pragma("unroll") for (int dt = 0; dt < AT<HD>::NDT; ++dt)   \
+    (acc)[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(trfrag<HD, CL>(s, j0, dt * 16, lane, rmax), f, (acc)[dt], 0, 0, 0);
+
+// bf16x8 dsf = dS = P * (dP - D) of a chunk pair, packed as the B operand of the next product
+#define ATT_DS_FRAG(dsf, P0, P1, G0, G1, D)           \
+  bf16x8 dsf;                                         \
+  {                                                   \
+    f32x4 d0_, d1_;                                   \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) {   \
+      d0_[r] = (P0)[r] * ((G0)[r] - (D));             \
+      d1_[r] = (P1)[r] * ((G1)[r] - (D));             \
+    }                                                 \
+    dsf = pack8(d0_, d1_);                            \
+  }
+
+// D prologue: the dot product of one 16-byte chunk of a dO row with the same chunk of the O row (0 for a dead slot; nothing is read
+// for one), summed over the CPR lanes that share the row
+template <int CPR>
+__device__ __forceinline__ float row_dot_reduce(bool live, const bf16x8* a, const bf16x8* o) {
+  float D = 0.f;
+  if (live) {
+    const bf16x8 av = *a, ov = *o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) D = fmaf((float)av[e], (float)ov[e], D);
+  }
+#pragma unroll
+  for (int off = CPR / 2; off > 0; off >>= 1) D += __shfl_xor(D, off, 64);
+  return D;
+}
+
+// one token's row of an NDT-tile accumulator, times mul, to p[dt * 16 + 0..3] (p points at the lane's column 4g); columns past hdv are dropped
+template <int HD>
+__device__ __forceinline__ void store_row(bf16* p, const f32x4 (&acc)[AT<HD>::NDT], float mul, int g, int hdv) {
+#pragma unroll
+  for (int dt = 0; dt < AT<HD>::NDT; ++dt)
+    if (dt * 16 + 4 * g < hdv) store4(p + dt * 16, acc[dt] * mul);
 }
 
 // Workgroup -> (image, head).  The hardware deals consecutive blockIdx round-robin over the 8 XCDs (one L2 each).  With 32-wide heads a
 // 128-byte line of a qkv / out / d_out row belongs to TWO heads: dealt in blockIdx order they land on different XCDs and the line is
 // fetched from HBM twice (PMC, round 2: decoder attention moved 1.75x its algorithmic bytes).  The remap gives XCD x the contiguous
 // range [x G/8, (x+1) G/8) of (image, head) pairs, so the two heads of a line run on the same L2 within a few dispatches of each other.
-__device__ __forceinline__ int att_block(int remap) {
-  if (!remap) return (int)blockIdx.x;
+__device__ __forceinline__ int att_block() {
   const int nb = (int)gridDim.x, bid = (int)blockIdx.x;
   const int q = nb >> 3, r = nb & 7, xcd = bid & 7, loc = bid >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
@@ -142,30 +204,24 @@ __device__ __forceinline__ int att_block(int remap) {
 
 // Threads per block: one wave per 16-token tile while the variant's registers allow 4 waves per SIMD (<= 128 VGPRs);
 // the wide unrolled variants keep 8 waves and walk their tiles in passes.
-template <int HD> struct FwdCap { static constexpr int v = 512; };  // (10 waves for the 145-token decoder forward measured 12 % slower than 5 waves x 2 passes)
-template <int NCH> struct BwdCap { static constexpr int v = NCH == 0 ? 1024 : 512; };
+constexpr int kFwdCap = 512;  // (10 waves for the 145-token decoder forward measured 12 % slower than 5 waves x 2 passes)
+constexpr int bwd_cap(int nch) { return nch == 0 ? 1024 : 512; }
 
-// row fragment of the caller's own tile straight from global memory (rows past T clamp to T - 1: masked or multiplied by zero downstream)
-template <int HD>
-__device__ __forceinline__ bf16x8 rowfrag_global(const bf16* g, int64_t gs, int row0, int ks, int lane, int T) {
-  int row = row0 + (lane & 15);
-  row = row < T ? row : T - 1;
-  return *reinterpret_cast<const bf16x8*>(g + row * gs + ks * 32 + 8 * (lane >> 4));
-}
+}  // namespace
 
+// NCH > 0: the number of 32-token chunks is a compile-time constant (Tp = 32 NCH), the chunk loops are fully unrolled and the
+// compiler overlaps the MFMA / exp chains of different chunks (a runtime loop serialises them); NCH == 0: any length.
 // FQ: the query tile's fragments come straight from global memory and only K and V are staged (sequences whose three images exceed the LDS)
 template <int HD, int NCH, bool FQ = false>
-__global__ void __launch_bounds__(FwdCap<HD>::v) attn_fwd_mfma_kernel(const bf16* __restrict__ qkv, int T, int Tp, int H, float scale,
-                                                            bf16* __restrict__ out, float* __restrict__ lse, int stagger, int gen1, int hdv, int remap) {
+__global__ void __launch_bounds__(kFwdCap) attn_fwd_mfma_kernel(const bf16* __restrict__ qkv, int T, int Tp, int H, float scale,
+                                                                bf16* __restrict__ out, float* __restrict__ lse, int hdv) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  first_generation_stagger(stagger, gen1);
-  constexpr bool CL = NCH >= 1 && NCH <= 3;
-  const int Ti = CL ? (T + 15) & ~15 : Tp, rmax = Ti - 1;   // rows an image holds (Tp = the 32-key chunk padding of the loops)
-  const int img = (Ti * AT<HD>::RS + 1023) & ~1023;
-  char* sQ = smem;
-  char* sK = FQ ? smem : sQ + img;
-  char* sV = sK + img;
-  const int vb = att_block(remap);
+  constexpr bool CL = attn_trims(NCH);   // NCH is the chunk count of the lengths that trim (the dispatch table below)
+  const AttnImage im = attn_image(T, Tp, AT<HD>::RS, CL);
+  const auto at = attn_fwd_lds<FQ>(smem, im.bytes);
+  const int Ti = im.rows, rmax = Ti - 1, img = im.bytes;
+  char *sQ = at.q, *sK = at.k, *sV = at.v;
+  const int vb = att_block();
   const int b = vb / H, h = vb - b * H;
   const int64_t gs = 3ll * H * hdv;  // hdv = head dim in memory (<= HD)
   const int cprv = hdv >> 3;
@@ -203,19 +259,9 @@ __global__ void __launch_bounds__(FwdCap<HD>::v) attn_fwd_mfma_kernel(const bf16
       for (int c = 0; c < NC; ++c) {
         s0[c] = f32x4{0.f, 0.f, 0.f, 0.f}; s1[c] = s0[c];
 #pragma unroll
-        for (int ks = 0; ks < AT<HD>::NKS; ++ks) {
-          s0[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sK, c * 32, ks, lane, rmax), qf[ks], s0[c], 0, 0, 0);
-          s1[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sK, c * 32 + 16, ks, lane, rmax), qf[ks], s1[c], 0, 0, 0);
-        }
+        for (int ks = 0; ks < AT<HD>::NKS; ++ks) pair_mfma<HD, CL>(sK, c * 32, ks, qf[ks], s0[c], s1[c], lane, rmax);
       }
-      {  // only the last chunk holds keys past T
-        const int j0 = (NC - 1) * 32 + 4 * g;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (j0 + r >= T) s0[NC - 1][r] = -INFINITY;
-          if (j0 + 16 + r >= T) s1[NC - 1][r] = -INFINITY;
-        }
-      }
+      ATT_MASK_TAIL(s0[NC - 1], s1[NC - 1], (NC - 1) * 32 + 4 * g, T)  // only the last chunk holds keys past T
       float mc = -INFINITY;
 #pragma unroll
       for (int c = 0; c < NC; ++c)
@@ -231,27 +277,16 @@ __global__ void __launch_bounds__(FwdCap<HD>::v) attn_fwd_mfma_kernel(const bf16
           lsum += s0[c][r] + s1[c][r];
         }
         const bf16x8 pf = pack8(s0[c], s1[c]);
-#pragma unroll
-        for (int dt = 0; dt < AT<HD>::NDT; ++dt)
-          oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(trfrag<HD, CL>(sV, c * 32, dt * 16, lane, rmax), pf, oacc[dt], 0, 0, 0);
+        ATT_TR_ACC(sV, c * 32, pf, oacc)
       }
     } else {
     for (int c = 0; c < nchunks; ++c) {
       f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < AT<HD>::NKS; ++ks) {
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sK, c * 32, ks, lane, rmax), qf[ks], s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sK, c * 32 + 16, ks, lane, rmax), qf[ks], s1, 0, 0, 0);
-      }
+      for (int ks = 0; ks < AT<HD>::NKS; ++ks) pair_mfma<HD, CL>(sK, c * 32, ks, qf[ks], s0, s1, lane, rmax);
       // lane: query i, keys j = c*32 + 4g + r (s0) and c*32 + 16 + 4g + r (s1)
       const int j0 = c * 32 + 4 * g;
-      if (c * 32 + 32 > T) {  // only the last chunk holds keys past T (wave-uniform)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (j0 + r >= T) s0[r] = -INFINITY;
-          if (j0 + 16 + r >= T) s1[r] = -INFINITY;
-        }
-      }
+      if (c * 32 + 32 > T) { ATT_MASK_TAIL(s0, s1, j0, T) }  // only the last chunk holds keys past T (wave-uniform)
       float mc = fmaxf(fmaxf(fmaxf(s0[0], s0[1]), fmaxf(s0[2], s0[3])), fmaxf(fmaxf(s1[0], s1[1]), fmaxf(s1[2], s1[3])));
       mc = group_max(mc);
       const float mn = fmaxf(m, mc);  // finite from chunk 0 on (key 0 is always valid)
@@ -269,7 +304,7 @@ __global__ void __launch_bounds__(FwdCap<HD>::v) attn_fwd_mfma_kernel(const bf16
       lsum = lsum * alpha + ps;
       const bf16x8 pf = pack8(s0, s1);
 #pragma unroll
-      for (int dt = 0; dt < AT<HD>::NDT; ++dt) {
+      for (int dt = 0; dt < AT<HD>::NDT; ++dt) {   // ATT_TR_ACC with the online form's rescale in front of each tile
         oacc[dt] *= alpha;
         oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(trfrag<HD, CL>(sV, c * 32, dt * 16, lane, rmax), pf, oacc[dt], 0, 0, 0);
       }
@@ -280,10 +315,7 @@ __global__ void __launch_bounds__(FwdCap<HD>::v) attn_fwd_mfma_kernel(const bf16
     const float inv = 1.0f / lsum;
     const int tq = qt * 16 + i;
     if (tq < T) {
-      bf16* po = out + ((int64_t)b * T + tq) * H * hdv + h * hdv + 4 * g;
-#pragma unroll
-      for (int dt = 0; dt < AT<HD>::NDT; ++dt)
-        if (dt * 16 + 4 * g < hdv) AT_ST(po + dt * 16, oacc[dt] * inv);
+      store_row<HD>(out + ((int64_t)b * T + tq) * H * hdv + h * hdv + 4 * g, oacc, inv, g, hdv);
       if (g == 0) lse[((int64_t)b * H + h) * T + tq] = m * scale + __logf(lsum);
     }
   }
@@ -293,21 +325,19 @@ __global__ void __launch_bounds__(FwdCap<HD>::v) attn_fwd_mfma_kernel(const bf16
 // two images each and take their own 16-token tile's fragments straight from global memory: PH = 1 (dQ: K, V staged) and PH = 2 (dK / dV:
 // Q, dO staged).  Same arithmetic in the same order as PH = 0.
 template <int HD, int NCH, int PH = 0>
-__global__ void __launch_bounds__(BwdCap<NCH>::v) attn_bwd_mfma_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
-                                                            const bf16* __restrict__ d_out, const float* __restrict__ lse, int T,
-                                                            int Tp, int H, float scale, bf16* __restrict__ d_qkv, int stagger, int gen1, int hdv, int remap) {
+__global__ void __launch_bounds__(bwd_cap(NCH)) attn_bwd_mfma_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
+                                                                     const bf16* __restrict__ d_out, const float* __restrict__ lse, int T,
+                                                                     int Tp, int H, float scale, bf16* __restrict__ d_qkv, int hdv) {
+  static_assert(NCH == 0 || PH == 0, "the two-launch form exists for long sequences only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  first_generation_stagger(stagger, gen1);
-  constexpr bool CL = NCH >= 1 && NCH <= 3;
-  const int Ti = CL ? (T + 15) & ~15 : Tp, rmax = Ti - 1;   // rows an image holds (Tp = the 32-key chunk padding of the loops)
-  const int img = (Ti * AT<HD>::RS + 1023) & ~1023;
-  char* sQ = smem;
-  char* sK = PH == 1 ? smem : sQ + img;
-  char* sV = sK + img;
-  char* sdO = PH == 2 ? smem + img : sV + img;
-  float* sLse = reinterpret_cast<float*>(smem + (PH == 0 ? 4 : 2) * img);  // pre-multiplied by log2(e); 1e30 on padded rows
-  float* sD = sLse + Tp;
-  const int vb = att_block(remap);
+  constexpr bool CL = attn_trims(NCH);   // NCH is the chunk count of the lengths that trim (the dispatch table below)
+  const AttnImage im = attn_image(T, Tp, AT<HD>::RS, CL);
+  const auto at = attn_bwd_lds<PH>(smem, im.bytes, Tp);
+  const int Ti = im.rows, rmax = Ti - 1, img = im.bytes;
+  char *sQ = at.q, *sK = at.k, *sV = at.v, *sdO = at.d_o;
+  float* sLse = reinterpret_cast<float*>(at.q + at.lse);  // pre-multiplied by log2(e); 1e30 on padded rows
+  float* sD = reinterpret_cast<float*>(at.d);
+  const int vb = att_block();
   const int b = vb / H, h = vb - b * H;
   const int64_t gs = 3ll * H * hdv, os = (int64_t)H * hdv;  // hdv = head dim in memory (<= HD)
   const int cprv = hdv >> 3;
@@ -328,7 +358,7 @@ __global__ void __launch_bounds__(BwdCap<NCH>::v) attn_bwd_mfma_kernel(const bf1
   // DPM (the unrolled lengths): D_t is not formed from dO_t . O_t at all but as sum_j P_tj dP_tj inside phase A, where a wave holds every
   // P and dP of its 16 queries in registers (the two sums are the same number: O = P V, dP = dO V^T) -- the O rows (a ninth of the
   // kernel's bytes) are never read, and the prologue shrinks to the log-sum-exps.
-  constexpr bool DPM = NCH > 0 && PH == 0;
+  constexpr bool DPM = NCH > 0;
   constexpr int CPR = AT<HD>::CPR, PF = 4;
   const int total = Tp * CPR;
   const bool pf = !DPM && PH == 0 && total <= PF * (int)blockDim.x;
@@ -364,14 +394,7 @@ __global__ void __launch_bounds__(BwdCap<NCH>::v) attn_bwd_mfma_kernel(const bf1
     for (int it = 0; it < PF; ++it) {
       const int idx = it * blockDim.x + threadIdx.x;
       const int t = idx / CPR, cc = idx - t * CPR;
-      float D = 0.f;
-      if (idx < total && t < T && cc < cprv) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(sdO + t * AT<HD>::RS + cc * 16);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) D = fmaf((float)a[e], (float)o_pf[it][e], D);
-      }
-#pragma unroll
-      for (int off = CPR / 2; off > 0; off >>= 1) D += __shfl_xor(D, off, 64);
+      const float D = row_dot_reduce<CPR>(idx < total && t < T && cc < cprv, reinterpret_cast<const bf16x8*>(sdO + t * AT<HD>::RS + cc * 16), &o_pf[it]);
       if (idx < total && cc == 0) {
         sD[t] = D;
         sLse[t] = t < T ? l_pf[it] * kLog2e : 1e30f;
@@ -381,15 +404,9 @@ __global__ void __launch_bounds__(BwdCap<NCH>::v) attn_bwd_mfma_kernel(const bf1
     for (int base = 0; base < total; base += blockDim.x) {
       const int idx = base + threadIdx.x;
       const int t = idx / CPR, cc = idx - t * CPR;
-      float D = 0.f;
-      if (idx < total && t < T && cc < cprv) {
-        const bf16x8 a = PH == 1 ? *reinterpret_cast<const bf16x8*>(dobase + t * os + cc * 8) : *reinterpret_cast<const bf16x8*>(sdO + t * AT<HD>::RS + cc * 16);
-        const bf16x8 o = *reinterpret_cast<const bf16x8*>(obase + t * os + cc * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) D = fmaf((float)a[e], (float)o[e], D);
-      }
-#pragma unroll
-      for (int off = CPR / 2; off > 0; off >>= 1) D += __shfl_xor(D, off, 64);
+      const float D = row_dot_reduce<CPR>(idx < total && t < T && cc < cprv,
+                                          reinterpret_cast<const bf16x8*>(PH == 1 ? (const char*)(dobase + t * os + cc * 8) : sdO + t * AT<HD>::RS + cc * 16),
+                                          reinterpret_cast<const bf16x8*>(obase + t * os + cc * 8));
       if (idx < total && cc == 0) {
         sD[t] = D;
         sLse[t] = t < T ? lse[((int64_t)b * H + h) * T + t] * kLog2e : 1e30f;
@@ -427,19 +444,10 @@ __global__ void __launch_bounds__(BwdCap<NCH>::v) attn_bwd_mfma_kernel(const bf1
         G0[c] = s0; G1[c] = s0;
 #pragma unroll
         for (int ks = 0; ks < AT<HD>::NKS; ++ks) {
-          s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sK, c * 32, ks, lane, rmax), qf[ks], s0, 0, 0, 0);
-          s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sK, c * 32 + 16, ks, lane, rmax), qf[ks], s1, 0, 0, 0);
-          G0[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sV, c * 32, ks, lane, rmax), dof[ks], G0[c], 0, 0, 0);
-          G1[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sV, c * 32 + 16, ks, lane, rmax), dof[ks], G1[c], 0, 0, 0);
+          pair_mfma<HD, CL>(sK, c * 32, ks, qf[ks], s0, s1, lane, rmax);
+          pair_mfma<HD, CL>(sV, c * 32, ks, dof[ks], G0[c], G1[c], lane, rmax);
         }
-        if (c == NC - 1) {  // only the last chunk holds keys past T
-          const int j0 = c * 32 + 4 * g;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            if (j0 + r >= T) s0[r] = -INFINITY;
-            if (j0 + 16 + r >= T) s1[r] = -INFINITY;
-          }
-        }
+        if (c == NC - 1) { ATT_MASK_TAIL(s0, s1, c * 32 + 4 * g, T) }  // only the last chunk holds keys past T
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           P0[c][r] = __builtin_amdgcn_exp2f(fmaf(s0[r], sl2, -li));
@@ -452,56 +460,31 @@ __global__ void __launch_bounds__(BwdCap<NCH>::v) attn_bwd_mfma_kernel(const bf1
       if (g == 0) sD[qt * 16 + i] = Di;    // phase B reads it per query
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
-        f32x4 d0, d1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          d0[r] = P0[c][r] * (G0[c][r] - Di);
-          d1[r] = P1[c][r] * (G1[c][r] - Di);
-        }
-        const bf16x8 dsf = pack8(d0, d1);
-#pragma unroll
-        for (int dt = 0; dt < AT<HD>::NDT; ++dt)
-          dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(trfrag<HD, CL>(sK, c * 32, dt * 16, lane, rmax), dsf, dq[dt], 0, 0, 0);
+        ATT_DS_FRAG(dsf, P0[c], P1[c], G0[c], G1[c], Di)
+        ATT_TR_ACC(sK, c * 32, dsf, dq)
       }
     } else {
     const float Di = sD[qt * 16 + i];
-#pragma unroll
     for (int c = 0; c < nchunks; ++c) {
       f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
 #pragma unroll
       for (int ks = 0; ks < AT<HD>::NKS; ++ks) {
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sK, c * 32, ks, lane, rmax), qf[ks], s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sK, c * 32 + 16, ks, lane, rmax), qf[ks], s1, 0, 0, 0);
-        p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sV, c * 32, ks, lane, rmax), dof[ks], p0, 0, 0, 0);
-        p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sV, c * 32 + 16, ks, lane, rmax), dof[ks], p1, 0, 0, 0);
+        pair_mfma<HD, CL>(sK, c * 32, ks, qf[ks], s0, s1, lane, rmax);
+        pair_mfma<HD, CL>(sV, c * 32, ks, dof[ks], p0, p1, lane, rmax);
       }
       const int j0 = c * 32 + 4 * g;
-      if (NCH > 0 ? c == NCH - 1 : c * 32 + 32 > T) {  // only the last chunk holds keys past T (static when unrolled, else wave-uniform)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (j0 + r >= T) s0[r] = -INFINITY;
-          if (j0 + 16 + r >= T) s1[r] = -INFINITY;
-        }
-      }
+      if (c * 32 + 32 > T) { ATT_MASK_TAIL(s0, s1, j0, T) }  // only the last chunk holds keys past T (wave-uniform)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float pa = __builtin_amdgcn_exp2f(fmaf(s0[r], sl2, -li));  // raw v_exp_f32: exp2(-inf) = 0, no denormal rescale
-        const float pb = __builtin_amdgcn_exp2f(fmaf(s1[r], sl2, -li));
-        s0[r] = pa * (p0[r] - Di);
-        s1[r] = pb * (p1[r] - Di);
+        s0[r] = __builtin_amdgcn_exp2f(fmaf(s0[r], sl2, -li));  // raw v_exp_f32: exp2(-inf) = 0, no denormal rescale
+        s1[r] = __builtin_amdgcn_exp2f(fmaf(s1[r], sl2, -li));
       }
-      const bf16x8 dsf = pack8(s0, s1);
-#pragma unroll
-      for (int dt = 0; dt < AT<HD>::NDT; ++dt)
-        dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(trfrag<HD, CL>(sK, c * 32, dt * 16, lane, rmax), dsf, dq[dt], 0, 0, 0);
+      ATT_DS_FRAG(dsf, s0, s1, p0, p1, Di)
+      ATT_TR_ACC(sK, c * 32, dsf, dq)
     }
     }
     const int tq = qt * 16 + i;
-    if (tq < T) {
-#pragma unroll
-      for (int dt = 0; dt < AT<HD>::NDT; ++dt)
-        if (dt * 16 + 4 * g < hdv) AT_ST(dbase + tq * gs + dt * 16 + 4 * g, dq[dt] * scale);
-    }
+    if (tq < T) store_row<HD>(dbase + tq * gs + 4 * g, dq, scale, g, hdv);
   }
   if (DPM) __syncthreads();   // every query's D is in sD before the key-owner phase reads it
 
@@ -520,19 +503,19 @@ __global__ void __launch_bounds__(BwdCap<NCH>::v) attn_bwd_mfma_kernel(const bf1
     f32x4 dk[AT<HD>::NDT], dv[AT<HD>::NDT];
 #pragma unroll
     for (int dt = 0; dt < AT<HD>::NDT; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = dk[dt]; }
-#pragma unroll
+#pragma unroll NCH > 0 ? NCH : 1   // a run-time trip count (NCH == 0) stays a loop
     for (int c = 0; c < nchunks; ++c) {
       f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
 #pragma unroll
       for (int ks = 0; ks < AT<HD>::NKS; ++ks) {
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sQ, c * 32, ks, lane, rmax), kf[ks], s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sQ, c * 32 + 16, ks, lane, rmax), kf[ks], s1, 0, 0, 0);
-        p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sdO, c * 32, ks, lane, rmax), vf[ks], p0, 0, 0, 0);
-        p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag<HD, CL>(sdO, c * 32 + 16, ks, lane, rmax), vf[ks], p1, 0, 0, 0);
+        pair_mfma<HD, CL>(sQ, c * 32, ks, kf[ks], s0, s1, lane, rmax);
+        pair_mfma<HD, CL>(sdO, c * 32, ks, vf[ks], p0, p1, lane, rmax);
       }
       // lane: key j = jt*16 + i; queries c*32 + 4g + r (tile 0), c*32 + 16 + 4g + r (tile 1); padded queries: lse = 1e30
       const f32x4 l0 = load4(sLse + c * 32 + 4 * g), l1 = load4(sLse + c * 32 + 16 + 4 * g);
       const f32x4 D0 = load4(sD + c * 32 + 4 * g), D1 = load4(sD + c * 32 + 16 + 4 * g);
+      // P and dS in one pass with a D per element, then the dV and dK tiles alternating: ATT_DS_FRAG / ATT_TR_ACC written out (as separate
+      // loops they move attn_bwd_mfma_kernel<32, 1> and seven more)
       f32x4 ds0, ds1;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -551,73 +534,43 @@ __global__ void __launch_bounds__(BwdCap<NCH>::v) attn_bwd_mfma_kernel(const bf1
     const int tj = jt * 16 + i;
     if (tj < T) {
 #pragma unroll
-      for (int dt = 0; dt < AT<HD>::NDT; ++dt) {
+      for (int dt = 0; dt < AT<HD>::NDT; ++dt) {   // store_row for two accumulators under one guard (two store_row calls cost the unrolled variants 2-4 VGPRs)
         if (dt * 16 + 4 * g < hdv) {
-          AT_ST(dbase + tj * gs + os + dt * 16 + 4 * g, dk[dt] * scale);
-          AT_ST(dbase + tj * gs + 2 * os + dt * 16 + 4 * g, dv[dt]);
+          store4(dbase + tj * gs + os + dt * 16 + 4 * g, dk[dt] * scale);
+          store4(dbase + tj * gs + 2 * os + dt * 16 + 4 * g, dv[dt]);
         }
       }
     }
   }
 }
 
-static int attn_waves(int T, int max_threads) {
+static int attn_threads(int T, int max_threads) {
   const int nt = (T + 15) / 16, maxw = max_threads / 64;
   const int passes = (nt + maxw - 1) / maxw;
-  return (nt + passes - 1) / passes;  // <= maxw waves, balanced over the 16-token tiles
-}
-
-static int attn_remap() {   // MAE_ATT_XCD=0: blockIdx order (A/B)
-  static const int v = [] { const char* e = getenv("MAE_ATT_XCD"); return e ? atoi(e) : 1; }();
-  return v;
-}
-static int attn_stagger() {
-  static const int v = [] { const char* e = getenv("MAE_ATT_STAGGER"); return e ? atoi(e) : 0; }();
-  return v;
-}
-// workgroups resident per CU (LDS and wave-slot limits; registers are covered by the launch bounds)
-static int attn_resident(size_t lds, int threads) {
-  const int by_lds = (int)((160 * 1024) / lds), by_waves = 32 / (threads / 64);
-  return std::max(1, std::min(std::min(by_lds, by_waves), 8));
+  return 64 * ((nt + passes - 1) / passes);  // <= maxw waves, balanced over the 16-token tiles
 }
 
 static bool attn_supported(int T, int H, int hd) {
   return (hd == 24 || hd == 32 || hd == 64) && T >= 1 && T <= 1024 && ((int64_t)H * hd) % 8 == 0;  // 24 runs zero-padded in the 32 kernels
 }
 
-template <int HD, int NCH>
-static int launch_attn_fwd(const bf16* qkv, int B, int T, int Tp, int H, int hdv, size_t lds, float scale, bf16* out, float* lse, hipStream_t s) {
-  auto kern = attn_fwd_mfma_kernel<HD, NCH>;
-  MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)B * H), dim3(64 * attn_waves(T, FwdCap<HD>::v)), lds, s, qkv, T, Tp, H, scale, out, lse, attn_stagger(), 256 * attn_resident(lds, 64 * attn_waves(T, FwdCap<HD>::v)), hdv, attn_remap());
+constexpr int kLdsBytes = 160 * 1024;
+
+// one workgroup per (image, head)
+template <class... KA, class... A>
+static int launch_attn(void (*kern)(KA...), int groups, int threads, int lds, hipStream_t s, A... args) {
+  MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3((unsigned)threads), (size_t)lds, s, args...);
   MAE_LAUNCH_CHECK();
   return 0;
 }
-template <int HD, int NCH>
-static int launch_attn_bwd(const bf16* qkv, const bf16* out, const bf16* d_out, const float* lse, int B, int T, int Tp, int H, int hdv, size_t lds,
-                           float scale, bf16* d_qkv, hipStream_t s) {
-  auto kern = attn_bwd_mfma_kernel<HD, NCH>;
-  static const int lds_pad = [] { const char* e = getenv("MAE_ATT_LDS_PAD"); return e ? atoi(e) : 0; }();   // residency experiment: extra LDS bytes per workgroup
-  lds += (size_t)lds_pad;
-  MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)B * H), dim3(64 * attn_waves(T, BwdCap<NCH>::v)), lds, s, qkv, out, d_out, lse, T, Tp, H, scale, d_qkv, attn_stagger(), 256 * attn_resident(lds, 64 * attn_waves(T, BwdCap<NCH>::v)), hdv, attn_remap());
-  MAE_LAUNCH_CHECK();
-  return 0;
+template <int HD, int NCH, class... A>
+static int attn_fwd(int groups, int T, int lds, hipStream_t s, A... args) {
+  return launch_attn(attn_fwd_mfma_kernel<HD, NCH>, groups, attn_threads(T, kFwdCap), lds, s, args...);
 }
-// long sequences: the backward pass as two launches staging two images each (PH = 1: dQ, PH = 2: dK / dV)
-template <int HD>
-static int launch_attn_bwd_split(const bf16* qkv, const bf16* out, const bf16* d_out, const float* lse, int B, int T, int Tp, int H, int hdv, size_t lds,
-                                 float scale, bf16* d_qkv, hipStream_t s) {
-  const int threads = 64 * attn_waves(T, BwdCap<0>::v);
-  auto k1 = attn_bwd_mfma_kernel<HD, 0, 1>;
-  auto k2 = attn_bwd_mfma_kernel<HD, 0, 2>;
-  MAE_HIP(hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  MAE_HIP(hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k1, dim3((unsigned)B * H), dim3(threads), lds, s, qkv, out, d_out, lse, T, Tp, H, scale, d_qkv, 0, 0, hdv, attn_remap());
-  MAE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k2, dim3((unsigned)B * H), dim3(threads), lds, s, qkv, out, d_out, lse, T, Tp, H, scale, d_qkv, 0, 0, hdv, attn_remap());
-  MAE_LAUNCH_CHECK();
-  return 0;
+template <int HD, int NCH, class... A>
+static int attn_bwd(int groups, int T, int lds, hipStream_t s, A... args) {
+  return launch_attn(attn_bwd_mfma_kernel<HD, NCH>, groups, attn_threads(T, bwd_cap(NCH)), lds, s, args...);
 }
 #define ATTN_DISPATCH(FN, BIG, ...)                                         \
   switch (hdt * 100 + (Tp >> 5)) {                                          \
@@ -632,42 +585,39 @@ static int launch_attn_bwd_split(const bf16* qkv, const bf16* out, const bf16* d
     default: return hdt == 64 ? FN<64, 0>(__VA_ARGS__) : FN<32, 0>(__VA_ARGS__); \
   }
 
-template <int HD>
-static int launch_attn_fwd_fq(const bf16* qkv, int B, int T, int Tp, int H, int hdv, size_t lds, float scale, bf16* out, float* lse, hipStream_t s) {
-  auto kern = attn_fwd_mfma_kernel<HD, 0, true>;
-  MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)B * H), dim3(64 * attn_waves(T, FwdCap<HD>::v)), lds, s, qkv, T, Tp, H, scale, out, lse, 0, 0, hdv, attn_remap());
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
 int mfma_attention_fwd(const bf16* qkv, int B, int T, int H, int hd, bf16* out, float* lse, hipStream_t s) {
   if (!attn_supported(T, H, hd) || (((uintptr_t)qkv | (uintptr_t)out) & 15)) return MFMA_UNSUPPORTED;
   const int Tp = (int)round_up(T, 32), hdt = hd == 24 ? 32 : hd;
-  const size_t img = (size_t)round_up(((Tp >> 5) <= 3 ? round_up((int64_t)T, 16) : (int64_t)Tp) * (hdt * 2 + 32), 1024);   // the short unrolled variants hold round_up(T, 16) rows
-  const size_t lds = 3 * img;
+  const int img = attn_image(T, Tp, hdt * 2 + 32, attn_trims(Tp >> 5)).bytes, lds = attn_fwd_lds<false>(0, img).end;
   const float scale = 1.0f / sqrtf((float)hd);
-  if (lds > 160 * 1024) {   // three images do not fit: K and V only, query fragments from global memory
-    if (2 * img > 160 * 1024 || hd != hdt) return MFMA_UNSUPPORTED;
-    return hdt == 64 ? launch_attn_fwd_fq<64>(qkv, B, T, Tp, H, hd, 2 * img, scale, out, lse, s) : launch_attn_fwd_fq<32>(qkv, B, T, Tp, H, hd, 2 * img, scale, out, lse, s);
+  if (lds > kLdsBytes) {   // three images do not fit: K and V only, query fragments from global memory
+    const int lds2 = attn_fwd_lds<true>(0, img).end;
+    if (lds2 > kLdsBytes || hd != hdt) return MFMA_UNSUPPORTED;
+    return launch_attn(hdt == 64 ? attn_fwd_mfma_kernel<64, 0, true> : attn_fwd_mfma_kernel<32, 0, true>, B * H, attn_threads(T, kFwdCap), lds2, s,
+                       qkv, T, Tp, H, scale, out, lse, hd);
   }
-  ATTN_DISPATCH(launch_attn_fwd, 5, qkv, B, T, Tp, H, hd, lds, scale, out, lse, s)
+  ATTN_DISPATCH(attn_fwd, 5, B * H, T, lds, s, qkv, T, Tp, H, scale, out, lse, hd)
 }
 
 int mfma_attention_bwd(const bf16* qkv, const bf16* out, const bf16* d_out, const float* lse, int B, int T, int H, int hd,
                        bf16* d_qkv, hipStream_t s) {
   if (!attn_supported(T, H, hd) || (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)d_out | (uintptr_t)d_qkv) & 15)) return MFMA_UNSUPPORTED;
   const int Tp = (int)round_up(T, 32), hdt = hd == 24 ? 32 : hd;
-  const size_t img = (size_t)round_up(((Tp >> 5) <= 3 ? round_up((int64_t)T, 16) : (int64_t)Tp) * (hdt * 2 + 32), 1024);   // the short unrolled variants hold round_up(T, 16) rows
-  const size_t lds = 4 * img + (size_t)2 * Tp * 4;
+  const int img = attn_image(T, Tp, hdt * 2 + 32, attn_trims(Tp >> 5)).bytes, lds = attn_bwd_lds<0>(0, img, Tp).end;
   const float scale = 1.0f / sqrtf((float)hd);
-  if (lds > 160 * 1024) {
-    const size_t lds2 = 2 * img + (size_t)2 * Tp * 4;
-    if (lds2 > 160 * 1024 || hd != hdt) return MFMA_UNSUPPORTED;
-    return hdt == 64 ? launch_attn_bwd_split<64>(qkv, out, d_out, lse, B, T, Tp, H, hd, lds2, scale, d_qkv, s)
-                     : launch_attn_bwd_split<32>(qkv, out, d_out, lse, B, T, Tp, H, hd, lds2, scale, d_qkv, s);
+  if (lds > kLdsBytes) {   // long sequences: two launches staging two images each (PH = 1: dQ, PH = 2: dK / dV)
+    const int lds1 = attn_bwd_lds<1>(0, img, Tp).end, lds2 = attn_bwd_lds<2>(0, img, Tp).end, threads = attn_threads(T, bwd_cap(0));
+    if (lds1 > kLdsBytes || lds2 > kLdsBytes || hd != hdt) return MFMA_UNSUPPORTED;
+    if (int e = launch_attn(hdt == 64 ? attn_bwd_mfma_kernel<64, 0, 1> : attn_bwd_mfma_kernel<32, 0, 1>, B * H, threads, lds1, s,
+                            qkv, out, d_out, lse, T, Tp, H, scale, d_qkv, hd)) return e;
+    return launch_attn(hdt == 64 ? attn_bwd_mfma_kernel<64, 0, 2> : attn_bwd_mfma_kernel<32, 0, 2>, B * H, threads, lds2, s,
+                       qkv, out, d_out, lse, T, Tp, H, scale, d_qkv, hd);
   }
-  ATTN_DISPATCH(launch_attn_bwd, 0, qkv, out, d_out, lse, B, T, Tp, H, hd, lds, scale, d_qkv, s)
+  ATTN_DISPATCH(attn_bwd, 0, B * H, T, lds, s, qkv, out, d_out, lse, T, Tp, H, scale, d_qkv, hd)
 }
+
+#undef ATT_MASK_TAIL
+#undef ATT_TR_ACC
+#undef ATT_DS_FRAG
 
 }  // namespace mae
