@@ -304,6 +304,46 @@ int mae_engine_extract_features(mae_engine_t* e, const float* params, const void
                                 int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, void* workspace,
                                 int64_t workspace_bytes, float* feats, void* stream);
 
+/* MAE reconstruction (additive in ABI v4; scripts/evaluation/visualize_reconstruction.py of the reference, MAEReconstructor):
+ * the inverse of mae_patchify_gather, fused with the whole-image error sums.  One pass over the OUTPUT pixels produces up to
+ * three results from images (batch, C, S, S) in image_dtype (MAE_F32 normalised | MAE_U8 raw pixels, normalised in the read),
+ * pred (batch, num_mask, p*p*C) fp32 in the per-patch order (py, px, c) of x_pred / mae_patchify_gather, and idx_mask
+ * (batch, num_mask) int64 token ids:
+ *   recon  (batch, C, S, S): the normalised image with every patch n = idx_mask[b][j] - 1 replaced by pred[b][j]
+ *                            (_reconstruct_full_images, :198-234: patchify -> set_at_index -> unpatchify);
+ *   masked (batch, C, S, S): the normalised image with those patches set to `fill` (_create_masked_images, :170-190; the
+ *                            reference fills with 0.5, :185);
+ *   stats  (batch, 2) fp32 : per image sum (recon - orig)^2 and sum |recon - orig| -- the numerators of nn.MSELoss() /
+ *                            nn.L1Loss()(original, reconstructed) (:324-334).  The sums run over the replaced pixels (a visible
+ *                            pixel contributes exactly 0), accumulate in fp32 in a fixed order that depends on the image shape
+ *                            alone (no atomics: bit-identical from run to run and for any batch the image is part of).
+ * Each of recon / masked / stats may be NULL (not all three).  recon and masked are written in out_dtype: MAE_F32 = normalised
+ * values (visible pixels bit-identical to the normalised input, replaced ones bit-identical copies of pred); MAE_U8 = display
+ * pixels round_half_even(clamp(v * 0.5 + 0.5, 0, 1) * 255) (_tensor_to_image, :311-322, then mul(255).round()), bit-identical
+ * to the torch fp32 expression.  Every output byte is written exactly once; recon and masked may overlap neither images, pred nor each other (checked, partial
+ * overlaps included).
+ * Indices: an entry <= 0 (the class token, __remove_cls_token :192-196) or > num_patches is ignored -- never used as an index,
+ * its pred row is skipped.  The entries of one image must be distinct (with a repeated entry either of its pred rows may win).
+ * Limits, checked before any launch: image_size % patch_size == 0, batch * num_patches < 2^31, num_mask >= 1; fp32 images /
+ * outputs 16-byte aligned and uint8 ones 4-byte (4 / 1 when patch_size or image_size is no multiple of 4), pred 4-byte.  scratch: mae_reconstruct_scratch_bytes(...) bytes, 256-byte aligned (-1 = arguments
+ * outside the limits). */
+int64_t mae_reconstruct_scratch_bytes(int32_t batch, int32_t in_chans, int32_t image_size, int32_t patch_size);
+int mae_reconstruct_compose(const void* images, int32_t image_dtype, const float* pred, const int64_t* idx_mask,
+                            int32_t batch, int32_t in_chans, int32_t image_size, int32_t patch_size, int32_t num_mask,
+                            float fill, int32_t out_dtype, void* recon, void* masked, float* stats,
+                            void* scratch, int64_t scratch_bytes, void* stream);
+/* MAEReconstructor.reconstruct_batch (:127-168) in one call on one stream: mae_engine_forward_encoder(images, idx_keep), then
+ * mae_engine_forward_decoder(idx_keep, idx_mask), then mae_reconstruct_compose on its x_pred -- the same kernels, so x_pred is
+ * what those two calls return.  workspace: mae_engine_workspace_bytes(batch, num_keep) bytes (the activations it saves are
+ * simply unused, and those of any earlier forward are overwritten); x_pred (batch, num_mask, p*p*C) fp32 may be NULL (it then
+ * lives in the workspace); recon / masked / stats / scratch / fill / out_dtype as mae_reconstruct_compose.  The engine must
+ * predict pixels (pred_dim = 0).  Compose arguments are checked before anything is launched. */
+int mae_engine_reconstruct(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                           const int64_t* idx_keep, const int64_t* idx_mask, int32_t batch, int32_t num_keep, int32_t num_mask,
+                           float fill, int32_t out_dtype, void* workspace, int64_t workspace_bytes,
+                           float* x_pred /* may be NULL */, void* recon, void* masked, float* stats,
+                           void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Weighted k-NN probe on features (no reference counterpart; DINO's k-NN evaluation).
  * mae_knn_topk: for every query row the k bank rows of highest fp32 dot product, sorted by similarity descending, then bank
  *   index ascending; a NaN similarity is reported and sorted as -inf.  queries (num_queries, dim), bank (bank_size, dim) fp32,

@@ -91,6 +91,10 @@ SIGNATURES = {
     "mae_engine_refresh_transposed_range": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "mae_engine_features_workspace_bytes": (_i64, [_vp, _i32, _i32]),
     "mae_engine_extract_features": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "mae_reconstruct_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "mae_reconstruct_compose": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mae_engine_reconstruct": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
+                                         _vp, _i64, _vp]),
     "mae_knn_scratch_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "mae_knn_topk": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "mae_knn_vote": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _f32, _vp, _vp, _vp]),

@@ -50,6 +50,10 @@ template <class T> __device__ __forceinline__ T from_f(float x);
 template <> __device__ __forceinline__ float from_f<float>(float x) { return x; }
 template <> __device__ __forceinline__ bf16 from_f<bf16>(float x) { return (bf16)x; }  // v_cvt_pk_bf16_f32 (RNE, NaN-safe)
 
+// uint8 pixel -> ToTensor + Normalize(.5, .5): (u8 / 255 - 0.5) / 0.5 with an IEEE-rounded division, bit-identical to the torch
+// fp32 expression (src/data.py:15-24); every kernel that reads raw pixels uses this one expression
+__device__ __forceinline__ float norm_u8(unsigned u) { return (__fdiv_rn((float)u, 255.0f) - 0.5f) / 0.5f; }
+
 // 4-wide vector load/store in either activation type
 __device__ __forceinline__ f32x4 load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x4 load4(const bf16* p) {

@@ -749,6 +749,33 @@ extern "C" int mae_engine_forward_decoder(mae_engine_t* e, const float* params, 
   return forward_decoder_impl(c, pl, x_pred);
 }
 
+// MAEReconstructor.reconstruct_batch (scripts/evaluation/visualize_reconstruction.py:127-168): the two forwards above, then the compose
+extern "C" int mae_engine_reconstruct(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                      const int64_t* idx_keep, const int64_t* idx_mask, int32_t batch, int32_t num_keep, int32_t num_mask,
+                                      float fill, int32_t out_dtype, void* workspace, int64_t workspace_bytes, float* x_pred, void* recon,
+                                      void* masked, float* stats, void* scratch, int64_t scratch_bytes, void* stream) {
+  Plan pl;
+  MAE_TRY(check_call(e, params, wcache, batch, num_keep, workspace, workspace_bytes, &pl, "mae_engine_reconstruct"));
+  MAE_REQUIRE(images && idx_keep && idx_mask, "mae_engine_reconstruct: null images/indices");
+  MAE_TRY(check_image_dtype(image_dtype, "mae_engine_reconstruct"));
+  MAE_REQUIRE(e->PO == e->P, "mae_engine_reconstruct: the engine predicts latents (pred_dim = %d), not pixels", e->PO);
+  MAE_REQUIRE(num_mask == pl.m && pl.m > 0, "mae_engine_reconstruct: num_keep + num_mask must equal the sequence length (%d + %d != %d)", num_keep, num_mask, e->L);
+  hipStream_t s = (hipStream_t)stream;
+  Ctx c{e, params, (const char*)wcache, nullptr, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  float* pred = x_pred ? x_pred : c.buf<float>(pl.pred);
+  MAE_TRY(check_reconstruct_compose(images, image_dtype, pred, idx_mask, batch, e->C, e->img, e->p, num_mask, out_dtype, recon, masked, stats,
+                                    scratch, scratch_bytes));
+  MAE_TRY(launch_idx_to_i32(idx_keep, c.buf<int32_t>(pl.keep32), pl.Me, s));
+  MAE_TRY(launch_idx_to_i32(idx_mask, c.buf<int32_t>(pl.mask32), pl.Mp, s));
+  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
+  MAE_TRY(forward_decoder_impl(c, pl, pred));
+  const int64_t px = (int64_t)batch * e->C * e->img * e->img;
+  RUN(TK_DATA, 0, px * (image_dtype == MAE_U8 ? 1 : 4) + pl.Mp * e->P * 4 + px * (out_dtype == MAE_U8 ? 1 : 4) * ((recon != nullptr) + (masked != nullptr)),
+      launch_reconstruct_compose(images, image_dtype, pred, idx_mask, batch, e->C, e->img, e->p, num_mask, fill, out_dtype, recon, masked, stats,
+                                 scratch, scratch_bytes, s));
+  return 0;
+}
+
 extern "C" int mae_engine_backward(mae_engine_t* e, const float* params, const void* wcache, const float* d_pred,
                                    const float* d_x_encoded_extra, int32_t batch, int32_t num_keep, int32_t num_mask,
                                    void* workspace, int64_t workspace_bytes, float* grads, void* stream) {

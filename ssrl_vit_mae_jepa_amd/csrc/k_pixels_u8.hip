@@ -18,8 +18,6 @@ namespace {
 // The tokens of one band are listed in LDS behind the band image: n_tok slots, so that even an index list that names one
 // band over and over (legal for a caller-made idx_keep) is served completely.
 
-__device__ __forceinline__ float norm_u8(unsigned u) { return (__fdiv_rn((float)u, 255.0f) - 0.5f) / 0.5f; }
-
 // band (b, ph) -> LDS image [C][p][W] bytes (W % 4 == 0)
 __device__ __forceinline__ void load_band(const uint8_t* __restrict__ images, int64_t b, int ph, int C, int img, int p, unsigned* lds32) {
   const int wpr = img >> 2, words = C * p * wpr;

@@ -103,6 +103,17 @@ int launch_knn_topk(const float* queries, int64_t Q, const float* bank, int64_t 
 int launch_knn_vote(const float* sim, const int64_t* idx, int64_t Q, int k_stride, int k, const int64_t* labels, int C, float T, float* scores,
                     int64_t* pred, hipStream_t s);
 
+// ---- k_reconstruct.hip: MAE reconstruction compose (inverse of patchify_gather) + whole-image error sums ---------------------
+// recon / masked (B, C, S, S) in out_dt and stats (B, 2) = {sum d^2, sum |d|} from images, pred (B, m, p*p*C) and idx_mask (int64);
+// any of the three outputs may be null.  check_ validates everything on the host and launches nothing.
+int64_t reconstruct_scratch_bytes(int B, int C, int S, int p);
+int check_reconstruct_compose(const void* images, int img_dt, const float* pred, const int64_t* idx_mask, int B, int C, int S, int p, int m,
+                              int out_dt, const void* recon, const void* masked, const float* stats, const void* scratch,
+                              int64_t scratch_bytes);
+int launch_reconstruct_compose(const void* images, int img_dt, const float* pred, const int64_t* idx_mask, int B, int C, int S, int p, int m,
+                               float fill, int out_dt, void* recon, void* masked, float* stats, void* scratch, int64_t scratch_bytes,
+                               hipStream_t s);
+
 // ---- k_loss_optim.hip -----------------------------------------------------------------------------
 // loss[0] = mean((pred-target)^2); d_pred (dt, may be null) = grad_scale*2*(pred-target)/n.  scratch >= 1024+ floats
 int launch_mse(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -24,6 +24,75 @@ def _stream(device: torch.device) -> C.c_void_p:
 
 
 _ptr = _lib.ptr  # keeps the tensor referenced until the call it is an argument of has returned
+
+
+class Reconstruction(NamedTuple):
+    """What ``MaskedAutoencoder.reconstruct`` / ``unpatchify_compose`` return (a field that was not asked for is None)."""
+    masked: Optional[torch.Tensor]         # (B, C, S, S): the image with the masked patches set to ``fill``
+    reconstructed: Optional[torch.Tensor]  # (B, C, S, S): the image with the masked patches replaced by the prediction
+    x_pred: torch.Tensor                   # (B, m, p*p*C) fp32
+    idx_keep: Optional[torch.Tensor]       # (B, k) int64
+    idx_mask: torch.Tensor                 # (B, m) int64
+    sum_sq: Optional[torch.Tensor]         # (B,) fp32: sum over the image of (reconstructed - original)^2
+    sum_abs: Optional[torch.Tensor]        # (B,) fp32: sum over the image of |reconstructed - original|
+
+
+_OUT_DTYPES = {"float": (_lib.MAE_F32, torch.float32), "uint8": (_lib.MAE_U8, torch.uint8)}
+
+
+def _compose_buffers(images: torch.Tensor, out: str, patch_size: int, reconstructed: bool, masked: bool, stats: bool):
+    if out not in _OUT_DTYPES:
+        raise ValueError(f"out must be 'float' or 'uint8', got {out!r}")
+    B, C, S, _ = images.shape
+    need = lib.mae_reconstruct_scratch_bytes(B, C, S, int(patch_size))
+    if need < 0:
+        raise ValueError(f"reconstruction shape outside the kernel's limits (batch {B}, image {S}, patch {patch_size}): "
+                         "image_size must be a multiple of patch_size and batch * num_patches < 2^31")
+    dt = _OUT_DTYPES[out][1]
+    dev = images.device
+    return (torch.empty(images.shape, dtype=dt, device=dev) if reconstructed else None,
+            torch.empty(images.shape, dtype=dt, device=dev) if masked else None,
+            torch.empty(B, 2, dtype=torch.float32, device=dev) if stats else None,
+            torch.empty(need, dtype=torch.uint8, device=dev))
+
+
+def _distinct_rows(idx: torch.Tensor, lo: int, hi: int) -> bool:
+    """No value in [lo, hi] twice in one row (values outside are ignored by the kernels and may repeat).  A device sort and
+    one host sync."""
+    srt = idx.sort(dim=1).values
+    return not bool(((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= lo) & (srt[:, 1:] <= hi)).any())
+
+
+def unpatchify_compose(images: torch.Tensor, pred: torch.Tensor, idx_mask: torch.Tensor, patch_size: int, fill: float = 0.5,
+                       out: str = "float", reconstructed: bool = True, masked: bool = True, stats: bool = True,
+                       check_distinct: bool = True) -> Reconstruction:
+    """The inverse of ``patchify_gather`` for a ``pred`` (B, m, p*p*C) from anywhere (``mae_reconstruct_compose``, no model
+    involved): images (B, C, S, S) uint8 or normalised fp32 on the device, idx_mask (B, m) token ids (patch n = id - 1; an id
+    <= 0 or > num_patches is ignored together with its pred row; the ids in [1, num_patches] of one image must be distinct).
+    ``out`` "float" = normalised values, "uint8" = display pixels.  Returns a ``Reconstruction`` (idx_keep None).
+    ``check_distinct`` costs a device sort and a host sync per call; pass False for indices known to be distinct."""
+    if images.dim() != 4 or images.shape[2] != images.shape[3]:
+        raise ValueError(f"images must be (B, C, S, S), got {tuple(images.shape)}")
+    if not images.is_cuda:
+        raise RuntimeError("unpatchify_compose runs on the MI355X only (move the tensors to cuda; there is no CPU fallback)")
+    dev = images.device
+    images = images.contiguous() if images.dtype == torch.uint8 else images.to(dtype=torch.float32).contiguous()
+    B, C, S, _ = images.shape
+    p = int(patch_size)
+    if idx_mask.dim() != 2 or idx_mask.shape[0] != B or idx_mask.shape[1] < 1:
+        raise ValueError(f"idx_mask must be ({B}, m >= 1), got {tuple(idx_mask.shape)}")
+    idx_mask = idx_mask.to(device=dev, dtype=torch.int64).contiguous()
+    m = idx_mask.shape[1]
+    if p < 1 or tuple(pred.shape) != (B, m, p * p * C):
+        raise ValueError(f"pred must be ({B}, {m}, {p * p * C}), got {tuple(pred.shape)}")
+    if check_distinct and not _distinct_rows(idx_mask, 1, (S // max(p, 1)) ** 2):
+        raise ValueError("idx_mask: the entries of one image must be distinct")
+    pred = pred.to(device=dev, dtype=torch.float32).contiguous()
+    recon_t, masked_t, stats_t, scratch = _compose_buffers(images, out, p, reconstructed, masked, stats)
+    check(lib.mae_reconstruct_compose(_ptr(images), MaskedAutoencoder._img_dt(images), _ptr(pred), _ptr(idx_mask), B, C, S, p, m, float(fill),
+                                      _OUT_DTYPES[out][0], _ptr(recon_t), _ptr(masked_t), _ptr(stats_t), _ptr(scratch), scratch.numel(),
+                                      _stream(dev)))
+    return Reconstruction(masked_t, recon_t, pred, None, idx_mask, None if stats_t is None else stats_t[:, 0], None if stats_t is None else stats_t[:, 1])
 
 
 class Engine:
@@ -436,10 +505,12 @@ class MaskedAutoencoder(nn.Module):
         return max(1, int(self.sequence_length * (1 - r)))  # lightly random_token_mask
 
     # ------------------------------------------------------------------ reference API
-    def random_token_mask(self, batch_size: int, noise: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """lightly utils.random_token_mask (called at src/models/mae.py:79-83): idx_keep, idx_mask int64."""
+    def random_token_mask(self, batch_size: int, noise: Optional[torch.Tensor] = None,
+                          mask_ratio: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """lightly utils.random_token_mask (called at src/models/mae.py:79-83): idx_keep, idx_mask int64 (at ``mask_ratio``,
+        default ``self.mask_ratio``)."""
         dev = self._require_cuda()
-        L, k = self.sequence_length, self.num_keep()
+        L, k = self.sequence_length, self.num_keep(mask_ratio)
         if noise is None:
             noise = torch.rand(batch_size, L, device=dev)
         noise = noise.to(device=dev, dtype=torch.float32).contiguous()
@@ -597,6 +668,47 @@ class MaskedAutoencoder(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._trainable):
             return _MAEFunction.apply(self, images, idx_keep, idx_mask, *self._trainable)
         return self._run_forward(images, idx_keep, idx_mask)
+
+    @torch.no_grad()
+    def reconstruct(self, images: torch.Tensor, idx_keep: Optional[torch.Tensor] = None, idx_mask: Optional[torch.Tensor] = None,
+                    noise: Optional[torch.Tensor] = None, mask_ratio: Optional[float] = None, fill: float = 0.5,
+                    out: str = "float") -> Reconstruction:
+        """MAEReconstructor.reconstruct_batch of the reference (scripts/evaluation/visualize_reconstruction.py:127-168) in one
+        native call (``mae_engine_reconstruct``): encoder and decoder forward at the given mask, then the masked and the
+        reconstructed images and the per-image error sums.  Without indices the mask is drawn by ``random_token_mask``
+        (from ``noise`` when given) at ``mask_ratio`` (default ``self.mask_ratio``); caller-made indices must partition the
+        sequence (distinct, k + m = L; checking that costs a device sort and a host sync, a drawn mask needs none).  images uint8 or normalised fp32; ``out`` "float" = normalised images, "uint8" =
+        display pixels round(clamp(v * 0.5 + 0.5, 0, 1) * 255).  Overwrites the workspace: a backward pending on an
+        earlier forward raises afterwards."""
+        dev = self._require_cuda()
+        if self._dims["pred_dim"]:
+            raise ValueError("reconstruct needs a model that predicts pixels (pred_dim = 0)")
+        images = self._check_images(images.to(dev))
+        B, L = images.shape[0], self.sequence_length
+        if (idx_keep is None) != (idx_mask is None):
+            raise ValueError("pass both idx_keep and idx_mask, or neither")
+        if idx_keep is None:
+            idx_keep, idx_mask = self.random_token_mask(B, noise, mask_ratio)
+        else:
+            if noise is not None or mask_ratio is not None:
+                raise ValueError("noise / mask_ratio draw a mask: they cannot be combined with explicit indices")
+            idx_keep = self._check_idx(idx_keep.to(dev), B, "idx_keep")
+            idx_mask = self._check_idx(idx_mask.to(dev), B, "idx_mask")
+            if idx_keep.shape[1] + idx_mask.shape[1] != L:
+                raise ValueError("idx_keep and idx_mask must partition the sequence")
+            if not _distinct_rows(torch.cat([idx_keep, idx_mask], dim=1), 0, L - 1):
+                raise ValueError("idx_keep and idx_mask must partition the sequence: the entries of one image must be distinct")
+        k, m = idx_keep.shape[1], idx_mask.shape[1]
+        if m < 1:
+            raise ValueError("reconstruct: nothing is masked")
+        recon_t, masked_t, stats_t, scratch = _compose_buffers(images, out, self.patch_size, True, True, True)
+        ws = self._ws(B, k)
+        self._gen_enc += 1; self._gen_dec += 1
+        x_pred = torch.empty(B, m, self.patch_dim, dtype=torch.float32, device=dev)
+        check(lib.mae_engine_reconstruct(self._engine.handle, _ptr(self._arena), _ptr(self._weights()), _ptr(images), self._img_dt(images),
+                                         _ptr(idx_keep), _ptr(idx_mask), B, k, m, float(fill), _OUT_DTYPES[out][0], _ptr(ws), ws.numel(),
+                                         _ptr(x_pred), _ptr(recon_t), _ptr(masked_t), _ptr(stats_t), _ptr(scratch), scratch.numel(), _stream(dev)))
+        return Reconstruction(masked_t, recon_t, x_pred, idx_keep, idx_mask, stats_t[:, 0], stats_t[:, 1])
 
     # ------------------------------------------------------------------ fused step pieces (used by training.py)
     def grad_ready_points(self) -> List[int]:
