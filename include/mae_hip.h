@@ -58,8 +58,18 @@ typedef struct mae_config {
   int32_t act_dtype;      /* MAE_F32 | MAE_BF16 */
   int32_t pred_dim;       /* width of the prediction head: 0 = patch_size^2 * in_chans (MAE pixel targets);
                              embed_dim for the I-JEPA engine (latent targets), where the "decoder" is the predictor */
-  int32_t reserved[4];
+  int32_t norm_pix_loss;  /* != 0: the MAE loss regresses every masked patch standardised by its own mean and variance (see
+                             MAE_NORM_PIX_EPS); needs pred_dim = 0.  0 = raw normalised pixels */
+  int32_t reserved[3];
 } mae_config_t;
+
+/* Normalised-pixel targets (the MAE paper's norm_pix_loss), fixed definition.  For a patch x of P = p*p*C values in (py, px, c)
+ * order, as mae_patchify_gather returns it (uint8 pixels after (u8/255 - 0.5)/0.5):
+ *   mean = sum(x) / P;  var = sum((x - mean)^2) / (P - 1)  (unbiased, torch.var);  t = (x - mean) / sqrt(var + MAE_NORM_PIX_EPS).
+ * Statistics are fp32 and two-pass (centred, then squared); a constant patch gives var == 0 and t == 0 exactly.  The
+ * summation order depends on P alone: no atomics, a row is bit-identical from run to run, in any batch and from either
+ * image dtype. */
+#define MAE_NORM_PIX_EPS 1e-6
 
 typedef struct mae_engine mae_engine_t;
 
@@ -120,6 +130,20 @@ int mae_patchify_gather(const void* images, int32_t image_dtype, const int64_t* 
                         int32_t in_chans, int32_t image_size, int32_t patch_size, int32_t num_mask, float* target,
                         void* stream);
 
+/* mae_patchify_gather with every row standardised (MAE_NORM_PIX_EPS above): target (batch, num_mask, p*p*C) fp32; mean / rstd
+ * (batch, num_mask) fp32 = the row's mean and 1 / sqrt(var + eps), each may be NULL.  idx_mask entries are clamped like
+ * mae_patchify_gather's (patch clamp(id - 1, 0, num_patches - 1)).  Limits, checked before the launch: image_size %
+ * patch_size == 0, 2 <= p*p*C <= 10236 (four patches share the LDS); fp32 buffers 4-byte aligned.  Any patch size (not only
+ * multiples of 4) and both image dtypes. */
+int mae_patchify_gather_norm(const void* images, int32_t image_dtype, const int64_t* idx_mask, int32_t batch, int32_t in_chans,
+                             int32_t image_size, int32_t patch_size, int32_t num_mask, float* target, float* mean /* may be NULL */,
+                             float* rstd /* may be NULL */, void* stream);
+/* The inverse: out = pred * sqrt(var + eps) + mean with the statistics of the ORIGINAL image's patch idx_mask[b][j] -- takes a
+ * prediction made in normalised space back to pixel space.  pred, out (batch, num_mask, p*p*C) fp32; out may be pred itself
+ * (a partial overlap is rejected).  Limits as mae_patchify_gather_norm. */
+int mae_norm_pix_restore(const void* images, int32_t image_dtype, const float* pred, const int64_t* idx_mask, int32_t batch,
+                         int32_t in_chans, int32_t image_size, int32_t patch_size, int32_t num_mask, float* out, void* stream);
+
 /* The augmentation step in front of the path: transforms.RandomResizedCrop(96, scale=(0.8, 1.0)) +
  * RandomHorizontalFlip() on the uint8 image, before ToTensor (src/data.py:15-20).  params (batch, 5)
  * int32 = (top, left, height, width, flip) per image, drawn by the caller (torchvision's get_params
@@ -134,6 +158,14 @@ int mae_augment_crop_flip_u8(const uint8_t* images, const int32_t* params, int32
  * scratch: >= 4096 floats. */
 int mae_mse_loss(const float* pred, const float* target, int64_t n, float grad_scale, float* loss,
                  float* d_pred /* may be NULL */, float* scratch, void* stream);
+
+/* The loss of an engine created with norm_pix_loss, on caller buffers: mae_mse_loss between pred (batch, num_mask, p*p*C) fp32 and
+ * the standardised patches idx_mask of images, which are never written to memory (n = batch * num_mask * p*p*C).
+ * d_pred (may be NULL) in d_pred_dtype MAE_F32 | MAE_BF16; the target carries no gradient.  scratch: >= 4096 floats.
+ * Limits as mae_patchify_gather_norm; d_pred 4-byte (fp32) / 2-byte (bf16) aligned. */
+int mae_mse_loss_norm_pix(const float* pred, const void* images, int32_t image_dtype, const int64_t* idx_mask, int32_t batch,
+                          int32_t in_chans, int32_t image_size, int32_t patch_size, int32_t num_mask, float grad_scale, float* loss,
+                          void* d_pred /* may be NULL */, int32_t d_pred_dtype, float* scratch, void* stream);
 
 /* Backward of forward_decoder(forward_encoder(.)) given d_pred (batch, num_mask, P) fp32.
  * Writes (not accumulates) every trainable gradient into grads[0 .. trainable_elems).
@@ -166,7 +198,8 @@ int mae_engine_decoder_decode(mae_engine_t* e, const float* params, const void* 
                               void* workspace, int64_t workspace_bytes, float* out, void* stream);
 
 /* One fused pass: zero_grad + mask + forward + MSE + backward (training_step + loss.backward(),
- * src/training/mae.py:45-50).  noise (batch, L) fp32.  loss_out[0] = batch-mean MSE.
+ * src/training/mae.py:45-50).  noise (batch, L) fp32.  loss_out[0] = batch-mean MSE (against the standardised patches when the
+ * engine was created with norm_pix_loss: mae_mse_loss_norm_pix; nothing else of the step changes).
  * grad_scale multiplies the loss gradient (1/world_size for data-parallel sum-all-reduce).
  * idx_keep_out/idx_mask_out: optional int64 outputs (may be NULL). */
 int mae_engine_loss_and_grads(mae_engine_t* e, const float* params, const void* wcache, const void* images,
@@ -337,7 +370,10 @@ int mae_reconstruct_compose(const void* images, int32_t image_dtype, const float
  * what those two calls return.  workspace: mae_engine_workspace_bytes(batch, num_keep) bytes (the activations it saves are
  * simply unused, and those of any earlier forward are overwritten); x_pred (batch, num_mask, p*p*C) fp32 may be NULL (it then
  * lives in the workspace); recon / masked / stats / scratch / fill / out_dtype as mae_reconstruct_compose.  The engine must
- * predict pixels (pred_dim = 0).  Compose arguments are checked before anything is launched. */
+ * predict pixels (pred_dim = 0).  Compose arguments are checked before anything is launched.
+ * With norm_pix_loss the decoder's output lives in normalised space: x_pred still receives exactly what mae_engine_forward_decoder
+ * returns, while recon / masked / stats are composed from its de-normalised copy (mae_norm_pix_restore), which is left in the
+ * workspace's prediction slot (x_pred == NULL: de-normalised in place there).  stats is pixel-space error either way. */
 int mae_engine_reconstruct(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
                            const int64_t* idx_keep, const int64_t* idx_mask, int32_t batch, int32_t num_keep, int32_t num_mask,
                            float fill, int32_t out_dtype, void* workspace, int64_t workspace_bytes,

@@ -2,7 +2,8 @@
 "Original / Masked / Reconstructed" of the first training images and the MSE / L1 / PSNR block, with the forward, the image
 composition and the error sums taken from the engine (``mae_engine_reconstruct``).  Same flags (--config, --model_path,
 --output_path_suffix), plus --model_path random (the chance baseline), --synthetic_images, --num_samples, --mask_seed,
---batch_size, --output_dir (default assets/visualizations) and --eval_split val (the same statistics over the whole
+--batch_size, --norm_pix_loss (weights trained against normalised-pixel targets, for checkpoints that do not record it),
+--output_dir (default assets/visualizations) and --eval_split val (the same statistics over the whole
 validation split).  Writes the PNG and ``reconstruction_stats.json`` next to it.
 
     python -m scripts.evaluation.visualize_reconstruction --config configs/mae.yaml --model_path outputs/pretrain/mae_pretrain/checkpoints/last.ckpt
@@ -34,6 +35,9 @@ def parse_args(argv=None):
     p.add_argument("--batch_size", type=int, default=None, help="default: train.batch_size of the config")
     p.add_argument("--output_dir", type=str, default=str(Path("assets") / "visualizations"))
     p.add_argument("--eval_split", type=str, choices=["none", "val"], default="none", help="val: also the statistics of the whole validation split")
+    p.add_argument("--norm_pix_loss", action="store_true",
+                   help="the weights were trained against normalised-pixel targets (for a bare state dict such as vit-mae.pt, which "
+                        "records no flag; a Lightning checkpoint carries its own)")
     return p.parse_args(argv)
 
 
@@ -59,14 +63,17 @@ def main(argv=None):
     mask_ratio = config.get("pretrain", {}).get("mask_ratio_end", 0.75)
     reconstructor = MAEReconstructor(model_path=args.model_path, device=str(dev), mask_ratio=mask_ratio, mask_seed=args.mask_seed,
                                      precision=config.get("engine", {}).get("precision"))
-    reconstructor.load_model(model_cfg["general"], model_cfg["encoder"], model_cfg["decoder"])
+    general_cfg = dict(model_cfg["general"], norm_pix_loss=True) if args.norm_pix_loss else model_cfg["general"]
+    reconstructor.load_model(general_cfg, model_cfg["encoder"], model_cfg["decoder"])
+    if reconstructor.model.norm_pix_loss:
+        print("norm_pix_loss: the model predicts standardised patches; images and statistics are de-normalised (pixel space)")
 
     save_dir = Path(args.output_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
     png = save_dir / args.output_path_suffix
     sample = reconstructor.validate_reconstruction(dataloader=train_batches, num_samples=args.num_samples, save_path=str(png))
     res = dict(model_path=args.model_path, layout=reconstructor.layout, data="stl10" if args.synthetic_images is None else "synthetic",
-               mask_ratio=mask_ratio, mask_seed=args.mask_seed, figure=str(png), sample=sample)
+               mask_ratio=mask_ratio, mask_seed=args.mask_seed, norm_pix_loss=reconstructor.model.norm_pix_loss, figure=str(png), sample=sample)
     if args.eval_split == "val":
         res["val"] = evaluate_reconstruction(reconstructor.model, val_batches, mask_ratio=mask_ratio, mask_seed=args.mask_seed)
         print(f"\nValidation split ({res['val']['images']} images): MSE {res['val']['mse']:.6f}, MAE {res['val']['l1']:.6f}, "

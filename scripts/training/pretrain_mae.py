@@ -6,7 +6,7 @@ config.yaml, vit-mae.pt}``, seed 73, per-epoch LR / mask-ratio schedules, clip 1
 The Lightning Trainer is replaced by the plain loop below (Lightning is not installed here); data is either the STL-10
 ``unlabeled_X.bin`` file if present or synthetic 96x96x3 batches (there is no network for the download).
 
-    python -m scripts.training.pretrain_mae --config configs/mae.yaml [--resume_from CKPT] [--output_dir_suffix NAME]
+    python -m scripts.training.pretrain_mae --config configs/mae.yaml [--resume_from CKPT] [--output_dir_suffix NAME] [--norm_pix_loss]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 -m scripts.training.pretrain_mae ...
 """
 from __future__ import annotations
@@ -36,7 +36,18 @@ def parse_args(argv=None):
     parser.add_argument("--max_epochs", type=int, default=None)
     parser.add_argument("--max_steps_per_epoch", type=int, default=None)
     parser.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic images instead of STL-10")
+    parser.add_argument("--norm_pix_loss", action="store_true",
+                        help="regress patches standardised by their own mean and variance (overrides model.general.norm_pix_loss)")
     return parser.parse_args(argv)
+
+
+def apply_overrides(cfg: dict, args) -> dict:
+    """The config with the command line's overrides of YAML keys applied (a copy; ``cfg`` is not modified)."""
+    if getattr(args, "norm_pix_loss", False):
+        model = dict(cfg["model"])
+        model["general"] = dict(model.get("general", {}), norm_pix_loss=True)
+        cfg = dict(cfg, model=model)
+    return cfg
 
 
 def save_checkpoint(path: Path, module: MAEPretrainModule, epoch: int, weights_only: bool = False, extra=None) -> None:
@@ -56,7 +67,7 @@ def load_checkpoint(path: str, module: MAEPretrainModule):
 def main(argv=None):
     args = parse_args(argv)
     with open(args.config, "r") as f:
-        cfg = yaml.safe_load(f)
+        cfg = apply_overrides(yaml.safe_load(f), args)
     pre_cfg, model_cfg, log_cfg = cfg["pretrain"], cfg["model"], cfg["logging"]
     eng_cfg = cfg.get("engine", {})
     model_cfg = dict(model_cfg, general=dict(model_cfg["general"], engine_precision=eng_cfg.get("precision", "bf16")))
@@ -124,7 +135,7 @@ def main(argv=None):
         module.gather_optimizer_state()   # a collective when the optimizer is sharded (MAE_DP_SHARDED_OPT=1): rank 0's checkpoint needs every slice
         if rank == 0:
             rec = dict(epoch=epoch, train_loss=train_loss, val_loss=val_loss, lr=module.current_lr(), mask_ratio=module.model.mask_ratio,
-                       images_per_s=seen / dt)
+                       images_per_s=seen / dt, norm_pix_loss=module.model.norm_pix_loss)
             with open(log_path, "a") as f:
                 f.write(json.dumps(rec) + "\n")
             print(json.dumps(rec))

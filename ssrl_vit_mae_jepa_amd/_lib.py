@@ -21,13 +21,14 @@ POOL_CLS, POOL_MEAN, POOL_MEAN_PATCHES = 0, 1, 2
 FEAT_NONE, FEAT_L2 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL, EPI_GELU_ACT = 0, 1, 2, 3, 4, 5, 6
 ABI_VERSION = 4
+NORM_PIX_EPS = 1e-6  # MAE_NORM_PIX_EPS
 
 
 class MaeConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "image_size", "patch_size", "in_chans", "embed_dim", "depth", "num_heads",
-        "decoder_embed_dim", "decoder_depth", "decoder_num_heads", "mlp_ratio", "act_dtype", "pred_dim")] + [
-        ("reserved", C.c_int32 * 4)]
+        "decoder_embed_dim", "decoder_depth", "decoder_num_heads", "mlp_ratio", "act_dtype", "pred_dim", "norm_pix_loss")] + [
+        ("reserved", C.c_int32 * 3)]
 
 
 class MaeHipError(RuntimeError):
@@ -65,6 +66,9 @@ SIGNATURES = {
     "mae_engine_forward_encoder": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
     "mae_engine_forward_decoder": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "mae_patchify_gather": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_patchify_gather_norm": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mae_norm_pix_restore": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_mse_loss_norm_pix": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp]),
     "mae_augment_crop_flip_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "mae_mse_loss": (C.c_int, [_vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "mae_engine_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),

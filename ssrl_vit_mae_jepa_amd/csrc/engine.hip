@@ -609,6 +609,8 @@ extern "C" int mae_engine_create(const mae_config_t* cfg, mae_engine_t** out) {
   const int P = cfg->patch_size * cfg->patch_size * cfg->in_chans;
   MAE_REQUIRE(P % 4 == 0, "patch_size^2 * in_chans must be a multiple of 4");
   MAE_REQUIRE(cfg->pred_dim >= 0 && cfg->pred_dim % 4 == 0, "pred_dim must be 0 (pixels) or a multiple of 4");
+  MAE_REQUIRE(cfg->norm_pix_loss == 0 || cfg->pred_dim == 0,
+              "norm_pix_loss needs pixel targets: it cannot be combined with pred_dim = %d (the I-JEPA engine predicts latents)", cfg->pred_dim);
   mae_engine* e = new mae_engine();
   e->cfg = *cfg;
   e->act = cfg->act_dtype;
@@ -763,15 +765,23 @@ extern "C" int mae_engine_reconstruct(mae_engine_t* e, const float* params, cons
   hipStream_t s = (hipStream_t)stream;
   Ctx c{e, params, (const char*)wcache, nullptr, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
   float* pred = x_pred ? x_pred : c.buf<float>(pl.pred);
+  // norm_pix_loss: the decoder predicts in normalised space; the compose reads a de-normalised copy kept in the workspace's slot
+  float* pixels = e->cfg.norm_pix_loss ? c.buf<float>(pl.pred) : pred;
   MAE_TRY(check_reconstruct_compose(images, image_dtype, pred, idx_mask, batch, e->C, e->img, e->p, num_mask, out_dtype, recon, masked, stats,
                                     scratch, scratch_bytes));
+  if (pixels != pred)
+    MAE_TRY(check_reconstruct_compose(images, image_dtype, pixels, idx_mask, batch, e->C, e->img, e->p, num_mask, out_dtype, recon, masked, stats,
+                                      scratch, scratch_bytes));
   MAE_TRY(launch_idx_to_i32(idx_keep, c.buf<int32_t>(pl.keep32), pl.Me, s));
   MAE_TRY(launch_idx_to_i32(idx_mask, c.buf<int32_t>(pl.mask32), pl.Mp, s));
   MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
   MAE_TRY(forward_decoder_impl(c, pl, pred));
+  if (e->cfg.norm_pix_loss)
+    RUN(TK_DATA, 0, pl.Mp * e->P * (8 + (image_dtype == MAE_U8 ? 1 : 4)),
+        launch_norm_pix_restore(images, image_dtype, pred, idx_mask, 1, batch, num_mask, e->C, e->img, e->p, pixels, s));
   const int64_t px = (int64_t)batch * e->C * e->img * e->img;
   RUN(TK_DATA, 0, px * (image_dtype == MAE_U8 ? 1 : 4) + pl.Mp * e->P * 4 + px * (out_dtype == MAE_U8 ? 1 : 4) * ((recon != nullptr) + (masked != nullptr)),
-      launch_reconstruct_compose(images, image_dtype, pred, idx_mask, batch, e->C, e->img, e->p, num_mask, fill, out_dtype, recon, masked, stats,
+      launch_reconstruct_compose(images, image_dtype, pixels, idx_mask, batch, e->C, e->img, e->p, num_mask, fill, out_dtype, recon, masked, stats,
                                  scratch, scratch_bytes, s));
   return 0;
 }
@@ -860,7 +870,9 @@ static int loss_and_grads_impl(mae_engine_t* e, const float* params, const void*
   }
   MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
   MAE_TRY(forward_decoder_impl(c, pl, nullptr));
-  if (image_dtype == MAE_U8)
+  if (e->cfg.norm_pix_loss)
+    RUN(TK_LOSS, 0, pl.Mp * e->P * (4 + c.as) + pl.Mp * e->P * (image_dtype == MAE_U8 ? 1 : 4), launch_mse_norm_pix(c.buf<float>(pl.pred), images, image_dtype, c.buf<int32_t>(pl.mask32), 0, batch, pl.m, e->C, e->img, e->p, grad_scale, loss_out, c.buf<>(pl.dpred), e->act, c.buf<float>(pl.loss_scratch), s));
+  else if (image_dtype == MAE_U8)
     RUN(TK_LOSS, 0, pl.Mp * e->P * (4 + c.as) + (int64_t)batch * e->C * e->img * e->img, launch_mse_from_images_u8(c.buf<float>(pl.pred), (const uint8_t*)images, c.buf<int32_t>(pl.mask32), batch, pl.m, e->C, e->img, e->p, grad_scale, loss_out, c.buf<>(pl.dpred), e->act, c.buf<float>(pl.loss_scratch), s));
   else
     RUN(TK_LOSS, 0, pl.Mp * e->P * (8 + c.as), launch_mse_from_images(c.buf<float>(pl.pred), (const float*)images, c.buf<int32_t>(pl.mask32), batch, pl.m, e->C, e->img, e->p, grad_scale, loss_out, c.buf<>(pl.dpred), e->act, c.buf<float>(pl.loss_scratch), s));

@@ -70,6 +70,13 @@ __global__ void __launch_bounds__(256) mean_finalize_kernel(const float* __restr
   if (threadIdx.x == 0) out[0] = acc * inv_n;
 }
 
+int launch_mean_finalize(const float* partial, int nb, float inv_n, float* out, hipStream_t s) {
+  MAE_REQUIRE(partial && out && nb > 0, "mean_finalize: bad arguments");
+  hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, s, partial, nb, inv_n, out);
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_mse(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,
                int dpred_dt, float* scratch, hipStream_t s) {
   MAE_REQUIRE(pred && target && loss && scratch && n > 0 && n % 4 == 0, "mse: need n %% 4 == 0 and non-null buffers");

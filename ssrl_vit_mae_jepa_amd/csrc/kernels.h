@@ -114,6 +114,17 @@ int launch_reconstruct_compose(const void* images, int img_dt, const float* pred
                                float fill, int out_dt, void* recon, void* masked, float* stats, void* scratch, int64_t scratch_bytes,
                                hipStream_t s);
 
+// ---- k_normpix.hip: targets standardised per patch (norm_pix_loss); idx is int64 when idx64 != 0, else int32 ---------------------
+// mae_mse_loss with the target (x - mean) * rstd of the image's patches, never materialised; stage-1 partials in scratch (1024+ floats)
+int launch_mse_norm_pix(const float* pred, const void* images, int img_dt, const void* idx, int idx64, int B, int m, int C, int img, int p,
+                        float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch, hipStream_t s);
+// the materialised target (B*m, P) and, optionally, each row's mean / rstd
+int launch_patchify_gather_norm(const void* images, int img_dt, const void* idx, int idx64, int B, int m, int C, int img, int p, float* target,
+                                float* mean, float* rstd, hipStream_t s);
+// out = pred * sqrt(var + eps) + mean (out may be pred)
+int launch_norm_pix_restore(const void* images, int img_dt, const float* pred, const void* idx, int idx64, int B, int m, int C, int img, int p,
+                            float* out, hipStream_t s);
+
 // ---- k_loss_optim.hip -----------------------------------------------------------------------------
 // loss[0] = mean((pred-target)^2); d_pred (dt, may be null) = grad_scale*2*(pred-target)/n.  scratch >= 1024+ floats
 int launch_mse(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,
@@ -125,6 +136,8 @@ int launch_mse_from_images_band_f32(const float* pred, const float* images, cons
 int launch_mse_from_images(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img,
                            int p, float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch,
                            hipStream_t s);
+// out[0] = inv_n * sum of partial[0 .. nb): the second stage of the loss reductions
+int launch_mean_finalize(const float* partial, int nb, float inv_n, float* out, hipStream_t s);
 // stats[0] = ||g||_2, stats[1] = min(1, max_norm/(norm+1e-6)).  scratch >= 1024+ floats
 int launch_grad_norm(const float* g, int64_t n, float max_norm, float* stats, float* scratch, hipStream_t s);
 int launch_grad_sumsq(const float* g, int64_t n, float* out, float* scratch, hipStream_t s);

@@ -30,7 +30,7 @@ class Reconstruction(NamedTuple):
     """What ``MaskedAutoencoder.reconstruct`` / ``unpatchify_compose`` return (a field that was not asked for is None)."""
     masked: Optional[torch.Tensor]         # (B, C, S, S): the image with the masked patches set to ``fill``
     reconstructed: Optional[torch.Tensor]  # (B, C, S, S): the image with the masked patches replaced by the prediction
-    x_pred: torch.Tensor                   # (B, m, p*p*C) fp32
+    x_pred: torch.Tensor                   # (B, m, p*p*C) fp32: the decoder's output (normalised space under norm_pix_loss)
     idx_keep: Optional[torch.Tensor]       # (B, k) int64
     idx_mask: torch.Tensor                 # (B, m) int64
     sum_sq: Optional[torch.Tensor]         # (B,) fp32: sum over the image of (reconstructed - original)^2
@@ -93,6 +93,36 @@ def unpatchify_compose(images: torch.Tensor, pred: torch.Tensor, idx_mask: torch
                                       _OUT_DTYPES[out][0], _ptr(recon_t), _ptr(masked_t), _ptr(stats_t), _ptr(scratch), scratch.numel(),
                                       _stream(dev)))
     return Reconstruction(masked_t, recon_t, pred, None, idx_mask, None if stats_t is None else stats_t[:, 0], None if stats_t is None else stats_t[:, 1])
+
+
+def restore_pixels(images: torch.Tensor, pred: torch.Tensor, idx_mask: torch.Tensor, patch_size: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Take a prediction made against normalised-pixel targets back to pixel space (``mae_norm_pix_restore``, no model
+    involved): ``pred * sqrt(var + eps) + mean`` with the statistics of the original image's patch ``idx_mask[b][j] - 1``.
+    images (B, C, S, S) uint8 or normalised fp32 on the device, pred (B, m, p*p*C), idx_mask (B, m) token ids; ``out`` may be
+    ``pred`` itself.  The result is what ``unpatchify_compose`` expects."""
+    if images.dim() != 4 or images.shape[2] != images.shape[3]:
+        raise ValueError(f"images must be (B, C, S, S), got {tuple(images.shape)}")
+    if not images.is_cuda:
+        raise RuntimeError("restore_pixels runs on the MI355X only (move the tensors to cuda; there is no CPU fallback)")
+    dev = images.device
+    images = images.contiguous() if images.dtype == torch.uint8 else images.to(dtype=torch.float32).contiguous()
+    B, C, S, _ = images.shape
+    p = int(patch_size)
+    if idx_mask.dim() != 2 or idx_mask.shape[0] != B or idx_mask.shape[1] < 1:
+        raise ValueError(f"idx_mask must be ({B}, m >= 1), got {tuple(idx_mask.shape)}")
+    idx_mask = idx_mask.to(device=dev, dtype=torch.int64).contiguous()
+    m = idx_mask.shape[1]
+    if p < 1 or tuple(pred.shape) != (B, m, p * p * C):
+        raise ValueError(f"pred must be ({B}, {m}, {p * p * C}), got {tuple(pred.shape)}")
+    pred = pred.to(device=dev, dtype=torch.float32).contiguous()
+    if out is None:
+        out = torch.empty_like(pred)
+    elif out.shape != pred.shape or out.dtype != torch.float32 or out.device != dev:
+        raise ValueError("out must be an fp32 device tensor of pred's shape")
+    check(lib.mae_norm_pix_restore(_ptr(images), MaskedAutoencoder._img_dt(images), _ptr(pred), _ptr(idx_mask), B, C, S, p, m, _ptr(out),
+                                   _stream(dev)))
+    return out
 
 
 class Engine:
@@ -313,6 +343,10 @@ class MaskedAutoencoder(nn.Module):
             decoder_num_heads=int(decoder_cfg.get("decoder_num_heads", 6)),
             pred_dim=int(general_cfg.get("pred_dim", 0)),  # 0 = pixels (MAE); the I-JEPA net sets the encoder width
         )
+        # the MAE paper's norm_pix_loss: targets standardised per patch (no counterpart in the reference, whose target is the raw patch)
+        self.norm_pix_loss = bool(general_cfg.get("norm_pix_loss", False))
+        if self.norm_pix_loss:
+            cfg["norm_pix_loss"] = 1  # an absent key leaves the engine's config exactly as it was
         self._dims = cfg
         self._engine = Engine(cfg, precision)
         self.sequence_length = (cfg["image_size"] // cfg["patch_size"]) ** 2 + 1
@@ -625,12 +659,17 @@ class MaskedAutoencoder(nn.Module):
             return _DecoderFunction.apply(self, x_encoded, idx_keep, idx_mask, *self._dec_params)
         return self._run_decoder(x_encoded, idx_keep, idx_mask)
 
-    def patchify_gather(self, images: torch.Tensor, idx_mask: torch.Tensor) -> torch.Tensor:
-        """utils.patchify + get_at_index(clamp(idx_mask - 1, 0)) (src/models/mae.py:90-92)."""
+    def patchify_gather(self, images: torch.Tensor, idx_mask: torch.Tensor, normalize: Optional[bool] = None) -> torch.Tensor:
+        """utils.patchify + get_at_index(clamp(idx_mask - 1, 0)) (src/models/mae.py:90-92).  ``normalize`` (default: the
+        model's ``norm_pix_loss``): every row standardised by its own mean and unbiased variance (``mae_patchify_gather_norm``)."""
         dev = self._require_cuda()
         B, m = idx_mask.shape
         target = torch.empty(B, m, self.patch_dim, dtype=torch.float32, device=dev)
         images = self._check_images(images)
+        if self.norm_pix_loss if normalize is None else normalize:
+            check(lib.mae_patchify_gather_norm(_ptr(images), self._img_dt(images), _ptr(idx_mask, torch.int64), B, self.in_chans, self.image_size,
+                                              self.patch_size, m, _ptr(target), None, None, _stream(dev)))
+            return target
         check(lib.mae_patchify_gather(_ptr(images), self._img_dt(images), _ptr(idx_mask, torch.int64), B, self.in_chans, self.image_size,
                                      self.patch_size, m, _ptr(target), _stream(dev)))
         return target
@@ -661,7 +700,8 @@ class MaskedAutoencoder(nn.Module):
         return out
 
     def forward(self, images: torch.Tensor, noise: Optional[torch.Tensor] = None):
-        """src/models/mae.py:77-94: returns (x_pred, target), both (B, num_masked, p*p*C) fp32."""
+        """src/models/mae.py:77-94: returns (x_pred, target), both (B, num_masked, p*p*C) fp32.  Under ``norm_pix_loss`` the
+        target is the standardised patch, so ``MSELoss(x_pred, target)`` is the norm-pix loss."""
         self._require_cuda()
         images = self._check_images(images)
         idx_keep, idx_mask = self.random_token_mask(images.shape[0], noise)
@@ -679,7 +719,10 @@ class MaskedAutoencoder(nn.Module):
         (from ``noise`` when given) at ``mask_ratio`` (default ``self.mask_ratio``); caller-made indices must partition the
         sequence (distinct, k + m = L; checking that costs a device sort and a host sync, a drawn mask needs none).  images uint8 or normalised fp32; ``out`` "float" = normalised images, "uint8" =
         display pixels round(clamp(v * 0.5 + 0.5, 0, 1) * 255).  Overwrites the workspace: a backward pending on an
-        earlier forward raises afterwards."""
+        earlier forward raises afterwards.
+        Under ``norm_pix_loss`` the returned ``x_pred`` is the decoder's output in NORMALISED space (what ``forward_decoder``
+        returns); the images and the error sums are composed from its de-normalised copy (``restore_pixels``), so they are
+        pixel-space and comparable between models trained with and without the flag."""
         dev = self._require_cuda()
         if self._dims["pred_dim"]:
             raise ValueError("reconstruct needs a model that predicts pixels (pred_dim = 0)")
@@ -709,6 +752,11 @@ class MaskedAutoencoder(nn.Module):
                                          _ptr(idx_keep), _ptr(idx_mask), B, k, m, float(fill), _OUT_DTYPES[out][0], _ptr(ws), ws.numel(),
                                          _ptr(x_pred), _ptr(recon_t), _ptr(masked_t), _ptr(stats_t), _ptr(scratch), scratch.numel(), _stream(dev)))
         return Reconstruction(masked_t, recon_t, x_pred, idx_keep, idx_mask, stats_t[:, 0], stats_t[:, 1])
+
+    def restore_pixels(self, images: torch.Tensor, pred: torch.Tensor, idx_mask: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A prediction made against normalised-pixel targets (``x_pred`` of a ``norm_pix_loss`` model) back in pixel space:
+        the module-level ``restore_pixels`` at this model's patch size."""
+        return restore_pixels(self._check_images(images), pred, idx_mask, self.patch_size, out=out)
 
     # ------------------------------------------------------------------ fused step pieces (used by training.py)
     def grad_ready_points(self) -> List[int]:

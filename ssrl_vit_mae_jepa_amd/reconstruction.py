@@ -39,20 +39,43 @@ def mae_state_dict(ckpt: Any) -> Tuple[Dict[str, torch.Tensor], str]:
     return {k[len("model."):] if k.startswith("model.") else k: v for k, v in state.items()}, layout
 
 
+def checkpoint_norm_pix_loss(ckpt: Any) -> Optional[bool]:
+    """The ``norm_pix_loss`` flag a checkpoint was trained with (``hyper_parameters.model_cfg.general``, where
+    ``MAEPretrainModule.checkpoint_dict`` puts the model config), or None when the checkpoint does not record one."""
+    try:
+        general = ckpt["hyper_parameters"]["model_cfg"]["general"]
+    except (KeyError, TypeError):
+        return None
+    if not isinstance(general, dict) or "norm_pix_loss" not in general:
+        return None
+    return bool(general["norm_pix_loss"])
+
+
 def load_mae_checkpoint(src: Union[str, Path, Dict[str, Any]], model_cfg: Dict[str, Any],
                         precision: Optional[str] = None) -> Tuple[MaskedAutoencoder, str]:
     """A ``MaskedAutoencoder`` built from ``model_cfg`` (the ``model`` section of a config: general / encoder / decoder) with
     the weights of ``src`` (a path or a loaded checkpoint), and the name of the layout found (``mae_state_dict``).
     Unlike the reference's ``load_state_dict(strict=False)`` (:119) a missing or an unexpected tensor raises: a model that
-    silently kept its random decoder would still draw a figure."""
+    silently kept its random decoder would still draw a figure.
+    ``norm_pix_loss``: a Lightning-layout checkpoint records the flag it was trained with (``checkpoint_norm_pix_loss``); when
+    ``model_cfg`` does not set the key the recorded value is used (one line is printed), when both are there and differ the
+    call raises.  A bare state dict carries no flag: ``model_cfg`` decides."""
     general = dict(model_cfg.get("general", {}))
     if precision is not None:
         general["engine_precision"] = precision
-    model = MaskedAutoencoder(general, model_cfg.get("encoder", {}), model_cfg.get("decoder", {}))
     if isinstance(src, (str, Path)):
         if not Path(src).exists():
             raise FileNotFoundError(f"Checkpoint not found at {src}")
         src = torch.load(src, map_location="cpu", weights_only=True)
+    recorded = checkpoint_norm_pix_loss(src)
+    if recorded is not None:
+        if "norm_pix_loss" not in general:
+            general["norm_pix_loss"] = recorded
+            print(f"norm_pix_loss = {recorded} (taken from the checkpoint's hyper_parameters; the config does not set it)")
+        elif bool(general["norm_pix_loss"]) != recorded:
+            raise ValueError(f"norm_pix_loss: the config says {bool(general['norm_pix_loss'])} but the checkpoint was trained with {recorded}; "
+                             "a prediction made in one target space cannot be read in the other")
+    model = MaskedAutoencoder(general, model_cfg.get("encoder", {}), model_cfg.get("decoder", {}))
     state, layout = mae_state_dict(src)
     expected = list(model.state_dict().keys())
     missing = [k for k in expected if k not in state]
