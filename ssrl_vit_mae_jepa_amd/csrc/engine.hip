@@ -69,14 +69,7 @@ struct mae_engine {
   std::vector<BlockRefs> enc, dec;
   bool timers_on = false;
   TimerSlot timers[TK_COUNT];
-  // weight-gradient GEMMs are off the backward critical path (their results are only read by the optimizer): they
-  // are enqueued on a side stream so they overlap the HBM-bound LayerNorm / attention backward kernels of the main chain
-  int side_mode = -1;  // -1 = undecided, 0 = off, 1 = on
-  hipStream_t side = nullptr;
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
   PartialsTable ln_tab;  // LayerNorm dgamma / dbeta second stages queued by the current backward pass
-  hipEvent_t pending[4] = {nullptr, nullptr, nullptr, nullptr};  // last side-stream reader of dres_c / d_hidden / d_qkv / one-off buffers
 };
 
 namespace mae {
@@ -237,36 +230,6 @@ struct TimerScope {
   } while (0)
 
 // ---------------------------------------------------------------------------------------------------
-// side stream for the weight-gradient GEMMs
-// ---------------------------------------------------------------------------------------------------
-enum DepTag { DEP_DRESC = 0, DEP_HIDDEN = 1, DEP_QKV = 2, DEP_MISC = 3 };
-
-static bool side_enabled(mae_engine* e) {
-  if (e->side_mode < 0) {
-    const char* v = getenv("MAE_WGRAD_STREAM");  // opt-in: measured neutral on MI355X (the GEMMs already fill every CU)
-    e->side_mode = (v && v[0] == '1') ? 1 : 0;
-    if (e->side_mode == 1 && hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) e->side_mode = 0;
-  }
-  return e->side_mode == 1;
-}
-static hipEvent_t next_event(mae_engine* e) {
-  if (e->ev_used == e->ev_pool.size()) {
-    hipEvent_t ev;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return nullptr;
-    e->ev_pool.push_back(ev);
-  }
-  return e->ev_pool[e->ev_used++];
-}
-// the main stream must not overwrite a buffer the side stream may still be reading
-static int await_side(mae_engine* e, int tag, hipStream_t s) {
-  if (e->pending[tag]) {
-    MAE_HIP(hipStreamWaitEvent(s, e->pending[tag], 0));
-    e->pending[tag] = nullptr;
-  }
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------
 // helpers bound to one call
 // ---------------------------------------------------------------------------------------------------
 struct Ctx {
@@ -291,6 +254,11 @@ struct Ctx {
   const void* WT(int i) const { return wcache + 2 * (e->trainable_elems + e->params[i].t_off); }
   template <class T = void> T* buf(int64_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
+
+// the one place a Ctx is built; `ready` / `fwd_only` / `skip_final_norm` are set by the few callers that need them
+static Ctx make_ctx(mae_engine* e, const float* params, const void* wcache, float* grads, void* ws, void* stream) {
+  return Ctx{e, params, (const char*)wcache, grads, (char*)ws, (hipStream_t)stream, e->act, (int64_t)dtype_size(e->act)};
+}
 
 // algorithmic HBM bytes of one Linear launch: both operands, every output (the GELU epilogues write two) and the (M,N) side input
 // of the RESID (fp32 residual) / MUL / DGELU (output-typed) epilogues
@@ -320,29 +288,15 @@ static int dgrad(const Ctx& c, const void* dY, int wi, int64_t M, int N, int K, 
   return 0;
 }
 
-static int wgrad(const Ctx& c, const Plan& pl, const void* dY, const void* A, int64_t M, int N, int K, int wi, int bi, int tag) {
-  mae_engine* e = c.e;
-  hipStream_t s = c.s;
-  const bool side = side_enabled(e);
-  if (side) {  // fork: the side stream waits for everything enqueued so far (the producer of dY)
-    hipEvent_t ready = next_event(e);
-    MAE_REQUIRE(ready, "wgrad: cannot create an event");
-    MAE_HIP(hipEventRecord(ready, c.s));
-    MAE_HIP(hipStreamWaitEvent(e->side, ready, 0));
-    s = e->side;
-  }
+static int wgrad(const Ctx& c, const Plan& pl, const void* dY, const void* A, int64_t M, int N, int K, int wi, int bi) {
+  mae_engine* e = c.e; hipStream_t s = c.s;
   RUN(TK_WGRAD, 2.0 * M * N * K, (double)(M * (N + K) * c.as + (int64_t)N * K * 4),
       launch_linear_wgrad(dY, A, M, N, K, c.act, c.Gp(wi), bi >= 0 ? c.Gp(bi) : nullptr, c.buf<>(pl.wgrad_scratch), s));
-  if (side) {
-    hipEvent_t done = next_event(e);
-    MAE_REQUIRE(done, "wgrad: cannot create an event");
-    MAE_HIP(hipEventRecord(done, e->side));
-    e->pending[tag] = done;
-  }
   return 0;
 }
 
-// two weight gradients over the same rows in one launch (k_gemm.hip: launch_linear_wgrad_pair); main stream only
+// two weight gradients over the same rows in one launch (k_gemm_tn.hip: launch_linear_wgrad_pair, which falls back to two
+// launches under MAE_WGRAD_PAIR=0 or below its size threshold)
 static int wgrad_pair(const Ctx& c, const Plan& pl, int64_t M, const void* dY0, const void* A0, int N0, int K0, int w0, int b0,
                       const void* dY1, const void* A1, int N1, int K1, int w1, int b1) {
   mae_engine* e = c.e;
@@ -353,16 +307,29 @@ static int wgrad_pair(const Ctx& c, const Plan& pl, int64_t M, const void* dY0, 
   return 0;
 }
 
-// join: everything on the side stream is finished before the main stream continues
-static int join_side(const Ctx& c) {
-  mae_engine* e = c.e;
-  if (e->side_mode == 1) {
-    hipEvent_t done = next_event(e);
-    MAE_REQUIRE(done, "cannot create an event");
-    MAE_HIP(hipEventRecord(done, e->side));
-    MAE_HIP(hipStreamWaitEvent(c.s, done, 0));
-    for (auto& p : e->pending) p = nullptr;
-  }
+// y = LayerNorm(x [+ branch]) * gamma + beta over `rows` rows of width d (the rows row_map names, when given).  With a branch (in
+// y's dtype) the sum x + branch is also written to x_sum (fp32): the fused residual add.
+// Traffic per element: x in (4) + y out; the fused add also reads the branch and writes the sum (4).
+static int ln_fwd(const Ctx& c, const float* x, const void* branch, float* x_sum, const int32_t* row_map, const float* gamma,
+                  const float* beta, float eps, int64_t rows, int d, int y_dt, void* y, float* mean, float* rstd) {
+  mae_engine* e = c.e; hipStream_t s = c.s;
+  const int64_t ys = (int64_t)dtype_size(y_dt);
+  RUN(TK_LN_FWD, 0, rows * d * (branch ? 8 + 2 * ys : 4 + ys),
+      launch_layernorm_fwd(x, branch, x_sum, row_map, gamma, beta, eps, rows, d, y_dt, y, mean, rstd, s));
+  return 0;
+}
+
+// Backward of the LayerNorm with weight wi / bias bi for dy (activation dtype).  dx is written to (accumulate = 0) or added into
+// (accumulate = 1) the residual gradient pl.dres, and pl.dres_c, its activation-dtype copy, is rewritten.  The dgamma / dbeta column
+// sums go to the next partial-sum slot of this pass; their second stage is queued in e->ln_tab (flushed by reach_point / backward_end).
+// Traffic per element: x in, dres in and out (12); dy in and dres_c out (two activation elements).
+static int ln_bwd(const Ctx& c, const Plan& pl, const void* dy, const float* x, const int32_t* row_map, int wi, int bi, const float* mean,
+                  const float* rstd, int64_t rows, int d, int accumulate) {
+  mae_engine* e = c.e; hipStream_t s = c.s;
+  float* slot = c.buf<float>(pl.ln_partial + (int64_t)(e->ln_tab.n % PartialsTable::MAX) * pl.ln_partial_stride);
+  RUN(TK_LN_BWD, 0, rows * d * (12 + 2 * c.as),
+      launch_layernorm_bwd(dy, c.act, x, row_map, c.P(wi), mean, rstd, rows, d, accumulate, c.buf<float>(pl.dres), c.buf<>(pl.dres_c),
+                           c.Gp(wi), c.Gp(bi), slot, s, &e->ln_tab));
   return 0;
 }
 
@@ -374,15 +341,13 @@ static int block_forward(const Ctx& c, const Plan& pl, const BlockRefs& r, const
   mae_engine* e = c.e; hipStream_t s = c.s;
   const int hd = d / heads, hid = e->mlp * d;
   const float eps = 1e-6f;
-  if (add_prev) {
-    RUN(TK_LN_FWD, 0, M * d * (8 + 2 * c.as), launch_layernorm_fwd(c.buf<float>(x_prev), c.buf<>(pl.branch_b), c.buf<float>(x_in), nullptr, c.P(r.ln1_w), c.P(r.ln1_b), eps, M, d, c.act, c.buf<>(b.ln1), c.buf<float>(b.mean1), c.buf<float>(b.rstd1), s));
-  } else {
-    RUN(TK_LN_FWD, 0, M * d * (4 + c.as), launch_layernorm_fwd(c.buf<float>(x_in), nullptr, nullptr, nullptr, c.P(r.ln1_w), c.P(r.ln1_b), eps, M, d, c.act, c.buf<>(b.ln1), c.buf<float>(b.mean1), c.buf<float>(b.rstd1), s));
-  }
+  MAE_TRY(ln_fwd(c, c.buf<float>(add_prev ? x_prev : x_in), add_prev ? c.buf<>(pl.branch_b) : nullptr, add_prev ? c.buf<float>(x_in) : nullptr,
+                 nullptr, c.P(r.ln1_w), c.P(r.ln1_b), eps, M, d, c.act, c.buf<>(b.ln1), c.buf<float>(b.mean1), c.buf<float>(b.rstd1)));
   MAE_TRY(linear(c, c.buf<>(b.ln1), r.qkv_w, r.qkv_b, M, 3 * d, d, MAE_EPI_NONE, c.act, c.buf<>(b.qkv), nullptr, nullptr));
   RUN(TK_ATTN_FWD, 4.0 * Bn * heads * (double)T * T * hd, M * 4 * d * c.as, launch_attention_fwd(c.buf<>(b.qkv), Bn, T, heads, hd, c.act, c.buf<>(b.att), c.buf<float>(b.lse), s));
   MAE_TRY(linear(c, c.buf<>(b.att), r.proj_w, r.proj_b, M, d, d, MAE_EPI_NONE, c.act, c.buf<>(pl.branch_a), nullptr, nullptr));
-  RUN(TK_LN_FWD, 0, M * d * (8 + 2 * c.as), launch_layernorm_fwd(c.buf<float>(x_in), c.buf<>(pl.branch_a), c.buf<float>(b.x_mid), nullptr, c.P(r.ln2_w), c.P(r.ln2_b), eps, M, d, c.act, c.buf<>(b.ln2), c.buf<float>(b.mean2), c.buf<float>(b.rstd2), s));
+  MAE_TRY(ln_fwd(c, c.buf<float>(x_in), c.buf<>(pl.branch_a), c.buf<float>(b.x_mid), nullptr, c.P(r.ln2_w), c.P(r.ln2_b), eps, M, d, c.act,
+                 c.buf<>(b.ln2), c.buf<float>(b.mean2), c.buf<float>(b.rstd2)));
   if (c.fwd_only)
     MAE_TRY(linear(c, c.buf<>(b.ln2), r.fc1_w, r.fc1_b, M, hid, d, MAE_EPI_GELU_ACT, c.act, c.buf<>(b.fc1_act), nullptr, nullptr));
   else
@@ -391,60 +356,49 @@ static int block_forward(const Ctx& c, const Plan& pl, const BlockRefs& r, const
   return 0;
 }
 
-// partial-sum slot of the next LayerNorm backward of this pass (its reduction is queued in e->ln_tab)
-static float* ln_slot(const Ctx& c, const Plan& pl) { return c.buf<float>(pl.ln_partial + (int64_t)(c.e->ln_tab.n % PartialsTable::MAX) * pl.ln_partial_stride); }
-
-// in: dres (fp32) / dres_c (act copy) = gradient w.r.t. the block output; out: same buffers = gradient w.r.t. the block input
+// in: dres (fp32) / dres_c (act copy) = gradient w.r.t. the block output; out: same buffers = gradient w.r.t. the block input.
+// Each branch's two weight gradients go out as ONE launch, placed where both of their dY operands exist and before the
+// LayerNorm backward that rewrites dres_c (fc2 / proj read it).
 static int block_backward(const Ctx& c, const Plan& pl, const BlockRefs& r, const LayerBufs& b, int64_t M, int d, int heads, int Bn, int T,
                           int64_t x_in) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   const int hd = d / heads, hid = e->mlp * d;
-  float* dres = c.buf<float>(pl.dres);
   void* dres_c = c.buf<>(pl.dres_c);
-  if (!side_enabled(e)) {
-    // Each branch's two weight gradients go out as ONE launch, placed where both of their dY operands exist and before the
-    // LayerNorm backward that rewrites dres_c (fc2 / proj read it).  Same dependencies as the separate launches below.
-    MAE_TRY(dgrad(c, dres_c, r.fc2_w, M, d, hid, MAE_EPI_MUL, c.buf<>(pl.d_hidden), c.buf<>(b.fc1_pre)));
-    MAE_TRY(wgrad_pair(c, pl, M, dres_c, c.buf<>(b.fc1_act), d, hid, r.fc2_w, r.fc2_b, c.buf<>(pl.d_hidden), c.buf<>(b.ln2), hid, d, r.fc1_w, r.fc1_b));
-    MAE_TRY(dgrad(c, c.buf<>(pl.d_hidden), r.fc1_w, M, hid, d, MAE_EPI_NONE, c.buf<>(pl.d_ln), nullptr));
-    RUN(TK_LN_BWD, 0, M * d * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(pl.d_ln), c.act, c.buf<float>(b.x_mid), nullptr, c.P(r.ln2_w), c.buf<float>(b.mean2), c.buf<float>(b.rstd2), M, d, 1, dres, dres_c, c.Gp(r.ln2_w), c.Gp(r.ln2_b), ln_slot(c, pl), s, &e->ln_tab));
-    MAE_TRY(dgrad(c, dres_c, r.proj_w, M, d, d, MAE_EPI_NONE, c.buf<>(pl.d_att), nullptr));
-    RUN(TK_ATTN_BWD, 10.0 * Bn * heads * (double)T * T * hd, M * 9 * d * c.as, launch_attention_bwd(c.buf<>(b.qkv), c.buf<>(b.att), c.buf<>(pl.d_att), c.buf<float>(b.lse), Bn, T, heads, hd, c.act, c.buf<>(pl.d_qkv), s));
-    MAE_TRY(wgrad_pair(c, pl, M, dres_c, c.buf<>(b.att), d, d, r.proj_w, r.proj_b, c.buf<>(pl.d_qkv), c.buf<>(b.ln1), 3 * d, d, r.qkv_w, r.qkv_b));
-    MAE_TRY(dgrad(c, c.buf<>(pl.d_qkv), r.qkv_w, M, 3 * d, d, MAE_EPI_NONE, c.buf<>(pl.d_ln), nullptr));
-    RUN(TK_LN_BWD, 0, M * d * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(pl.d_ln), c.act, c.buf<float>(x_in), nullptr, c.P(r.ln1_w), c.buf<float>(b.mean1), c.buf<float>(b.rstd1), M, d, 1, dres, dres_c, c.Gp(r.ln1_w), c.Gp(r.ln1_b), ln_slot(c, pl), s, &e->ln_tab));
-    return 0;
-  }
-  // MLP branch (weight gradients on the side stream, MAE_WGRAD_STREAM=1: separate launches)
-  MAE_TRY(wgrad(c, pl, dres_c, c.buf<>(b.fc1_act), M, d, hid, r.fc2_w, r.fc2_b, DEP_DRESC));
-  MAE_TRY(await_side(e, DEP_HIDDEN, s));  // the previous block's fc1 wgrad reads d_hidden
+  // MLP branch
   MAE_TRY(dgrad(c, dres_c, r.fc2_w, M, d, hid, MAE_EPI_MUL, c.buf<>(pl.d_hidden), c.buf<>(b.fc1_pre)));
-  MAE_TRY(wgrad(c, pl, c.buf<>(pl.d_hidden), c.buf<>(b.ln2), M, hid, d, r.fc1_w, r.fc1_b, DEP_HIDDEN));
+  MAE_TRY(wgrad_pair(c, pl, M, dres_c, c.buf<>(b.fc1_act), d, hid, r.fc2_w, r.fc2_b, c.buf<>(pl.d_hidden), c.buf<>(b.ln2), hid, d, r.fc1_w, r.fc1_b));
   MAE_TRY(dgrad(c, c.buf<>(pl.d_hidden), r.fc1_w, M, hid, d, MAE_EPI_NONE, c.buf<>(pl.d_ln), nullptr));
-  MAE_TRY(await_side(e, DEP_DRESC, s));  // fc2 wgrad reads dres_c, which this kernel rewrites
-  RUN(TK_LN_BWD, 0, M * d * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(pl.d_ln), c.act, c.buf<float>(b.x_mid), nullptr, c.P(r.ln2_w), c.buf<float>(b.mean2), c.buf<float>(b.rstd2), M, d, 1, dres, dres_c, c.Gp(r.ln2_w), c.Gp(r.ln2_b), ln_slot(c, pl), s, &e->ln_tab));
+  MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(b.x_mid), nullptr, r.ln2_w, r.ln2_b, c.buf<float>(b.mean2), c.buf<float>(b.rstd2), M, d, 1));
   // attention branch
-  MAE_TRY(wgrad(c, pl, dres_c, c.buf<>(b.att), M, d, d, r.proj_w, r.proj_b, DEP_DRESC));
   MAE_TRY(dgrad(c, dres_c, r.proj_w, M, d, d, MAE_EPI_NONE, c.buf<>(pl.d_att), nullptr));
-  MAE_TRY(await_side(e, DEP_QKV, s));  // the previous block's qkv wgrad reads d_qkv
   RUN(TK_ATTN_BWD, 10.0 * Bn * heads * (double)T * T * hd, M * 9 * d * c.as, launch_attention_bwd(c.buf<>(b.qkv), c.buf<>(b.att), c.buf<>(pl.d_att), c.buf<float>(b.lse), Bn, T, heads, hd, c.act, c.buf<>(pl.d_qkv), s));
-  MAE_TRY(wgrad(c, pl, c.buf<>(pl.d_qkv), c.buf<>(b.ln1), M, 3 * d, d, r.qkv_w, r.qkv_b, DEP_QKV));
+  MAE_TRY(wgrad_pair(c, pl, M, dres_c, c.buf<>(b.att), d, d, r.proj_w, r.proj_b, c.buf<>(pl.d_qkv), c.buf<>(b.ln1), 3 * d, d, r.qkv_w, r.qkv_b));
   MAE_TRY(dgrad(c, c.buf<>(pl.d_qkv), r.qkv_w, M, 3 * d, d, MAE_EPI_NONE, c.buf<>(pl.d_ln), nullptr));
-  MAE_TRY(await_side(e, DEP_DRESC, s));  // proj wgrad reads dres_c
-  RUN(TK_LN_BWD, 0, M * d * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(pl.d_ln), c.act, c.buf<float>(x_in), nullptr, c.P(r.ln1_w), c.buf<float>(b.mean1), c.buf<float>(b.rstd1), M, d, 1, dres, dres_c, c.Gp(r.ln1_w), c.Gp(r.ln1_b), ln_slot(c, pl), s, &e->ln_tab));
+  MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(x_in), nullptr, r.ln1_w, r.ln1_b, c.buf<float>(b.mean1), c.buf<float>(b.rstd1), M, d, 1));
+  return 0;
+}
+
+static bool batch_in_bound(const mae_engine* e, int B) {  // the engine's batch bound: B * L * widest layer < 2^40
+  return (int64_t)B * e->L * std::max(3 * e->D, e->mlp * std::max(e->D, e->Dd)) < (1ll << 40);
+}
+
+// The rules every engine call shares: engine, arena and workspace present and aligned, the weight cache of a bf16 engine, the
+// batch bound.  Each entry point adds its own workspace plan and token-count rules.
+static int check_common(const mae_engine* e, const void* params, const void* wcache, int B, const void* ws, const char* who) {
+  MAE_REQUIRE(e, "%s: null engine", who);
+  MAE_REQUIRE(params && ws, "%s: null params/workspace", who);
+  MAE_REQUIRE(e->act == MAE_F32 || wcache, "%s: bf16 engine needs the weight cache", who);
+  MAE_REQUIRE(batch_in_bound(e, B), "%s: batch too large", who);
+  MAE_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)params & 15) == 0, "%s: workspace must be 256-byte aligned, params 16-byte", who);
   return 0;
 }
 
 static int check_call(const mae_engine* e, const void* params, const void* wcache, int B, int k, const void* ws, int64_t ws_bytes,
                       Plan* pl, const char* who) {
-  MAE_REQUIRE(e, "%s: null engine", who);
-  MAE_REQUIRE(params && ws, "%s: null params/workspace", who);
-  MAE_REQUIRE(e->act == MAE_F32 || wcache, "%s: bf16 engine needs the weight cache", who);
+  MAE_TRY(check_common(e, params, wcache, B, ws, who));
   MAE_REQUIRE(B > 0 && k >= 1 && k <= e->L, "%s: batch %d / num_keep %d out of range (L = %d)", who, B, k, e->L);
-  MAE_REQUIRE((int64_t)B * e->L * std::max(3 * e->D, e->mlp * std::max(e->D, e->Dd)) < (1ll << 40), "%s: batch too large", who);
   *pl = make_plan(e, B, k);
   MAE_REQUIRE(ws_bytes >= pl->total, "%s: workspace too small (%lld < %lld bytes)", who, (long long)ws_bytes, (long long)pl->total);
-  MAE_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)params & 15) == 0, "%s: workspace must be 256-byte aligned, params 16-byte", who);
   return 0;
 }
 
@@ -465,10 +419,13 @@ static int forward_encoder_impl(const Ctx& c, const Plan& pl, const void* images
   for (int i = 0; i < e->depth; ++i)
     MAE_TRY(block_forward(c, pl, e->enc[i], pl.enc[i], pl.Me, e->D, e->H, pl.B, pl.k, i ? pl.enc[i - 1].x_mid : 0, i > 0, pl.enc_x[i]));
   if (c.skip_final_norm) return 0;
-  RUN(TK_LN_FWD, 0, pl.Me * e->D * (8 + 2 * c.as), launch_layernorm_fwd(c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w), c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, c.act, c.buf<>(pl.enc_norm), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), s));
+  MAE_TRY(ln_fwd(c, c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w),
+                 c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, c.act, c.buf<>(pl.enc_norm), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd)));
   if (x_encoded_out) {
     if (c.act == MAE_F32) MAE_HIP(hipMemcpyAsync(x_encoded_out, c.buf<>(pl.enc_norm), (size_t)pl.Me * e->D * 4, hipMemcpyDeviceToDevice, s));
-    else RUN(TK_LN_FWD, 0, pl.Me * e->D * 8, launch_layernorm_fwd(c.buf<float>(pl.enc_x[e->depth]), nullptr, nullptr, nullptr, c.P(e->i_norm_w), c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, MAE_F32, x_encoded_out, c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), s));
+    else  // a second pass over the residual sum just formed writes the fp32 rows
+      MAE_TRY(ln_fwd(c, c.buf<float>(pl.enc_x[e->depth]), nullptr, nullptr, nullptr, c.P(e->i_norm_w), c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, MAE_F32,
+                     x_encoded_out, c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd)));
   }
   return 0;
 }
@@ -497,14 +454,15 @@ static int forward_decoder_impl(const Ctx& c, const Plan& pl, float* x_pred_out,
   for (int i = 0; i < e->dd; ++i)
     MAE_TRY(block_forward(c, pl, e->dec[i], pl.dec[i], pl.Md, e->Dd, e->Hd, pl.dec_B, pl.dec_T, i ? pl.dec[i - 1].x_mid : 0, i > 0, pl.dec_x[i]));
   // decoder_norm on the masked rows only; the residual add of the last MLP branch is done for exactly those rows
-  RUN(TK_LN_FWD, 0, pl.Mp * e->Dd * (8 + 2 * c.as), launch_layernorm_fwd(c.buf<float>(pl.dec[e->dd - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.dec_x[e->dd]), c.buf<int32_t>(pl.pred_rows), c.P(e->i_dn_w), c.P(e->i_dn_b), 1e-6f, pl.Mp, e->Dd, c.act, c.buf<>(pl.dec_norm), c.buf<float>(pl.dec_mean), c.buf<float>(pl.dec_rstd), s));
+  MAE_TRY(ln_fwd(c, c.buf<float>(pl.dec[e->dd - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.dec_x[e->dd]), c.buf<int32_t>(pl.pred_rows),
+                 c.P(e->i_dn_w), c.P(e->i_dn_b), 1e-6f, pl.Mp, e->Dd, c.act, c.buf<>(pl.dec_norm), c.buf<float>(pl.dec_mean), c.buf<float>(pl.dec_rstd)));
   MAE_TRY(linear(c, c.buf<>(pl.dec_norm), e->i_pred_w, e->i_pred_b, pl.Mp, e->PO, e->Dd, MAE_EPI_NONE, MAE_F32, x_pred_out ? (void*)x_pred_out : c.buf<>(pl.pred), nullptr, nullptr));
   return 0;
 }
 
 // Gradient-ready points (data-parallel overlap): point 0 = the whole decoder range of the gradient arena is final, point
 // i (1 .. depth-1) = encoder block depth-i and everything behind it, point depth = everything.  Reaching a point that the
-// caller gave an event for first retires what was deferred (LayerNorm dgamma / dbeta second stages, side-stream wgrads).
+// caller gave an event for first retires what was deferred (the LayerNorm dgamma / dbeta second stages).
 static int reach_point(const Ctx& c, int j) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   if (!c.ready || !c.ready[j]) return 0;
@@ -512,22 +470,16 @@ static int reach_point(const Ctx& c, int j) {
     RUN(TK_LN_BWD, 0, 0, launch_sum_partials_many(e->ln_tab, s));
     e->ln_tab.n = 0;  // slots are reused in stream order behind the reduction just enqueued
   }
-  MAE_TRY(join_side(c));
   MAE_HIP(hipEventRecord((hipEvent_t)c.ready[j], s));
   return 0;
 }
 
-static void backward_begin(const Ctx& c) {
-  mae_engine* e = c.e;
-  e->ev_used = 0;
-  for (auto& p : e->pending) p = nullptr;
-  e->ln_tab.n = 0;
-}
+static void backward_begin(const Ctx& c) { c.e->ln_tab.n = 0; }
 static int backward_end(const Ctx& c) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   if (e->ln_tab.n > 0) RUN(TK_LN_BWD, 0, 0, launch_sum_partials_many(e->ln_tab, s));  // dgamma / dbeta of every LayerNorm not yet retired: one launch
   e->ln_tab.n = 0;
-  return join_side(c);
+  return 0;
 }
 
 // Decoder half: dpred (act dtype) must already sit in the workspace; leaves d(x_encoded) (act dtype) in pl.d_ln and
@@ -535,14 +487,13 @@ static int backward_end(const Ctx& c) {
 static int backward_decoder_impl(const Ctx& c, const Plan& pl, const JepaSeq* jp = nullptr) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   float* dres = c.buf<float>(pl.dres);
-  void* dres_c = c.buf<>(pl.dres_c);
   // prediction head
-  MAE_TRY(wgrad(c, pl, c.buf<>(pl.dpred), c.buf<>(pl.dec_norm), pl.Mp, e->PO, e->Dd, e->i_pred_w, e->i_pred_b, DEP_MISC));
+  MAE_TRY(wgrad(c, pl, c.buf<>(pl.dpred), c.buf<>(pl.dec_norm), pl.Mp, e->PO, e->Dd, e->i_pred_w, e->i_pred_b));
   MAE_TRY(dgrad(c, c.buf<>(pl.dpred), e->i_pred_w, pl.Mp, e->PO, e->Dd, MAE_EPI_NONE, c.buf<>(pl.d_decn), nullptr));
   // decoder_norm over the masked rows only: every other row of the residual gradient is zero
-  MAE_TRY(await_side(e, DEP_DRESC, s));
-  RUN(TK_DATA, 0, (pl.Md - pl.Mp) * e->Dd * (4 + c.as), launch_zero_unpredicted_rows(jp ? nullptr : c.buf<int32_t>(pl.inv), pl.Md, pl.dec_T, pl.m, e->Dd, c.act, dres, dres_c, s));
-  RUN(TK_LN_BWD, 0, pl.Mp * e->Dd * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(pl.d_decn), c.act, c.buf<float>(pl.dec_x[e->dd]), c.buf<int32_t>(pl.pred_rows), c.P(e->i_dn_w), c.buf<float>(pl.dec_mean), c.buf<float>(pl.dec_rstd), pl.Mp, e->Dd, 0, dres, dres_c, c.Gp(e->i_dn_w), c.Gp(e->i_dn_b), ln_slot(c, pl), s, &e->ln_tab));
+  RUN(TK_DATA, 0, (pl.Md - pl.Mp) * e->Dd * (4 + c.as), launch_zero_unpredicted_rows(jp ? nullptr : c.buf<int32_t>(pl.inv), pl.Md, pl.dec_T, pl.m, e->Dd, c.act, dres, c.buf<>(pl.dres_c), s));
+  MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_decn), c.buf<float>(pl.dec_x[e->dd]), c.buf<int32_t>(pl.pred_rows), e->i_dn_w, e->i_dn_b, c.buf<float>(pl.dec_mean),
+                 c.buf<float>(pl.dec_rstd), pl.Mp, e->Dd, 0));
   for (int i = e->dd - 1; i >= 0; --i)
     MAE_TRY(block_backward(c, pl, e->dec[i], pl.dec[i], pl.Md, e->Dd, e->Hd, pl.dec_B, pl.dec_T, pl.dec_x[i]));
   if (jp)
@@ -550,7 +501,7 @@ static int backward_decoder_impl(const Ctx& c, const Plan& pl, const JepaSeq* jp
   else
     RUN(TK_DATA, 0, pl.Md * e->Dd * 4 + pl.Me * e->Dd * c.as, launch_decoder_assemble_bwd(dres, c.buf<int32_t>(pl.inv), c.buf<int32_t>(pl.keep32), pl.B, pl.k, e->L, e->Dd, c.act, c.buf<>(pl.d_xdec), c.Gp(e->i_dec_mask), c.buf<float>(pl.split_partial), s));
   // decoder_embed
-  MAE_TRY(wgrad(c, pl, c.buf<>(pl.d_xdec), c.buf<>(pl.enc_norm), pl.Me, e->Dd, e->D, e->i_de_w, e->i_de_b, DEP_MISC));
+  MAE_TRY(wgrad(c, pl, c.buf<>(pl.d_xdec), c.buf<>(pl.enc_norm), pl.Me, e->Dd, e->D, e->i_de_w, e->i_de_b));
   MAE_TRY(dgrad(c, c.buf<>(pl.d_xdec), e->i_de_w, pl.Me, e->Dd, e->D, MAE_EPI_NONE, c.buf<>(pl.d_ln), nullptr));
   return reach_point(c, 0);
 }
@@ -558,17 +509,15 @@ static int backward_decoder_impl(const Ctx& c, const Plan& pl, const JepaSeq* jp
 // Encoder half: d(x_encoded) (act dtype) sits in pl.d_ln; writes the arena range [0, offset(decoder.mask_token)).
 static int backward_encoder_impl(const Ctx& c, const Plan& pl) {
   mae_engine* e = c.e; hipStream_t s = c.s;
-  float* dres = c.buf<float>(pl.dres);
-  void* dres_c = c.buf<>(pl.dres_c);
-  MAE_TRY(await_side(e, DEP_DRESC, s));
-  RUN(TK_LN_BWD, 0, pl.Me * e->D * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(pl.d_ln), c.act, c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), pl.Me, e->D, 0, dres, dres_c, c.Gp(e->i_norm_w), c.Gp(e->i_norm_b), ln_slot(c, pl), s, &e->ln_tab));
+  MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(pl.enc_x[e->depth]), nullptr, e->i_norm_w, e->i_norm_b, c.buf<float>(pl.enc_mean),
+                 c.buf<float>(pl.enc_rstd), pl.Me, e->D, 0));
   for (int i = e->depth - 1; i >= 0; --i) {
     MAE_TRY(block_backward(c, pl, e->enc[i], pl.enc[i], pl.Me, e->D, e->H, pl.B, pl.k, pl.enc_x[i]));
     if (i > 0) MAE_TRY(reach_point(c, e->depth - i));
   }
   // token assembly and patch projection
-  RUN(TK_DATA, 0, pl.Me * e->D * (4 + c.as), launch_visible_grad_split(dres, c.buf<int32_t>(pl.keep32), pl.Me, e->D, c.act, c.buf<>(pl.dtok), c.Gp(e->i_cls), c.buf<float>(pl.split_partial), s));
-  MAE_TRY(wgrad(c, pl, c.buf<>(pl.dtok), c.buf<>(pl.patchA), pl.Me, e->D, e->P, e->i_patch_w, e->i_patch_b, DEP_MISC));
+  RUN(TK_DATA, 0, pl.Me * e->D * (4 + c.as), launch_visible_grad_split(c.buf<float>(pl.dres), c.buf<int32_t>(pl.keep32), pl.Me, e->D, c.act, c.buf<>(pl.dtok), c.Gp(e->i_cls), c.buf<float>(pl.split_partial), s));
+  MAE_TRY(wgrad(c, pl, c.buf<>(pl.dtok), c.buf<>(pl.patchA), pl.Me, e->D, e->P, e->i_patch_w, e->i_patch_b));
   return 0;
 }
 
@@ -659,8 +608,6 @@ extern "C" void mae_engine_destroy(mae_engine_t* e) {
   if (!e) return;
   for (auto& t : e->timers)
     for (auto& pr : t.ev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
-  if (e->side) (void)hipStreamDestroy(e->side);
   delete e;
 }
 
@@ -730,8 +677,8 @@ extern "C" int mae_engine_forward_encoder(mae_engine_t* e, const float* params, 
   MAE_TRY(check_call(e, params, wcache, batch, num_keep, workspace, workspace_bytes, &pl, "mae_engine_forward_encoder"));
   MAE_REQUIRE(images && idx_keep, "mae_engine_forward_encoder: null images/idx_keep");
   MAE_TRY(check_image_dtype(image_dtype, "mae_engine_forward_encoder"));
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, nullptr, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  hipStream_t s = c.s;
   MAE_TRY(launch_idx_to_i32(idx_keep, c.buf<int32_t>(pl.keep32), pl.Me, s));
   return forward_encoder_impl(c, pl, images, image_dtype, x_encoded);
 }
@@ -743,8 +690,8 @@ extern "C" int mae_engine_forward_decoder(mae_engine_t* e, const float* params, 
   MAE_TRY(check_call(e, params, wcache, batch, num_keep, workspace, workspace_bytes, &pl, "mae_engine_forward_decoder"));
   MAE_REQUIRE(idx_keep && idx_mask, "mae_engine_forward_decoder: null indices");
   MAE_REQUIRE(num_mask == pl.m, "mae_engine_forward_decoder: num_keep + num_mask must equal the sequence length (%d + %d != %d)", num_keep, num_mask, e->L);
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, nullptr, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  hipStream_t s = c.s;
   MAE_TRY(launch_idx_to_i32(idx_keep, c.buf<int32_t>(pl.keep32), pl.Me, s));
   MAE_TRY(launch_idx_to_i32(idx_mask, c.buf<int32_t>(pl.mask32), pl.Mp, s));
   if (x_encoded) MAE_TRY(launch_cast(x_encoded, MAE_F32, c.buf<>(pl.enc_norm), e->act, pl.Me * e->D, s));
@@ -762,8 +709,8 @@ extern "C" int mae_engine_reconstruct(mae_engine_t* e, const float* params, cons
   MAE_TRY(check_image_dtype(image_dtype, "mae_engine_reconstruct"));
   MAE_REQUIRE(e->PO == e->P, "mae_engine_reconstruct: the engine predicts latents (pred_dim = %d), not pixels", e->PO);
   MAE_REQUIRE(num_mask == pl.m && pl.m > 0, "mae_engine_reconstruct: num_keep + num_mask must equal the sequence length (%d + %d != %d)", num_keep, num_mask, e->L);
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, nullptr, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  hipStream_t s = c.s;
   float* pred = x_pred ? x_pred : c.buf<float>(pl.pred);
   // norm_pix_loss: the decoder predicts in normalised space; the compose reads a de-normalised copy kept in the workspace's slot
   float* pixels = e->cfg.norm_pix_loss ? c.buf<float>(pl.pred) : pred;
@@ -793,8 +740,8 @@ extern "C" int mae_engine_backward(mae_engine_t* e, const float* params, const v
   MAE_TRY(check_call(e, params, wcache, batch, num_keep, workspace, workspace_bytes, &pl, "mae_engine_backward"));
   MAE_REQUIRE(d_pred && grads, "mae_engine_backward: null d_pred/grads");
   MAE_REQUIRE(num_mask == pl.m && pl.m > 0, "mae_engine_backward: num_mask mismatch");
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, grads, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, grads, workspace, stream);
+  hipStream_t s = c.s;
   MAE_TRY(launch_cast(d_pred, MAE_F32, c.buf<>(pl.dpred), e->act, pl.Mp * e->PO, s));
   return backward_impl(c, pl, d_x_encoded_extra);
 }
@@ -806,8 +753,8 @@ extern "C" int mae_engine_backward_decoder(mae_engine_t* e, const float* params,
   MAE_TRY(check_call(e, params, wcache, batch, num_keep, workspace, workspace_bytes, &pl, "mae_engine_backward_decoder"));
   MAE_REQUIRE(d_pred && grads, "mae_engine_backward_decoder: null d_pred/grads");
   MAE_REQUIRE(num_mask == pl.m && pl.m > 0, "mae_engine_backward_decoder: num_mask mismatch");
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, grads, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, grads, workspace, stream);
+  hipStream_t s = c.s;
   MAE_TRY(launch_cast(d_pred, MAE_F32, c.buf<>(pl.dpred), e->act, pl.Mp * e->PO, s));
   backward_begin(c);
   MAE_TRY(backward_decoder_impl(c, pl));
@@ -822,8 +769,8 @@ extern "C" int mae_engine_backward_encoder(mae_engine_t* e, const float* params,
   Plan pl;
   MAE_TRY(check_call(e, params, wcache, batch, num_keep, workspace, workspace_bytes, &pl, "mae_engine_backward_encoder"));
   MAE_REQUIRE(d_x_encoded && grads, "mae_engine_backward_encoder: null d_x_encoded/grads");
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, grads, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, grads, workspace, stream);
+  hipStream_t s = c.s;
   MAE_TRY(launch_cast(d_x_encoded, MAE_F32, c.buf<>(pl.d_ln), e->act, pl.Me * e->D, s));
   backward_begin(c);
   MAE_TRY(backward_encoder_impl(c, pl));
@@ -838,18 +785,18 @@ extern "C" int mae_engine_decoder_decode(mae_engine_t* e, const float* params, c
   Plan pl;
   MAE_TRY(check_call(e, params, wcache, batch, 1, workspace, workspace_bytes, &pl, "mae_engine_decoder_decode"));
   MAE_REQUIRE(x && out, "mae_engine_decoder_decode: null x/out");
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, nullptr, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  hipStream_t s = c.s;
   MAE_TRY(launch_add_rows_pos(x, c.P(e->i_dec_pos), pl.Md, e->L, e->Dd, c.buf<float>(pl.dec_x[0]), s));
   for (int i = 0; i < e->dd; ++i)
     MAE_TRY(block_forward(c, pl, e->dec[i], pl.dec[i], pl.Md, e->Dd, e->Hd, pl.B, e->L, i ? pl.dec[i - 1].x_mid : 0, i > 0, pl.dec_x[i]));
   // the fused add + LayerNorm kernel reads the branch in its OUTPUT dtype: first pass in the activation dtype (forms the last
   // residual sum in dec_x[dd]; its normalised output goes to scratch), second pass writes fp32 rows for the caller
   float* stat = c.buf<float>(pl.dres);  // statistics of all B*L rows (dec_mean / dec_rstd hold the masked rows only)
-  MAE_TRY(launch_layernorm_fwd(c.buf<float>(pl.dec[e->dd - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.dec_x[e->dd]), nullptr,
-                               c.P(e->i_dn_w), c.P(e->i_dn_b), 1e-6f, pl.Md, e->Dd, c.act, c.buf<>(pl.d_ln), stat, stat + pl.Md, s));
-  return launch_layernorm_fwd(c.buf<float>(pl.dec_x[e->dd]), nullptr, nullptr, nullptr, c.P(e->i_dn_w), c.P(e->i_dn_b), 1e-6f, pl.Md,
-                              e->Dd, MAE_F32, out, stat, stat + pl.Md, s);
+  MAE_TRY(ln_fwd(c, c.buf<float>(pl.dec[e->dd - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.dec_x[e->dd]), nullptr, c.P(e->i_dn_w),
+                 c.P(e->i_dn_b), 1e-6f, pl.Md, e->Dd, c.act, c.buf<>(pl.d_ln), stat, stat + pl.Md));
+  return ln_fwd(c, c.buf<float>(pl.dec_x[e->dd]), nullptr, nullptr, nullptr, c.P(e->i_dn_w), c.P(e->i_dn_b), 1e-6f, pl.Md, e->Dd, MAE_F32, out,
+                stat, stat + pl.Md);
 }
 
 static int loss_and_grads_impl(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
@@ -861,8 +808,8 @@ static int loss_and_grads_impl(mae_engine_t* e, const float* params, const void*
   MAE_REQUIRE(images && noise && grads && loss_out, "%s: null argument", who);
   MAE_TRY(check_image_dtype(image_dtype, who));
   MAE_REQUIRE(pl.m > 0, "%s: nothing is masked", who);
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, grads, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, grads, workspace, stream);
+  hipStream_t s = c.s;
   c.ready = ready;
   {
     TimerScope ts(e, TK_DATA, 0, (double)pl.Md * 12, s);
@@ -963,16 +910,15 @@ extern "C" int mae_engine_jepa_loss_and_grads(mae_engine_t* e, const float* para
                                               void* workspace, int64_t workspace_bytes, float* grads, float* loss_out, float* h_out,
                                               float* pred_out, void* const* ready_events, int32_t num_ready, void* stream) {
   const char* who = "mae_engine_jepa_loss_and_grads";
-  MAE_REQUIRE(e, "%s: null engine", who);
+  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
+  MAE_TRY(check_common(e, target_params, target_wcache, batch, workspace, who));  // the EMA arena and its weight cache: same rules
   MAE_REQUIRE(e->PO == e->D, "%s: the engine was not created with pred_dim = embed_dim (I-JEPA predicts latents of the encoder width)", who);
-  MAE_REQUIRE(params && target_params && images && idx_context && idx_target && workspace && loss_out, "%s: null argument", who);
-  MAE_REQUIRE(e->act == MAE_F32 || (wcache && target_wcache), "%s: bf16 engine needs both weight caches", who);
+  MAE_REQUIRE(images && idx_context && idx_target && loss_out, "%s: null argument", who);
   MAE_REQUIRE(batch > 0 && num_context >= 1 && num_blocks >= 1 && block_tokens >= 1 && num_context + block_tokens <= e->L - 1 + block_tokens &&
               num_context < e->L && block_tokens < e->L, "%s: bad token counts (context %d, blocks %d x %d, %d patches)", who, num_context, num_blocks, block_tokens, e->L - 1);
   MAE_REQUIRE(loss_kind == MAE_LOSS_MSE || loss_kind == MAE_LOSS_SMOOTH_L1, "%s: loss_kind must be MAE_LOSS_MSE or MAE_LOSS_SMOOTH_L1", who);
   MAE_REQUIRE(!ready_events || num_ready == e->depth + 1, "%s: need one event slot per gradient-ready point (%d)", who, e->depth + 1);
   MAE_TRY(check_image_dtype(image_dtype, who));
-  MAE_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)params & 15) == 0 && ((uintptr_t)target_params & 15) == 0, "%s: workspace must be 256-byte aligned, params 16-byte", who);
   const JepaPlan jp = make_jepa_plan(e, batch, num_context, num_blocks, block_tokens);
   MAE_REQUIRE(workspace_bytes >= jp.total, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)jp.total);
   hipStream_t s = (hipStream_t)stream;
@@ -987,7 +933,7 @@ extern "C" int mae_engine_jepa_loss_and_grads(mae_engine_t* e, const float* para
   MAE_TRY(launch_idx_to_i32(idx_target, tgt32, Mp, s));
   // ---- phase A: target encoder over all patch tokens (EMA weights), fp32 output, parameter-free LayerNorm of the target rows
   {
-    Ctx c{e, target_params, (const char*)target_wcache, nullptr, ws + jp.phase, s, e->act, (int64_t)dtype_size(e->act)};
+    Ctx c = make_ctx(e, target_params, target_wcache, nullptr, ws + jp.phase, stream);
     c.fwd_only = true;
     float* xenc = reinterpret_cast<float*>(ws + jp.phase + jp.xenc);
     MAE_TRY(launch_iota_tokens(c.buf<int32_t>(jp.tgt.keep32), batch, N, s));
@@ -996,12 +942,12 @@ extern "C" int mae_engine_jepa_loss_and_grads(mae_engine_t* e, const float* para
     MAE_TRY(launch_fill(reinterpret_cast<float*>(ws + jp.ones), 1.0f, e->D, s));
     MAE_HIP(hipMemsetAsync(ws + jp.zeros, 0, (size_t)e->D * 4, s));
     float* stat = reinterpret_cast<float*>(ws + jp.stat);
-    RUN(TK_LN_FWD, 0, Mp * e->D * 8, launch_layernorm_fwd(xenc, nullptr, nullptr, tgt_rows, reinterpret_cast<float*>(ws + jp.ones), reinterpret_cast<float*>(ws + jp.zeros),
-                                                          1e-5f, Mp, e->D, MAE_F32, h, stat, stat + Mp, s));  // F.layer_norm default eps
+    MAE_TRY(ln_fwd(c, xenc, nullptr, nullptr, tgt_rows, reinterpret_cast<float*>(ws + jp.ones), reinterpret_cast<float*>(ws + jp.zeros),
+                   1e-5f, Mp, e->D, MAE_F32, h, stat, stat + Mp));  // F.layer_norm default eps
   }
   if (!grads) return 0;  // targets only
   // ---- phase B: context encoder, predictor, loss, backward
-  Ctx c{e, params, (const char*)wcache, grads, ws + jp.phase, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, grads, ws + jp.phase, stream);
   c.ready = ready_events;
   const Plan& pl = jp.ctx;
   MAE_HIP(hipMemcpyAsync(c.buf<int32_t>(pl.keep32), ctx32, (size_t)batch * num_context * 4, hipMemcpyDeviceToDevice, s));
@@ -1016,6 +962,20 @@ extern "C" int mae_engine_jepa_loss_and_grads(mae_engine_t* e, const float* para
   return backward_impl(c, pl, nullptr, &seq);
 }
 
+// Adam's bias corrections 1 - beta^step of the 1-based step, computed in double
+struct AdamBias { float c1, c2; };
+static AdamBias adam_bias(float beta1, float beta2, int64_t step) {
+  return {(float)(1.0 - std::pow((double)beta1, (double)step)), (float)(1.0 - std::pow((double)beta2, (double)step))};
+}
+
+// [lo, lo + count) lies inside the trainable range of the arena, on 4-element boundaries (the optimizer kernels take multiples of 4 elements)
+static int check_arena_range(const mae_engine* e, int64_t lo, int64_t count, const char* who) {
+  MAE_REQUIRE(lo >= 0 && count >= 0 && lo % 4 == 0 && count % 4 == 0 && lo + count <= e->trainable_elems,
+              "%s: range [%lld, +%lld) outside the %lld trainable elements or not a multiple of 4", who, (long long)lo, (long long)count,
+              (long long)e->trainable_elems);
+  return 0;
+}
+
 static int optimizer_step_impl(mae_engine_t* e, float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* wcache,
                                float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, int64_t step,
                                float* stats_out, float* scratch, float* ema_target, void* ema_wcache, float ema_momentum, void* stream) {
@@ -1024,11 +984,10 @@ static int optimizer_step_impl(mae_engine_t* e, float* params, float* grads, flo
   MAE_REQUIRE(e->act == MAE_F32 || wcache, "mae_engine_optimizer_step: bf16 engine needs the weight cache");
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = e->trainable_elems;
-  const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-  const float bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));
+  const AdamBias bc = adam_bias(beta1, beta2, step);
   RUN(TK_OPTIM, 0, n * 4, launch_grad_norm(grads, n, max_norm, stats_out, scratch, s));
   RUN(TK_OPTIM, 0, n * (28 + (e->act == MAE_BF16 ? 2 : 0)),
-      launch_adamw(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, stats_out,
+      launch_adamw(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc.c1, bc.c2, stats_out,
                    e->act == MAE_BF16 ? reinterpret_cast<bf16*>(wcache) : nullptr, s, ema_target,
                    e->act == MAE_BF16 ? reinterpret_cast<bf16*>(ema_wcache) : nullptr, ema_target ? e->params[e->i_dec_mask].offset : 0, ema_momentum));
   if (e->act == MAE_BF16) RUN(TK_OPTIM, 0, e->trans_elems * 6, refresh_transposed(e, params, wcache, s));
@@ -1046,9 +1005,7 @@ extern "C" int mae_engine_optimizer_step(mae_engine_t* e, float* params, float* 
 extern "C" int mae_engine_grad_sumsq_range(mae_engine_t* e, const float* grads, int64_t lo, int64_t count, float* sumsq_out, float* scratch,
                                            void* stream) {
   MAE_REQUIRE(e && grads && sumsq_out && scratch, "mae_engine_grad_sumsq_range: null argument");
-  MAE_REQUIRE(lo >= 0 && count >= 0 && lo % 4 == 0 && count % 4 == 0 && lo + count <= e->trainable_elems,
-              "mae_engine_grad_sumsq_range: range [%lld, +%lld) outside the %lld trainable elements or not a multiple of 4", (long long)lo,
-              (long long)count, (long long)e->trainable_elems);
+  MAE_TRY(check_arena_range(e, lo, count, "mae_engine_grad_sumsq_range"));
   return launch_grad_sumsq(grads + lo, count, sumsq_out, scratch, (hipStream_t)stream);
 }
 
@@ -1062,16 +1019,13 @@ extern "C" int mae_engine_adamw_range(mae_engine_t* e, float* params, const floa
                                       int64_t lo, int64_t count, void* stream) {
   MAE_REQUIRE(e && params && grads && exp_avg && exp_avg_sq && stats, "mae_engine_adamw_range: null argument");
   MAE_REQUIRE(step >= 1, "mae_engine_adamw_range: step is 1-based");
-  MAE_REQUIRE(lo >= 0 && count >= 0 && lo % 4 == 0 && count % 4 == 0 && lo + count <= e->trainable_elems,
-              "mae_engine_adamw_range: range [%lld, +%lld) outside the %lld trainable elements or not a multiple of 4", (long long)lo,
-              (long long)count, (long long)e->trainable_elems);
+  MAE_TRY(check_arena_range(e, lo, count, "mae_engine_adamw_range"));
   MAE_REQUIRE(e->act == MAE_F32 || wcache, "mae_engine_adamw_range: bf16 engine needs the weight cache");
   if (count == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-  const float bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));
+  const AdamBias bc = adam_bias(beta1, beta2, step);
   RUN(TK_OPTIM, 0, count * (28 + (e->act == MAE_BF16 ? 2 : 0)),
-      launch_adamw(params + lo, grads + lo, exp_avg + lo, exp_avg_sq + lo, count, lr, beta1, beta2, eps, weight_decay, bc1, bc2, stats,
+      launch_adamw(params + lo, grads + lo, exp_avg + lo, exp_avg_sq + lo, count, lr, beta1, beta2, eps, weight_decay, bc.c1, bc.c2, stats,
                    e->act == MAE_BF16 ? reinterpret_cast<bf16*>(wcache) + lo : nullptr, s));
   return 0;   // the bf16 operand copies of the OTHER ranks' shards and the transposes: mae_engine_refresh_weights after the all-gather
 }
@@ -1142,8 +1096,8 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
     MAE_REQUIRE(train_blocks < 0 || grads, "%s: train_blocks >= 0 needs the gradient arena", who);
     MAE_REQUIRE(!train_embed || pos_grad, "%s: train_embed needs the pos_embed gradient buffer", who);
   }
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, grads, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, grads, workspace, stream);
+  hipStream_t s = c.s;
   const bool enc_bwd = train && train_blocks >= 0;
   c.fwd_only = !enc_bwd;  // the linear probe and evaluation save no GELU derivative
   const int B = batch, L = e->L, D = e->D, C = num_classes;
@@ -1162,22 +1116,22 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
                                                                                     c.buf<float>(cp.head_partial), c.buf<float>(cp.head_sum), head_grads, s));
   if (!enc_bwd) return 0;
   float* dres = c.buf<float>(pl.dres);
-  void* dres_c = c.buf<>(pl.dres_c);
   backward_begin(c);
-  MAE_TRY(await_side(e, DEP_DRESC, s));
   if (cls) {
     // only the B class-token rows carry gradient: zero the rest of the residual gradient, then a row-mapped final LayerNorm backward
-    RUN(TK_DATA, 0, (pl.Me - B) * D * (4 + c.as), launch_zero_token_rows(pl.Me, L, D, e->act, dres, dres_c, s));
-    RUN(TK_LN_BWD, 0, (int64_t)B * D * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(cp.dpooled), e->act, c.buf<float>(pl.enc_x[e->depth]), c.buf<int32_t>(cp.cls_rows), c.P(e->i_norm_w), c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c), B, D, 0, dres, dres_c, c.Gp(e->i_norm_w), c.Gp(e->i_norm_b), ln_slot(c, pl), s, &e->ln_tab));
+    RUN(TK_DATA, 0, (pl.Me - B) * D * (4 + c.as), launch_zero_token_rows(pl.Me, L, D, e->act, dres, c.buf<>(pl.dres_c), s));
+    MAE_TRY(ln_bwd(c, pl, c.buf<>(cp.dpooled), c.buf<float>(pl.enc_x[e->depth]), c.buf<int32_t>(cp.cls_rows), e->i_norm_w, e->i_norm_b,
+                   c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c), B, D, 0));
   } else {
-    RUN(TK_LN_BWD, 0, pl.Me * D * (12 + 2 * c.as), launch_layernorm_bwd(c.buf<>(pl.d_ln), e->act, c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), pl.Me, D, 0, dres, dres_c, c.Gp(e->i_norm_w), c.Gp(e->i_norm_b), ln_slot(c, pl), s, &e->ln_tab));
+    MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(pl.enc_x[e->depth]), nullptr, e->i_norm_w, e->i_norm_b, c.buf<float>(pl.enc_mean),
+                   c.buf<float>(pl.enc_rstd), pl.Me, D, 0));
   }
   for (int i = e->depth - 1; i >= e->depth - train_blocks; --i)  // the trainable suffix only: the sweep stops below blocks[depth-n]
     MAE_TRY(block_backward(c, pl, e->enc[i], pl.enc[i], pl.Me, D, e->H, B, L, pl.enc_x[i]));
   if (train_embed) {
     // token assembly: d pos_embed, d cls_token and the patch rows from one read of dres, then the patch projection
     RUN(TK_DATA, 0, pl.Me * D * (4 + c.as), launch_full_grad_split(dres, B, L, D, e->act, c.buf<>(pl.dtok), pos_grad, c.Gp(e->i_cls), c.buf<float>(cp.pos_partial), s));
-    MAE_TRY(wgrad(c, pl, c.buf<>(pl.dtok), c.buf<>(pl.patchA), pl.Me, D, e->P, e->i_patch_w, e->i_patch_b, DEP_MISC));
+    MAE_TRY(wgrad(c, pl, c.buf<>(pl.dtok), c.buf<>(pl.patchA), pl.Me, D, e->P, e->i_patch_w, e->i_patch_b));
   }
   return backward_end(c);
 }
@@ -1218,7 +1172,7 @@ extern "C" int mae_engine_classifier_loss_and_grads(mae_engine_t* e, const float
 extern "C" int64_t mae_engine_features_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls) {
   if (!e || batch <= 0 || (with_cls != 0 && with_cls != 1) || e->D % 4 != 0 || e->D > 1024) return -1;  // the pool kernel's width limit
   const int T = with_cls ? e->L : e->L - 1;
-  if ((int64_t)batch * e->L * std::max(3 * e->D, e->mlp * std::max(e->D, e->Dd)) >= (1ll << 40)) return -1;
+  if (!batch_in_bound(e, batch)) return -1;
   return make_plan_ex(e, batch, T, 1, 1, 1).total;
 }
 
@@ -1226,9 +1180,8 @@ extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params,
                                            int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, void* workspace,
                                            int64_t workspace_bytes, float* feats, void* stream) {
   const char* who = "mae_engine_extract_features";
-  MAE_REQUIRE(e, "%s: null engine", who);
-  MAE_REQUIRE(params && workspace && images && feats, "%s: null argument", who);
-  MAE_REQUIRE(e->act == MAE_F32 || wcache, "%s: bf16 engine needs the weight cache", who);
+  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
+  MAE_REQUIRE(images && feats, "%s: null argument", who);
   MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
   MAE_REQUIRE(e->D % 4 == 0 && e->D <= 1024, "%s: embed_dim = %d must be a multiple of 4 and at most 1024", who, e->D);
   MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES, "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
@@ -1238,11 +1191,10 @@ extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params,
   const int64_t need = mae_engine_features_workspace_bytes(e, batch, with_cls);
   MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
   MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
-  MAE_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)params & 15) == 0, "%s: workspace must be 256-byte aligned, params 16-byte", who);
   const int T = with_cls ? e->L : e->L - 1;
   const Plan pl = make_plan_ex(e, batch, T, 1, 1, 1);
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{e, params, (const char*)wcache, nullptr, (char*)workspace, s, e->act, (int64_t)dtype_size(e->act)};
+  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  hipStream_t s = c.s;
   c.fwd_only = true;
   c.skip_final_norm = true;
   if (with_cls) MAE_TRY(launch_iota_rows(c.buf<int32_t>(pl.keep32), batch, T, s));
@@ -1271,9 +1223,8 @@ extern "C" int mae_engine_adamw_buffer(mae_engine_t* e, float* params, const flo
   MAE_REQUIRE(count >= 0 && count % 4 == 0, "mae_engine_adamw_buffer: count %lld is not a multiple of 4", (long long)count);
   if (count == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-  const float bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));
-  RUN(TK_OPTIM, 0, count * 28, launch_adamw(params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2, eps, weight_decay, bc1, bc2, stats, nullptr, s));
+  const AdamBias bc = adam_bias(beta1, beta2, step);
+  RUN(TK_OPTIM, 0, count * 28, launch_adamw(params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2, eps, weight_decay, bc.c1, bc.c2, stats, nullptr, s));
   return 0;
 }
 

@@ -300,27 +300,6 @@ def test_pretrain_cli_synthetic_run_and_resume(dev, tmp_path, monkeypatch):
     assert len(recs) == 3 and 0.0 < recs[2]["train_loss"] < 2 * recs[0]["train_loss"]  # per-epoch mean, not divided by all steps since the start
 
 
-def test_side_stream_wgrad_is_bitwise_identical(dev, monkeypatch):
-    """Weight-gradient GEMMs run on a side stream (overlapping the LayerNorm / attention backward of the main chain);
-    the event dependencies must make that invisible: same bits as the single-stream order."""
-    cfg, B = O.VIT_S8_YAMLDEC, 64
-    g = torch.Generator(device=dev).manual_seed(3)
-    images = torch.rand(B, 3, 96, 96, device=dev, generator=g) * 2 - 1
-    noise = torch.rand(B, cfg.sequence_length, device=dev, generator=g)
-    results = []
-    monkeypatch.setenv("MAE_WGRAD_PAIR", "0")  # the single-stream order pairs a block's weight gradients into one launch (other M-splits, other rounding); compare like with like
-    for mode in ("0", "1"):
-        monkeypatch.setenv("MAE_WGRAD_STREAM", mode)
-        torch.manual_seed(5)
-        model = MaskedAutoencoder(*cfg_dicts(cfg, "bf16")).to(dev)
-        losses = []
-        for _ in range(3):
-            losses.append(model.loss_and_grads(images, noise).clone())
-        torch.cuda.synchronize()
-        results.append((torch.cat(losses).cpu(), model.flat_grads.clone().cpu()))
-    assert torch.equal(results[0][0], results[1][0]) and torch.equal(results[0][1], results[1][1])
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # ViT-S/8 geometry (the MFMA kernels' shapes) at other mask ratios: k = 72 / 36 / 21 visible tokens
 # ------------------------------------------------------------------------------------------------------------------

@@ -171,7 +171,7 @@ def _deep_model(dev):
 def test_more_than_64_layernorms_in_one_backward(dev, monkeypatch):
     """31 encoder blocks + 1 decoder block = 66 LayerNorms: the table of deferred dgamma / dbeta reductions is flushed in the middle of the
     backward and its partial slots are reused.  The gradient of every LayerNorm weight and bias, of the class token and of the mask token
-    matches the oracle tensor by tensor, and the side-stream weight-gradient path gives the same bits."""
+    matches the oracle tensor by tensor, also with the weight gradients of a block launched apart (MAE_WGRAD_PAIR=0)."""
     B = 2
     images = O.synthetic_images(B, DEEP)
     noise = O.make_noise(B, DEEP.sequence_length, torch.Generator().manual_seed(74))
@@ -189,16 +189,11 @@ def test_more_than_64_layernorms_in_one_backward(dev, monkeypatch):
     assert all(float(grads_ref[n].norm()) > 0 for n in names)
     bad = {n: e for n, e in errs.items() if not e < DEEP_TOL}
     assert not bad, bad
-    results = []
-    monkeypatch.setenv("MAE_WGRAD_PAIR", "0")   # as in test_side_stream_wgrad_is_bitwise_identical: compare like with like
-    for mode in ("0", "1"):
-        monkeypatch.setenv("MAE_WGRAD_STREAM", mode)
-        m, _ = _deep_model(dev)
-        l = m.loss_and_grads(images.to(dev), noise.to(dev)).clone()
-        torch.cuda.synchronize()
-        results.append((l.cpu(), m.flat_grads.clone().cpu()))
-    assert torch.equal(results[0][0], results[1][0]) and torch.equal(results[0][1], results[1][1])
-    gs = m.named_flat_views(results[1][1])
+    monkeypatch.setenv("MAE_WGRAD_PAIR", "0")   # the A/B switch of k_gemm_tn.hip: every weight gradient in a launch of its own
+    m, _ = _deep_model(dev)
+    m.loss_and_grads(images.to(dev), noise.to(dev))
+    torch.cuda.synchronize()
+    gs = m.named_flat_views(m.flat_grads.clone().cpu())
     assert all(rel_err(gs[n], grads_ref[n]) < DEEP_TOL for n in names)
 
 
