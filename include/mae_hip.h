@@ -291,7 +291,7 @@ int mae_engine_adamw_range(mae_engine_t* e, float* params, const float* grads, f
  *   train_embed = 1   : n = depth only -- also cls_token, patch_embed.proj.* (in `grads`) and pos_embed, whose gradient
  *                       goes to pos_grad (L * embed_dim floats, it lies outside the trainable range) (unfreeze_encoder(), :134).
  *   head_grads: dW then db, same layout as head.  grad_scale multiplies every gradient (not the loss). */
-enum { MAE_POOL_CLS = 0, MAE_POOL_MEAN = 1, MAE_POOL_MEAN_PATCHES = 2 /* features only: the classifier rejects it */ };
+enum { MAE_POOL_CLS = 0, MAE_POOL_MEAN = 1, MAE_POOL_MEAN_PATCHES = 2 /* features and the _ex classifier calls; the three calls below reject it */ };
 int64_t mae_engine_classifier_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t num_classes);
 int mae_engine_classifier_forward(mae_engine_t* e, const float* params, const void* wcache, const float* head, const void* images,
                                   int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes,
@@ -303,6 +303,33 @@ int mae_engine_classifier_loss_and_grads(mae_engine_t* e, const float* params, c
                                          float grad_scale, void* workspace, int64_t workspace_bytes, float* grads,
                                          float* head_grads, float* pos_grad, float* logits, float* loss_out,
                                          int32_t* correct_out, void* stream);
+/* The classifier on a sequence with or without the class token, and the patch-row mean (additive in ABI v4).  Arguments as
+ * the three calls above, plus with_cls in front of pool:
+ *   with_cls = 1: [cls | patch 1..N], L = N + 1 rows per image (the calls above);
+ *   with_cls = 0: patch tokens 1..N only -- the sequence an I-JEPA encoder was trained on.  Row j carries pos_embed[j + 1];
+ *                 cls_token and pos_embed[0] take no part in the forward.
+ *   pool: MAE_POOL_CLS          row 0; with_cls = 1 only (with_cls = 0 is an error before any launch: no class token);
+ *         MAE_POOL_MEAN         mean over every row of the sequence (L with the class token, N without);
+ *         MAE_POOL_MEAN_PATCHES mean over the patch rows: rows 1..L-1 with the class token (timm global_pool = "avg", the
+ *                               MAE fine-tuning recipe), every row without (the same as MAE_POOL_MEAN, bit for bit).
+ *   Backward: the feature gradient is d_pooled / rows_pooled on the pooled rows; with MAE_POOL_MEAN_PATCHES the class-token
+ *   row gets exact zeros and the final LayerNorm backward still runs over all rows.  With with_cls = 0 and train_embed = 1,
+ *   pos_grad (still L * embed_dim floats) holds the sums in rows 1..N and exact zeros in row 0, and the cls_token slot of
+ *   `grads` is written as exact zeros: an optimizer with weight decay must leave those two tensors out.
+ *   Deterministic: fixed summation orders, no atomics.  embed_dim a multiple of 4, at most 1024.
+ *   with_cls = 1 and MAE_POOL_CLS / MAE_POOL_MEAN run exactly the launches of the calls above.
+ *   workspace: mae_engine_classifier_workspace_bytes_ex(batch, num_classes, with_cls) bytes. */
+int64_t mae_engine_classifier_workspace_bytes_ex(const mae_engine_t* e, int32_t batch, int32_t num_classes, int32_t with_cls);
+int mae_engine_classifier_forward_ex(mae_engine_t* e, const float* params, const void* wcache, const float* head, const void* images,
+                                     int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t with_cls, int32_t pool,
+                                     int32_t num_classes, void* workspace, int64_t workspace_bytes, float* logits, float* loss_out,
+                                     int32_t* correct_out, void* stream);
+int mae_engine_classifier_loss_and_grads_ex(mae_engine_t* e, const float* params, const void* wcache, const float* head,
+                                            const void* images, int32_t image_dtype, const int64_t* labels, int32_t batch,
+                                            int32_t with_cls, int32_t pool, int32_t num_classes, int32_t train_blocks,
+                                            int32_t train_embed, float grad_scale, void* workspace, int64_t workspace_bytes,
+                                            float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
+                                            int32_t* correct_out, void* stream);
 /* The classifier's optimizer (Lightning gradient_clip_val = 1.0 + one-group torch AdamW over the requires_grad tensors,
  * scripts/training/train_mae.py:213, src/training/classifier.py:106-108) over buffers that are not the arena's trainable range:
  *   mae_engine_grad_sumsq_buffer       : sumsq_io[0] = (accumulate ? sumsq_io[0] : 0) + sum of grads[0 .. count)^2
@@ -443,6 +470,13 @@ int mae_classifier_head(const void* feats, int32_t dtype, int32_t batch, int32_t
                         const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
                         float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
                         int64_t scratch_bytes, void* stream);
+/* mae_classifier_head on feats whose seq_len rows do (with_cls = 1) or do not (0) start with a class-token row; pool as in
+ * mae_engine_classifier_forward_ex (MAE_POOL_MEAN_PATCHES with with_cls = 1 needs seq_len >= 2).  d_feats is (batch, seq_len,
+ * dim) for the mean pools, the class-token row exact zeros under MAE_POOL_MEAN_PATCHES.  Same scratch. */
+int mae_classifier_head_ex(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls, int32_t pool,
+                           const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
+                           float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
+                           int64_t scratch_bytes, void* stream);
 
 /* Epilogues of the GEMM family. */
 enum {

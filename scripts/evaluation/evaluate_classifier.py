@@ -1,7 +1,8 @@
 """Test-split accuracy of a trained classifier on the MI355X engine (the reference's
 scripts/evaluation/evaluate_classifier.py): ``--checkpoint`` defaults to
 ``outputs/train/<train.output_dir_suffix or "default">/checkpoints/best.ckpt``; a Lightning-shaped ``.ckpt`` or the
-``.pt`` state_dict the fine-tuning CLI writes.  Prints test_acc / test_loss and writes ``outputs/test/<suffix>/metrics.json``.
+``.pt`` state_dict the fine-tuning CLI writes.  A ``.ckpt`` of a classifier fine-tuned from an I-JEPA encoder carries
+``with_cls: False`` and its pool, so it is evaluated over the patch tokens alone without further flags.  Prints test_acc / test_loss and writes ``outputs/test/<suffix>/metrics.json``.
 
     python -m scripts.evaluation.evaluate_classifier --config configs/mae.yaml --checkpoint outputs/train/mae_finetune/checkpoints/best.ckpt
 """

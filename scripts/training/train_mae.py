@@ -5,7 +5,11 @@ scripts/training/train_mae.py, without Lightning): same flags, YAML keys and out
     python -m scripts.training.train_mae --config configs/mae.yaml --encoder_ckpt outputs/pretrain/mae_pretrain/checkpoints/last.ckpt
 
 Model branches as the reference (:85-161): --classifier_ckpt (weights only, fresh optimizer), --encoder_ckpt (encoder
-weights found by prefix), or the random-init baseline.  Freeze precedence (:167-176): train.unfreeze_last_layers, then
+weights found by prefix), or the random-init baseline.  --encoder_ckpt also takes an I-JEPA checkpoint (detected by its
+layout): --encoder picks the EMA target (default) or the context encoder, the classifier then runs over the patch tokens
+alone and pools with mean_patches unless model.head.pool / --pool says otherwise (cls is refused: no class token).
+
+    python -m scripts.training.train_mae --config configs/ijepa_vits8.yaml --encoder_ckpt outputs/pretrain/ijepa_pretrain/checkpoints/last.ckpt  Freeze precedence (:167-176): train.unfreeze_last_layers, then
 train.freeze_encoder.  Each epoch: the native fused step over the training split, a no-grad validation pass, the
 per-epoch LR, one metrics line; best.ckpt on a new maximum of val_acc, last.ckpt every epoch.
 """
@@ -20,20 +24,26 @@ from pathlib import Path
 import torch
 import yaml
 
-from ssrl_vit_mae_jepa_amd.classifier import ViTClassifierTrainModule, encoder_mae, load_encoder_weights
+from ssrl_vit_mae_jepa_amd.classifier import ViTClassifierTrainModule, checkpoint_with_cls, encoder_mae, load_encoder_weights
 from ssrl_vit_mae_jepa_amd.data import get_train_batches
+from ssrl_vit_mae_jepa_amd.representation import checkpoint_layout, load_ijepa_encoder
 
 SEED = 73
 PREFIXES = ("model.encoder.", "encoder.", "module.encoder.")
+IJEPA_LAYOUTS = ("ijepa_ckpt", "ijepa_pt")
+NO_CLS = "train_mae: I-JEPA encoders see no class token: --pool must be mean or mean_patches"
 
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="Fine-tune / linear-probe the ViT classifier")
     parser.add_argument("--config", type=str, default="configs/mae.yaml")
-    parser.add_argument("--encoder_ckpt", type=str, default=None, help="Path to a pretrained MAE checkpoint (encoder weights)")
+    parser.add_argument("--encoder_ckpt", type=str, default=None, help="Path to a pretrained MAE or I-JEPA checkpoint (encoder weights)")
     parser.add_argument("--classifier_ckpt", type=str, default=None, help="Path to a full classifier checkpoint")
     parser.add_argument("--output_dir_suffix", type=str, default="mae_finetune", help="Suffix for the output directory")
-    # additions (not in the reference): bounded runs
+    # additions (not in the reference): I-JEPA encoders and the pool override; bounded runs
+    parser.add_argument("--encoder", type=str, choices=["target", "context"], default="target",
+                        help="which I-JEPA encoder to fine-tune (ignored for MAE checkpoints)")
+    parser.add_argument("--pool", type=str, choices=["cls", "mean", "mean_patches"], default=None, help="overrides model.head.pool")
     parser.add_argument("--max_epochs", type=int, default=None)
     parser.add_argument("--max_steps_per_epoch", type=int, default=None)
     parser.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic labeled images instead of STL-10")
@@ -50,27 +60,61 @@ def load_state(path: str) -> dict:
     return ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
 
 
-def build_module(cfg: dict, encoder_ckpt=None, classifier_ckpt=None) -> ViTClassifierTrainModule:
+def is_ijepa_state(state: dict) -> bool:
+    try:
+        return checkpoint_layout(state) in IJEPA_LAYOUTS
+    except ValueError:
+        return False
+
+
+def resolve_pool(model_cfg: dict, pool=None, ijepa: bool = False) -> dict:
+    """model_cfg with the pool the run uses: --pool, else model.head.pool, else mean_patches for an I-JEPA encoder (cls for
+    everything else, the reference's default).  cls on an I-JEPA encoder ends the run."""
+    head = dict(model_cfg.get("head") or {})
+    if pool is not None:
+        head["pool"] = pool
+    elif ijepa and "pool" not in head:
+        head["pool"] = "mean_patches"
+    if ijepa and head.get("pool", "cls") == "cls":
+        raise SystemExit(NO_CLS)
+    return dict(model_cfg, head=head)
+
+
+def build_module(cfg: dict, encoder_ckpt=None, classifier_ckpt=None, encoder: str = "target", pool=None) -> ViTClassifierTrainModule:
     model_cfg, train_cfg = model_config(cfg), cfg["train"]
     if classifier_ckpt:
         print(f"Loading full classifier checkpoint: {classifier_ckpt}")
-        module = ViTClassifierTrainModule(pretrained_encoder=encoder_mae(model_cfg).encoder.vit, model_cfg=model_cfg, training_cfg=train_cfg)
-        state = load_state(classifier_ckpt)
+        ckpt = torch.load(classifier_ckpt, map_location="cpu", weights_only=True)
+        state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
+        vit = encoder_mae(model_cfg).encoder.vit
+        vit.with_cls = checkpoint_with_cls(ckpt)  # a classifier fine-tuned from I-JEPA stays on the patch tokens alone
+        hp = (ckpt.get("hyper_parameters") or {}) if isinstance(ckpt, dict) else {}
+        if pool is None and "with_cls" in hp:  # such a checkpoint carries the pool its head was trained with
+            pool = ((hp.get("model_cfg") or {}).get("head") or {}).get("pool")
+        model_cfg = resolve_pool(model_cfg, pool, ijepa=not vit.with_cls)
+        module = ViTClassifierTrainModule(pretrained_encoder=vit, model_cfg=model_cfg, training_cfg=train_cfg)
         if not any(k.startswith("model.") for k in state):
             state = {"model." + k: v for k, v in state.items()}  # a bare module.model.state_dict() (.pt)
         module.load_state_dict(state, strict=False)
     elif encoder_ckpt:
         print(f"Loading pretrained encoder: {encoder_ckpt}")
-        mae = encoder_mae(model_cfg)
         state = load_state(encoder_ckpt)
-        if not any(k.startswith(p) for p in PREFIXES for k in state):
-            raise ValueError("Could not find encoder weights in checkpoint. Expected keys starting with one of: " + ", ".join(PREFIXES))
-        missing, unexpected = load_encoder_weights(mae, state)
-        print(f"Loaded encoder weights ({len(missing)} missing, {len(unexpected)} unexpected)")
-        module = ViTClassifierTrainModule(pretrained_encoder=mae.encoder.vit, model_cfg=model_cfg, training_cfg=train_cfg)
+        if is_ijepa_state(state):
+            model_cfg = resolve_pool(model_cfg, pool, ijepa=True)
+            vit = load_ijepa_encoder(state, model_cfg, encoder=encoder)
+            print(f"Loaded the I-JEPA {encoder} encoder (patch tokens only, pool {model_cfg['head']['pool']})")
+        else:
+            model_cfg = resolve_pool(model_cfg, pool)
+            mae = encoder_mae(model_cfg)
+            if not any(k.startswith(p) for p in PREFIXES for k in state):
+                raise ValueError("Could not find encoder weights in checkpoint. Expected keys starting with one of: " + ", ".join(PREFIXES))
+            missing, unexpected = load_encoder_weights(mae, state)
+            print(f"Loaded encoder weights ({len(missing)} missing, {len(unexpected)} unexpected)")
+            vit = mae.encoder.vit
+        module = ViTClassifierTrainModule(pretrained_encoder=vit, model_cfg=model_cfg, training_cfg=train_cfg)
     else:
         print("Baseline: random-initialized VisionTransformer (no MAE)")
-        module = ViTClassifierTrainModule(pretrained_encoder=None, model_cfg=model_cfg, training_cfg=train_cfg)
+        module = ViTClassifierTrainModule(pretrained_encoder=None, model_cfg=resolve_pool(model_cfg, pool), training_cfg=train_cfg)
     if train_cfg.get("unfreeze_last_layers", None) is not None:
         module.unfreeze_last_layers(int(train_cfg["unfreeze_last_layers"]))
     elif train_cfg.get("freeze_encoder", True):
@@ -103,7 +147,7 @@ def main(argv=None):
         yaml.safe_dump(cfg, f_out)
 
     train_batches, val_batches = get_train_batches(cfg, dev, synthetic_images=args.synthetic_images, seed=SEED)
-    module = build_module(cfg, args.encoder_ckpt, args.classifier_ckpt).to(dev)
+    module = build_module(cfg, args.encoder_ckpt, args.classifier_ckpt, encoder=args.encoder, pool=args.pool).to(dev)
     total = int(train_cfg["total_epochs"]) if args.max_epochs is None else min(int(train_cfg["total_epochs"]), args.max_epochs)
     best_acc, log_path = -1.0, output_dir / "logs" / "metrics.jsonl"
     for epoch in range(total):

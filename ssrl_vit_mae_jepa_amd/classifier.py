@@ -21,7 +21,8 @@ from ._lib import check, lib
 from .mae import MaskedAutoencoder, _ptr, _stream, _ViT
 from .training import lr_lambda
 
-POOLS = {"cls": _lib.POOL_CLS, "mean": _lib.POOL_MEAN}
+POOLS = {"cls": _lib.POOL_CLS, "mean": _lib.POOL_MEAN, "mean_patches": _lib.POOL_MEAN_PATCHES}
+NO_CLS_POOL = "pool 'cls' needs a class token: I-JEPA encoders are trained on the patch tokens only (use 'mean' or 'mean_patches')"
 MAX_CLASSES = 128
 
 
@@ -68,8 +69,12 @@ class ClassificationHead(nn.Module):
 
 class ViTClassifier(nn.Module):
     """src/models/classifier.py:25-57 over the engine: ``encoder`` is the engine's ``_ViT`` node, ``head`` the linear head,
-    ``pool_type`` "cls" or "mean".  ``forward`` is an inference call (the training route is the native step of
-    ``ViTClassifierTrainModule``)."""
+    ``pool_type`` "cls", "mean" (every row of the sequence) or "mean_patches" (the patch rows: timm's global_pool="avg").
+    ``forward`` is an inference call (the training route is the native step of ``ViTClassifierTrainModule``).
+
+    The sequence follows the encoder node's ``with_cls``: True is [cls | patches]; False (an encoder loaded by
+    ``representation.load_ijepa_encoder``) is the patch tokens alone, where "mean" and "mean_patches" are the same pool and
+    "cls" is refused."""
 
     def __init__(self, pretrained_encoder: _ViT, num_classes: int = 10, head_cfg: Optional[Dict[str, Any]] = None):
         super().__init__()
@@ -81,7 +86,9 @@ class ViTClassifier(nn.Module):
             raise ValueError(f"head embed_dim {embed_dim} != encoder width {pretrained_encoder.embed_dim}")
         pool_type = head_cfg.get("pool", "cls")
         if pool_type not in POOLS:
-            raise ValueError(f"pool must be 'cls' or 'mean', got {pool_type!r}")
+            raise ValueError(f"pool must be 'cls', 'mean' or 'mean_patches', got {pool_type!r}")
+        if pool_type == "cls" and not pretrained_encoder.with_cls:
+            raise ValueError(NO_CLS_POOL)
         if not 2 <= int(num_classes) <= MAX_CLASSES:
             raise ValueError(f"num_classes must be in [2, {MAX_CLASSES}], got {num_classes}")
         self.encoder = pretrained_encoder
@@ -93,6 +100,15 @@ class ViTClassifier(nn.Module):
     def mae(self) -> MaskedAutoencoder:
         return self.encoder._owner()
 
+    @property
+    def with_cls(self) -> bool:
+        return bool(self.encoder.with_cls)
+
+    @property
+    def extended(self) -> bool:
+        """True when the call needs the ``_ex`` entry points: a patch-only sequence or the patch-row mean."""
+        return not self.with_cls or self.pool_type == "mean_patches"
+
     def _apply(self, fn, recurse=True):
         # the encoder's tensors are views into the MAE's arena: move them through their owner, which re-flattens them
         self.mae._apply(fn)
@@ -103,7 +119,10 @@ class ViTClassifier(nn.Module):
         """The owner's workspace grown to the classifier's size.  It is shared with the MAE's forwards, so every saved
         activation of an earlier call is invalidated: a pending hand-off backward refuses to run."""
         m = self.mae
-        need = lib.mae_engine_classifier_workspace_bytes(m.engine.handle, batch, self.num_classes)
+        if self.extended:
+            need = lib.mae_engine_classifier_workspace_bytes_ex(m.engine.handle, batch, self.num_classes, int(self.with_cls))
+        else:
+            need = lib.mae_engine_classifier_workspace_bytes(m.engine.handle, batch, self.num_classes)
         if need < 0:
             raise ValueError(f"bad batch {batch} / num_classes {self.num_classes}")
         if m._workspace is None or m._workspace.numel() < need or m._workspace.device != m.flat_params.device:
@@ -132,9 +151,12 @@ class ViTClassifier(nn.Module):
             loss = torch.empty(1, dtype=torch.float32, device=dev)
             correct = torch.empty(1, dtype=torch.int32, device=dev)
         ws = self.workspace(B)
-        check(lib.mae_engine_classifier_forward(m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(self.head.flat), _ptr(images),
-                                                m._img_dt(images), _ptr(labels), B, POOLS[self.pool_type], self.num_classes, _ptr(ws), ws.numel(),
-                                                _ptr(out), _ptr(loss), _ptr(correct), _stream(dev)))
+        head = (m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(self.head.flat), _ptr(images), m._img_dt(images), _ptr(labels), B)
+        tail = (self.num_classes, _ptr(ws), ws.numel(), _ptr(out), _ptr(loss), _ptr(correct), _stream(dev))
+        if self.extended:
+            check(lib.mae_engine_classifier_forward_ex(*head, int(self.with_cls), POOLS[self.pool_type], *tail))
+        else:
+            check(lib.mae_engine_classifier_forward(*head, POOLS[self.pool_type], *tail))
         return out, loss, correct
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -285,6 +307,19 @@ class ViTClassifierTrainModule(nn.Module):
         first = f"encoder.vit.blocks.{depth - train_blocks}.norm1.weight" if train_blocks else "encoder.vit.norm.weight"
         return m._offsets[first][1], hi
 
+    def _update_ranges(self, train_blocks: int, train_embed: int) -> Tuple[List[Tuple[int, int]], int]:
+        """What AdamW may touch: the (lo, count) pieces of the arena range and the first pos_embed row.  A patch-only
+        encoder never reads cls_token or pos_embed[:, 0]; their gradients are zero, but weight decay alone would shrink
+        them, so they are cut out of the update (every piece stays a multiple of 4 floats: offsets are, and so is D)."""
+        lo, hi = self._arena_range(train_blocks, train_embed)
+        if hi <= lo:
+            return [], 0
+        if not train_embed or self.model.with_cls:
+            return [(lo, hi - lo)], 0
+        _n, c_off, c_n, _s, _f = self.model.mae._offsets["encoder.vit.cls_token"]
+        pieces = [(a, b - a) for a, b in ((lo, c_off), (c_off + c_n, hi)) if b > a]
+        return pieces, 1
+
     # ---- native step -------------------------------------------------------------------------------
     def _grad_buffers(self):
         m = self.model.mae
@@ -319,10 +354,13 @@ class ViTClassifierTrainModule(nn.Module):
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         correct = torch.empty(1, dtype=torch.int32, device=dev)
         ws = clf.workspace(B)
-        check(lib.mae_engine_classifier_loss_and_grads(
-            m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(clf.head.flat), _ptr(images), m._img_dt(images), _ptr(labels),
-            B, POOLS[clf.pool_type], clf.num_classes, tb, te, float(grad_scale), _ptr(ws), ws.numel(), _ptr(m.flat_grads), _ptr(head_g),
-            _ptr(pos_g), _ptr(logits_out), _ptr(loss), _ptr(correct), _stream(dev)))
+        head = (m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(clf.head.flat), _ptr(images), m._img_dt(images), _ptr(labels), B)
+        tail = (clf.num_classes, tb, te, float(grad_scale), _ptr(ws), ws.numel(), _ptr(m.flat_grads), _ptr(head_g), _ptr(pos_g), _ptr(logits_out),
+                _ptr(loss), _ptr(correct), _stream(dev))
+        if clf.extended:
+            check(lib.mae_engine_classifier_loss_and_grads_ex(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail))
+        else:
+            check(lib.mae_engine_classifier_loss_and_grads(*head, POOLS[clf.pool_type], *tail))
         self._last_mode = (tb, te)
         return loss, correct
 
@@ -356,16 +394,19 @@ class ViTClassifierTrainModule(nn.Module):
         if te:
             check(lib.mae_engine_grad_sumsq_buffer(h, _ptr(pos_g), pos_g.numel(), 1, _ptr(sums), _ptr(scratch), s))
         check(lib.mae_engine_clip_from_sumsq(h, _ptr(sums), float(self.gradient_clip_val), _ptr(stats), s))
-        if hi > lo:
+        pieces, pos_row0 = self._update_ranges(tb, te)
+        for p_lo, p_n in pieces:
             ea, eq = self._state("arena_m", n_arena, dev), self._state("arena_v", n_arena, dev)
             check(lib.mae_engine_adamw_range(h, _ptr(m.flat_params), _ptr(m.flat_grads), _ptr(ea), _ptr(eq), _ptr(m._weights()), *hyper[:5],
-                                             step, _ptr(stats), lo, hi - lo, s))
+                                             step, _ptr(stats), p_lo, p_n, s))
         check(lib.mae_engine_adamw_buffer(h, _ptr(clf.head.flat), _ptr(head_g), _ptr(self._state("head_m", head_g.numel(), dev)),
                                           _ptr(self._state("head_v", head_g.numel(), dev)), head_g.numel(), *hyper[:5], step, _ptr(stats), s))
         if te:
             _n, pos_off, pos_n, _s, _f = m._offsets["encoder.vit.pos_embed"]
-            check(lib.mae_engine_adamw_buffer(h, _ptr(m.flat_params[pos_off:pos_off + pos_n]), _ptr(pos_g), _ptr(self._state("pos_m", pos_n, dev)),
-                                              _ptr(self._state("pos_v", pos_n, dev)), pos_n, *hyper[:5], step, _ptr(stats), s))
+            skip = pos_row0 * m._dims["embed_dim"]  # the class-token row of a patch-only encoder stays as it is
+            check(lib.mae_engine_adamw_buffer(h, _ptr(m.flat_params[pos_off + skip:pos_off + pos_n]), _ptr(pos_g[skip:]),
+                                              _ptr(self._state("pos_m", pos_n, dev)[skip:]), _ptr(self._state("pos_v", pos_n, dev)[skip:]),
+                                              pos_n - skip, *hyper[:5], step, _ptr(stats), s))
         if hi > lo:
             check(lib.mae_engine_refresh_transposed_range(h, _ptr(m.flat_params), _ptr(m._weights()), lo, hi - lo, s))
         m.mark_weights_fresh()
@@ -381,10 +422,19 @@ class ViTClassifierTrainModule(nn.Module):
 
     # ---- checkpoints -------------------------------------------------------------------------------
     def checkpoint(self, epoch: int = 0, global_step: int = 0) -> Dict[str, Any]:
-        """Lightning-shaped: state_dict keys model.encoder.<timm name> / model.head.classification.*."""
+        """Lightning-shaped: state_dict keys model.encoder.<timm name> / model.head.classification.*.  ``hyper_parameters``
+        gains ``with_cls: False`` for a patch-only encoder (with a class token the key set is the reference's, unchanged);
+        ``checkpoint_with_cls`` reads it back."""
         return {"epoch": epoch, "global_step": global_step,
                 "state_dict": {k: v.detach().cpu().clone() for k, v in self.state_dict().items()},
-                "hyper_parameters": dict(self.hparams)}
+                "hyper_parameters": dict(self.hparams) if self.model.with_cls else dict(self.hparams, with_cls=False)}
+
+
+def checkpoint_with_cls(ckpt: Dict[str, Any]) -> bool:
+    """Whether a classifier checkpoint's encoder runs over [cls | patches] (True, also when the key is missing: every
+    checkpoint written before the key existed) or over the patch tokens alone."""
+    hp = ckpt.get("hyper_parameters") if isinstance(ckpt, dict) else None
+    return bool((hp or {}).get("with_cls", True))
 
 
 def encoder_mae(model_cfg: Dict[str, Any]) -> MaskedAutoencoder:

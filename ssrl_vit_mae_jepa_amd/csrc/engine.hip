@@ -1046,17 +1046,20 @@ extern "C" int mae_engine_optimizer_step_ema(mae_engine_t* e, float* params, flo
 //   train_blocks = -1: linear probe -- the forward saves nothing for a backward, only the head gets gradients;
 //   train_blocks = n : final LayerNorm + blocks[depth-n:] (unfreeze_last_layers(n)); nothing below them runs;
 //   train_embed  = 1 : (n = depth only) also cls_token, the patch projection and pos_embed (unfreeze_encoder()).
+// The _ex entry points add the patch-only sequence (with_cls = 0: tokens 1..N, what an I-JEPA encoder was trained on) and
+// the patch-row mean (MAE_POOL_MEAN_PATCHES); both pool through the row-range head kernel.
 // =====================================================================================================
 namespace mae {
 
 struct ClsPlan {
-  Plan pl;  // the full-sequence plan (num_keep = L) at offset 0; the classifier's own buffers follow it
+  Plan pl;  // the full-sequence plan (num_keep = L, or L - 1 without the class token) at offset 0; the classifier's own buffers follow it
   int64_t pooled, dlogits, row_loss, row_correct, dpooled, mean_c, rstd_c, cls_rows, head_partial, head_sum, pos_partial, total;
 };
 
-static ClsPlan make_cls_plan(const mae_engine* e, int B, int C) {
+static ClsPlan make_cls_plan(const mae_engine* e, int B, int C, bool with_cls = true) {
   ClsPlan cp;
-  cp.pl = make_plan(e, B, e->L);
+  const int T = with_cls ? e->L : e->L - 1;
+  cp.pl = with_cls ? make_plan(e, B, e->L) : make_plan_ex(e, B, T, 1, 1, 1);  // patch-only: a token-sized decoder stub, as the features plan
   int64_t off = round_up(cp.pl.total, 256);
   auto take = [&](int64_t bytes) { const int64_t o = off; off += round_up(std::max<int64_t>(bytes, 4), 256); return o; };
   const int64_t D = e->D;
@@ -1070,7 +1073,7 @@ static ClsPlan make_cls_plan(const mae_engine* e, int B, int C) {
   cp.cls_rows = take((int64_t)B * 4);
   cp.head_partial = take(classifier_wgrad_partial_floats(B, C, e->D) * 4);
   cp.head_sum = take(round_up((int64_t)C * D + C, 4) * 4);
-  cp.pos_partial = take((int64_t)full_grad_split_slices(B, e->L, e->D) * e->L * D * 4);
+  cp.pos_partial = take((int64_t)full_grad_split_slices(B, T, e->D) * T * D * 4);
   cp.total = off;
   return cp;
 }
@@ -1078,14 +1081,24 @@ static ClsPlan make_cls_plan(const mae_engine* e, int B, int C) {
 static int classifier_impl(mae_engine* e, const float* params, const void* wcache, const float* head, const void* images, int32_t image_dtype,
                            const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes, int32_t train_blocks, int32_t train_embed,
                            float grad_scale, void* workspace, int64_t workspace_bytes, float* grads, float* head_grads, float* pos_grad,
-                           float* logits, float* loss_out, int32_t* correct_out, void* stream, const char* who) {
-  Plan pl;
-  MAE_TRY(check_call(e, params, wcache, batch, e ? e->L : 1, workspace, workspace_bytes, &pl, who));
+                           float* logits, float* loss_out, int32_t* correct_out, void* stream, const char* who, int32_t with_cls = 1,
+                           bool ex = false) {
+  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
+  MAE_REQUIRE(batch > 0, "%s: batch %d out of range", who, batch);
   MAE_REQUIRE(head && images, "%s: null head/images", who);
   MAE_TRY(check_image_dtype(image_dtype, who));
   MAE_REQUIRE(num_classes >= 2 && num_classes <= HEAD_MAX_CLASSES, "%s: num_classes = %d outside [2, %d]", who, num_classes, HEAD_MAX_CLASSES);
-  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN, "%s: pool must be MAE_POOL_CLS or MAE_POOL_MEAN (got %d)", who, pool);
-  const ClsPlan cp = make_cls_plan(e, batch, num_classes);
+  if (ex) {
+    MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+    MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES,
+                "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
+    MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
+    MAE_REQUIRE(e->L >= 2 && e->D % 4 == 0 && e->D <= 1024, "%s: needs a patch row and embed_dim a multiple of 4 up to 1024", who);
+  } else {
+    MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN, "%s: pool must be MAE_POOL_CLS or MAE_POOL_MEAN (got %d)", who, pool);
+  }
+  const ClsPlan cp = make_cls_plan(e, batch, num_classes, with_cls != 0);
+  const Plan& pl = cp.pl;
   MAE_REQUIRE(workspace_bytes >= cp.total, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)cp.total);
   const bool train = head_grads != nullptr;
   if (train) {
@@ -1100,17 +1113,27 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
   hipStream_t s = c.s;
   const bool enc_bwd = train && train_blocks >= 0;
   c.fwd_only = !enc_bwd;  // the linear probe and evaluation save no GELU derivative
-  const int B = batch, L = e->L, D = e->D, C = num_classes;
-  MAE_TRY(launch_iota_rows(c.buf<int32_t>(pl.keep32), B, L, s));
+  const int B = batch, L = pl.k, D = e->D, C = num_classes;  // L rows per image: the class token (if any) and every patch
+  if (with_cls) MAE_TRY(launch_iota_rows(c.buf<int32_t>(pl.keep32), B, L, s));
+  else MAE_TRY(launch_iota_tokens(c.buf<int32_t>(pl.keep32), B, L, s));
   MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
   const bool cls = pool == MAE_POOL_CLS;
+  const bool range = !with_cls || pool == MAE_POOL_MEAN_PATCHES;  // the mean over the patch rows [lo, L)
+  const int lo = with_cls ? 1 : 0;
   void* dfeat = enc_bwd ? (cls ? c.buf<>(cp.dpooled) : c.buf<>(pl.d_ln)) : nullptr;
-  RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), (cls ? (double)B * D : (double)pl.Me * D) * c.as + (double)C * D * 4 + (enc_bwd && !cls ? (double)pl.Me * D * c.as : 0.0),
-      launch_classifier_head(c.buf<>(pl.enc_norm), e->act, B, L, D, pool, head, head + (int64_t)C * D, C, labels, grad_scale, logits,
-                             c.buf<float>(cp.row_loss), c.buf<int32_t>(cp.row_correct), loss_out, correct_out,
-                             train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat,
-                             c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c),
-                             enc_bwd && cls ? c.buf<int32_t>(cp.cls_rows) : nullptr, s));
+  if (range) {
+    RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), (double)B * (L - lo) * D * c.as + (double)C * D * 4 + (enc_bwd ? (double)pl.Me * D * c.as : 0.0),
+        launch_classifier_head_range(c.buf<>(pl.enc_norm), e->act, B, L, D, lo, L, head, head + (int64_t)C * D, C, labels, grad_scale, logits,
+                                     c.buf<float>(cp.row_loss), c.buf<int32_t>(cp.row_correct), loss_out, correct_out,
+                                     train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat, s));
+  } else {
+    RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), (cls ? (double)B * D : (double)pl.Me * D) * c.as + (double)C * D * 4 + (enc_bwd && !cls ? (double)pl.Me * D * c.as : 0.0),
+        launch_classifier_head(c.buf<>(pl.enc_norm), e->act, B, L, D, pool, head, head + (int64_t)C * D, C, labels, grad_scale, logits,
+                               c.buf<float>(cp.row_loss), c.buf<int32_t>(cp.row_correct), loss_out, correct_out,
+                               train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat,
+                               c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c),
+                               enc_bwd && cls ? c.buf<int32_t>(cp.cls_rows) : nullptr, s));
+  }
   if (!train) return 0;
   RUN(TK_WGRAD, 2.0 * B * C * D, (double)B * (C + D) * 4, launch_classifier_head_wgrad(c.buf<float>(cp.dlogits), c.buf<float>(cp.pooled), B, C, D,
                                                                                     c.buf<float>(cp.head_partial), c.buf<float>(cp.head_sum), head_grads, s));
@@ -1130,7 +1153,10 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
     MAE_TRY(block_backward(c, pl, e->enc[i], pl.enc[i], pl.Me, D, e->H, B, L, pl.enc_x[i]));
   if (train_embed) {
     // token assembly: d pos_embed, d cls_token and the patch rows from one read of dres, then the patch projection
-    RUN(TK_DATA, 0, pl.Me * D * (4 + c.as), launch_full_grad_split(dres, B, L, D, e->act, c.buf<>(pl.dtok), pos_grad, c.Gp(e->i_cls), c.buf<float>(cp.pos_partial), s));
+    if (with_cls)
+      RUN(TK_DATA, 0, pl.Me * D * (4 + c.as), launch_full_grad_split(dres, B, L, D, e->act, c.buf<>(pl.dtok), pos_grad, c.Gp(e->i_cls), c.buf<float>(cp.pos_partial), s));
+    else  // no class row: every row feeds the patch projection; pos_embed[0] and cls_token get exact zeros
+      RUN(TK_DATA, 0, pl.Me * D * (4 + c.as), launch_patch_grad_split(dres, B, L, D, e->act, c.buf<>(pl.dtok), pos_grad, c.Gp(e->i_cls), c.buf<float>(cp.pos_partial), s));
     MAE_TRY(wgrad(c, pl, c.buf<>(pl.dtok), c.buf<>(pl.patchA), pl.Me, D, e->P, e->i_patch_w, e->i_patch_b));
   }
   return backward_end(c);
@@ -1162,6 +1188,33 @@ extern "C" int mae_engine_classifier_loss_and_grads(mae_engine_t* e, const float
   return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
                          workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
                          "mae_engine_classifier_loss_and_grads");
+}
+
+extern "C" int64_t mae_engine_classifier_workspace_bytes_ex(const mae_engine_t* e, int32_t batch, int32_t num_classes, int32_t with_cls) {
+  if (!e || batch <= 0 || num_classes < 2 || num_classes > HEAD_MAX_CLASSES || (with_cls != 0 && with_cls != 1) || e->L < 2) return -1;
+  if (!batch_in_bound(e, batch)) return -1;
+  return make_cls_plan(e, batch, num_classes, with_cls != 0).total;
+}
+
+extern "C" int mae_engine_classifier_forward_ex(mae_engine_t* e, const float* params, const void* wcache, const float* head, const void* images,
+                                                int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t with_cls, int32_t pool,
+                                                int32_t num_classes, void* workspace, int64_t workspace_bytes, float* logits, float* loss_out,
+                                                int32_t* correct_out, void* stream) {
+  MAE_REQUIRE(labels || (!loss_out && !correct_out), "mae_engine_classifier_forward_ex: loss / correct count need labels");
+  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, -1, 0, 1.f, workspace, workspace_bytes,
+                         nullptr, nullptr, nullptr, logits, loss_out, correct_out, stream, "mae_engine_classifier_forward_ex", with_cls, true);
+}
+
+extern "C" int mae_engine_classifier_loss_and_grads_ex(mae_engine_t* e, const float* params, const void* wcache, const float* head,
+                                                       const void* images, int32_t image_dtype, const int64_t* labels, int32_t batch,
+                                                       int32_t with_cls, int32_t pool, int32_t num_classes, int32_t train_blocks,
+                                                       int32_t train_embed, float grad_scale, void* workspace, int64_t workspace_bytes,
+                                                       float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
+                                                       int32_t* correct_out, void* stream) {
+  MAE_REQUIRE(head_grads, "mae_engine_classifier_loss_and_grads_ex: null head_grads");
+  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
+                         workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
+                         "mae_engine_classifier_loss_and_grads_ex", with_cls, true);
 }
 
 // =====================================================================================================

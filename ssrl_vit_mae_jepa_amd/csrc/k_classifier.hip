@@ -1,6 +1,7 @@
 // Downstream classifier: pooled linear head + cross-entropy (forward and backward) and the full-sequence embedding
-// gradient.  Reference: src/models/classifier.py:47-57 (pool + head), src/training/classifier.py:75-105 (F.cross_entropy,
-// accuracy), src/training/classifier.py:134 (unfreeze_encoder: cls_token, pos_embed and the patch projection train too).
+// gradient, over [cls | patches] or the patch tokens alone (classifier_head_range_kernel, the HAS_CLS = false split).
+// Reference: src/models/classifier.py:47-57 (pool + head), src/training/classifier.py:75-105 (F.cross_entropy, accuracy),
+// src/training/classifier.py:134 (unfreeze_encoder: cls_token, pos_embed and the patch projection train too).
 //
 // bf16 engine rounding points (each one a GEMM operand of the head, fp32 accumulation everywhere):
 //   (1) the pooled feature vector  -- with "mean" the rows are the engine's bf16 LayerNorm outputs, summed in fp32, then rounded;
@@ -27,36 +28,17 @@ int launch_iota_rows(int32_t* keep32, int B, int L, hipStream_t s) {
   return 0;
 }
 
-// One block per image.  Thread t owns feature columns [4t, 4t+4) (t < D/4); wave w owns classes w, w+4, ...
+// The phases both head kernels share once the pooled vector sits in sp[0 .. D): logits, row loss / correct flag, d_logits and
+// the pooled copy.  Wave w owns classes w, w+4, ...; returns false when the caller has nothing left to do (no backward asked).
 template <class T>
-__global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restrict__ feats, int L, int D, int pool,
-                                                              const float* __restrict__ W, const float* __restrict__ bias, int C,
-                                                              const int64_t* __restrict__ labels, float grad_scale, int B,
-                                                              float* __restrict__ logits_out, float* __restrict__ row_loss,
-                                                              int32_t* __restrict__ row_correct, float* __restrict__ pooled_out,
-                                                              float* __restrict__ dlogits_out, T* __restrict__ dfeat_out,
-                                                              const float* __restrict__ mean_all, const float* __restrict__ rstd_all,
-                                                              float* __restrict__ mean_c, float* __restrict__ rstd_c,
-                                                              int32_t* __restrict__ cls_rows) {
-  __shared__ __attribute__((aligned(16))) float sp[1024];
-  __shared__ float sl[HEAD_MAX_CLASSES], sdl[HEAD_MAX_CLASSES], sstat[2];
-  __shared__ int sy;
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+__device__ __forceinline__ bool head_after_pool(const float* sp, float* sl, float* sdl, float* sstat, int* sy, int b, int D,
+                                                const float* __restrict__ W, const float* __restrict__ bias, int C,
+                                                const int64_t* __restrict__ labels, float grad_scale, int B,
+                                                float* __restrict__ logits_out, float* __restrict__ row_loss,
+                                                int32_t* __restrict__ row_correct, float* __restrict__ pooled_out,
+                                                float* __restrict__ dlogits_out) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int D4 = D / 4;
-  const int64_t row0 = (int64_t)b * L;
-  // pooled features: feats[:, 0] or feats.mean(dim=1) over all L rows (class token included)
-  if (t < D4) {
-    f32x4 v;
-    if (pool == MAE_POOL_CLS) {
-      v = load4(feats + row0 * D + 4 * t);
-    } else {
-      v = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int j = 0; j < L; ++j) v += load4(feats + (row0 + j) * D + 4 * t);
-      v = v / (float)L;
-    }
-    for (int i = 0; i < 4; ++i) sp[4 * t + i] = head_round<T>(v[i]);  // rounding point (1)
-  }
-  __syncthreads();
   // logits = pooled @ W.T + b
   for (int c = wave; c < C; c += 4) {
     float acc = 0.f;
@@ -79,23 +61,18 @@ __global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restric
     const float lse = mx + logf(se);
     const int64_t y = labels ? labels[b] : -1;
     const bool valid = y >= 0 && y < C;   // an out-of-range label is never used as an index: its row's loss is NaN
-    sy = valid ? (int)y : -1;
+    *sy = valid ? (int)y : -1;
     sstat[0] = lse;
     row_loss[b] = valid ? lse - sl[y] : __builtin_nanf("");
     row_correct[b] = (valid && am == (int)y) ? 1 : 0;
-    if (cls_rows) {  // compact statistics of the class-token rows for the row-mapped final LayerNorm backward
-      cls_rows[b] = (int32_t)row0;
-      mean_c[b] = mean_all[row0];
-      rstd_c[b] = rstd_all[row0];
-    }
   }
   __syncthreads();
   if (logits_out)
     for (int c = t; c < C; c += 256) logits_out[(int64_t)b * C + c] = sl[c];
-  if (!dlogits_out) return;
+  if (!dlogits_out) return false;
   // d_logits = (softmax - onehot(y)) * grad_scale / B
   const float lse = sstat[0];
-  const int y = sy;
+  const int y = *sy;
   for (int c = t; c < C; c += 256) {
     float g = (expf(sl[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale / (float)B;
     if (y < 0) g = __builtin_nanf("");
@@ -104,21 +81,135 @@ __global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restric
     dlogits_out[(int64_t)b * C + c] = g;
   }
   if (t < D4) store4(pooled_out + (int64_t)b * D + 4 * t, f32x4{sp[4 * t], sp[4 * t + 1], sp[4 * t + 2], sp[4 * t + 3]});
+  return true;
+}
+
+// columns [4t, 4t+4) of d_pooled = d_logits . W (W rounded as it is read)
+template <class T>
+__device__ __forceinline__ f32x4 head_dpooled(const float* sdl, const float* __restrict__ W, int C, int D, int t) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int c = 0; c < C; ++c) {
+    const f32x4 w = load4(W + (int64_t)c * D + 4 * t);
+    const f32x4 wr = {head_round<T>(w[0]), head_round<T>(w[1]), head_round<T>(w[2]), head_round<T>(w[3])};
+    acc += sdl[c] * wr;
+  }
+  return acc;
+}
+
+// One block per image.  Thread t owns feature columns [4t, 4t+4) (t < D/4); wave w owns classes w, w+4, ...
+template <class T>
+__global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restrict__ feats, int L, int D, int pool,
+                                                              const float* __restrict__ W, const float* __restrict__ bias, int C,
+                                                              const int64_t* __restrict__ labels, float grad_scale, int B,
+                                                              float* __restrict__ logits_out, float* __restrict__ row_loss,
+                                                              int32_t* __restrict__ row_correct, float* __restrict__ pooled_out,
+                                                              float* __restrict__ dlogits_out, T* __restrict__ dfeat_out,
+                                                              const float* __restrict__ mean_all, const float* __restrict__ rstd_all,
+                                                              float* __restrict__ mean_c, float* __restrict__ rstd_c,
+                                                              int32_t* __restrict__ cls_rows) {
+  __shared__ __attribute__((aligned(16))) float sp[1024];
+  __shared__ float sl[HEAD_MAX_CLASSES], sdl[HEAD_MAX_CLASSES], sstat[2];
+  __shared__ int sy;
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int D4 = D / 4;
+  const int64_t row0 = (int64_t)b * L;
+  // pooled features: feats[:, 0] or feats.mean(dim=1) over all L rows (class token included)
+  if (t < D4) {
+    f32x4 v;
+    if (pool == MAE_POOL_CLS) {
+      v = load4(feats + row0 * D + 4 * t);
+    } else {
+      v = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < L; ++j) v += load4(feats + (row0 + j) * D + 4 * t);
+      v = v / (float)L;
+    }
+    for (int i = 0; i < 4; ++i) sp[4 * t + i] = head_round<T>(v[i]);  // rounding point (1)
+  }
+  if (t == 0 && cls_rows) {  // compact statistics of the class-token rows for the row-mapped final LayerNorm backward
+    cls_rows[b] = (int32_t)row0;
+    mean_c[b] = mean_all[row0];
+    rstd_c[b] = rstd_all[row0];
+  }
+  __syncthreads();
+  if (!head_after_pool<T>(sp, sl, sdl, sstat, &sy, b, D, W, bias, C, labels, grad_scale, B, logits_out, row_loss, row_correct, pooled_out,
+                          dlogits_out))
+    return;
   if (!dfeat_out) return;
   __syncthreads();
   // d_pooled = d_logits . W  ->  cls: row 0 of the image only (compact, row-mapped by the caller); mean: d_pooled / L on every row
   if (t < D4) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < C; ++c) {
-      const f32x4 w = load4(W + (int64_t)c * D + 4 * t);
-      const f32x4 wr = {head_round<T>(w[0]), head_round<T>(w[1]), head_round<T>(w[2]), head_round<T>(w[3])};
-      acc += sdl[c] * wr;
-    }
+    f32x4 acc = head_dpooled<T>(sdl, W, C, D, t);
     if (pool == MAE_POOL_CLS) {
       store4(dfeat_out + (int64_t)b * D + 4 * t, acc);
     } else {
       acc = acc / (float)L;
       for (int j = 0; j < L; ++j) store4(dfeat_out + (row0 + j) * D + 4 * t, acc);
+    }
+  }
+}
+
+// The same head over the mean of rows [lo, hi) of each image's `seq` rows: a patch-only sequence (lo = 0) or the patch rows
+// behind a class token (lo = 1).  All four waves load rows: wave w sums rows lo + w, lo + w + 4, ... (lane l owns the 4-column
+// groups l, l + 64, ...), and the four partial sums are added through LDS in wave order 0, 1, 2, 3, so the summation order is
+// fixed by (lo, hi) alone.  The feature gradient is d_pooled / (hi - lo) on the pooled rows and exact zeros on the others.
+template <class T>
+__global__ void __launch_bounds__(256) classifier_head_range_kernel(const T* __restrict__ feats, int seq, int D, int lo, int hi,
+                                                                    const float* __restrict__ W, const float* __restrict__ bias, int C,
+                                                                    const int64_t* __restrict__ labels, float grad_scale, int B,
+                                                                    float* __restrict__ logits_out, float* __restrict__ row_loss,
+                                                                    int32_t* __restrict__ row_correct, float* __restrict__ pooled_out,
+                                                                    float* __restrict__ dlogits_out, T* __restrict__ dfeat_out) {
+  __shared__ __attribute__((aligned(16))) float sp[1024];
+  __shared__ __attribute__((aligned(16))) float part[3][1024];  // the partial sums of waves 1..3; then d_pooled in part[0]
+  __shared__ float sl[HEAD_MAX_CLASSES], sdl[HEAD_MAX_CLASSES], sstat[2];
+  __shared__ int sy;
+  constexpr int Q = 4;  // 4-column groups per lane: D / 4 <= 256 = 64 * Q
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int D4 = D / 4;
+  const int64_t row0 = (int64_t)b * seq;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[Q] = {z, z, z, z};
+#pragma unroll 2
+  for (int j = lo + wave; j < hi; j += 4) {
+    const T* row = feats + (row0 + j) * D;
+#pragma unroll
+    for (int i = 0; i < Q; ++i)
+      if (lane + 64 * i < D4) acc[i] += load4(row + 4 * (lane + 64 * i));
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int i = 0; i < Q; ++i)
+      if (lane + 64 * i < D4) store4(&part[wave - 1][4 * (lane + 64 * i)], acc[i]);
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const float n = (float)(hi - lo);
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+      const int q = lane + 64 * i;
+      if (q < D4) {
+        f32x4 v = acc[i];
+        for (int w = 0; w < 3; ++w) v += load4(&part[w][4 * q]);
+        v = v / n;
+        for (int k = 0; k < 4; ++k) sp[4 * q + k] = head_round<T>(v[k]);  // rounding point (1)
+      }
+    }
+  }
+  __syncthreads();
+  if (!head_after_pool<T>(sp, sl, sdl, sstat, &sy, b, D, W, bias, C, labels, grad_scale, B, logits_out, row_loss, row_correct, pooled_out,
+                          dlogits_out))
+    return;
+  if (!dfeat_out) return;
+  __syncthreads();
+  if (t < D4) store4(&part[0][4 * t], head_dpooled<T>(sdl, W, C, D, t) / (float)(hi - lo));
+  __syncthreads();
+  for (int j = wave; j < seq; j += 4) {
+    T* row = dfeat_out + (row0 + j) * D;
+    const bool pooled = j >= lo && j < hi;
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+      const int q = lane + 64 * i;
+      if (q < D4) store4(row + 4 * q, pooled ? load4(&part[0][4 * q]) : z);
     }
   }
 }
@@ -157,6 +248,27 @@ int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int p
   MAE_REQUIRE(!cls_rows || (mean_all && rstd_all && mean_c && rstd_c), "classifier_head: class-row statistics need every buffer");
 #define HEAD(T) hipLaunchKernelGGL(classifier_head_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)feats, L, D, pool, W, bias, C, labels, grad_scale, B, \
                                    logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out, mean_all, rstd_all, mean_c, rstd_c, cls_rows)
+  if (dt == MAE_BF16) HEAD(bf16); else HEAD(float);
+#undef HEAD
+  MAE_LAUNCH_CHECK();
+  if (loss_out || correct_out) {
+    hipLaunchKernelGGL(classifier_reduce_kernel, dim3(1), dim3(256), 0, s, row_loss, row_correct, B, loss_out, correct_out);
+    MAE_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+int launch_classifier_head_range(const void* feats, int dt, int B, int seq, int D, int lo, int hi, const float* W, const float* bias, int C,
+                                 const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
+                                 float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out, hipStream_t s) {
+  MAE_REQUIRE(feats && W && bias && row_loss && row_correct && B > 0 && seq > 0, "classifier_head_range: bad arguments");
+  MAE_REQUIRE(lo >= 0 && lo < hi && hi <= seq, "classifier_head_range: rows [%d, %d) outside the sequence of %d", lo, hi, seq);
+  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "classifier_head_range: D = %d must be a multiple of 4 in [4, 1024]", D);
+  MAE_REQUIRE(C >= 2 && C <= HEAD_MAX_CLASSES, "classifier_head_range: num_classes = %d outside [2, %d]", C, HEAD_MAX_CLASSES);
+  MAE_REQUIRE(!dlogits_out || pooled_out, "classifier_head_range: the backward needs the pooled-feature buffer");
+  MAE_REQUIRE(!dfeat_out || dlogits_out, "classifier_head_range: the feature gradient needs d_logits");
+#define HEAD(T) hipLaunchKernelGGL(classifier_head_range_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)feats, seq, D, lo, hi, W, bias, C, labels, \
+                                   grad_scale, B, logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out)
   if (dt == MAE_BF16) HEAD(bf16); else HEAD(float);
 #undef HEAD
   MAE_LAUNCH_CHECK();
@@ -235,7 +347,8 @@ int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, voi
 //   partial[slice][t][d] = sum of dres[b, t, d] over the slice's images in ascending order.
 // The slices' partials are then added in order: d pos_embed[t] = sum_b dres[b, t], and d cls_token = d pos_embed[0].
 // Thread (t, 4 columns) of slice s walks its images with four rows in flight.
-template <class T>
+// HAS_CLS = false is the patch-only sequence (L = num_patches rows, row t is patch token t + 1): no row is zeroed in dtok.
+template <class T, bool HAS_CLS>
 __global__ void __launch_bounds__(256) full_grad_split_kernel(const float* __restrict__ dx, int B, int L, int D, T* __restrict__ dtok,
                                                               float* __restrict__ partial) {
   const int D4 = D / 4;
@@ -258,7 +371,7 @@ __global__ void __launch_bounds__(256) full_grad_split_kernel(const float* __res
     for (int u = 0; u < U; ++u) {
       if (bb + u < b1) {
         acc += v[u];
-        store4(dtok + (((int64_t)(bb + u) * L + t) * D) + d, t == 0 ? z : v[u]);
+        store4(dtok + (((int64_t)(bb + u) * L + t) * D) + d, HAS_CLS && t == 0 ? z : v[u]);
       }
     }
   }
@@ -276,12 +389,30 @@ int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* d
   const int S = full_grad_split_slices(B, L, D);
   const dim3 grid((unsigned)cdiv((int64_t)L * (D / 4), 256), S);
   if (dt == MAE_BF16)
-    hipLaunchKernelGGL(full_grad_split_kernel<bf16>, grid, dim3(256), 0, s, dx, B, L, D, (bf16*)dtok, partial);
+    hipLaunchKernelGGL((full_grad_split_kernel<bf16, true>), grid, dim3(256), 0, s, dx, B, L, D, (bf16*)dtok, partial);
   else
-    hipLaunchKernelGGL(full_grad_split_kernel<float>, grid, dim3(256), 0, s, dx, B, L, D, (float*)dtok, partial);
+    hipLaunchKernelGGL((full_grad_split_kernel<float, true>), grid, dim3(256), 0, s, dx, B, L, D, (float*)dtok, partial);
   MAE_LAUNCH_CHECK();
   MAE_TRY(launch_sum_partials(partial, S, L * D, dpos, nullptr, L * D, s));
   MAE_HIP(hipMemcpyAsync(dcls, dpos, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// The patch-only sibling: dx is (B, N, D) with row t = patch token t + 1.  Same slices and summation order; the sums land in
+// rows 1..N of dpos ((N + 1) * D floats), and row 0 of dpos and dcls (D floats) -- no token carries them -- become exact zeros.
+int launch_patch_grad_split(const float* dx, int B, int N, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s) {
+  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && N > 0 && D % 4 == 0 && D <= 1024, "patch_grad_split: bad arguments");
+  MAE_REQUIRE((int64_t)B * N < (1ll << 31), "patch_grad_split: B * N < 2^31");
+  const int S = full_grad_split_slices(B, N, D);
+  const dim3 grid((unsigned)cdiv((int64_t)N * (D / 4), 256), S);
+  if (dt == MAE_BF16)
+    hipLaunchKernelGGL((full_grad_split_kernel<bf16, false>), grid, dim3(256), 0, s, dx, B, N, D, (bf16*)dtok, partial);
+  else
+    hipLaunchKernelGGL((full_grad_split_kernel<float, false>), grid, dim3(256), 0, s, dx, B, N, D, (float*)dtok, partial);
+  MAE_LAUNCH_CHECK();
+  MAE_TRY(launch_sum_partials(partial, S, N * D, dpos + D, nullptr, N * D, s));
+  MAE_HIP(hipMemsetAsync(dpos, 0, (size_t)D * 4, s));
+  MAE_HIP(hipMemsetAsync(dcls, 0, (size_t)D * 4, s));
   return 0;
 }
 
@@ -305,6 +436,21 @@ extern "C" int64_t mae_classifier_head_scratch_bytes(int32_t batch, int32_t num_
   return 4 * (seg(B * D) + seg(B * C) + 2 * seg(B) + seg(mae::classifier_wgrad_partial_floats(batch, num_classes, dim)) + seg(C * D + C));
 }
 
+namespace mae {
+struct HeadScratch { float *pooled, *dlogits, *row_loss; int32_t* row_correct; float *partial, *hsum; };
+static HeadScratch head_scratch(void* scratch, int64_t B, int64_t C, int64_t D) {
+  auto seg = [](int64_t n) { return round_up(n, 64); };
+  HeadScratch h;
+  h.pooled = reinterpret_cast<float*>(scratch);
+  h.dlogits = h.pooled + seg(B * D);
+  h.row_loss = h.dlogits + seg(B * C);
+  h.row_correct = reinterpret_cast<int32_t*>(h.row_loss + seg(B));
+  h.partial = h.row_loss + 2 * seg(B);
+  h.hsum = h.partial + seg(classifier_wgrad_partial_floats((int)B, (int)C, (int)D));
+  return h;
+}
+}  // namespace mae
+
 extern "C" int mae_classifier_head(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t pool,
                                    const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
                                    float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
@@ -317,18 +463,43 @@ extern "C" int mae_classifier_head(const void* feats, int32_t dtype, int32_t bat
   MAE_REQUIRE(!d_feats || head_grads, "mae_classifier_head: d_feats needs head_grads");
   MAE_REQUIRE(!head_grads || labels, "mae_classifier_head: gradients need labels");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t B = batch, C = num_classes, D = dim;
-  auto seg = [](int64_t n) { return round_up(n, 64); };
-  float* pooled = reinterpret_cast<float*>(scratch);
-  float* dlogits = pooled + seg(B * D);
-  float* row_loss = dlogits + seg(B * C);
-  int32_t* row_correct = reinterpret_cast<int32_t*>(row_loss + seg(B));
-  float* partial = row_loss + 2 * seg(B);
-  float* hsum = partial + seg(classifier_wgrad_partial_floats(batch, num_classes, dim));
-  MAE_TRY(launch_classifier_head(feats, dtype, batch, seq_len, dim, pool, head, head + C * D, num_classes, labels, grad_scale, logits, row_loss,
-                                 row_correct, loss_out, correct_out, head_grads ? pooled : nullptr, head_grads ? dlogits : nullptr, d_feats,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, s));
+  const HeadScratch hs = head_scratch(scratch, batch, num_classes, dim);
+  MAE_TRY(launch_classifier_head(feats, dtype, batch, seq_len, dim, pool, head, head + (int64_t)num_classes * dim, num_classes, labels, grad_scale,
+                                 logits, hs.row_loss, hs.row_correct, loss_out, correct_out, head_grads ? hs.pooled : nullptr,
+                                 head_grads ? hs.dlogits : nullptr, d_feats, nullptr, nullptr, nullptr, nullptr, nullptr, s));
   if (!head_grads) return 0;
-  return launch_classifier_head_wgrad(dlogits, pooled, batch, num_classes, dim, partial, hsum, head_grads, s);
+  return launch_classifier_head_wgrad(hs.dlogits, hs.pooled, batch, num_classes, dim, hs.partial, hs.hsum, head_grads, s);
+}
+
+// the same on a sequence with (with_cls = 1) or without (0) a class-token row, with the patch-row mean: see mae_hip.h
+extern "C" int mae_classifier_head_ex(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls,
+                                      int32_t pool, const float* head, int32_t num_classes, const int64_t* labels, float grad_scale,
+                                      float* logits, float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats,
+                                      void* scratch, int64_t scratch_bytes, void* stream) {
+  using namespace mae;
+  const char* who = "mae_classifier_head_ex";
+  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES,
+              "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
+  MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
+  if (with_cls && pool != MAE_POOL_MEAN_PATCHES)
+    return mae_classifier_head(feats, dtype, batch, seq_len, dim, pool, head, num_classes, labels, grad_scale, logits, loss_out, correct_out,
+                               head_grads, d_feats, scratch, scratch_bytes, stream);
+  MAE_REQUIRE(dtype == MAE_F32 || dtype == MAE_BF16, "%s: dtype must be MAE_F32 or MAE_BF16", who);
+  const int lo = with_cls ? 1 : 0;
+  MAE_REQUIRE(seq_len > lo, "%s: seq_len = %d leaves no patch row to pool", who, seq_len);
+  const int64_t need = mae_classifier_head_scratch_bytes(batch, num_classes, dim);
+  MAE_REQUIRE(need > 0 && scratch && scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0,
+              "%s: scratch must hold mae_classifier_head_scratch_bytes (%lld) bytes, 256-byte aligned", who, (long long)need);
+  MAE_REQUIRE(!d_feats || head_grads, "%s: d_feats needs head_grads", who);
+  MAE_REQUIRE(!head_grads || labels, "%s: gradients need labels", who);
+  MAE_REQUIRE(head && (labels || (!loss_out && !correct_out)), "%s: null head, or loss / correct count without labels", who);
+  hipStream_t s = (hipStream_t)stream;
+  const HeadScratch hs = head_scratch(scratch, batch, num_classes, dim);
+  MAE_TRY(launch_classifier_head_range(feats, dtype, batch, seq_len, dim, lo, seq_len, head, head + (int64_t)num_classes * dim, num_classes, labels,
+                                       grad_scale, logits, hs.row_loss, hs.row_correct, loss_out, correct_out, head_grads ? hs.pooled : nullptr,
+                                       head_grads ? hs.dlogits : nullptr, d_feats, s));
+  if (!head_grads) return 0;
+  return launch_classifier_head_wgrad(hs.dlogits, hs.pooled, batch, num_classes, dim, hs.partial, hs.hsum, head_grads, s);
 }
 

@@ -77,6 +77,11 @@ int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int p
                            const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
                            float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out,
                            const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s);
+// the same head over the mean of rows [lo, hi) of each image's seq rows, four waves loading rows; dfeat_out (B*seq, D): d_pooled /
+// (hi - lo) on the pooled rows, exact zeros on the others
+int launch_classifier_head_range(const void* feats, int dt, int B, int seq, int D, int lo, int hi, const float* W, const float* bias, int C,
+                                 const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
+                                 float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out, hipStream_t s);
 // head_grads[0 .. C*D) = dW, [C*D .. C*D+C) = db; partial >= classifier_wgrad_partial_floats, sum_out >= round_up(C*D+C, 4) floats
 int64_t classifier_wgrad_partial_floats(int B, int C, int D);
 int launch_classifier_head_wgrad(const float* dlogits, const float* pooled, int B, int C, int D, float* partial, float* sum_out,
@@ -87,6 +92,9 @@ int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, voi
 // partial >= full_grad_split_slices(B, L, D) * L * D floats
 int full_grad_split_slices(int B, int L, int D);
 int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s);
+// patch-only sequence, dx (B, N, D): dtok = dx, dpos rows 1..N = sum over images, dpos row 0 and dcls = exact zeros.
+// partial >= full_grad_split_slices(B, N, D) * N * D floats
+int launch_patch_grad_split(const float* dx, int B, int N, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s);
 // io[0] += sum(g^2) (io[1] is a temporary)
 int launch_grad_sumsq_accumulate(const float* g, int64_t n, float* io, float* scratch, hipStream_t s);
 

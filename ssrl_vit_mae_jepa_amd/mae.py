@@ -184,8 +184,11 @@ class _Node(nn.Module):
 class _ViT(_Node):
     """Stands where timm's VisionTransformer stands (``mae.encoder.vit``): ``blocks`` (indexable), ``norm``,
     ``embed_dim``, ``forward_features`` -- what the reference's classifier touches (src/models/classifier.py:47-57,
-    src/training/classifier.py:144-165)."""
+    src/training/classifier.py:144-165).  ``with_cls`` tells a downstream consumer (the classifier, the feature
+    extraction of the evaluation tools) which sequence the encoder was trained on: [cls | patches] (True, MAE and the
+    baseline ViT) or the patch tokens alone (False, set by the I-JEPA loaders)."""
     embed_dim: int = 0
+    with_cls: bool = True
 
     def forward_features(self, images: torch.Tensor) -> torch.Tensor:
         """timm VisionTransformer.forward_features: every token, no masking (scripts/training/train_mae.py:143).

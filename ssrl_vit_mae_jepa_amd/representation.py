@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .classifier import build_baseline_encoder, encoder_mae
+from .classifier import build_baseline_encoder, checkpoint_with_cls, encoder_mae
 from .mae import _ViT, _stream
 
 _ptr = _lib.ptr
@@ -149,7 +149,8 @@ class EvalEncoder:
 
     @property
     def with_cls(self) -> bool:
-        return self.kind != "ijepa"
+        """False for every encoder trained on the patch tokens alone: I-JEPA, and a classifier fine-tuned from one."""
+        return self.kind != "ijepa" and (self.vit is None or bool(self.vit.with_cls))
 
     @property
     def embed_dim(self) -> int:
@@ -233,12 +234,46 @@ def load_eval_encoder(src: Union[str, Path, Dict[str, Any]], model_cfg: Dict[str
         vit = encoder_mae(cfg).encoder.vit
         if layout == "ijepa_pt":
             _load_vit(vit, state, "target_encoder.vit." if encoder == "target" else "encoder.vit.")
+            vit.with_cls = False
             out = EvalEncoder("ijepa", layout, encoder, vit=vit)
         else:
             prefix = {"mae_ckpt": "model.encoder.vit.", "mae_pt": "encoder.vit.", "classifier_ckpt": "model.encoder."}[layout]
             _load_vit(vit, state, prefix)
+            if layout == "classifier_ckpt":  # a classifier fine-tuned from I-JEPA keeps running on the patch tokens alone
+                vit.with_cls = checkpoint_with_cls(ckpt)
             out = EvalEncoder("classifier" if layout == "classifier_ckpt" else "mae", layout, "vit", vit=vit)
     return out.to(device) if device is not None else out
+
+
+def load_ijepa_encoder(src: Union[str, Path, Dict[str, Any]], model_cfg: Dict[str, Any], encoder: str = "target",
+                       precision: Optional[str] = None) -> _ViT:
+    """An I-JEPA checkpoint as the classifier's encoder node (``ViTClassifier(pretrained_encoder=...)``): a fresh ViT of
+    ``model_cfg`` holding the EMA target encoder (``encoder="target"``, what I-JEPA evaluates) or the context encoder, with
+    ``with_cls = False`` so that the classifier runs over the patch tokens alone.  Accepts the ``ijepa_ckpt`` layout
+    (model.net.* + model.target_arena; needs model.predictor in the config, which fixes the arena layout) and ``ijepa_pt``
+    (encoder.vit.* + target_encoder.vit.*).  Strict: any other layout, or a missing encoder tensor, raises."""
+    if encoder not in ("target", "context"):
+        raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
+    cfg = _general(model_cfg, precision)
+    ckpt = torch.load(src, map_location="cpu", weights_only=False) if isinstance(src, (str, Path)) else src
+    state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
+    layout = checkpoint_layout(state)
+    if layout == "ijepa_ckpt":
+        from .jepa import IJEPAPretrainModule
+        if "predictor" not in cfg:
+            raise ValueError("an I-JEPA checkpoint needs model.predictor in the config")
+        module = IJEPAPretrainModule(cfg, {})
+        module.load_checkpoint_dict({"state_dict": state})
+        source = module.model.target_state_dict() if encoder == "target" else module.model.net.state_dict()
+        prefix = "encoder.vit."
+    elif layout == "ijepa_pt":
+        source, prefix = state, "target_encoder.vit." if encoder == "target" else "encoder.vit."
+    else:
+        raise ValueError(f"not an I-JEPA checkpoint (layout {layout}): expected model.net.* + model.target_arena, or encoder.vit.* + target_encoder.vit.*")
+    vit = encoder_mae({k: v for k, v in cfg.items() if k != "decoder"}).encoder.vit  # the classifier never runs a decoder: the smallest one
+    _load_vit(vit, source, prefix)
+    vit.with_cls = False
+    return vit
 
 
 @torch.no_grad()

@@ -6,8 +6,11 @@ For each model (the configs/mae.yaml encoder and ViT-S/8 of configs/vits8_dec192
     in the last-1 and full modes, alternated with the fused step in the same process;
   * the evaluation forward (no grad).
 Device events time `--steps` steps after `--warmup` steps; each number is the median of `--repeats` timed runs.
+`--patch_only` runs the encoder over the patch tokens alone (an I-JEPA encoder; no hand-off: forward_features has no such
+sequence), `--pool` overrides the config's pool, `--timers` adds the engine's per-kernel-class milliseconds of one fused step.
 
     python tools/classifier_bench.py --batch 2000 --steps 10 --warmup 3 --out profiles/r04_classifier_bench.json
+    python tools/classifier_bench.py --models vits8 --patch_only --pool mean_patches --timers
 """
 from __future__ import annotations
 
@@ -50,11 +53,15 @@ def set_mode(mod, mode):
 
 
 def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repeats: int, modes=("frozen", "last1", "full"),
-                handoff: bool = True) -> dict:
+                handoff: bool = True, patch_only: bool = False, pool=None, timers: bool = False) -> dict:
     cfg = yaml.safe_load(cfg_path.read_text())
     mc = dict(cfg["model"], general=dict(cfg["model"]["general"], engine_precision=cfg.get("engine", {}).get("precision", "bf16")))
+    if pool is not None:
+        mc["head"] = dict(mc.get("head") or {}, pool=pool)
     dev = torch.device("cuda", 0)
     mae = encoder_mae(mc)
+    mae.encoder.vit.with_cls = not patch_only
+    handoff = handoff and not patch_only and mc.get("head", {}).get("pool", "cls") == "cls"  # the hand-off below pools the class token
     mod = ViTClassifierTrainModule(pretrained_encoder=mae.encoder.vit, model_cfg=mc, training_cfg=dict(cfg.get("train", {}))).to(dev)
     S = mc["general"]["image_size"]
     g = torch.Generator(device=dev).manual_seed(0)
@@ -63,7 +70,7 @@ def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repe
     m = mod.model.mae
     ws_bytes = int(mod.model.workspace(B).numel())
     res = {"model": name, "config": str(cfg_path.relative_to(ROOT)), "batch": B, "precision": m.engine.precision,
-           "workspace_gib": ws_bytes / 2 ** 30, "ms": {}, "images_per_s": {}}
+           "with_cls": not patch_only, "pool": mod.model.pool_type, "workspace_gib": ws_bytes / 2 ** 30, "ms": {}, "images_per_s": {}}
 
     def fused():
         mod.fused_training_step(images, labels, lr=1e-5)
@@ -95,6 +102,13 @@ def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repe
         for _r in range(repeats):  # alternated: fused, hand-off, fused, hand-off, ...
             for key, fn in cases:
                 runs.setdefault(key, []).append(timed(fn, steps, warmup))
+        if timers:  # one more fused step with the engine's event timers on: milliseconds per kernel class
+            m.engine.timers_enable(True)
+            m.engine.timers_reset()
+            fused()
+            torch.cuda.synchronize()
+            res.setdefault("timers_ms", {})[f"fused_{mode}"] = {k: round(v["ms"], 4) for k, v in m.engine.timers_read().items() if v["launches"]}
+            m.engine.timers_enable(False)
     mod.freeze_encoder()
     for _r in range(repeats):
         runs.setdefault("eval_forward", []).append(timed(evaluate, steps, warmup))
@@ -115,6 +129,9 @@ def main(argv=None):
     ap.add_argument("--models", default="yaml,vits8")
     ap.add_argument("--modes", default="frozen,last1,full")
     ap.add_argument("--no-handoff", action="store_true", help="fused steps only (e.g. under a kernel trace)")
+    ap.add_argument("--patch_only", action="store_true", help="the encoder over the patch tokens alone (with_cls = False)")
+    ap.add_argument("--pool", choices=["cls", "mean", "mean_patches"], default=None, help="overrides model.head.pool of the config")
+    ap.add_argument("--timers", action="store_true", help="per-kernel-class milliseconds of one fused step per mode")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -122,7 +139,7 @@ def main(argv=None):
     out = {"tool": "tools/classifier_bench.py", "argv": sys.argv[1:], "device": torch.cuda.get_device_name(0), "results": []}
     for name in args.models.split(","):
         out["results"].append(bench_model(name, cfgs[name], args.batch, args.steps, args.warmup, args.repeats,
-                                              tuple(args.modes.split(",")), not args.no_handoff))
+                                              tuple(args.modes.split(",")), not args.no_handoff, args.patch_only, args.pool, args.timers))
         torch.cuda.empty_cache()
     text = json.dumps(out, indent=1)
     print(text)
