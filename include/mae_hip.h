@@ -518,6 +518,70 @@ int mae_attention_fwd(const void* qkv, int32_t batch, int32_t T, int32_t H, int3
 int mae_attention_bwd(const void* qkv, const void* out, const void* d_out, const float* lse, int32_t batch,
                       int32_t T, int32_t H, int32_t hd, int32_t dtype, void* d_qkv, void* stream);
 
+/* Token and pixel movement between those pieces, and the losses that read the image.  Index arguments are int32, as the kernels
+ * take them; token id 0 is the class token, id t >= 1 is patch t - 1 (row-major over the patch grid).  Unless a function says
+ * otherwise the ids must lie in [0, seq_len): nothing here range-checks them on the device.  `partial` is scratch of
+ * >= 512 * dim floats.  Column sums are two-stage, in a fixed order (no atomics): bit-identical from run to run. */
+
+/* Rows of the patch-embedding GEMM: out (batch * num_keep, C*p*p) in out_dtype, row (b, j) = patch tok32[b][j] - 1 of image b in
+ * conv-weight order (c, py, px); a class-token id (<= 0) gives a zero row.  images as mae_engine_forward_encoder (MAE_U8: normalised
+ * in the read; needs patch_size % 4 == 0, at most 64 patches per side and C * p * image_size <= 96 KiB, else an error before
+ * the launch).  MAE_F32 images: ids in [0, num_patches] (not clamped). */
+int mae_gather_patches(const void* images, int32_t image_dtype, const int32_t* tok32, int32_t batch, int32_t num_keep,
+                       int32_t in_chans, int32_t image_size, int32_t patch_size, int32_t out_dtype, void* out, void* stream);
+/* In place on x (rows, dim) fp32: x[r] = (tok32[r] == 0 ? cls : x[r]) + pos[tok32[r]] -- one fp32 addition.  dim % 4 == 0. */
+int mae_assemble_visible(float* x, const int32_t* tok32, const float* cls, const float* pos, int64_t rows, int32_t dim,
+                         void* stream);
+/* Its adjoint: dtok (rows, dim) in dtype = dx with the class-token rows (tok32[r] == 0) replaced by exact zeros; dcls (dim)
+ * fp32 = the sum of those rows.  dx fp32; dim % 4 == 0, dim <= 1024. */
+int mae_visible_grad_split(const float* dx, const int32_t* tok32, int64_t rows, int32_t dim, int32_t dtype, void* dtok,
+                           float* dcls, float* partial, void* stream);
+/* inv (batch, seq_len): inv[b][keep32[b][j]] = j, every other entry -1 (ids outside [0, seq_len) are ignored). */
+int mae_build_inverse(const int32_t* keep32, int32_t batch, int32_t num_keep, int32_t seq_len, int32_t* inv, void* stream);
+/* rows[b * n_per + j] = b * seq_len + clamp(idx32[b][j], 0, seq_len - 1): rows of the (batch * seq_len) decoder matrix. */
+int mae_build_row_map(const int32_t* idx32, int32_t batch, int32_t n_per, int32_t seq_len, int32_t* rows, void* stream);
+/* Decoder input: out[b][t] (fp32) = (inv[b][t] >= 0 ? xdec[b * num_keep + inv[b][t]] : mask_token) + pos[t]; xdec in dtype,
+ * widened to fp32 before the one fp32 addition.  dim % 4 == 0, dim <= 1024, batch * seq_len < 2^31. */
+int mae_decoder_assemble(const void* xdec, int32_t dtype, const int32_t* inv, const float* mask_token, const float* pos,
+                         int32_t batch, int32_t num_keep, int32_t seq_len, int32_t dim, float* out, void* stream);
+/* Its adjoint: d_xdec[b * num_keep + inv[b][t]] (dtype) = dx[b][t] for every t with inv >= 0 (rows no inv entry names are not
+ * written); d_mask_token (dim) fp32 = the sum of the rows with inv < 0 (exact zeros when there are none). */
+int mae_decoder_assemble_bwd(const float* dx, const int32_t* inv, int32_t batch, int32_t num_keep, int32_t seq_len, int32_t dim,
+                             int32_t dtype, void* d_xdec, float* d_mask_token, float* partial, void* stream);
+/* Exact zeros in every row of dres (fp32) and dres_c (dtype), both (rows, dim), that the prediction head never saw: rows with
+ * inv[row] >= 0, or with inv == NULL the first seq_len - num_pred rows of every sequence of seq_len.  No other row is touched. */
+int mae_zero_unpredicted_rows(const int32_t* inv_or_null, int64_t rows, int32_t seq_len, int32_t num_pred, int32_t dim,
+                              int32_t dtype, float* dres, void* dres_c, void* stream);
+/* mae_mse_loss between pred (batch, num_mask, p*p*C) fp32 and the patches mask32 of images in (py, px, c) order, never written
+ * to memory: n = batch * num_mask * p*p*C, d_pred (may be NULL) in d_pred_dtype.  One rule for every variant (band walk over
+ * float images, band walk over uint8 images, per-pixel gather): entry t reads patch clamp(t - 1, 0, num_patches - 1).
+ *   path = 0: what the engine launches (MAE_U8: the uint8 band walk, or an error when patch_size % 4 != 0, more than 64 patches
+ *             per side or a band beyond the LDS; MAE_F32: the band walk where it applies, else the per-pixel gather);
+ *   path = 1: the per-pixel gather, MAE_F32 images only.
+ * scratch: >= 4096 floats. */
+int mae_mse_loss_from_images(const float* pred, const void* images, int32_t image_dtype, const int32_t* mask32, int32_t batch,
+                             int32_t num_mask, int32_t in_chans, int32_t image_size, int32_t patch_size, float grad_scale,
+                             float* loss, void* d_pred /* may be NULL */, int32_t d_pred_dtype, float* scratch, int32_t path,
+                             void* stream);
+/* I-JEPA predictor input: num_blocks sequences per image of num_context + block_tokens rows,
+ * out[(b, blk, t)] (fp32) = t < num_context ? xdec[b * num_context + t] + pos[ctx32[b][t]]
+ *                                           : mask_token + pos[tgt32[b][blk][t - num_context]]   (ids clamped into [0, seq_len)). */
+int mae_predictor_assemble(const void* xdec, int32_t dtype, const int32_t* ctx32, const int32_t* tgt32, const float* mask_token,
+                           const float* pos, int32_t batch, int32_t num_context, int32_t num_blocks, int32_t block_tokens,
+                           int32_t seq_len, int32_t dim, float* out, void* stream);
+/* Its adjoint: d_xdec[b * num_context + t] (dtype) = sum over blk (ascending) of dx[(b, blk, t)]; d_mask_token (dim) fp32 = the sum
+ * of every mask-token row. */
+int mae_predictor_assemble_bwd(const float* dx, int32_t batch, int32_t num_context, int32_t num_blocks, int32_t block_tokens,
+                               int32_t dim, int32_t dtype, void* d_xdec, float* d_mask_token, float* partial, void* stream);
+/* rows[seq * num_pred + j] = seq * seq_len + (seq_len - num_pred) + j: the last num_pred rows of every sequence. */
+int mae_build_tail_row_map(int32_t seqs, int32_t seq_len, int32_t num_pred, int32_t* rows, void* stream);
+/* rows[i] = (i / per_image) * num_patches + clamp(tok32[i] - 1, 0, num_patches - 1). */
+int mae_rows_from_tokens(const int32_t* tok32, int32_t batch, int32_t per_image, int32_t num_patches, int32_t* rows, void* stream);
+/* torch.nn.functional.smooth_l1_loss (beta = 1, mean) over n elements (n % 4 == 0) and its gradient:
+ * d_pred (may be NULL, d_pred_dtype) = clamp(pred - target, -1, 1) * (grad_scale / n).  scratch: >= 4096 floats. */
+int mae_smooth_l1_loss(const float* pred, const float* target, int64_t n, float grad_scale, float* loss,
+                       void* d_pred /* may be NULL */, int32_t d_pred_dtype, float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

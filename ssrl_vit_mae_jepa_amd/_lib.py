@@ -125,6 +125,20 @@ SIGNATURES = {
     "mae_linear_wgrad_pair": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
     "mae_attention_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mae_attention_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_gather_patches": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_assemble_visible": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "mae_visible_grad_split": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mae_build_inverse": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "mae_build_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "mae_decoder_assemble": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_decoder_assemble_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mae_zero_unpredicted_rows": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mae_mse_loss_from_images": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "mae_predictor_assemble": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_predictor_assemble_bwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mae_build_tail_row_map": (C.c_int, [_i32, _i32, _i32, _vp, _vp]),
+    "mae_rows_from_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "mae_smooth_l1_loss": (C.c_int, [_vp, _vp, _i64, _f32, _vp, _vp, _i32, _vp, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -115,3 +115,11 @@ extern "C" int mae_mask_from_noise(const float* noise, int32_t batch, int32_t se
   return mae::launch_mask_from_noise(noise, batch, seq_len, num_keep, idx_keep, idx_mask, nullptr, nullptr,
                                      (hipStream_t)stream);
 }
+
+extern "C" int mae_build_inverse(const int32_t* keep32, int32_t batch, int32_t num_keep, int32_t seq_len, int32_t* inv, void* stream) {
+  return mae::launch_build_inverse(keep32, batch, num_keep, seq_len, inv, (hipStream_t)stream);
+}
+
+extern "C" int mae_build_row_map(const int32_t* idx32, int32_t batch, int32_t n_per, int32_t seq_len, int32_t* rows, void* stream) {
+  return mae::launch_build_row_map(idx32, batch, n_per, seq_len, rows, (hipStream_t)stream);
+}

@@ -191,3 +191,31 @@ int launch_smooth_l1(const float* pred, const float* target, int64_t n, float gr
 }
 
 }  // namespace mae
+
+extern "C" int mae_build_tail_row_map(int32_t seqs, int32_t seq_len, int32_t num_pred, int32_t* rows, void* stream) {
+  return mae::launch_build_tail_row_map(seqs, seq_len, num_pred, rows, (hipStream_t)stream);
+}
+
+extern "C" int mae_rows_from_tokens(const int32_t* tok32, int32_t batch, int32_t per_image, int32_t num_patches, int32_t* rows, void* stream) {
+  return mae::launch_rows_from_tokens(tok32, batch, per_image, num_patches, rows, (hipStream_t)stream);
+}
+
+extern "C" int mae_predictor_assemble(const void* xdec, int32_t dtype, const int32_t* ctx32, const int32_t* tgt32, const float* mask_token,
+                                      const float* pos, int32_t batch, int32_t num_context, int32_t num_blocks, int32_t block_tokens,
+                                      int32_t seq_len, int32_t dim, float* out, void* stream) {
+  MAE_REQUIRE(batch > 0 && num_context > 0 && num_blocks > 0 && block_tokens > 0 && seq_len > 0, "mae_predictor_assemble: bad arguments");
+  return mae::launch_predictor_assemble(xdec, dtype, ctx32, tgt32, mask_token, pos, batch, num_context, num_blocks, block_tokens, seq_len, dim, out,
+                                        (hipStream_t)stream);
+}
+
+extern "C" int mae_predictor_assemble_bwd(const float* dx, int32_t batch, int32_t num_context, int32_t num_blocks, int32_t block_tokens, int32_t dim,
+                                          int32_t dtype, void* d_xdec, float* d_mask_token, float* partial, void* stream) {
+  MAE_REQUIRE(batch > 0 && num_context > 0 && num_blocks > 0 && block_tokens > 0, "mae_predictor_assemble_bwd: bad arguments");
+  return mae::launch_predictor_assemble_bwd(dx, batch, num_context, num_blocks, block_tokens, dim, dtype, d_xdec, d_mask_token, partial,
+                                            (hipStream_t)stream);
+}
+
+extern "C" int mae_smooth_l1_loss(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,
+                                  int32_t d_pred_dtype, float* scratch, void* stream) {
+  return mae::launch_smooth_l1(pred, target, n, grad_scale, loss, d_pred, d_pred_dtype, scratch, (hipStream_t)stream);
+}

@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(256) mse_images_kernel(const float* __restrict
     const int py = q / p, px = q - py * p;
     const int64_t b = r / m;
     int n = mask32[r] - 1;
-    n = n < 0 ? 0 : n;
+    n = n < 0 ? 0 : (n >= g * g ? g * g - 1 : n);   // the clamp of band_tokens and patchify_gather_kernel: the variants agree on every id
     const int ph = n / g, pw = n - ph * g;
     const float* src = images + (b * C * (int64_t)img + (ph * p + py)) * img + pw * p + px;
     const int64_t o = r * (int64_t)(pp * C) + q * C;
@@ -95,15 +95,11 @@ int launch_mse(const float* pred, const float* target, int64_t n, float grad_sca
   return 0;
 }
 
-int launch_mse_from_images(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img,
-                           int p, float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch,
-                           hipStream_t s) {
-  MAE_REQUIRE(pred && images && mask32 && loss && scratch && B > 0 && m > 0 && img % p == 0, "mse_from_images: bad arguments");
-  {
-    static const bool band = [] { const char* v = getenv("MAE_MSE_BAND"); return !v || v[0] != '0'; }();   // MAE_MSE_BAND=0: the per-pixel gather (A/B)
-    const int r = band ? launch_mse_from_images_band_f32(pred, images, mask32, B, m, C, img, p, grad_scale, loss, d_pred, dpred_dt, scratch, s) : -1;
-    if (r >= 0) return r;
-  }
+// the per-pixel gather: any patch size, any alignment
+int launch_mse_from_images_gather(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img,
+                                  int p, float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch,
+                                  hipStream_t s) {
+  MAE_REQUIRE(pred && images && mask32 && loss && scratch && B > 0 && m > 0 && p > 0 && img % p == 0, "mse_from_images: bad arguments");
   const int64_t rows = (int64_t)B * m;
   const int64_t n = rows * p * p * C;
   const int grid = (int)std::min<int64_t>(cdiv(rows * p * p, 256), RED_BLOCKS);
@@ -118,6 +114,18 @@ int launch_mse_from_images(const float* pred, const float* images, const int32_t
   hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, s, scratch, grid, 1.0f / (float)n, loss);
   MAE_LAUNCH_CHECK();
   return 0;
+}
+
+int launch_mse_from_images(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img,
+                           int p, float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch,
+                           hipStream_t s) {
+  MAE_REQUIRE(pred && images && mask32 && loss && scratch && B > 0 && m > 0 && p > 0 && img % p == 0, "mse_from_images: bad arguments");
+  {
+    static const bool band = [] { const char* v = getenv("MAE_MSE_BAND"); return !v || v[0] != '0'; }();   // MAE_MSE_BAND=0: the per-pixel gather (A/B)
+    const int r = band ? launch_mse_from_images_band_f32(pred, images, mask32, B, m, C, img, p, grad_scale, loss, d_pred, dpred_dt, scratch, s) : -1;
+    if (r >= 0) return r;
+  }
+  return launch_mse_from_images_gather(pred, images, mask32, B, m, C, img, p, grad_scale, loss, d_pred, dpred_dt, scratch, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -332,4 +340,21 @@ int launch_transpose_to_bf16(const float* src, bf16* dst, int rows, int cols, hi
 extern "C" int mae_mse_loss(const float* pred, const float* target, int64_t n, float grad_scale, float* loss,
                             float* d_pred, float* scratch, void* stream) {
   return mae::launch_mse(pred, target, n, grad_scale, loss, d_pred, MAE_F32, scratch, (hipStream_t)stream);
+}
+
+extern "C" int mae_mse_loss_from_images(const float* pred, const void* images, int32_t image_dtype, const int32_t* mask32, int32_t batch,
+                                        int32_t num_mask, int32_t in_chans, int32_t image_size, int32_t patch_size, float grad_scale, float* loss,
+                                        void* d_pred, int32_t d_pred_dtype, float* scratch, int32_t path, void* stream) {
+  MAE_REQUIRE(image_dtype == MAE_F32 || image_dtype == MAE_U8, "mae_mse_loss_from_images: image_dtype must be MAE_F32 or MAE_U8 (got %d)", image_dtype);
+  MAE_REQUIRE(path == 0 || (path == 1 && image_dtype == MAE_F32), "mae_mse_loss_from_images: path must be 0, or 1 with MAE_F32 images (got %d)", path);
+  MAE_REQUIRE(in_chans > 0 && patch_size > 0, "mae_mse_loss_from_images: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  if (image_dtype == MAE_U8)
+    return mae::launch_mse_from_images_u8(pred, (const uint8_t*)images, mask32, batch, num_mask, in_chans, image_size, patch_size, grad_scale, loss,
+                                          d_pred, d_pred_dtype, scratch, s);
+  if (path == 1)
+    return mae::launch_mse_from_images_gather(pred, (const float*)images, mask32, batch, num_mask, in_chans, image_size, patch_size, grad_scale,
+                                              loss, d_pred, d_pred_dtype, scratch, s);
+  return mae::launch_mse_from_images(pred, (const float*)images, mask32, batch, num_mask, in_chans, image_size, patch_size, grad_scale, loss,
+                                     d_pred, d_pred_dtype, scratch, s);
 }

@@ -464,3 +464,40 @@ extern "C" int mae_patchify_gather(const void* images, int32_t image_dtype, cons
   return mae::launch_patchify_gather_i64((const float*)images, idx_mask, batch, num_mask, in_chans, image_size, patch_size, target,
                                          (hipStream_t)stream);
 }
+
+extern "C" int mae_gather_patches(const void* images, int32_t image_dtype, const int32_t* tok32, int32_t batch, int32_t num_keep, int32_t in_chans,
+                                  int32_t image_size, int32_t patch_size, int32_t out_dtype, void* out, void* stream) {
+  MAE_REQUIRE(image_dtype == MAE_F32 || image_dtype == MAE_U8, "mae_gather_patches: image_dtype must be MAE_F32 or MAE_U8 (got %d)", image_dtype);
+  if (image_dtype == MAE_U8)
+    return mae::launch_gather_patches_u8((const uint8_t*)images, tok32, batch, num_keep, in_chans, image_size, patch_size, out_dtype, out,
+                                         (hipStream_t)stream);
+  return mae::launch_gather_patches((const float*)images, tok32, batch, num_keep, in_chans, image_size, patch_size, out_dtype, out,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int mae_assemble_visible(float* x, const int32_t* tok32, const float* cls, const float* pos, int64_t rows, int32_t dim, void* stream) {
+  return mae::launch_assemble_visible(x, tok32, cls, pos, rows, dim, (hipStream_t)stream);
+}
+
+extern "C" int mae_visible_grad_split(const float* dx, const int32_t* tok32, int64_t rows, int32_t dim, int32_t dtype, void* dtok, float* dcls,
+                                      float* partial, void* stream) {
+  return mae::launch_visible_grad_split(dx, tok32, rows, dim, dtype, dtok, dcls, partial, (hipStream_t)stream);
+}
+
+extern "C" int mae_decoder_assemble(const void* xdec, int32_t dtype, const int32_t* inv, const float* mask_token, const float* pos, int32_t batch,
+                                    int32_t num_keep, int32_t seq_len, int32_t dim, float* out, void* stream) {
+  MAE_REQUIRE(batch > 0 && num_keep > 0 && num_keep <= seq_len, "mae_decoder_assemble: bad arguments");
+  return mae::launch_decoder_assemble(xdec, dtype, inv, mask_token, pos, batch, num_keep, seq_len, dim, out, (hipStream_t)stream);
+}
+
+extern "C" int mae_decoder_assemble_bwd(const float* dx, const int32_t* inv, int32_t batch, int32_t num_keep, int32_t seq_len, int32_t dim,
+                                        int32_t dtype, void* d_xdec, float* d_mask_token, float* partial, void* stream) {
+  MAE_REQUIRE(batch > 0 && num_keep > 0 && num_keep <= seq_len, "mae_decoder_assemble_bwd: bad arguments");
+  return mae::launch_decoder_assemble_bwd(dx, inv, nullptr, batch, num_keep, seq_len, dim, dtype, d_xdec, d_mask_token, partial,
+                                          (hipStream_t)stream);
+}
+
+extern "C" int mae_zero_unpredicted_rows(const int32_t* inv, int64_t rows, int32_t seq_len, int32_t num_pred, int32_t dim, int32_t dtype,
+                                         float* dres, void* dres_c, void* stream) {
+  return mae::launch_zero_unpredicted_rows(inv, rows, seq_len, num_pred, dim, dtype, dres, dres_c, (hipStream_t)stream);
+}
