@@ -75,7 +75,8 @@ __device__ __forceinline__ void stage_image_dma(char* s, int img_bytes, const bf
 }
 
 // Head dims below the template's HD (the tiny config's 24 runs the HD = 32 kernels): the 16-byte slots [cprv, CPR) of every
-// row take part in the 32-deep contractions, so they are zeroed after the DMAs have landed (a DMA cannot write zeros).
+// row take part in the 32-deep contractions, so they are zeroed after the DMAs have landed (a DMA cannot write zeros): after ALL
+// waves' DMAs, since a thread zeroes slots of 1 KiB blocks that other waves staged (the callers put a barrier in front).
 template <int HD>
 __device__ __forceinline__ void zero_pad_chunks(char* s, int rows, int cprv) {
   const int npad = AT<HD>::CPR - cprv;
@@ -233,6 +234,7 @@ __global__ void __launch_bounds__(kFwdCap) attn_fwd_mfma_kernel(const bf16* __re
   stage_image_dma<HD>(sV, img, base + 2ll * H * hdv, gs, T, wave, nwaves, lane, cprv);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (hdv < HD) {
+    __syncthreads();   // a wave has waited for its own DMAs only: a pad slot zeroed under another wave's DMA still in flight is overwritten
     if (!FQ) zero_pad_chunks<HD>(sQ, Ti, cprv);
     zero_pad_chunks<HD>(sK, Ti, cprv);
     zero_pad_chunks<HD>(sV, Ti, cprv);
@@ -383,6 +385,7 @@ __global__ void __launch_bounds__(bwd_cap(NCH)) attn_bwd_mfma_kernel(const bf16*
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (hdv < HD) {
+    __syncthreads();   // a wave has waited for its own DMAs only: a pad slot zeroed under another wave's DMA still in flight is overwritten
     if (PH != 1) zero_pad_chunks<HD>(sQ, Ti, cprv);
     if (PH != 2) zero_pad_chunks<HD>(sK, Ti, cprv);
     if (PH != 2) zero_pad_chunks<HD>(sV, Ti, cprv);
