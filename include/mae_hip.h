@@ -330,6 +330,41 @@ int mae_engine_classifier_loss_and_grads_ex(mae_engine_t* e, const float* params
                                             int32_t train_embed, float grad_scale, void* workspace, int64_t workspace_bytes,
                                             float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
                                             int32_t* correct_out, void* stream);
+/* Soft targets for fine-tuning (additive in ABI v4): mae_engine_classifier_loss_and_grads_ex with the loss of the MAE / DeiT
+ * fine-tuning recipe -- mixup / CutMix label pairs and label smoothing.  The target of row b is
+ *   t[b][c] = eps / C + (1 - eps) * (lam[b] * [c == labels[b]] + (1 - lam[b]) * [c == labels_b[b]]),   C = num_classes,
+ * loss = mean_b (lse_b - sum_c t[b][c] * logit[b][c]) and d_logits = (softmax - t) * grad_scale / batch, rounded where the hard
+ * loss rounds it; this is lam * CE(labels, label_smoothing = eps) + (1 - lam) * CE(labels_b, label_smoothing = eps) of torch.
+ *   labels_b: (batch) int64 on the device, NULL = labels;  lam: (batch) fp32 on the device, NULL = 1;
+ *   label_smoothing = eps in [0, 1) (else an error before any launch).
+ *   correct_out still counts argmax == labels[b] (the first label of a pair).  A label outside [0, num_classes) in labels OR
+ *   labels_b is never used as an index: that row's loss and gradients are NaN.  Deterministic as the calls above.
+ * With labels_b == NULL, lam == NULL and label_smoothing == 0 the call runs exactly the launches of
+ * mae_engine_classifier_loss_and_grads_ex (same bits).  Evaluation stays hard-label: there is no soft forward call. */
+int mae_engine_classifier_loss_and_grads_soft(mae_engine_t* e, const float* params, const void* wcache, const float* head,
+                                              const void* images, int32_t image_dtype, const int64_t* labels, int32_t batch,
+                                              int32_t with_cls, int32_t pool, int32_t num_classes, int32_t train_blocks,
+                                              int32_t train_embed, float grad_scale, void* workspace, int64_t workspace_bytes,
+                                              float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
+                                              int32_t* correct_out, const int64_t* labels_b, const float* lam, float label_smoothing,
+                                              void* stream);
+/* Batch mixing in front of that loss (additive in ABI v4; timm's Mixup in `batch` mode): image b is mixed with image
+ * partner[b] of the same batch into out (batch, C, S, S), which may not overlap images (checked).
+ *   images : (batch, C, S, S), MAE_U8 raw pixels or MAE_F32 normalised values; n() below is the engine's uint8 normalisation
+ *            (x / 255 - 0.5) / 0.5 for MAE_U8 (bit-identical to what its pixel kernels produce) and the identity for MAE_F32;
+ *   partner: (batch) int32; a value outside [0, batch) is never used as an index -- that image is its own partner;
+ *   lam    : (batch) fp32;   box: (batch, 4) int32 (y0, y1, x0, x1), half-open, clamped to [0, S] by the kernel; may be empty.
+ *   out_dtype = MAE_F32: inside the box n(partner pixel); outside it lam * n(own) + (1 - lam) * n(partner) in fp32 (1 - lam, one
+ *                        product and the sum round; lam == 1 copies n(own) bit for bit).
+ *   out_dtype = MAE_U8 : pure CutMix on MAE_U8 images (MAE_F32 images are an error): the partner's byte inside the box, the own
+ *                        byte outside; lam is not read (may be NULL).  The batch stays 1 byte per pixel for the engine.
+ * Any C >= 1 and 1 <= S <= 16384.  A thread moves V pixels, 16 bytes of output where the row length allows: V = 16 for MAE_U8
+ * output with S % 16 == 0, else V = 4 when S % 4 == 0, else V = 1.  Limits, checked before the launch: batch * C * S * S / V <= 2^31 - 256;
+ * MAE_U8 buffers V-byte aligned and MAE_F32 buffers 4 V-byte aligned (fp32 output at S = 96: images 4-byte if MAE_U8, 16-byte
+ * if MAE_F32, out 16-byte; uint8 output at S = 96: both 16-byte); partner / lam / box 4-byte. */
+int mae_mix_batch(const void* images, int32_t image_dtype, const int32_t* partner, const float* lam, const int32_t* box,
+                  int32_t batch, int32_t in_chans, int32_t image_size, int32_t out_dtype, void* out, void* stream);
+
 /* The classifier's optimizer (Lightning gradient_clip_val = 1.0 + one-group torch AdamW over the requires_grad tensors,
  * scripts/training/train_mae.py:213, src/training/classifier.py:106-108) over buffers that are not the arena's trainable range:
  *   mae_engine_grad_sumsq_buffer       : sumsq_io[0] = (accumulate ? sumsq_io[0] : 0) + sum of grads[0 .. count)^2
@@ -477,6 +512,13 @@ int mae_classifier_head_ex(const void* feats, int32_t dtype, int32_t batch, int3
                            const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
                            float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
                            int64_t scratch_bytes, void* stream);
+
+/* mae_classifier_head_ex with the soft targets of mae_engine_classifier_loss_and_grads_soft (labels_b / lam / label_smoothing as
+ * there).  With labels_b == NULL, lam == NULL and label_smoothing == 0 it is mae_classifier_head_ex: same launches, same bits. */
+int mae_classifier_head_soft(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls, int32_t pool,
+                             const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
+                             float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
+                             int64_t scratch_bytes, const int64_t* labels_b, const float* lam, float label_smoothing, void* stream);
 
 /* Epilogues of the GEMM family. */
 enum {

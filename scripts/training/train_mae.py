@@ -12,6 +12,13 @@ alone and pools with mean_patches unless model.head.pool / --pool says otherwise
     python -m scripts.training.train_mae --config configs/ijepa_vits8.yaml --encoder_ckpt outputs/pretrain/ijepa_pretrain/checkpoints/last.ckpt  Freeze precedence (:167-176): train.unfreeze_last_layers, then
 train.freeze_encoder.  Each epoch: the native fused step over the training split, a no-grad validation pass, the
 per-epoch LR, one metrics line; best.ckpt on a new maximum of val_acc, last.ckpt every epoch.
+
+The fine-tuning recipe of the MAE paper: --label_smoothing, --mixup, --cutmix and --layer_decay override the YAML keys
+train.label_smoothing / mixup_alpha / cutmix_alpha / layer_decay (configs/vits8_dec192_finetune.yaml sets 0.1, 0.8, 1.0, 0.75).
+Under mixup / CutMix the metrics line's ``train_loss`` is the soft-target loss and ``train_acc`` counts argmax == the image's
+own label (the first of each mixed pair), so it reads lower than the accuracy on clean images; ``val_*`` stay hard-label.
+
+    python -m scripts.training.train_mae --config configs/vits8_dec192_finetune.yaml --encoder_ckpt outputs/pretrain/mae_pretrain/checkpoints/last.ckpt
 """
 from __future__ import annotations
 
@@ -44,10 +51,22 @@ def parse_args(argv=None):
     parser.add_argument("--encoder", type=str, choices=["target", "context"], default="target",
                         help="which I-JEPA encoder to fine-tune (ignored for MAE checkpoints)")
     parser.add_argument("--pool", type=str, choices=["cls", "mean", "mean_patches"], default=None, help="overrides model.head.pool")
+    # the fine-tuning recipe (not in the reference): each overrides its train.* key
+    parser.add_argument("--label_smoothing", type=float, default=None, help="overrides train.label_smoothing (eps of the soft target)")
+    parser.add_argument("--mixup", type=float, default=None, help="overrides train.mixup_alpha (0 = off)")
+    parser.add_argument("--cutmix", type=float, default=None, help="overrides train.cutmix_alpha (0 = off)")
+    parser.add_argument("--layer_decay", type=float, default=None, help="overrides train.layer_decay (1 = one learning rate)")
     parser.add_argument("--max_epochs", type=int, default=None)
     parser.add_argument("--max_steps_per_epoch", type=int, default=None)
     parser.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic labeled images instead of STL-10")
     return parser.parse_args(argv)
+
+
+def apply_recipe_flags(cfg: dict, args) -> None:
+    """--label_smoothing / --mixup / --cutmix / --layer_decay into cfg["train"]; a flag that was not given changes nothing."""
+    for flag, key in (("label_smoothing", "label_smoothing"), ("mixup", "mixup_alpha"), ("cutmix", "cutmix_alpha"), ("layer_decay", "layer_decay")):
+        if getattr(args, flag, None) is not None:
+            cfg["train"][key] = float(getattr(args, flag))
 
 
 def model_config(cfg: dict) -> dict:
@@ -134,6 +153,7 @@ def main(argv=None):
     args = parse_args(argv)
     with open(args.config, "r") as f:
         cfg = yaml.safe_load(f)
+    apply_recipe_flags(cfg, args)
     if not torch.cuda.is_available():
         raise SystemExit("train_mae: the MI355X engine has no CPU fallback")
     dev = torch.device("cuda", 0)
@@ -148,6 +168,7 @@ def main(argv=None):
 
     train_batches, val_batches = get_train_batches(cfg, dev, synthetic_images=args.synthetic_images, seed=SEED)
     module = build_module(cfg, args.encoder_ckpt, args.classifier_ckpt, encoder=args.encoder, pool=args.pool).to(dev)
+    module.mix_seed = int(cfg.get("seed", SEED))  # the mixup / CutMix draw of a step is a function of (seed, epoch, step)
     total = int(train_cfg["total_epochs"]) if args.max_epochs is None else min(int(train_cfg["total_epochs"]), args.max_epochs)
     best_acc, log_path = -1.0, output_dir / "logs" / "metrics.jsonl"
     for epoch in range(total):

@@ -6,6 +6,11 @@ b, the layout the C ABI reads).  ``ViTClassifierTrainModule`` keeps the referenc
 logged names, and adds the native step: one call for forward + pooled head + cross-entropy + a backward that stops where
 the trainable blocks end, then clip_grad_norm_(1.0) + one-group AdamW over exactly the tensors whose ``requires_grad``
 is set (Lightning ``gradient_clip_val=1.0``, scripts/training/train_mae.py:213; src/training/classifier.py:106-108).
+
+The fine-tuning recipe of the MAE paper (not in the reference; every option off by default, and off means the calls above
+unchanged): ``train.label_smoothing``, ``train.mixup_alpha`` / ``train.cutmix_alpha`` (+ ``mix_prob``, ``mix_switch_prob``)
+mix each training batch on the device (``data.mix_batch``) and train on the soft targets inside the head kernel;
+``train.layer_decay`` scales the learning rate of layer l by ``layer_decay ** (depth + 1 - l)`` (BEiT / MAE numbering).
 """
 from __future__ import annotations
 
@@ -188,6 +193,20 @@ class ViTClassifierTrainModule(nn.Module):
         self.freeze_encoder_flag = self.training_cfg.get("freeze_encoder", True)
         self.num_classes = num_classes
         self.gradient_clip_val = 1.0
+        self.label_smoothing = float(self.training_cfg.get("label_smoothing", 0.0) or 0.0)
+        self.mixup_alpha = float(self.training_cfg.get("mixup_alpha", 0.0) or 0.0)
+        self.cutmix_alpha = float(self.training_cfg.get("cutmix_alpha", 0.0) or 0.0)
+        self.mix_prob = float(self.training_cfg.get("mix_prob", 1.0))
+        self.mix_switch_prob = float(self.training_cfg.get("mix_switch_prob", 0.5))
+        self.layer_decay = float(self.training_cfg.get("layer_decay", 1.0))
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"train.label_smoothing must be in [0, 1), got {self.label_smoothing}")
+        if self.mixup_alpha < 0 or self.cutmix_alpha < 0 or not 0.0 < self.layer_decay <= 1.0:
+            raise ValueError("train.mixup_alpha / cutmix_alpha must be >= 0 and train.layer_decay in (0, 1]")
+        if not (0.0 <= self.mix_prob <= 1.0 and 0.0 <= self.mix_switch_prob <= 1.0):
+            raise ValueError(f"train.mix_prob / mix_switch_prob must be in [0, 1], got {self.mix_prob} / {self.mix_switch_prob}")
+        self.mix_seed = 73
+        self._mix_step = 0
         self.current_epoch = 0
         self.logged: Dict[str, Any] = {}
         encoder = pretrained_encoder if pretrained_encoder is not None else build_baseline_encoder(self.model_cfg)
@@ -320,6 +339,36 @@ class ViTClassifierTrainModule(nn.Module):
         pieces = [(a, b - a) for a, b in ((lo, c_off), (c_off + c_n, hi)) if b > a]
         return pieces, 1
 
+    def layer_of(self, name: str) -> int:
+        """Layer number of an encoder tensor (timm name) or "head": embeddings 0, blocks.i -> i + 1, norm and the head
+        depth + 1 (BEiT's get_num_layer_for_vit, the numbering of MAE's param_groups_lrd)."""
+        depth = len(self.model.encoder.blocks)
+        if name.startswith("blocks."):
+            return int(name.split(".")[1]) + 1
+        if name in ("cls_token", "pos_embed") or name.startswith("patch_embed."):
+            return 0
+        return depth + 1
+
+    def layer_scale(self, layer: int) -> float:
+        return self.layer_decay ** (len(self.model.encoder.blocks) + 1 - layer)
+
+    def _decay_groups(self, train_blocks: int, train_embed: int) -> Tuple[List[Tuple[int, int, float]], int]:
+        """``_update_ranges`` cut at the block boundaries: (lo, count, lr scale) per piece and layer.  The boundaries are tensor
+        offsets, multiples of 64.  layer_decay == 1 returns the pieces of ``_update_ranges`` themselves, scale 1.0."""
+        pieces, pos_row0 = self._update_ranges(train_blocks, train_embed)
+        if self.layer_decay == 1.0:
+            return [(lo, n, 1.0) for lo, n in pieces], pos_row0
+        m = self.model.mae
+        depth = len(self.model.encoder.blocks)
+        starts = [m._offsets[f"encoder.vit.blocks.{i}.norm1.weight"][1] for i in range(depth)] + [m._offsets["encoder.vit.norm.weight"][1]]
+        groups: List[Tuple[int, int, float]] = []
+        for lo, n in pieces:
+            cuts = [lo] + [c for c in starts if lo < c < lo + n] + [lo + n]
+            for a, b in zip(cuts, cuts[1:]):
+                layer = sum(1 for c in starts if c <= a)  # 0 below blocks.0, i + 1 inside blocks.i, depth + 1 from norm on
+                groups.append((a, b - a, self.layer_scale(layer)))
+        return groups, pos_row0
+
     # ---- native step -------------------------------------------------------------------------------
     def _grad_buffers(self):
         m = self.model.mae
@@ -338,10 +387,14 @@ class ViTClassifierTrainModule(nn.Module):
         return self._grad_buffers()[1]
 
     def loss_and_grads(self, images: torch.Tensor, labels: torch.Tensor, grad_scale: float = 1.0,
-                       logits_out: Optional[torch.Tensor] = None):
+                       logits_out: Optional[torch.Tensor] = None, labels_b: Optional[torch.Tensor] = None,
+                       lam: Optional[torch.Tensor] = None, label_smoothing: Optional[float] = None):
         """Forward + cross-entropy + backward of the trainable set in one native call.  Gradients land in
         ``model.mae.flat_grads`` (blocks / norm / embeddings, at their arena offsets; frozen rows are not written),
-        ``head_grads`` (W then b) and ``pos_grads``.  Returns device tensors (loss[1], correct[1]); no host sync."""
+        ``head_grads`` (W then b) and ``pos_grads``.  Returns device tensors (loss[1], correct[1]); no host sync.
+        Soft targets: ``labels_b`` (B) and ``lam`` (B, fp32) mix the labels as lam * labels + (1 - lam) * labels_b,
+        ``label_smoothing`` (None: ``train.label_smoothing``) smooths them; ``correct`` counts argmax == labels.  With none
+        of the three active this is the hard-label call, unchanged."""
         tb, te = self.train_mode()
         clf, m = self.model, self.model.mae
         dev = m._require_cuda()
@@ -357,7 +410,17 @@ class ViTClassifierTrainModule(nn.Module):
         head = (m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(clf.head.flat), _ptr(images), m._img_dt(images), _ptr(labels), B)
         tail = (clf.num_classes, tb, te, float(grad_scale), _ptr(ws), ws.numel(), _ptr(m.flat_grads), _ptr(head_g), _ptr(pos_g), _ptr(logits_out),
                 _ptr(loss), _ptr(correct), _stream(dev))
-        if clf.extended:
+        eps = self.label_smoothing if label_smoothing is None else float(label_smoothing)
+        if labels_b is not None or lam is not None or eps != 0.0:
+            if labels_b is not None:
+                labels_b = labels_b.to(device=dev, dtype=torch.int64).contiguous()
+            if lam is not None:
+                lam = lam.to(device=dev, dtype=torch.float32).contiguous()
+            if any(t is not None and t.shape != (B,) for t in (labels_b, lam)):
+                raise ValueError(f"labels_b and lam must be ({B},)")
+            check(lib.mae_engine_classifier_loss_and_grads_soft(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail[:-1], _ptr(labels_b),
+                                                                _ptr(lam), eps, tail[-1]))
+        elif clf.extended:
             check(lib.mae_engine_classifier_loss_and_grads_ex(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail))
         else:
             check(lib.mae_engine_classifier_loss_and_grads(*head, POOLS[clf.pool_type], *tail))
@@ -394,11 +457,11 @@ class ViTClassifierTrainModule(nn.Module):
         if te:
             check(lib.mae_engine_grad_sumsq_buffer(h, _ptr(pos_g), pos_g.numel(), 1, _ptr(sums), _ptr(scratch), s))
         check(lib.mae_engine_clip_from_sumsq(h, _ptr(sums), float(self.gradient_clip_val), _ptr(stats), s))
-        pieces, pos_row0 = self._update_ranges(tb, te)
-        for p_lo, p_n in pieces:
+        pieces, pos_row0 = self._decay_groups(tb, te)  # layer_decay == 1: the pieces of _update_ranges, lr unchanged
+        for p_lo, p_n, scale in pieces:
             ea, eq = self._state("arena_m", n_arena, dev), self._state("arena_v", n_arena, dev)
-            check(lib.mae_engine_adamw_range(h, _ptr(m.flat_params), _ptr(m.flat_grads), _ptr(ea), _ptr(eq), _ptr(m._weights()), *hyper[:5],
-                                             step, _ptr(stats), p_lo, p_n, s))
+            check(lib.mae_engine_adamw_range(h, _ptr(m.flat_params), _ptr(m.flat_grads), _ptr(ea), _ptr(eq), _ptr(m._weights()), lr * scale,
+                                             *hyper[1:5], step, _ptr(stats), p_lo, p_n, s))
         check(lib.mae_engine_adamw_buffer(h, _ptr(clf.head.flat), _ptr(head_g), _ptr(self._state("head_m", head_g.numel(), dev)),
                                           _ptr(self._state("head_v", head_g.numel(), dev)), head_g.numel(), *hyper[:5], step, _ptr(stats), s))
         if te:
@@ -406,15 +469,27 @@ class ViTClassifierTrainModule(nn.Module):
             skip = pos_row0 * m._dims["embed_dim"]  # the class-token row of a patch-only encoder stays as it is
             check(lib.mae_engine_adamw_buffer(h, _ptr(m.flat_params[pos_off + skip:pos_off + pos_n]), _ptr(pos_g[skip:]),
                                               _ptr(self._state("pos_m", pos_n, dev)[skip:]), _ptr(self._state("pos_v", pos_n, dev)[skip:]),
-                                              pos_n - skip, *hyper[:5], step, _ptr(stats), s))
+                                              pos_n - skip, lr * self.layer_scale(0), *hyper[1:5], step, _ptr(stats), s))
         if hi > lo:
             check(lib.mae_engine_refresh_transposed_range(h, _ptr(m.flat_params), _ptr(m._weights()), lo, hi - lo, s))
         m.mark_weights_fresh()
         return stats[:2]
 
     def fused_training_step(self, images: torch.Tensor, labels: torch.Tensor, lr: Optional[float] = None):
-        """training_step + clip + AdamW, all native; returns device (loss, correct)."""
-        loss, correct = self.loss_and_grads(images, labels)
+        """training_step + clip + AdamW, all native; returns device (loss, correct).  With mixup / CutMix configured the batch
+        is mixed first (the draw is a function of (mix_seed, current_epoch, step)), and ``correct`` -- so the logged
+        train_acc -- is counted against the batch's own labels, the first of each mixed pair."""
+        if self.mixup_alpha > 0 or self.cutmix_alpha > 0:
+            from .data import draw_mix_params, mix_batch
+            params = draw_mix_params(images.shape[0], images.shape[-1], (self.mix_seed, self.current_epoch, self._mix_step),
+                                     self.mixup_alpha, self.cutmix_alpha, self.mix_prob, self.mix_switch_prob)
+            self._mix_step += 1
+            m = self.model.mae
+            images = m._check_images(images).to(m._require_cuda())
+            images, labels, labels_b, lam = mix_batch(images, labels.to(images.device), params)
+            loss, correct = self.loss_and_grads(images, labels, labels_b=labels_b, lam=lam)
+        else:
+            loss, correct = self.loss_and_grads(images, labels)
         self.optimizer_step(lr)
         self.log("train_loss", loss[0])
         self.log("train_acc", correct[0].float() / images.shape[0])

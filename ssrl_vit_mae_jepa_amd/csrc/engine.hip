@@ -1082,7 +1082,7 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
                            const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes, int32_t train_blocks, int32_t train_embed,
                            float grad_scale, void* workspace, int64_t workspace_bytes, float* grads, float* head_grads, float* pos_grad,
                            float* logits, float* loss_out, int32_t* correct_out, void* stream, const char* who, int32_t with_cls = 1,
-                           bool ex = false) {
+                           bool ex = false, const HeadSoft* soft = nullptr) {
   MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
   MAE_REQUIRE(batch > 0, "%s: batch %d out of range", who, batch);
   MAE_REQUIRE(head && images, "%s: null head/images", who);
@@ -1125,14 +1125,14 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
     RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), (double)B * (L - lo) * D * c.as + (double)C * D * 4 + (enc_bwd ? (double)pl.Me * D * c.as : 0.0),
         launch_classifier_head_range(c.buf<>(pl.enc_norm), e->act, B, L, D, lo, L, head, head + (int64_t)C * D, C, labels, grad_scale, logits,
                                      c.buf<float>(cp.row_loss), c.buf<int32_t>(cp.row_correct), loss_out, correct_out,
-                                     train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat, s));
+                                     train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat, s, soft));
   } else {
     RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), (cls ? (double)B * D : (double)pl.Me * D) * c.as + (double)C * D * 4 + (enc_bwd && !cls ? (double)pl.Me * D * c.as : 0.0),
         launch_classifier_head(c.buf<>(pl.enc_norm), e->act, B, L, D, pool, head, head + (int64_t)C * D, C, labels, grad_scale, logits,
                                c.buf<float>(cp.row_loss), c.buf<int32_t>(cp.row_correct), loss_out, correct_out,
                                train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat,
                                c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c),
-                               enc_bwd && cls ? c.buf<int32_t>(cp.cls_rows) : nullptr, s));
+                               enc_bwd && cls ? c.buf<int32_t>(cp.cls_rows) : nullptr, s, soft));
   }
   if (!train) return 0;
   RUN(TK_WGRAD, 2.0 * B * C * D, (double)B * (C + D) * 4, launch_classifier_head_wgrad(c.buf<float>(cp.dlogits), c.buf<float>(cp.pooled), B, C, D,
@@ -1215,6 +1215,23 @@ extern "C" int mae_engine_classifier_loss_and_grads_ex(mae_engine_t* e, const fl
   return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
                          workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
                          "mae_engine_classifier_loss_and_grads_ex", with_cls, true);
+}
+
+// mae_engine_classifier_loss_and_grads_ex with the head's soft targets; with nothing soft asked for, the same launches and bits
+extern "C" int mae_engine_classifier_loss_and_grads_soft(mae_engine_t* e, const float* params, const void* wcache, const float* head,
+                                                         const void* images, int32_t image_dtype, const int64_t* labels, int32_t batch,
+                                                         int32_t with_cls, int32_t pool, int32_t num_classes, int32_t train_blocks,
+                                                         int32_t train_embed, float grad_scale, void* workspace, int64_t workspace_bytes,
+                                                         float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
+                                                         int32_t* correct_out, const int64_t* labels_b, const float* lam,
+                                                         float label_smoothing, void* stream) {
+  MAE_REQUIRE(head_grads, "mae_engine_classifier_loss_and_grads_soft: null head_grads");
+  MAE_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "mae_engine_classifier_loss_and_grads_soft: label_smoothing = %g outside [0, 1)",
+              (double)label_smoothing);
+  const HeadSoft soft{labels_b, lam, label_smoothing};
+  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
+                         workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
+                         "mae_engine_classifier_loss_and_grads_soft", with_cls, true, soft.active() ? &soft : nullptr);
 }
 
 // =====================================================================================================

@@ -8,6 +8,11 @@
 //   (2) the head weight W          -- rounded as it is read (the head's fp32 buffer has no bf16 copy);
 //   (3) d_logits                   -- rounded before dW, db and d_pooled are formed from it.
 // The feature gradient leaves in the activation dtype (the input of the final LayerNorm backward), as every other dy does.
+//
+// Soft targets (SOFT = true: mixup / CutMix label pairs and label smoothing, the MAE / DeiT fine-tuning loss):
+//   t[b][c] = eps / C + (1 - eps) * (lam[b] * [c == ya[b]] + (1 - lam[b]) * [c == yb[b]]),  sum_c t = 1, so
+//   row_loss = lse - sum_c t[c] * logit[c]  and  d_logits = (softmax - t) * grad_scale / B, rounded at the same point (3).
+// SOFT = false is the hard-label head as it always was: the launchers pick it whenever no soft option is active.
 #include "kernels.h"
 
 namespace mae {
@@ -30,10 +35,10 @@ int launch_iota_rows(int32_t* keep32, int B, int L, hipStream_t s) {
 
 // The phases both head kernels share once the pooled vector sits in sp[0 .. D): logits, row loss / correct flag, d_logits and
 // the pooled copy.  Wave w owns classes w, w+4, ...; returns false when the caller has nothing left to do (no backward asked).
-template <class T>
+template <class T, bool SOFT>
 __device__ __forceinline__ bool head_after_pool(const float* sp, float* sl, float* sdl, float* sstat, int* sy, int b, int D,
                                                 const float* __restrict__ W, const float* __restrict__ bias, int C,
-                                                const int64_t* __restrict__ labels, float grad_scale, int B,
+                                                const int64_t* __restrict__ labels, const HeadSoft soft, float grad_scale, int B,
                                                 float* __restrict__ logits_out, float* __restrict__ row_loss,
                                                 int32_t* __restrict__ row_correct, float* __restrict__ pooled_out,
                                                 float* __restrict__ dlogits_out) {
@@ -60,11 +65,29 @@ __device__ __forceinline__ bool head_after_pool(const float* sp, float* sl, floa
     for (int c = 0; c < C; ++c) se += expf(sl[c] - mx);
     const float lse = mx + logf(se);
     const int64_t y = labels ? labels[b] : -1;
-    const bool valid = y >= 0 && y < C;   // an out-of-range label is never used as an index: its row's loss is NaN
-    *sy = valid ? (int)y : -1;
     sstat[0] = lse;
-    row_loss[b] = valid ? lse - sl[y] : __builtin_nanf("");
-    row_correct[b] = (valid && am == (int)y) ? 1 : 0;
+    if constexpr (SOFT) {
+      const int64_t yb = soft.labels_b ? soft.labels_b[b] : y;
+      const float lam = soft.lam ? soft.lam[b] : 1.f;
+      const bool ya_ok = y >= 0 && y < C;
+      const bool valid = ya_ok && yb >= 0 && yb < C;  // either label out of range: never an index, the row's loss is NaN
+      sy[0] = valid ? (int)y : -1;
+      sy[1] = valid ? (int)yb : -1;
+      sstat[1] = lam;
+      float dot = __builtin_nanf("");
+      if (valid) {  // sum_c t[c] * logit[c]: the classes in ascending order, then the two label terms
+        float all = 0.f;
+        for (int c = 0; c < C; ++c) all += sl[c];
+        dot = soft.eps / (float)C * all + (1.f - soft.eps) * (lam * sl[y] + (1.f - lam) * sl[yb]);
+      }
+      row_loss[b] = lse - dot;
+      row_correct[b] = (ya_ok && am == (int)y) ? 1 : 0;
+    } else {
+      const bool valid = y >= 0 && y < C;   // an out-of-range label is never used as an index: its row's loss is NaN
+      sy[0] = valid ? (int)y : -1;
+      row_loss[b] = valid ? lse - sl[y] : __builtin_nanf("");
+      row_correct[b] = (valid && am == (int)y) ? 1 : 0;
+    }
   }
   __syncthreads();
   if (logits_out)
@@ -72,9 +95,14 @@ __device__ __forceinline__ bool head_after_pool(const float* sp, float* sl, floa
   if (!dlogits_out) return false;
   // d_logits = (softmax - onehot(y)) * grad_scale / B
   const float lse = sstat[0];
-  const int y = *sy;
+  const int y = sy[0];
   for (int c = t; c < C; c += 256) {
-    float g = (expf(sl[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale / (float)B;
+    float tgt = c == y ? 1.f : 0.f;
+    if constexpr (SOFT) {
+      const float lam = sstat[1];
+      tgt = soft.eps / (float)C + (1.f - soft.eps) * (lam * tgt + (1.f - lam) * (c == sy[1] ? 1.f : 0.f));
+    }
+    float g = (expf(sl[c] - lse) - tgt) * grad_scale / (float)B;
     if (y < 0) g = __builtin_nanf("");
     g = head_round<T>(g);  // rounding point (3)
     sdl[c] = g;
@@ -97,10 +125,10 @@ __device__ __forceinline__ f32x4 head_dpooled(const float* sdl, const float* __r
 }
 
 // One block per image.  Thread t owns feature columns [4t, 4t+4) (t < D/4); wave w owns classes w, w+4, ...
-template <class T>
+template <class T, bool SOFT>
 __global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restrict__ feats, int L, int D, int pool,
                                                               const float* __restrict__ W, const float* __restrict__ bias, int C,
-                                                              const int64_t* __restrict__ labels, float grad_scale, int B,
+                                                              const int64_t* __restrict__ labels, const HeadSoft soft, float grad_scale, int B,
                                                               float* __restrict__ logits_out, float* __restrict__ row_loss,
                                                               int32_t* __restrict__ row_correct, float* __restrict__ pooled_out,
                                                               float* __restrict__ dlogits_out, T* __restrict__ dfeat_out,
@@ -109,7 +137,7 @@ __global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restric
                                                               int32_t* __restrict__ cls_rows) {
   __shared__ __attribute__((aligned(16))) float sp[1024];
   __shared__ float sl[HEAD_MAX_CLASSES], sdl[HEAD_MAX_CLASSES], sstat[2];
-  __shared__ int sy;
+  __shared__ int sy[2];
   const int b = blockIdx.x, t = threadIdx.x;
   const int D4 = D / 4;
   const int64_t row0 = (int64_t)b * L;
@@ -131,7 +159,7 @@ __global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restric
     rstd_c[b] = rstd_all[row0];
   }
   __syncthreads();
-  if (!head_after_pool<T>(sp, sl, sdl, sstat, &sy, b, D, W, bias, C, labels, grad_scale, B, logits_out, row_loss, row_correct, pooled_out,
+  if (!head_after_pool<T, SOFT>(sp, sl, sdl, sstat, sy, b, D, W, bias, C, labels, soft, grad_scale, B, logits_out, row_loss, row_correct, pooled_out,
                           dlogits_out))
     return;
   if (!dfeat_out) return;
@@ -152,17 +180,17 @@ __global__ void __launch_bounds__(256) classifier_head_kernel(const T* __restric
 // behind a class token (lo = 1).  All four waves load rows: wave w sums rows lo + w, lo + w + 4, ... (lane l owns the 4-column
 // groups l, l + 64, ...), and the four partial sums are added through LDS in wave order 0, 1, 2, 3, so the summation order is
 // fixed by (lo, hi) alone.  The feature gradient is d_pooled / (hi - lo) on the pooled rows and exact zeros on the others.
-template <class T>
+template <class T, bool SOFT>
 __global__ void __launch_bounds__(256) classifier_head_range_kernel(const T* __restrict__ feats, int seq, int D, int lo, int hi,
                                                                     const float* __restrict__ W, const float* __restrict__ bias, int C,
-                                                                    const int64_t* __restrict__ labels, float grad_scale, int B,
+                                                                    const int64_t* __restrict__ labels, const HeadSoft soft, float grad_scale, int B,
                                                                     float* __restrict__ logits_out, float* __restrict__ row_loss,
                                                                     int32_t* __restrict__ row_correct, float* __restrict__ pooled_out,
                                                                     float* __restrict__ dlogits_out, T* __restrict__ dfeat_out) {
   __shared__ __attribute__((aligned(16))) float sp[1024];
   __shared__ __attribute__((aligned(16))) float part[3][1024];  // the partial sums of waves 1..3; then d_pooled in part[0]
   __shared__ float sl[HEAD_MAX_CLASSES], sdl[HEAD_MAX_CLASSES], sstat[2];
-  __shared__ int sy;
+  __shared__ int sy[2];
   constexpr int Q = 4;  // 4-column groups per lane: D / 4 <= 256 = 64 * Q
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int D4 = D / 4;
@@ -196,7 +224,7 @@ __global__ void __launch_bounds__(256) classifier_head_range_kernel(const T* __r
     }
   }
   __syncthreads();
-  if (!head_after_pool<T>(sp, sl, sdl, sstat, &sy, b, D, W, bias, C, labels, grad_scale, B, logits_out, row_loss, row_correct, pooled_out,
+  if (!head_after_pool<T, SOFT>(sp, sl, sdl, sstat, sy, b, D, W, bias, C, labels, soft, grad_scale, B, logits_out, row_loss, row_correct, pooled_out,
                           dlogits_out))
     return;
   if (!dfeat_out) return;
@@ -238,7 +266,8 @@ __global__ void __launch_bounds__(256) classifier_reduce_kernel(const float* __r
 int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int pool, const float* W, const float* bias, int C,
                            const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
                            float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out,
-                           const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s) {
+                           const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s,
+                           const HeadSoft* soft) {
   MAE_REQUIRE(feats && W && bias && row_loss && row_correct && B > 0 && L > 0, "classifier_head: bad arguments");
   MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "classifier_head: D = %d must be a multiple of 4 in [4, 1024]", D);
   MAE_REQUIRE(C >= 2 && C <= HEAD_MAX_CLASSES, "classifier_head: num_classes = %d outside [2, %d]", C, HEAD_MAX_CLASSES);
@@ -246,9 +275,14 @@ int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int p
   MAE_REQUIRE(!dlogits_out || pooled_out, "classifier_head: the backward needs the pooled-feature buffer");
   MAE_REQUIRE(!dfeat_out || dlogits_out, "classifier_head: the feature gradient needs d_logits");
   MAE_REQUIRE(!cls_rows || (mean_all && rstd_all && mean_c && rstd_c), "classifier_head: class-row statistics need every buffer");
-#define HEAD(T) hipLaunchKernelGGL(classifier_head_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)feats, L, D, pool, W, bias, C, labels, grad_scale, B, \
-                                   logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out, mean_all, rstd_all, mean_c, rstd_c, cls_rows)
-  if (dt == MAE_BF16) HEAD(bf16); else HEAD(float);
+  const bool on = soft && soft->active();
+  MAE_REQUIRE(!on || (labels && soft->eps >= 0.f && soft->eps < 1.f), "classifier_head: soft targets need labels and label_smoothing in [0, 1)");
+  const HeadSoft hs = on ? *soft : HeadSoft{nullptr, nullptr, 0.f};
+#define HEAD(T, SOFT) hipLaunchKernelGGL((classifier_head_kernel<T, SOFT>), dim3(B), dim3(256), 0, s, (const T*)feats, L, D, pool, W, bias, C, labels, hs, \
+                                         grad_scale, B, logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out, mean_all, rstd_all,  \
+                                         mean_c, rstd_c, cls_rows)
+  if (on) { if (dt == MAE_BF16) HEAD(bf16, true); else HEAD(float, true); }
+  else    { if (dt == MAE_BF16) HEAD(bf16, false); else HEAD(float, false); }
 #undef HEAD
   MAE_LAUNCH_CHECK();
   if (loss_out || correct_out) {
@@ -260,16 +294,21 @@ int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int p
 
 int launch_classifier_head_range(const void* feats, int dt, int B, int seq, int D, int lo, int hi, const float* W, const float* bias, int C,
                                  const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
-                                 float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out, hipStream_t s) {
+                                 float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out, hipStream_t s,
+                                 const HeadSoft* soft) {
   MAE_REQUIRE(feats && W && bias && row_loss && row_correct && B > 0 && seq > 0, "classifier_head_range: bad arguments");
   MAE_REQUIRE(lo >= 0 && lo < hi && hi <= seq, "classifier_head_range: rows [%d, %d) outside the sequence of %d", lo, hi, seq);
   MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "classifier_head_range: D = %d must be a multiple of 4 in [4, 1024]", D);
   MAE_REQUIRE(C >= 2 && C <= HEAD_MAX_CLASSES, "classifier_head_range: num_classes = %d outside [2, %d]", C, HEAD_MAX_CLASSES);
   MAE_REQUIRE(!dlogits_out || pooled_out, "classifier_head_range: the backward needs the pooled-feature buffer");
   MAE_REQUIRE(!dfeat_out || dlogits_out, "classifier_head_range: the feature gradient needs d_logits");
-#define HEAD(T) hipLaunchKernelGGL(classifier_head_range_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)feats, seq, D, lo, hi, W, bias, C, labels, \
-                                   grad_scale, B, logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out)
-  if (dt == MAE_BF16) HEAD(bf16); else HEAD(float);
+  const bool on = soft && soft->active();
+  MAE_REQUIRE(!on || (labels && soft->eps >= 0.f && soft->eps < 1.f), "classifier_head_range: soft targets need labels and label_smoothing in [0, 1)");
+  const HeadSoft hs = on ? *soft : HeadSoft{nullptr, nullptr, 0.f};
+#define HEAD(T, SOFT) hipLaunchKernelGGL((classifier_head_range_kernel<T, SOFT>), dim3(B), dim3(256), 0, s, (const T*)feats, seq, D, lo, hi, W, bias, C, \
+                                         labels, hs, grad_scale, B, logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out)
+  if (on) { if (dt == MAE_BF16) HEAD(bf16, true); else HEAD(float, true); }
+  else    { if (dt == MAE_BF16) HEAD(bf16, false); else HEAD(float, false); }
 #undef HEAD
   MAE_LAUNCH_CHECK();
   if (loss_out || correct_out) {
@@ -451,24 +490,52 @@ static HeadScratch head_scratch(void* scratch, int64_t B, int64_t C, int64_t D) 
 }
 }  // namespace mae
 
+namespace mae {
+// The one body of mae_classifier_head / _ex / _soft.  ex = false is the first call (with_cls = 1, pool cls or mean); soft null or
+// inactive launches the hard-label kernels.
+static int classifier_head_impl(const char* who, bool ex, const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim,
+                                int32_t with_cls, int32_t pool, const float* head, int32_t num_classes, const int64_t* labels,
+                                float grad_scale, float* logits, float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats,
+                                void* scratch, int64_t scratch_bytes, void* stream, const HeadSoft* soft) {
+  if (ex) {
+    MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+    MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES,
+                "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
+    MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
+  }
+  const bool range = ex && (!with_cls || pool == MAE_POOL_MEAN_PATCHES);  // the mean over the patch rows [lo, seq_len)
+  const int lo = with_cls ? 1 : 0;
+  MAE_REQUIRE(dtype == MAE_F32 || dtype == MAE_BF16, "%s: dtype must be MAE_F32 or MAE_BF16", who);
+  MAE_REQUIRE(!range || seq_len > lo, "%s: seq_len = %d leaves no patch row to pool", who, seq_len);
+  const int64_t need = mae_classifier_head_scratch_bytes(batch, num_classes, dim);
+  MAE_REQUIRE(need > 0 && scratch && scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0,
+              "%s: scratch must hold mae_classifier_head_scratch_bytes (%lld) bytes, 256-byte aligned", who, (long long)need);
+  MAE_REQUIRE(!d_feats || head_grads, "%s: d_feats needs head_grads", who);
+  MAE_REQUIRE(!head_grads || labels, "%s: gradients need labels", who);
+  MAE_REQUIRE(!range || (head && (labels || (!loss_out && !correct_out))), "%s: null head, or loss / correct count without labels", who);
+  hipStream_t s = (hipStream_t)stream;
+  const HeadScratch hs = head_scratch(scratch, batch, num_classes, dim);
+  const float* bias = head + (int64_t)num_classes * dim;
+  float* pooled = head_grads ? hs.pooled : nullptr;
+  float* dlogits = head_grads ? hs.dlogits : nullptr;
+  if (range)
+    MAE_TRY(launch_classifier_head_range(feats, dtype, batch, seq_len, dim, lo, seq_len, head, bias, num_classes, labels, grad_scale, logits,
+                                         hs.row_loss, hs.row_correct, loss_out, correct_out, pooled, dlogits, d_feats, s, soft));
+  else
+    MAE_TRY(launch_classifier_head(feats, dtype, batch, seq_len, dim, pool, head, bias, num_classes, labels, grad_scale, logits, hs.row_loss,
+                                   hs.row_correct, loss_out, correct_out, pooled, dlogits, d_feats, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   s, soft));
+  if (!head_grads) return 0;
+  return launch_classifier_head_wgrad(hs.dlogits, hs.pooled, batch, num_classes, dim, hs.partial, hs.hsum, head_grads, s);
+}
+}  // namespace mae
+
 extern "C" int mae_classifier_head(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t pool,
                                    const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
                                    float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
                                    int64_t scratch_bytes, void* stream) {
-  using namespace mae;
-  MAE_REQUIRE(dtype == MAE_F32 || dtype == MAE_BF16, "mae_classifier_head: dtype must be MAE_F32 or MAE_BF16");
-  const int64_t need = mae_classifier_head_scratch_bytes(batch, num_classes, dim);
-  MAE_REQUIRE(need > 0 && scratch && scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0,
-              "mae_classifier_head: scratch must hold mae_classifier_head_scratch_bytes (%lld) bytes, 256-byte aligned", (long long)need);
-  MAE_REQUIRE(!d_feats || head_grads, "mae_classifier_head: d_feats needs head_grads");
-  MAE_REQUIRE(!head_grads || labels, "mae_classifier_head: gradients need labels");
-  hipStream_t s = (hipStream_t)stream;
-  const HeadScratch hs = head_scratch(scratch, batch, num_classes, dim);
-  MAE_TRY(launch_classifier_head(feats, dtype, batch, seq_len, dim, pool, head, head + (int64_t)num_classes * dim, num_classes, labels, grad_scale,
-                                 logits, hs.row_loss, hs.row_correct, loss_out, correct_out, head_grads ? hs.pooled : nullptr,
-                                 head_grads ? hs.dlogits : nullptr, d_feats, nullptr, nullptr, nullptr, nullptr, nullptr, s));
-  if (!head_grads) return 0;
-  return launch_classifier_head_wgrad(hs.dlogits, hs.pooled, batch, num_classes, dim, hs.partial, hs.hsum, head_grads, s);
+  return mae::classifier_head_impl("mae_classifier_head", false, feats, dtype, batch, seq_len, dim, 1, pool, head, num_classes, labels, grad_scale,
+                                   logits, loss_out, correct_out, head_grads, d_feats, scratch, scratch_bytes, stream, nullptr);
 }
 
 // the same on a sequence with (with_cls = 1) or without (0) a class-token row, with the patch-row mean: see mae_hip.h
@@ -476,30 +543,19 @@ extern "C" int mae_classifier_head_ex(const void* feats, int32_t dtype, int32_t 
                                       int32_t pool, const float* head, int32_t num_classes, const int64_t* labels, float grad_scale,
                                       float* logits, float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats,
                                       void* scratch, int64_t scratch_bytes, void* stream) {
-  using namespace mae;
-  const char* who = "mae_classifier_head_ex";
-  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
-  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES,
-              "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
-  MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
-  if (with_cls && pool != MAE_POOL_MEAN_PATCHES)
-    return mae_classifier_head(feats, dtype, batch, seq_len, dim, pool, head, num_classes, labels, grad_scale, logits, loss_out, correct_out,
-                               head_grads, d_feats, scratch, scratch_bytes, stream);
-  MAE_REQUIRE(dtype == MAE_F32 || dtype == MAE_BF16, "%s: dtype must be MAE_F32 or MAE_BF16", who);
-  const int lo = with_cls ? 1 : 0;
-  MAE_REQUIRE(seq_len > lo, "%s: seq_len = %d leaves no patch row to pool", who, seq_len);
-  const int64_t need = mae_classifier_head_scratch_bytes(batch, num_classes, dim);
-  MAE_REQUIRE(need > 0 && scratch && scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0,
-              "%s: scratch must hold mae_classifier_head_scratch_bytes (%lld) bytes, 256-byte aligned", who, (long long)need);
-  MAE_REQUIRE(!d_feats || head_grads, "%s: d_feats needs head_grads", who);
-  MAE_REQUIRE(!head_grads || labels, "%s: gradients need labels", who);
-  MAE_REQUIRE(head && (labels || (!loss_out && !correct_out)), "%s: null head, or loss / correct count without labels", who);
-  hipStream_t s = (hipStream_t)stream;
-  const HeadScratch hs = head_scratch(scratch, batch, num_classes, dim);
-  MAE_TRY(launch_classifier_head_range(feats, dtype, batch, seq_len, dim, lo, seq_len, head, head + (int64_t)num_classes * dim, num_classes, labels,
-                                       grad_scale, logits, hs.row_loss, hs.row_correct, loss_out, correct_out, head_grads ? hs.pooled : nullptr,
-                                       head_grads ? hs.dlogits : nullptr, d_feats, s));
-  if (!head_grads) return 0;
-  return launch_classifier_head_wgrad(hs.dlogits, hs.pooled, batch, num_classes, dim, hs.partial, hs.hsum, head_grads, s);
+  return mae::classifier_head_impl("mae_classifier_head_ex", true, feats, dtype, batch, seq_len, dim, with_cls, pool, head, num_classes, labels,
+                                   grad_scale, logits, loss_out, correct_out, head_grads, d_feats, scratch, scratch_bytes, stream, nullptr);
 }
 
+// mae_classifier_head_ex with soft targets (see mae_hip.h); with nothing soft asked for, the hard-label launches of _ex
+extern "C" int mae_classifier_head_soft(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls,
+                                        int32_t pool, const float* head, int32_t num_classes, const int64_t* labels, float grad_scale,
+                                        float* logits, float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats,
+                                        void* scratch, int64_t scratch_bytes, const int64_t* labels_b, const float* lam,
+                                        float label_smoothing, void* stream) {
+  MAE_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "mae_classifier_head_soft: label_smoothing = %g outside [0, 1)",
+              (double)label_smoothing);
+  const mae::HeadSoft soft{labels_b, lam, label_smoothing};
+  return mae::classifier_head_impl("mae_classifier_head_soft", true, feats, dtype, batch, seq_len, dim, with_cls, pool, head, num_classes, labels,
+                                   grad_scale, logits, loss_out, correct_out, head_grads, d_feats, scratch, scratch_bytes, stream, &soft);
+}

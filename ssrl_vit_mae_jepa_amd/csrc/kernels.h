@@ -67,6 +67,14 @@ int launch_sum_partials(const float* partial, int G, int C, float* out0, float* 
 constexpr int HEAD_MAX_CLASSES = 128;   // classes held in LDS by the head kernel
 constexpr int CLS_WGRAD_SLICES = 64;    // batch slices of the head weight-gradient partials
 constexpr int CLS_EMBED_SLICES = 64;    // batch slices of the d pos_embed partials
+// soft targets of the head: t[c] = eps / C + (1 - eps) * (lam[b] * [c == labels[b]] + (1 - lam[b]) * [c == labels_b[b]]);
+// labels_b null = labels, lam (device, B floats) null = 1.  Nothing active = the hard-label kernels, launched as before.
+struct HeadSoft {
+  const int64_t* labels_b;
+  const float* lam;
+  float eps;
+  bool active() const { return labels_b || lam || eps != 0.f; }
+};
 // keep[b*L + j] = j (every token of every image)
 int launch_iota_rows(int32_t* keep32, int B, int L, hipStream_t s);
 // one block per image: pooled = feats[b, 0] or mean over L rows; logits = pooled W^T + bias; row loss / correct flag;
@@ -76,12 +84,14 @@ int launch_iota_rows(int32_t* keep32, int B, int L, hipStream_t s);
 int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int pool, const float* W, const float* bias, int C,
                            const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
                            float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out,
-                           const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s);
+                           const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s,
+                           const HeadSoft* soft = nullptr);
 // the same head over the mean of rows [lo, hi) of each image's seq rows, four waves loading rows; dfeat_out (B*seq, D): d_pooled /
 // (hi - lo) on the pooled rows, exact zeros on the others
 int launch_classifier_head_range(const void* feats, int dt, int B, int seq, int D, int lo, int hi, const float* W, const float* bias, int C,
                                  const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
-                                 float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out, hipStream_t s);
+                                 float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out, hipStream_t s,
+                                 const HeadSoft* soft = nullptr);
 // head_grads[0 .. C*D) = dW, [C*D .. C*D+C) = db; partial >= classifier_wgrad_partial_floats, sum_out >= round_up(C*D+C, 4) floats
 int64_t classifier_wgrad_partial_floats(int B, int C, int D);
 int launch_classifier_head_wgrad(const float* dlogits, const float* pooled, int B, int C, int D, float* partial, float* sum_out,
@@ -121,6 +131,11 @@ int check_reconstruct_compose(const void* images, int img_dt, const float* pred,
 int launch_reconstruct_compose(const void* images, int img_dt, const float* pred, const int64_t* idx_mask, int B, int C, int S, int p, int m,
                                float fill, int out_dt, void* recon, void* masked, float* stats, void* scratch, int64_t scratch_bytes,
                                hipStream_t s);
+
+// ---- k_mix.hip: mixup / CutMix of a batch with its partner images ------------------------------------------------------------
+// out[b] = box ? partner pixel : lam[b] * own + (1 - lam[b]) * partner (MAE_F32 out), or the byte select alone (MAE_U8 out)
+int launch_mix_batch(const void* images, int img_dt, const int32_t* partner, const float* lam, const int32_t* box, int B, int C, int S,
+                     int out_dt, void* out, hipStream_t s);
 
 // ---- k_normpix.hip: targets standardised per patch (norm_pix_loss); idx is int64 when idx64 != 0, else int32 ---------------------
 // mae_mse_loss with the target (x - mean) * rstd of the image's patches, never materialised; stage-1 partials in scratch (1024+ floats)

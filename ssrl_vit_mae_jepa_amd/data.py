@@ -22,7 +22,7 @@ from __future__ import annotations
 
 from pathlib import Path
 import math
-from typing import Callable, Iterator, List, Optional, Tuple
+from typing import Callable, Iterator, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -367,3 +367,87 @@ def get_test_batches(cfg: dict, device: torch.device, synthetic_images: Optional
         imgs, labels = loaded
     bs = int(cfg.get("test", {}).get("batch_size", 64))
     return LabeledBatches(imgs.to(device), torch.from_numpy(labels).to(device), list(range(len(labels))), bs, False, seed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# mixup / CutMix for fine-tuning (timm.data.Mixup, mode="batch"; MAE main_finetune.py: mixup 0.8, cutmix 1.0, prob 1, switch 0.5)
+# ---------------------------------------------------------------------------------------------------------------------
+class MixParams(NamedTuple):
+    """One batch's draw, host tensors: ``partner`` (B) int32, ``lam`` (B) fp32, ``box`` (B, 4) int32 (y0, y1, x0, x1),
+    ``cutmix`` True when the batch is pure CutMix (nothing is blended outside the box)."""
+    partner: torch.Tensor
+    lam: torch.Tensor
+    box: torch.Tensor
+    cutmix: bool
+
+    @property
+    def identity(self) -> bool:
+        """lam = 1 and an empty box in a host draw: the mixed batch is the batch (a device draw is never inspected: no sync)."""
+        if self.cutmix or self.lam.is_cuda or self.box.is_cuda:
+            return False
+        return bool((self.lam == 1).all()) and bool((self.box[:, 0] >= self.box[:, 1]).logical_or(self.box[:, 2] >= self.box[:, 3]).all())
+
+
+def draw_mix_params(batch: int, size: int, gen_or_seed: Union[np.random.Generator, int, Sequence[int]], mixup_alpha: float = 0.8,
+                    cutmix_alpha: float = 1.0, prob: float = 1.0, switch_prob: float = 0.5) -> MixParams:
+    """timm's ``Mixup._params_per_batch`` + ``cutmix_bbox_and_lam`` (correct_lam=True) for one batch of square images:
+    with probability ``prob`` the batch is mixed -- CutMix with probability ``switch_prob`` when both alphas are positive
+    (the one positive alpha decides otherwise) -- with ONE lam ~ Beta(alpha, alpha) for the whole batch.  CutMix cuts the box
+    of ratio sqrt(1 - lam): cut = int(S * ratio), centre randint(0, S) per axis, edges clip(c -+ cut // 2, 0, S), and lam
+    becomes 1 - area / S^2.  The partner of image b is b flipped, B - 1 - b.  ``gen_or_seed``: a numpy Generator, or the
+    entropy of one (an int, or a tuple such as (seed, epoch, step): the same numbers give the same draw).  Host arithmetic
+    only: nothing here touches the device."""
+    rng = gen_or_seed if isinstance(gen_or_seed, np.random.Generator) else np.random.default_rng(gen_or_seed)
+    B, S = int(batch), int(size)
+    lam, cutmix = 1.0, False
+    box = (0, 0, 0, 0)
+    if (mixup_alpha > 0 or cutmix_alpha > 0) and rng.random() < prob:
+        if mixup_alpha > 0 and cutmix_alpha > 0:
+            cutmix = bool(rng.random() < switch_prob)
+        else:
+            cutmix = cutmix_alpha > 0
+        alpha = cutmix_alpha if cutmix else mixup_alpha
+        lam = float(rng.beta(alpha, alpha))
+        if cutmix:
+            cut = int(S * math.sqrt(1.0 - lam))
+            cy, cx = int(rng.integers(0, S)), int(rng.integers(0, S))
+            y0, y1 = int(np.clip(cy - cut // 2, 0, S)), int(np.clip(cy + cut // 2, 0, S))
+            x0, x1 = int(np.clip(cx - cut // 2, 0, S)), int(np.clip(cx + cut // 2, 0, S))
+            box = (y0, y1, x0, x1)
+            lam = 1.0 - ((y1 - y0) * (x1 - x0)) / float(S * S)
+    return MixParams(partner=torch.arange(B - 1, -1, -1, dtype=torch.int32),
+                     lam=torch.full((B,), lam, dtype=torch.float64).to(torch.float32),
+                     box=torch.tensor(box, dtype=torch.int32).repeat(B, 1), cutmix=cutmix)
+
+
+def mix_batch(images: torch.Tensor, labels: torch.Tensor, params: MixParams):
+    """The batch mixed by the HIP kernel behind ``mae_mix_batch``: returns (mixed, ya, yb, lam) on the images' device with
+    ya = labels, yb = labels[partner], lam the (B) fp32 weights of ya.  Pure CutMix on a uint8 batch stays uint8 (the engine
+    keeps reading 1 byte per pixel); everything else leaves as normalised fp32.  An identity draw returns the batch itself.
+    A host draw (what ``draw_mix_params`` returns) reaches the device through pinned memory: no host-device synchronisation;
+    one whose tensors are already on the device is used as it is.  No torch fallback."""
+    from . import _lib
+    from ._lib import check, lib, ptr
+    from .mae import _stream
+    if images.dtype not in (torch.uint8, torch.float32) or not images.is_cuda or images.dim() != 4 or images.shape[2] != images.shape[3]:
+        raise ValueError(f"mix_batch needs a square (B, C, S, S) uint8 or float32 CUDA batch, got {tuple(images.shape)} {images.dtype} on {images.device}")
+    B, C, S, _ = images.shape
+    if params.partner.shape != (B,) or params.lam.shape != (B,) or params.box.shape != (B, 4) or labels.shape != (B,):
+        raise ValueError(f"mix_batch: labels / parameters are not those of a batch of {B}")
+    dev = images.device
+    def up(t: torch.Tensor, dt: torch.dtype) -> torch.Tensor:  # a draw already on the device passes through
+        t = t.to(dt).contiguous()
+        return t.to(dev) if t.is_cuda else t.pin_memory().to(dev, non_blocking=True)
+    lam = up(params.lam, torch.float32)
+    if params.identity:
+        return images, labels, labels, lam
+    partner, box = up(params.partner, torch.int32), up(params.box, torch.int32)
+    images = images.contiguous()
+    u8_out = params.cutmix and images.dtype == torch.uint8
+    out = torch.empty((B, C, S, S), dtype=torch.uint8 if u8_out else torch.float32, device=dev)
+    check(lib.mae_mix_batch(ptr(images), _lib.MAE_U8 if images.dtype == torch.uint8 else _lib.MAE_F32, ptr(partner), ptr(lam), ptr(box), B, C, S,
+                            _lib.MAE_U8 if u8_out else _lib.MAE_F32, ptr(out), _stream(dev)))
+    own = torch.arange(B, dtype=torch.int64, device=dev)
+    idx = partner.to(torch.int64)
+    yb = labels[torch.where((idx < 0) | (idx >= B), own, idx)]  # the kernel's rule: an out-of-range partner is the image itself
+    return out, labels, yb, lam
