@@ -348,6 +348,23 @@ int mae_engine_classifier_loss_and_grads_soft(mae_engine_t* e, const float* para
                                               float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
                                               int32_t* correct_out, const int64_t* labels_b, const float* lam, float label_smoothing,
                                               void* stream);
+/* Stochastic depth / drop path for fine-tuning (additive in ABI v4; timm DropPath, scale_by_keep): the _soft call above plus
+ * branch_scale, a caller-owned device table (2 * depth, batch) fp32.  Row 2i holds the per-image scale of the attention branch of
+ * encoder block i, row 2i + 1 that of its MLP branch:
+ *   x_mid = x_in + branch_scale[2i][b] * attn(LN1(x_in)),   x_out = x_mid + branch_scale[2i + 1][b] * mlp(LN2(x_mid)).
+ * The engine does not draw: any finite values are taken (0 = dropped, 1 / (1 - p) = kept at rate p).  The product is formed in fp32
+ * inside the LayerNorm kernel that does the residual add, after the branch was rounded to the activation dtype; a scale of exactly 0
+ * does not read the branch.  The backward multiplies the activation-dtype copy of the residual gradient that each branch reads by the
+ * same scale (one fp32 product, then the rounding of the copy).  No extra launch, buffer or pass over memory.
+ *   branch_scale == NULL: exactly the launches of mae_engine_classifier_loss_and_grads_soft (same bits).
+ *   branch_scale != NULL with train_blocks = -1 is refused before any launch: the probe's encoder is in inference and never drops. */
+int mae_engine_classifier_loss_and_grads_sd(mae_engine_t* e, const float* params, const void* wcache, const float* head,
+                                            const void* images, int32_t image_dtype, const int64_t* labels, int32_t batch,
+                                            int32_t with_cls, int32_t pool, int32_t num_classes, int32_t train_blocks,
+                                            int32_t train_embed, float grad_scale, void* workspace, int64_t workspace_bytes,
+                                            float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
+                                            int32_t* correct_out, const int64_t* labels_b, const float* lam, float label_smoothing,
+                                            const float* branch_scale, void* stream);
 /* Batch mixing in front of that loss (additive in ABI v4; timm's Mixup in `batch` mode): image b is mixed with image
  * partner[b] of the same batch into out (batch, C, S, S), which may not overlap images (checked).
  *   images : (batch, C, S, S), MAE_U8 raw pixels or MAE_F32 normalised values; n() below is the engine's uint8 normalisation
@@ -495,6 +512,20 @@ int mae_add_layernorm_fwd(const float* x, const void* branch, float* x_out, cons
 int mae_layernorm_bwd(const void* dy, int32_t dy_dtype, const float* x, const int32_t* row_map, const float* gamma,
                       const float* mean, const float* rstd, int64_t rows, int32_t dim, int32_t accumulate,
                       float* dx_io, void* dx_copy, float* dgamma, float* dbeta, float* partial, void* stream);
+/* The two calls above with a per-image scale (drop path).  The full-matrix row src (row_map[r], or r without a map) belongs to image
+ * src / rows_per_image; that quotient indexes the scale vector, which the caller sizes (at least max(src) / rows_per_image + 1 floats).
+ * rows_per_image <= 0 is refused before the launch; a NULL scale vector runs the unscaled call (same launches, same bits).
+ *   forward : v = x[src] + image_scale[src / rows_per_image] * branch[src] in fp32; x_out[src] = v; y = LN(v).  A scale of exactly 0
+ *             does not load the branch row: x_out[src] = x[src] bit for bit, whatever the branch holds.
+ *   backward: dx_io, dgamma and dbeta as mae_layernorm_bwd; dx_copy[src] = copy_scale[src / rows_per_image] * dx_io[src], one fp32
+ *             product of the value stored to dx_io, then the rounding to dx_copy's dtype.  copy_scale needs dx_copy. */
+int mae_add_layernorm_fwd_scaled(const float* x, const void* branch, float* x_out, const int32_t* row_map, const float* gamma,
+                                 const float* beta, float eps, int64_t rows, int32_t dim, int32_t y_dtype, void* y, float* mean,
+                                 float* rstd, const float* image_scale, int32_t rows_per_image, void* stream);
+int mae_layernorm_bwd_scaled(const void* dy, int32_t dy_dtype, const float* x, const int32_t* row_map, const float* gamma,
+                             const float* mean, const float* rstd, int64_t rows, int32_t dim, int32_t accumulate,
+                             float* dx_io, void* dx_copy, float* dgamma, float* dbeta, float* partial, const float* copy_scale,
+                             int32_t rows_per_image, void* stream);
 
 /* The classifier head alone (what mae_engine_classifier_* run after the encoder): feats (batch, seq_len, dim) in dtype,
  * head / labels / logits / loss_out / correct_out / head_grads as there.  d_feats (dtype, may be NULL): MAE_POOL_CLS ->

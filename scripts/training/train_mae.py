@@ -14,7 +14,8 @@ train.freeze_encoder.  Each epoch: the native fused step over the training split
 per-epoch LR, one metrics line; best.ckpt on a new maximum of val_acc, last.ckpt every epoch.
 
 The fine-tuning recipe of the MAE paper: --label_smoothing, --mixup, --cutmix and --layer_decay override the YAML keys
-train.label_smoothing / mixup_alpha / cutmix_alpha / layer_decay (configs/vits8_dec192_finetune.yaml sets 0.1, 0.8, 1.0, 0.75).
+train.label_smoothing / mixup_alpha / cutmix_alpha / layer_decay (configs/vits8_dec192_finetune.yaml sets 0.1, 0.8, 1.0, 0.75);
+--drop_path overrides train.drop_path (stochastic depth, default 0; the MAE recipe uses 0.1; ignored by a frozen encoder).
 Under mixup / CutMix the metrics line's ``train_loss`` is the soft-target loss and ``train_acc`` counts argmax == the image's
 own label (the first of each mixed pair), so it reads lower than the accuracy on clean images; ``val_*`` stay hard-label.
 
@@ -56,6 +57,7 @@ def parse_args(argv=None):
     parser.add_argument("--mixup", type=float, default=None, help="overrides train.mixup_alpha (0 = off)")
     parser.add_argument("--cutmix", type=float, default=None, help="overrides train.cutmix_alpha (0 = off)")
     parser.add_argument("--layer_decay", type=float, default=None, help="overrides train.layer_decay (1 = one learning rate)")
+    parser.add_argument("--drop_path", type=float, default=None, help="overrides train.drop_path (stochastic depth rate, 0 = off)")
     parser.add_argument("--max_epochs", type=int, default=None)
     parser.add_argument("--max_steps_per_epoch", type=int, default=None)
     parser.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic labeled images instead of STL-10")
@@ -63,8 +65,9 @@ def parse_args(argv=None):
 
 
 def apply_recipe_flags(cfg: dict, args) -> None:
-    """--label_smoothing / --mixup / --cutmix / --layer_decay into cfg["train"]; a flag that was not given changes nothing."""
-    for flag, key in (("label_smoothing", "label_smoothing"), ("mixup", "mixup_alpha"), ("cutmix", "cutmix_alpha"), ("layer_decay", "layer_decay")):
+    """--label_smoothing / --mixup / --cutmix / --layer_decay / --drop_path into cfg["train"]; a flag that was not given changes nothing."""
+    for flag, key in (("label_smoothing", "label_smoothing"), ("mixup", "mixup_alpha"), ("cutmix", "cutmix_alpha"), ("layer_decay", "layer_decay"),
+                      ("drop_path", "drop_path")):
         if getattr(args, flag, None) is not None:
             cfg["train"][key] = float(getattr(args, flag))
 
@@ -168,7 +171,7 @@ def main(argv=None):
 
     train_batches, val_batches = get_train_batches(cfg, dev, synthetic_images=args.synthetic_images, seed=SEED)
     module = build_module(cfg, args.encoder_ckpt, args.classifier_ckpt, encoder=args.encoder, pool=args.pool).to(dev)
-    module.mix_seed = int(cfg.get("seed", SEED))  # the mixup / CutMix draw of a step is a function of (seed, epoch, step)
+    module.mix_seed = module.drop_seed = int(cfg.get("seed", SEED))  # the mixup / CutMix and the drop-path draw of a step are functions of (seed, epoch, step)
     total = int(train_cfg["total_epochs"]) if args.max_epochs is None else min(int(train_cfg["total_epochs"]), args.max_epochs)
     best_acc, log_path = -1.0, output_dir / "logs" / "metrics.jsonl"
     for epoch in range(total):

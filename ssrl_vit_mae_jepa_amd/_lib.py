@@ -96,6 +96,8 @@ SIGNATURES = {
                                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mae_engine_classifier_loss_and_grads_soft": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i64,
                                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp]),
+    "mae_engine_classifier_loss_and_grads_sd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i64,
+                                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp]),
     "mae_mix_batch": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mae_engine_grad_sumsq_buffer": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "mae_engine_adamw_buffer": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _vp, _vp]),
@@ -118,6 +120,8 @@ SIGNATURES = {
     "mae_layernorm_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _f32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mae_add_layernorm_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mae_layernorm_bwd": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mae_add_layernorm_fwd_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "mae_layernorm_bwd_scaled": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mae_classifier_head_scratch_bytes": (_i64, [_i32, _i32, _i32]),
     "mae_classifier_head": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mae_classifier_head_ex": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

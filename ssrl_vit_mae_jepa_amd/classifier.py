@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import sys
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
@@ -205,8 +206,14 @@ class ViTClassifierTrainModule(nn.Module):
             raise ValueError("train.mixup_alpha / cutmix_alpha must be >= 0 and train.layer_decay in (0, 1]")
         if not (0.0 <= self.mix_prob <= 1.0 and 0.0 <= self.mix_switch_prob <= 1.0):
             raise ValueError(f"train.mix_prob / mix_switch_prob must be in [0, 1], got {self.mix_prob} / {self.mix_switch_prob}")
+        self.drop_path = float(self.training_cfg.get("drop_path", 0.0) or 0.0)
+        if not 0.0 <= self.drop_path < 1.0:
+            raise ValueError(f"train.drop_path must be in [0, 1), got {self.drop_path}")
         self.mix_seed = 73
         self._mix_step = 0
+        self.drop_seed = 73
+        self._drop_step = 0
+        self._drop_ignored_said = False
         self.current_epoch = 0
         self.logged: Dict[str, Any] = {}
         encoder = pretrained_encoder if pretrained_encoder is not None else build_baseline_encoder(self.model_cfg)
@@ -268,7 +275,7 @@ class ViTClassifierTrainModule(nn.Module):
     def training_step(self, batch, batch_idx):
         """Loss + gradients of the trainable set (native); ``optimizer_step`` applies them."""
         imgs, labels = batch
-        loss, correct = self.loss_and_grads(imgs, labels)
+        loss, correct = self.loss_and_grads(imgs, labels, branch_scale=self._draw_branch_scale(imgs.shape[0]))
         self.log("train_loss", loss[0])
         self.log("train_acc", correct[0].float() / imgs.shape[0])
         return loss[0]
@@ -388,13 +395,17 @@ class ViTClassifierTrainModule(nn.Module):
 
     def loss_and_grads(self, images: torch.Tensor, labels: torch.Tensor, grad_scale: float = 1.0,
                        logits_out: Optional[torch.Tensor] = None, labels_b: Optional[torch.Tensor] = None,
-                       lam: Optional[torch.Tensor] = None, label_smoothing: Optional[float] = None):
+                       lam: Optional[torch.Tensor] = None, label_smoothing: Optional[float] = None,
+                       branch_scale: Optional[torch.Tensor] = None):
         """Forward + cross-entropy + backward of the trainable set in one native call.  Gradients land in
         ``model.mae.flat_grads`` (blocks / norm / embeddings, at their arena offsets; frozen rows are not written),
         ``head_grads`` (W then b) and ``pos_grads``.  Returns device tensors (loss[1], correct[1]); no host sync.
         Soft targets: ``labels_b`` (B) and ``lam`` (B, fp32) mix the labels as lam * labels + (1 - lam) * labels_b,
         ``label_smoothing`` (None: ``train.label_smoothing``) smooths them; ``correct`` counts argmax == labels.  With none
-        of the three active this is the hard-label call, unchanged."""
+        of the three active this is the hard-label call, unchanged.
+        Drop path: ``branch_scale`` (2 * depth, B) fp32, the table ``data.draw_drop_path`` returns (row 2i: the attention branch
+        of blocks.i, 2i + 1: its MLP branch), scales each image's residual branches in the forward and their gradients in the
+        backward.  A host table is uploaded through pinned memory (no synchronisation); a frozen encoder refuses one."""
         tb, te = self.train_mode()
         clf, m = self.model, self.model.mae
         dev = m._require_cuda()
@@ -411,21 +422,49 @@ class ViTClassifierTrainModule(nn.Module):
         tail = (clf.num_classes, tb, te, float(grad_scale), _ptr(ws), ws.numel(), _ptr(m.flat_grads), _ptr(head_g), _ptr(pos_g), _ptr(logits_out),
                 _ptr(loss), _ptr(correct), _stream(dev))
         eps = self.label_smoothing if label_smoothing is None else float(label_smoothing)
-        if labels_b is not None or lam is not None or eps != 0.0:
+        if branch_scale is not None:
+            depth = len(clf.encoder.blocks)
+            if tb < 0:
+                raise ValueError("branch_scale (drop path) needs a training encoder: the linear probe's encoder is in inference")
+            if branch_scale.shape != (2 * depth, B):
+                raise ValueError(f"branch_scale must be ({2 * depth}, {B}), got {tuple(branch_scale.shape)}")
+            branch_scale = branch_scale.to(torch.float32).contiguous()
+            branch_scale = branch_scale.to(dev) if branch_scale.is_cuda else branch_scale.pin_memory().to(dev, non_blocking=True)
+        if branch_scale is not None or labels_b is not None or lam is not None or eps != 0.0:
             if labels_b is not None:
                 labels_b = labels_b.to(device=dev, dtype=torch.int64).contiguous()
             if lam is not None:
                 lam = lam.to(device=dev, dtype=torch.float32).contiguous()
             if any(t is not None and t.shape != (B,) for t in (labels_b, lam)):
                 raise ValueError(f"labels_b and lam must be ({B},)")
-            check(lib.mae_engine_classifier_loss_and_grads_soft(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail[:-1], _ptr(labels_b),
-                                                                _ptr(lam), eps, tail[-1]))
+            if branch_scale is not None:
+                check(lib.mae_engine_classifier_loss_and_grads_sd(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail[:-1], _ptr(labels_b),
+                                                                  _ptr(lam), eps, _ptr(branch_scale), tail[-1]))
+            else:
+                check(lib.mae_engine_classifier_loss_and_grads_soft(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail[:-1], _ptr(labels_b),
+                                                                    _ptr(lam), eps, tail[-1]))
         elif clf.extended:
             check(lib.mae_engine_classifier_loss_and_grads_ex(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail))
         else:
             check(lib.mae_engine_classifier_loss_and_grads(*head, POOLS[clf.pool_type], *tail))
         self._last_mode = (tb, te)
         return loss, correct
+
+    def _draw_branch_scale(self, batch: int) -> Optional[torch.Tensor]:
+        """This step's drop-path table (host), a function of (drop_seed, current_epoch, step); None with rate 0.  With a frozen
+        encoder (the linear probe, whose encoder is in inference) the rate is ignored, and said so once."""
+        if self.drop_path <= 0.0:
+            return None
+        if self.train_mode()[0] < 0:
+            if not self._drop_ignored_said:
+                print(f"train.drop_path = {self.drop_path} is ignored: the encoder is frozen (linear probe), and a frozen encoder never drops",
+                      file=sys.stderr)
+                self._drop_ignored_said = True
+            return None
+        from .data import draw_drop_path
+        table = draw_drop_path(len(self.model.encoder.blocks), batch, self.drop_path, (self.drop_seed, self.current_epoch, self._drop_step))
+        self._drop_step += 1
+        return table
 
     def _state(self, key: str, n: int, dev) -> torch.Tensor:
         t = self._opt.get(key)
@@ -479,6 +518,7 @@ class ViTClassifierTrainModule(nn.Module):
         """training_step + clip + AdamW, all native; returns device (loss, correct).  With mixup / CutMix configured the batch
         is mixed first (the draw is a function of (mix_seed, current_epoch, step)), and ``correct`` -- so the logged
         train_acc -- is counted against the batch's own labels, the first of each mixed pair."""
+        scale = self._draw_branch_scale(images.shape[0])
         if self.mixup_alpha > 0 or self.cutmix_alpha > 0:
             from .data import draw_mix_params, mix_batch
             params = draw_mix_params(images.shape[0], images.shape[-1], (self.mix_seed, self.current_epoch, self._mix_step),
@@ -487,9 +527,9 @@ class ViTClassifierTrainModule(nn.Module):
             m = self.model.mae
             images = m._check_images(images).to(m._require_cuda())
             images, labels, labels_b, lam = mix_batch(images, labels.to(images.device), params)
-            loss, correct = self.loss_and_grads(images, labels, labels_b=labels_b, lam=lam)
+            loss, correct = self.loss_and_grads(images, labels, labels_b=labels_b, lam=lam, branch_scale=scale)
         else:
-            loss, correct = self.loss_and_grads(images, labels)
+            loss, correct = self.loss_and_grads(images, labels, branch_scale=scale)
         self.optimizer_step(lr)
         self.log("train_loss", loss[0])
         self.log("train_acc", correct[0].float() / images.shape[0])

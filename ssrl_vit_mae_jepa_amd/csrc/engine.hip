@@ -244,6 +244,9 @@ struct Ctx {
   void* const* ready = nullptr;  // hipEvent_t per gradient-ready point (entries may be null), or null
   bool fwd_only = false;         // no backward will follow (I-JEPA target encoder): the MLP saves no derivative
   bool skip_final_norm = false;  // forward_encoder_impl stops after the last block: x_mid + branch_b is left for the caller
+  const float* branch_scale = nullptr;  // drop path (classifier training only): (2 * depth, batch) per-image scales of the encoder's branches
+  // row j of the table (row 2i: attention branch of encoder block i, 2i + 1: its MLP branch), or null without a table
+  const float* scale_row(int j, int batch) const { return branch_scale ? branch_scale + (int64_t)j * batch : nullptr; }
   const float* P(int i) const { return params + e->params[i].offset; }
   float* Gp(int i) const { return grads + e->params[i].offset; }
   // GEMM operand view of weight i: (out, in) row-major in the activation dtype
@@ -310,12 +313,14 @@ static int wgrad_pair(const Ctx& c, const Plan& pl, int64_t M, const void* dY0, 
 // y = LayerNorm(x [+ branch]) * gamma + beta over `rows` rows of width d (the rows row_map names, when given).  With a branch (in
 // y's dtype) the sum x + branch is also written to x_sum (fp32): the fused residual add.
 // Traffic per element: x in (4) + y out; the fused add also reads the branch and writes the sum (4).
+// image_scale (drop path, optional): the branch of an image of T rows is multiplied by image_scale[image] in the add.
 static int ln_fwd(const Ctx& c, const float* x, const void* branch, float* x_sum, const int32_t* row_map, const float* gamma,
-                  const float* beta, float eps, int64_t rows, int d, int y_dt, void* y, float* mean, float* rstd) {
+                  const float* beta, float eps, int64_t rows, int d, int y_dt, void* y, float* mean, float* rstd,
+                  const float* image_scale = nullptr, int T = 0) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   const int64_t ys = (int64_t)dtype_size(y_dt);
   RUN(TK_LN_FWD, 0, rows * d * (branch ? 8 + 2 * ys : 4 + ys),
-      launch_layernorm_fwd(x, branch, x_sum, row_map, gamma, beta, eps, rows, d, y_dt, y, mean, rstd, s));
+      launch_layernorm_fwd(x, branch, x_sum, row_map, gamma, beta, eps, rows, d, y_dt, y, mean, rstd, s, image_scale, T));
   return 0;
 }
 
@@ -323,31 +328,34 @@ static int ln_fwd(const Ctx& c, const float* x, const void* branch, float* x_sum
 // (accumulate = 1) the residual gradient pl.dres, and pl.dres_c, its activation-dtype copy, is rewritten.  The dgamma / dbeta column
 // sums go to the next partial-sum slot of this pass; their second stage is queued in e->ln_tab (flushed by reach_point / backward_end).
 // Traffic per element: x in, dres in and out (12); dy in and dres_c out (two activation elements).
+// copy_scale (drop path, optional): dres_c gets copy_scale[image] * dres, the gradient entering the branch that reads dres_c next.
 static int ln_bwd(const Ctx& c, const Plan& pl, const void* dy, const float* x, const int32_t* row_map, int wi, int bi, const float* mean,
-                  const float* rstd, int64_t rows, int d, int accumulate) {
+                  const float* rstd, int64_t rows, int d, int accumulate, const float* copy_scale = nullptr, int T = 0) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   float* slot = c.buf<float>(pl.ln_partial + (int64_t)(e->ln_tab.n % PartialsTable::MAX) * pl.ln_partial_stride);
   RUN(TK_LN_BWD, 0, rows * d * (12 + 2 * c.as),
       launch_layernorm_bwd(dy, c.act, x, row_map, c.P(wi), mean, rstd, rows, d, accumulate, c.buf<float>(pl.dres), c.buf<>(pl.dres_c),
-                           c.Gp(wi), c.Gp(bi), slot, s, &e->ln_tab));
+                           c.Gp(wi), c.Gp(bi), slot, s, &e->ln_tab, copy_scale, T));
   return 0;
 }
 
 // One transformer block.  The residual adds are done by the LayerNorm kernels: LN1 first forms this block's input
 // x_in = x_prev + prev_branch (the previous block's MLP output; none for the first block), LN2 forms x_mid = x_in + proj(att).
 // The block's own MLP output is left in pl.branch_b for whoever normalises next.
+// Drop path: scale_prev (Bn) scales the previous block's MLP branch in LN1's add, scale_att (Bn) this block's attention branch in LN2's.
 static int block_forward(const Ctx& c, const Plan& pl, const BlockRefs& r, const LayerBufs& b, int64_t M, int d, int heads, int Bn, int T,
-                         int64_t x_prev, bool add_prev, int64_t x_in) {
+                         int64_t x_prev, bool add_prev, int64_t x_in, const float* scale_prev = nullptr, const float* scale_att = nullptr) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   const int hd = d / heads, hid = e->mlp * d;
   const float eps = 1e-6f;
   MAE_TRY(ln_fwd(c, c.buf<float>(add_prev ? x_prev : x_in), add_prev ? c.buf<>(pl.branch_b) : nullptr, add_prev ? c.buf<float>(x_in) : nullptr,
-                 nullptr, c.P(r.ln1_w), c.P(r.ln1_b), eps, M, d, c.act, c.buf<>(b.ln1), c.buf<float>(b.mean1), c.buf<float>(b.rstd1)));
+                 nullptr, c.P(r.ln1_w), c.P(r.ln1_b), eps, M, d, c.act, c.buf<>(b.ln1), c.buf<float>(b.mean1), c.buf<float>(b.rstd1),
+                 add_prev ? scale_prev : nullptr, T));
   MAE_TRY(linear(c, c.buf<>(b.ln1), r.qkv_w, r.qkv_b, M, 3 * d, d, MAE_EPI_NONE, c.act, c.buf<>(b.qkv), nullptr, nullptr));
   RUN(TK_ATTN_FWD, 4.0 * Bn * heads * (double)T * T * hd, M * 4 * d * c.as, launch_attention_fwd(c.buf<>(b.qkv), Bn, T, heads, hd, c.act, c.buf<>(b.att), c.buf<float>(b.lse), s));
   MAE_TRY(linear(c, c.buf<>(b.att), r.proj_w, r.proj_b, M, d, d, MAE_EPI_NONE, c.act, c.buf<>(pl.branch_a), nullptr, nullptr));
   MAE_TRY(ln_fwd(c, c.buf<float>(x_in), c.buf<>(pl.branch_a), c.buf<float>(b.x_mid), nullptr, c.P(r.ln2_w), c.P(r.ln2_b), eps, M, d, c.act,
-                 c.buf<>(b.ln2), c.buf<float>(b.mean2), c.buf<float>(b.rstd2)));
+                 c.buf<>(b.ln2), c.buf<float>(b.mean2), c.buf<float>(b.rstd2), scale_att, T));
   if (c.fwd_only)
     MAE_TRY(linear(c, c.buf<>(b.ln2), r.fc1_w, r.fc1_b, M, hid, d, MAE_EPI_GELU_ACT, c.act, c.buf<>(b.fc1_act), nullptr, nullptr));
   else
@@ -359,8 +367,11 @@ static int block_forward(const Ctx& c, const Plan& pl, const BlockRefs& r, const
 // in: dres (fp32) / dres_c (act copy) = gradient w.r.t. the block output; out: same buffers = gradient w.r.t. the block input.
 // Each branch's two weight gradients go out as ONE launch, placed where both of their dY operands exist and before the
 // LayerNorm backward that rewrites dres_c (fc2 / proj read it).
+// Drop path: whoever writes dres_c scales it for the branch that reads it next, so the copy arrives here scaled for this block's MLP
+// branch; LN2's backward scales its copy by scale_att (Bn) for the attention branch, LN1's by scale_prev (Bn) for the MLP branch of the
+// block below (null for the first block, whose copy nobody reads as a branch gradient).
 static int block_backward(const Ctx& c, const Plan& pl, const BlockRefs& r, const LayerBufs& b, int64_t M, int d, int heads, int Bn, int T,
-                          int64_t x_in) {
+                          int64_t x_in, const float* scale_prev = nullptr, const float* scale_att = nullptr) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   const int hd = d / heads, hid = e->mlp * d;
   void* dres_c = c.buf<>(pl.dres_c);
@@ -368,13 +379,13 @@ static int block_backward(const Ctx& c, const Plan& pl, const BlockRefs& r, cons
   MAE_TRY(dgrad(c, dres_c, r.fc2_w, M, d, hid, MAE_EPI_MUL, c.buf<>(pl.d_hidden), c.buf<>(b.fc1_pre)));
   MAE_TRY(wgrad_pair(c, pl, M, dres_c, c.buf<>(b.fc1_act), d, hid, r.fc2_w, r.fc2_b, c.buf<>(pl.d_hidden), c.buf<>(b.ln2), hid, d, r.fc1_w, r.fc1_b));
   MAE_TRY(dgrad(c, c.buf<>(pl.d_hidden), r.fc1_w, M, hid, d, MAE_EPI_NONE, c.buf<>(pl.d_ln), nullptr));
-  MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(b.x_mid), nullptr, r.ln2_w, r.ln2_b, c.buf<float>(b.mean2), c.buf<float>(b.rstd2), M, d, 1));
+  MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(b.x_mid), nullptr, r.ln2_w, r.ln2_b, c.buf<float>(b.mean2), c.buf<float>(b.rstd2), M, d, 1, scale_att, T));
   // attention branch
   MAE_TRY(dgrad(c, dres_c, r.proj_w, M, d, d, MAE_EPI_NONE, c.buf<>(pl.d_att), nullptr));
   RUN(TK_ATTN_BWD, 10.0 * Bn * heads * (double)T * T * hd, M * 9 * d * c.as, launch_attention_bwd(c.buf<>(b.qkv), c.buf<>(b.att), c.buf<>(pl.d_att), c.buf<float>(b.lse), Bn, T, heads, hd, c.act, c.buf<>(pl.d_qkv), s));
   MAE_TRY(wgrad_pair(c, pl, M, dres_c, c.buf<>(b.att), d, d, r.proj_w, r.proj_b, c.buf<>(pl.d_qkv), c.buf<>(b.ln1), 3 * d, d, r.qkv_w, r.qkv_b));
   MAE_TRY(dgrad(c, c.buf<>(pl.d_qkv), r.qkv_w, M, 3 * d, d, MAE_EPI_NONE, c.buf<>(pl.d_ln), nullptr));
-  MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(x_in), nullptr, r.ln1_w, r.ln1_b, c.buf<float>(b.mean1), c.buf<float>(b.rstd1), M, d, 1));
+  MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(x_in), nullptr, r.ln1_w, r.ln1_b, c.buf<float>(b.mean1), c.buf<float>(b.rstd1), M, d, 1, scale_prev, T));
   return 0;
 }
 
@@ -417,10 +428,12 @@ static int forward_encoder_impl(const Ctx& c, const Plan& pl, const void* images
   MAE_TRY(linear(c, c.buf<>(pl.patchA), e->i_patch_w, e->i_patch_b, pl.Me, e->D, e->P, MAE_EPI_NONE, MAE_F32, c.buf<>(pl.enc_x[0]), nullptr, nullptr));
   RUN(TK_DATA, 0, pl.Me * e->D * 12, launch_assemble_visible(c.buf<float>(pl.enc_x[0]), keep32, c.P(e->i_cls), c.P(e->i_pos), pl.Me, e->D, s));
   for (int i = 0; i < e->depth; ++i)
-    MAE_TRY(block_forward(c, pl, e->enc[i], pl.enc[i], pl.Me, e->D, e->H, pl.B, pl.k, i ? pl.enc[i - 1].x_mid : 0, i > 0, pl.enc_x[i]));
+    MAE_TRY(block_forward(c, pl, e->enc[i], pl.enc[i], pl.Me, e->D, e->H, pl.B, pl.k, i ? pl.enc[i - 1].x_mid : 0, i > 0, pl.enc_x[i],
+                          i ? c.scale_row(2 * i - 1, pl.B) : nullptr, c.scale_row(2 * i, pl.B)));
   if (c.skip_final_norm) return 0;
   MAE_TRY(ln_fwd(c, c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w),
-                 c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, c.act, c.buf<>(pl.enc_norm), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd)));
+                 c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, c.act, c.buf<>(pl.enc_norm), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd),
+                 c.scale_row(2 * e->depth - 1, pl.B), pl.k));
   if (x_encoded_out) {
     if (c.act == MAE_F32) MAE_HIP(hipMemcpyAsync(x_encoded_out, c.buf<>(pl.enc_norm), (size_t)pl.Me * e->D * 4, hipMemcpyDeviceToDevice, s));
     else  // a second pass over the residual sum just formed writes the fp32 rows
@@ -1082,8 +1095,10 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
                            const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes, int32_t train_blocks, int32_t train_embed,
                            float grad_scale, void* workspace, int64_t workspace_bytes, float* grads, float* head_grads, float* pos_grad,
                            float* logits, float* loss_out, int32_t* correct_out, void* stream, const char* who, int32_t with_cls = 1,
-                           bool ex = false, const HeadSoft* soft = nullptr) {
+                           bool ex = false, const HeadSoft* soft = nullptr, const float* branch_scale = nullptr) {
   MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
+  MAE_REQUIRE(!branch_scale || (head_grads && train_blocks >= 0),
+              "%s: branch_scale needs a training encoder (train_blocks >= 0); the probe's encoder is in inference and never drops", who);
   MAE_REQUIRE(batch > 0, "%s: batch %d out of range", who, batch);
   MAE_REQUIRE(head && images, "%s: null head/images", who);
   MAE_TRY(check_image_dtype(image_dtype, who));
@@ -1113,6 +1128,7 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
   hipStream_t s = c.s;
   const bool enc_bwd = train && train_blocks >= 0;
   c.fwd_only = !enc_bwd;  // the linear probe and evaluation save no GELU derivative
+  c.branch_scale = branch_scale;
   const int B = batch, L = pl.k, D = e->D, C = num_classes;  // L rows per image: the class token (if any) and every patch
   if (with_cls) MAE_TRY(launch_iota_rows(c.buf<int32_t>(pl.keep32), B, L, s));
   else MAE_TRY(launch_iota_tokens(c.buf<int32_t>(pl.keep32), B, L, s));
@@ -1144,13 +1160,14 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
     // only the B class-token rows carry gradient: zero the rest of the residual gradient, then a row-mapped final LayerNorm backward
     RUN(TK_DATA, 0, (pl.Me - B) * D * (4 + c.as), launch_zero_token_rows(pl.Me, L, D, e->act, dres, c.buf<>(pl.dres_c), s));
     MAE_TRY(ln_bwd(c, pl, c.buf<>(cp.dpooled), c.buf<float>(pl.enc_x[e->depth]), c.buf<int32_t>(cp.cls_rows), e->i_norm_w, e->i_norm_b,
-                   c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c), B, D, 0));
+                   c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c), B, D, 0, c.scale_row(2 * e->depth - 1, B), L));
   } else {
     MAE_TRY(ln_bwd(c, pl, c.buf<>(pl.d_ln), c.buf<float>(pl.enc_x[e->depth]), nullptr, e->i_norm_w, e->i_norm_b, c.buf<float>(pl.enc_mean),
-                   c.buf<float>(pl.enc_rstd), pl.Me, D, 0));
+                   c.buf<float>(pl.enc_rstd), pl.Me, D, 0, c.scale_row(2 * e->depth - 1, B), L));
   }
   for (int i = e->depth - 1; i >= e->depth - train_blocks; --i)  // the trainable suffix only: the sweep stops below blocks[depth-n]
-    MAE_TRY(block_backward(c, pl, e->enc[i], pl.enc[i], pl.Me, D, e->H, B, L, pl.enc_x[i]));
+    MAE_TRY(block_backward(c, pl, e->enc[i], pl.enc[i], pl.Me, D, e->H, B, L, pl.enc_x[i], i ? c.scale_row(2 * i - 1, B) : nullptr,
+                           c.scale_row(2 * i, B)));
   if (train_embed) {
     // token assembly: d pos_embed, d cls_token and the patch rows from one read of dres, then the patch projection
     if (with_cls)
@@ -1232,6 +1249,23 @@ extern "C" int mae_engine_classifier_loss_and_grads_soft(mae_engine_t* e, const 
   return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
                          workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
                          "mae_engine_classifier_loss_and_grads_soft", with_cls, true, soft.active() ? &soft : nullptr);
+}
+
+// mae_engine_classifier_loss_and_grads_soft with stochastic depth: branch_scale (2 * depth, batch) scales each image's residual branches
+extern "C" int mae_engine_classifier_loss_and_grads_sd(mae_engine_t* e, const float* params, const void* wcache, const float* head,
+                                                       const void* images, int32_t image_dtype, const int64_t* labels, int32_t batch,
+                                                       int32_t with_cls, int32_t pool, int32_t num_classes, int32_t train_blocks,
+                                                       int32_t train_embed, float grad_scale, void* workspace, int64_t workspace_bytes,
+                                                       float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
+                                                       int32_t* correct_out, const int64_t* labels_b, const float* lam,
+                                                       float label_smoothing, const float* branch_scale, void* stream) {
+  MAE_REQUIRE(head_grads, "mae_engine_classifier_loss_and_grads_sd: null head_grads");
+  MAE_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "mae_engine_classifier_loss_and_grads_sd: label_smoothing = %g outside [0, 1)",
+              (double)label_smoothing);
+  const HeadSoft soft{labels_b, lam, label_smoothing};
+  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
+                         workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
+                         "mae_engine_classifier_loss_and_grads_sd", with_cls, true, soft.active() ? &soft : nullptr, branch_scale);
 }
 
 // =====================================================================================================

@@ -48,12 +48,24 @@ static int ln_lanes_per_row(int d4) {
 // NV = float4 vectors per lane: covers dim <= 4*LPR*NV
 // ADD: the LayerNorm input is x + branch (the residual add of the preceding attention / MLP branch, whose GEMM then
 // keeps the plain bf16 epilogue); the sum is written to x_out as the new fp32 residual stream.
-template <class T, int NV, bool ADD, int LPR>
+// SCALE (with ADD; drop path): instantiated with the trailing arguments (const float* image_scale, int
+// rows_per_image), the branch of full-matrix row src is multiplied by image_scale[src / rows_per_image] in fp32 before the add.  A
+// scale of exactly 0 skips the branch load: x_out is then x bit for bit whatever the branch rows hold.  The lane groups of a wave can
+// belong to images with different scales, so only the loads and the add sit under the test on the scale; the group_sum shuffles
+// stay outside it.  Without the trailing arguments (the empty pack) the kernel has the signature and the code it had before.
+__device__ __forceinline__ const float* ln_scale_ptr() { return nullptr; }
+__device__ __forceinline__ const float* ln_scale_ptr(const float* p, int) { return p; }
+__device__ __forceinline__ int ln_scale_rows() { return 1; }
+__device__ __forceinline__ int ln_scale_rows(const float*, int rows_per_image) { return rows_per_image; }
+
+template <class T, int NV, bool ADD, int LPR, class... S>
 __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restrict__ x, const T* __restrict__ branch,
                                                             float* __restrict__ x_out, const int32_t* __restrict__ row_map,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             float eps, int64_t rows, int dim, T* __restrict__ y,
-                                                            float* __restrict__ mean_out, float* __restrict__ rstd_out) {
+                                                            float* __restrict__ mean_out, float* __restrict__ rstd_out, S... scale_args) {
+  constexpr bool SCALE = sizeof...(S) != 0;
+  static_assert(ADD || !SCALE, "an image scale needs the fused add");
   constexpr int RPW = 64 / LPR;  // rows per wave and iteration
   const int lane = threadIdx.x & 63, li = lane & (LPR - 1), sub = lane / LPR;
   const int D4 = dim >> 2;
@@ -63,6 +75,8 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
     const int64_t r = live ? r0 + sub : rows - 1;
     const int64_t src = row_map ? (int64_t)row_map[r] : r;
     const float* px = x + src * dim;
+    float sc = 1.f;
+    if (SCALE) sc = ln_scale_ptr(scale_args...)[src / ln_scale_rows(scale_args...)];  // lane groups past the last row: row rows - 1 and its scale
     f32x4 v[NV];
     float sum = 0.f;
 #pragma unroll
@@ -71,7 +85,8 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
       if (c < D4) {
         v[i] = LN_LD(px + c * 4);
         if (ADD) {
-          v[i] += LN_LD(branch + src * dim + c * 4);
+          if (!SCALE) v[i] += LN_LD(branch + src * dim + c * 4);
+          else if (sc != 0.f) v[i] += LN_LD(branch + src * dim + c * 4) * sc;
           if (live) LN_ST_A(x_out + src * dim + c * 4, v[i]);
         }
         sum += v[i][0] + v[i][1] + v[i][2] + v[i][3];
@@ -107,19 +122,28 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
   }
 }
 
+// image_scale (NULL: none, the launches of before): the drop-path scale per image of the fused add; src / rows_per_image indexes it.
 int launch_layernorm_fwd(const float* x, const void* branch, float* x_out, const int32_t* row_map, const float* gamma,
                          const float* beta, float eps, int64_t rows, int dim, int y_dt, void* y, float* mean, float* rstd,
-                         hipStream_t s) {
+                         hipStream_t s, const float* image_scale, int rows_per_image) {
   MAE_REQUIRE(x && gamma && beta && y && mean && rstd && rows > 0, "layernorm_fwd: null buffer");
   MAE_REQUIRE(!branch || x_out, "layernorm_fwd: the fused residual add needs x_out");
+  MAE_REQUIRE(!image_scale || (branch && rows_per_image > 0), "layernorm_fwd: an image scale needs a branch and rows_per_image > 0");
   MAE_REQUIRE(dim % 4 == 0 && dim >= 4 && dim <= 1024, "layernorm: dim %d must be a multiple of 4 in [4, 1024]", dim);
   const int lpr = ln_lanes_per_row(dim / 4), nv = (int)cdiv(dim / 4, lpr);
   const int grid = (int)std::min<int64_t>(cdiv(rows, 4 * (64 / lpr)), 256 * 32);
 #define LN(T, NV, ADD, LPR) hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV, ADD, LPR>), dim3(grid), dim3(256), 0, s, x, (const T*)branch, x_out, row_map, gamma, beta, eps, rows, dim, (T*)y, mean, rstd)
 #define LN_NV(T, ADD, LPR) switch (nv) { case 1: LN(T, 1, ADD, LPR); break; case 2: LN(T, 2, ADD, LPR); break; case 3: LN(T, 3, ADD, LPR); break; default: LN(T, 4, ADD, LPR); }
 #define LN_LPR(T, ADD) switch (lpr) { case 16: LN_NV(T, ADD, 16) break; case 32: LN_NV(T, ADD, 32) break; default: LN_NV(T, ADD, 64) }
-  if (y_dt == MAE_BF16) { if (branch) { LN_LPR(bf16, true) } else { LN_LPR(bf16, false) } }
+#define LNS(T, NV, LPR) hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV, true, LPR, const float*, int>), dim3(grid), dim3(256), 0, s, x, (const T*)branch, x_out, row_map, gamma, beta, eps, rows, dim, (T*)y, mean, rstd, image_scale, rows_per_image)
+#define LNS_NV(T, LPR) switch (nv) { case 1: LNS(T, 1, LPR); break; case 2: LNS(T, 2, LPR); break; case 3: LNS(T, 3, LPR); break; default: LNS(T, 4, LPR); }
+#define LNS_LPR(T) switch (lpr) { case 16: LNS_NV(T, 16) break; case 32: LNS_NV(T, 32) break; default: LNS_NV(T, 64) }
+  if (image_scale) { if (y_dt == MAE_BF16) { LNS_LPR(bf16) } else { LNS_LPR(float) } }
+  else if (y_dt == MAE_BF16) { if (branch) { LN_LPR(bf16, true) } else { LN_LPR(bf16, false) } }
   else { if (branch) { LN_LPR(float, true) } else { LN_LPR(float, false) } }
+#undef LNS_LPR
+#undef LNS_NV
+#undef LNS
 #undef LN_LPR
 #undef LN_NV
 #undef LN
@@ -131,13 +155,17 @@ int launch_layernorm_fwd(const float* x, const void* branch, float* x_out, const
 //   dx = rstd * (g - mean(g) - xhat*mean(g*xhat));  dgamma = sum_rows dy*xhat;  dbeta = sum_rows dy
 // Each wave keeps per-lane column partials of dgamma/dbeta across the rows it walks; the block's 4 waves are
 // combined through LDS into partial[block][2][dim]; a second kernel adds the blocks in order (deterministic).
-template <class T, int NV, int LPR>
+// SCALE (drop path; the trailing arguments const float* copy_scale, int rows_per_image): dx_copy[src] =
+// T(fl32(copy_scale[src / rows_per_image] * d)), d the fp32 value stored to dx_io[src]: the copy is the gradient entering the branch
+// that reads it next.  dx_io, dgamma and dbeta do not see the scale.  Without the trailing arguments: the kernel as it was.
+template <class T, int NV, int LPR, class... S>
 __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict__ dy, const float* __restrict__ x,
                                                             const int32_t* __restrict__ row_map,
                                                             const float* __restrict__ gamma, const float* __restrict__ mean,
                                                             const float* __restrict__ rstd, int64_t rows, int dim,
                                                             int accumulate, float* __restrict__ dx_io, T* __restrict__ dx_copy,
-                                                            float* __restrict__ partial) {
+                                                            float* __restrict__ partial, S... scale_args) {
+  constexpr bool SCALE = sizeof...(S) != 0;
   constexpr int RPW = 64 / LPR;
   extern __shared__ __attribute__((aligned(16))) float red[];  // [4 waves x RPW lane groups][2][dim]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & (LPR - 1), sub = lane / LPR;
@@ -156,6 +184,8 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict_
     const int64_t r = live ? r0 + sub : rows - 1;
     const int64_t src = row_map ? (int64_t)row_map[r] : r;
     const float mu = mean[r], rs = rstd[r];
+    float sc = 1.f;
+    if (SCALE) sc = ln_scale_ptr(scale_args...)[src / ln_scale_rows(scale_args...)];
     f32x4 xh[NV], g[NV];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -183,7 +213,8 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict_
         float* pd = dx_io + src * dim + c * 4;
         if (accumulate) d += load4(pd);
         LN_ST_A(pd, d);
-        if (dx_copy) LN_ST_B(dx_copy + src * dim + c * 4, d);
+        if (SCALE) LN_ST_B(dx_copy + src * dim + c * 4, d * sc);
+        else if (dx_copy) LN_ST_B(dx_copy + src * dim + c * 4, d);
       }
     }
   }
@@ -207,8 +238,10 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict_
 
 int launch_layernorm_bwd(const void* dy, int dy_dt, const float* x, const int32_t* row_map, const float* gamma,
                          const float* mean, const float* rstd, int64_t rows, int dim, int accumulate, float* dx_io,
-                         void* dx_copy, float* dgamma, float* dbeta, float* partial, hipStream_t s, PartialsTable* defer) {
+                         void* dx_copy, float* dgamma, float* dbeta, float* partial, hipStream_t s, PartialsTable* defer,
+                         const float* copy_scale, int rows_per_image) {
   MAE_REQUIRE(dy && x && gamma && mean && rstd && dx_io && dgamma && dbeta && partial && rows > 0, "layernorm_bwd: null buffer");
+  MAE_REQUIRE(!copy_scale || (dx_copy && rows_per_image > 0), "layernorm_bwd: a copy scale needs dx_copy and rows_per_image > 0");
   MAE_REQUIRE(dim % 4 == 0 && dim >= 4 && dim <= 1024, "layernorm: dim %d must be a multiple of 4 in [4, 1024]", dim);
   if (defer && defer->n == PartialsTable::MAX) {  // deep models: run what is queued before `partial` (slot 0 again) is rewritten
     MAE_TRY(launch_sum_partials_many(*defer, s));
@@ -220,7 +253,14 @@ int launch_layernorm_bwd(const void* dy, int dy_dt, const float* x, const int32_
 #define LNB(T, NV, LPR) hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV, LPR>), dim3(grid), dim3(256), lds, s, (const T*)dy, x, row_map, gamma, mean, rstd, rows, dim, accumulate, dx_io, (T*)dx_copy, partial)
 #define LNB_NV(T, LPR) switch (nv) { case 1: LNB(T, 1, LPR); break; case 2: LNB(T, 2, LPR); break; case 3: LNB(T, 3, LPR); break; default: LNB(T, 4, LPR); }
 #define LNB_LPR(T) switch (lpr) { case 16: LNB_NV(T, 16) break; case 32: LNB_NV(T, 32) break; default: LNB_NV(T, 64) }
-  if (dy_dt == MAE_BF16) { LNB_LPR(bf16) } else { LNB_LPR(float) }
+#define LNBS(T, NV, LPR) hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV, LPR, const float*, int>), dim3(grid), dim3(256), lds, s, (const T*)dy, x, row_map, gamma, mean, rstd, rows, dim, accumulate, dx_io, (T*)dx_copy, partial, copy_scale, rows_per_image)
+#define LNBS_NV(T, LPR) switch (nv) { case 1: LNBS(T, 1, LPR); break; case 2: LNBS(T, 2, LPR); break; case 3: LNBS(T, 3, LPR); break; default: LNBS(T, 4, LPR); }
+#define LNBS_LPR(T) switch (lpr) { case 16: LNBS_NV(T, 16) break; case 32: LNBS_NV(T, 32) break; default: LNBS_NV(T, 64) }
+  if (copy_scale) { if (dy_dt == MAE_BF16) { LNBS_LPR(bf16) } else { LNBS_LPR(float) } }
+  else if (dy_dt == MAE_BF16) { LNB_LPR(bf16) } else { LNB_LPR(float) }
+#undef LNBS_LPR
+#undef LNBS_NV
+#undef LNBS
 #undef LNB_LPR
 #undef LNB_NV
 #undef LNB
@@ -257,4 +297,23 @@ extern "C" int mae_layernorm_bwd(const void* dy, int32_t dy_dtype, const float* 
                                  float* partial, void* stream) {
   return mae::launch_layernorm_bwd(dy, dy_dtype, x, row_map, gamma, mean, rstd, rows, dim, accumulate, dx_io, dx_copy,
                                    dgamma, dbeta, partial, (hipStream_t)stream);
+}
+
+extern "C" int mae_add_layernorm_fwd_scaled(const float* x, const void* branch, float* x_out, const int32_t* row_map, const float* gamma,
+                                            const float* beta, float eps, int64_t rows, int32_t dim, int32_t y_dtype, void* y, float* mean,
+                                            float* rstd, const float* image_scale, int32_t rows_per_image, void* stream) {
+  MAE_REQUIRE(branch && x_out, "mae_add_layernorm_fwd_scaled: null branch/x_out");
+  MAE_REQUIRE(rows_per_image > 0, "mae_add_layernorm_fwd_scaled: rows_per_image = %d must be positive", rows_per_image);
+  return mae::launch_layernorm_fwd(x, branch, x_out, row_map, gamma, beta, eps, rows, dim, y_dtype, y, mean, rstd, (hipStream_t)stream,
+                                   image_scale, rows_per_image);
+}
+
+extern "C" int mae_layernorm_bwd_scaled(const void* dy, int32_t dy_dtype, const float* x, const int32_t* row_map,
+                                        const float* gamma, const float* mean, const float* rstd, int64_t rows, int32_t dim,
+                                        int32_t accumulate, float* dx_io, void* dx_copy, float* dgamma, float* dbeta,
+                                        float* partial, const float* copy_scale, int32_t rows_per_image, void* stream) {
+  MAE_REQUIRE(rows_per_image > 0, "mae_layernorm_bwd_scaled: rows_per_image = %d must be positive", rows_per_image);
+  MAE_REQUIRE(!copy_scale || dx_copy, "mae_layernorm_bwd_scaled: a copy scale needs dx_copy");
+  return mae::launch_layernorm_bwd(dy, dy_dtype, x, row_map, gamma, mean, rstd, rows, dim, accumulate, dx_io, dx_copy,
+                                   dgamma, dbeta, partial, (hipStream_t)stream, nullptr, copy_scale, rows_per_image);
 }

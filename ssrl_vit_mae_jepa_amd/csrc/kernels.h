@@ -190,7 +190,7 @@ int launch_transpose_many(const float* params, bf16* tbase, const TransposeTable
 // y = LN(x [+ branch]); with a branch (dtype y_dt) the sum is also written to x_out (fp32): the fused residual add
 int launch_layernorm_fwd(const float* x, const void* branch, float* x_out, const int32_t* row_map, const float* gamma,
                          const float* beta, float eps, int64_t rows, int dim, int y_dt, void* y, float* mean, float* rstd,
-                         hipStream_t s);
+                         hipStream_t s, const float* image_scale = nullptr, int rows_per_image = 0);
 // Second stages of several two-stage column reductions, run by ONE launch (passed by value as a kernel argument): the
 // backward pass queues the dgamma / dbeta reduction of each of its LayerNorms here instead of launching 27 small,
 // latency-bound kernels between the big ones.
@@ -206,7 +206,8 @@ int launch_sum_partials_many(const PartialsTable& tab, hipStream_t s);
 // launch_sum_partials_many later) instead of being launched here
 int launch_layernorm_bwd(const void* dy, int dy_dt, const float* x, const int32_t* row_map, const float* gamma,
                          const float* mean, const float* rstd, int64_t rows, int dim, int accumulate, float* dx_io,
-                         void* dx_copy, float* dgamma, float* dbeta, float* partial, hipStream_t s, PartialsTable* defer = nullptr);
+                         void* dx_copy, float* dgamma, float* dbeta, float* partial, hipStream_t s, PartialsTable* defer = nullptr,
+                         const float* copy_scale = nullptr, int rows_per_image = 0);
 constexpr int LN_BWD_MAX_BLOCKS = 1024;
 
 // Compute units of the current device (256 on MI355X), queried once: the persistent GEMMs launch one workgroup per CU.

@@ -451,3 +451,27 @@ def mix_batch(images: torch.Tensor, labels: torch.Tensor, params: MixParams):
     idx = partner.to(torch.int64)
     yb = labels[torch.where((idx < 0) | (idx >= B), own, idx)]  # the kernel's rule: an out-of-range partner is the image itself
     return out, labels, yb, lam
+
+
+def drop_path_rates(depth: int, rate: float) -> np.ndarray:
+    """Per-block drop rates of timm's VisionTransformer: ``torch.linspace(0, rate, depth)``, p_i = rate * i / (depth - 1) (depth 1: 0)."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"drop_path rate must be in [0, 1), got {rate}")
+    if depth < 1:
+        raise ValueError(f"depth must be positive, got {depth}")
+    return np.array([rate * i / (depth - 1) if depth > 1 else 0.0 for i in range(depth)], dtype=np.float64)
+
+
+def draw_drop_path(depth: int, batch: int, rate: float, gen_or_seed: Union[np.random.Generator, int, Sequence[int]]) -> torch.Tensor:
+    """One step's stochastic-depth draw (timm ``DropPath``, scale_by_keep=True) as the engine's branch-scale table: a
+    (2 * depth, batch) fp32 host tensor, row 2i the attention branch of block i and row 2i + 1 its MLP branch, each image kept
+    independently where u >= p_i with u = default_rng(entropy).random((2 * depth, batch)).  Values are 0 (dropped) or
+    float32(1 / (1 - p_i)) (kept); rows with p_i == 0 are exactly 1.  ``gen_or_seed`` as in ``draw_mix_params``.  Host arithmetic
+    only: nothing here touches the device."""
+    p = drop_path_rates(depth, rate)
+    rng = gen_or_seed if isinstance(gen_or_seed, np.random.Generator) else np.random.default_rng(gen_or_seed)
+    u = rng.random((2 * int(depth), int(batch)))
+    p_rows = np.repeat(p, 2)[:, None]
+    kept = (1.0 / (1.0 - p_rows)).astype(np.float32)
+    return torch.from_numpy(np.where(u >= p_rows, kept, np.float32(0.0)).astype(np.float32))

@@ -11,10 +11,14 @@ sequence), `--pool` overrides the config's pool, `--timers` adds the engine's pe
 `--mix` trains with the fine-tuning recipe (mixup 0.8 + CutMix 1.0 + label smoothing 0.1: the batch is mixed on the device every
 step and the head takes soft targets) and also times `mae_mix_batch` alone (both kinds of batch, with the bytes it moves);
 `--layer_decay X` gives every layer its own learning rate (one AdamW launch per layer instead of one).
+`--drop_path X` trains with stochastic depth at rate X: every fused step of an unfrozen mode draws a (2 * depth, B) scale table on
+the host, uploads it and runs the scaled LayerNorm kernels (the frozen mode ignores the rate; the hand-off has no drop path and is
+not timed then).
 
     python tools/classifier_bench.py --batch 2000 --steps 10 --warmup 3 --out profiles/r04_classifier_bench.json
     python tools/classifier_bench.py --models vits8 --patch_only --pool mean_patches --timers
     python tools/classifier_bench.py --models vits8 --no-handoff --mix --layer_decay 0.75
+    python tools/classifier_bench.py --models vits8 --no-handoff --drop_path 0.1
 """
 from __future__ import annotations
 
@@ -58,7 +62,7 @@ def set_mode(mod, mode):
 
 def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repeats: int, modes=("frozen", "last1", "full"),
                 handoff: bool = True, patch_only: bool = False, pool=None, timers: bool = False, mix: bool = False,
-                layer_decay: float = 1.0) -> dict:
+                layer_decay: float = 1.0, drop_path: float = 0.0) -> dict:
     cfg = yaml.safe_load(cfg_path.read_text())
     mc = dict(cfg["model"], general=dict(cfg["model"]["general"], engine_precision=cfg.get("engine", {}).get("precision", "bf16")))
     if pool is not None:
@@ -67,9 +71,10 @@ def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repe
     mae = encoder_mae(mc)
     mae.encoder.vit.with_cls = not patch_only
     handoff = handoff and not patch_only and mc.get("head", {}).get("pool", "cls") == "cls"  # the hand-off below pools the class token
+    handoff = handoff and drop_path == 0.0  # the hand-off has no drop path: not comparable
     recipe = dict(label_smoothing=0.1, mixup_alpha=0.8, cutmix_alpha=1.0) if mix else {}
     mod = ViTClassifierTrainModule(pretrained_encoder=mae.encoder.vit, model_cfg=mc,
-                                   training_cfg=dict(cfg.get("train", {}), layer_decay=layer_decay, **recipe)).to(dev)
+                                   training_cfg=dict(cfg.get("train", {}), layer_decay=layer_decay, drop_path=drop_path, **recipe)).to(dev)
     S = mc["general"]["image_size"]
     g = torch.Generator(device=dev).manual_seed(0)
     images = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, device=dev, generator=g)
@@ -78,6 +83,7 @@ def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repe
     ws_bytes = int(mod.model.workspace(B).numel())
     res = {"model": name, "config": str(cfg_path.relative_to(ROOT)), "batch": B, "precision": m.engine.precision,
            "with_cls": not patch_only, "pool": mod.model.pool_type, "workspace_gib": ws_bytes / 2 ** 30, "mix": mix, "layer_decay": layer_decay,
+           "drop_path": drop_path,
            "ms": {}, "images_per_s": {}}
 
     def fused():
@@ -167,6 +173,7 @@ def main(argv=None):
     ap.add_argument("--timers", action="store_true", help="per-kernel-class milliseconds of one fused step per mode")
     ap.add_argument("--mix", action="store_true", help="mixup 0.8 + CutMix 1.0 + label smoothing 0.1 in the fused step; times the mix kernel too")
     ap.add_argument("--layer_decay", type=float, default=1.0, help="layer-wise learning-rate decay of the fused step (1 = off)")
+    ap.add_argument("--drop_path", type=float, default=0.0, help="stochastic depth rate of the fused step (0 = off)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -175,7 +182,7 @@ def main(argv=None):
     for name in args.models.split(","):
         out["results"].append(bench_model(name, cfgs[name], args.batch, args.steps, args.warmup, args.repeats,
                                               tuple(args.modes.split(",")), not args.no_handoff, args.patch_only, args.pool, args.timers, args.mix,
-                                              args.layer_decay))
+                                              args.layer_decay, args.drop_path))
         torch.cuda.empty_cache()
     text = json.dumps(out, indent=1)
     print(text)
