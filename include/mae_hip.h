@@ -382,6 +382,38 @@ int mae_engine_classifier_loss_and_grads_sd(mae_engine_t* e, const float* params
 int mae_mix_batch(const void* images, int32_t image_dtype, const int32_t* partner, const float* lam, const int32_t* box,
                   int32_t batch, int32_t in_chans, int32_t image_size, int32_t out_dtype, void* out, void* stream);
 
+/* Per-image augmentation in front of the mixing (additive in ABI v4): RandomResizedCrop + flip, RandAugment and random erasing
+ * of the MAE / BEiT / DeiT fine-tuning recipe on uint8 images, with the semantics of the PIL calls timm makes, per element.
+ * One workgroup per image; the image stays in LDS through the whole chain (two buffers: op k + 1 reads the rounded uint8 result
+ * of op k), so 2 * C * S * S + 3200 bytes must fit 160 KiB: S <= 160 at C = 3, else an error before the launch.
+ *   images  : (batch, C, S, S) uint8;   out: (batch, C, S, S) in out_dtype, may neither be nor overlap images (checked);
+ *   op_codes: (batch, num_ops, 2) int32: the op id and its integer argument;   num_ops in 0..8, ops applied in slot order;
+ *   op_args : (batch, num_ops, 6) fp64: the blend factor in [0], or the affine matrix;
+ *   erase   : (batch, 5) int32 (y0, y1, x0, x1, seed), half-open, clamped to [0, S] by the kernel, empty / inverted = nothing
+ *             erased; NULL = none.
+ * Ops (an id outside the list is NONE; an id is never used as an index):
+ *   INVERT 255 - v;  SOLARIZE(t) v < t ? v : 255 - v;  SOLARIZE_ADD(a) v < 128 ? clamp(v + a, 0, 255) : v;
+ *   POSTERIZE(bits) v & ~(2^(8 - bits) - 1) (bits >= 8 identity, bits <= 0 black);
+ *   AUTOCONTRAST / EQUALIZE: ImageOps.autocontrast(cutoff 0) / ImageOps.equalize, per channel;
+ *   COLOR / CONTRAST / BRIGHTNESS / SHARPNESS(f): ImageEnhance, Image.blend(degenerate, image, f) in fp32;
+ *   AFFINE(m; integer argument = mode | fill << 8, fill = 0xRRGGBB, a one-channel image takes its low byte):
+ *     Image.transform(AFFINE, m, resample, fillcolor) in fp64: mode 0 bilinear and 1 bicubic as PIL rounds them (truncation),
+ *     2 / 3 the same filters rounded to nearest.  The random-resized crop is the map (w / S, 0, left, 0, h / S, top) of slot 0,
+ *     (-w / S, 0, left + w, 0, h / S, top) when flipped; the identity box returns the image bit for bit.
+ * Every op but AFFINE needs in_chans == 3: with another in_chans, num_ops > 0 is an error unless out_dtype carries
+ * MAE_AUG_GEOMETRIC, the caller's statement that every id is AFFINE or NONE (the kernel then skips any other id).
+ *   out_dtype = MAE_U8 : the bytes; erase is ignored (normal noise has no byte form).
+ *   out_dtype = MAE_F32: (v / 255 - 0.5) / 0.5, bit-identical to the engine's pixel kernels; element e = (c S + y) S + x inside
+ *     the erase box is N(0, 1) noise (timm RandomErasing, `pixel` mode): with fmix32 murmur3's finaliser and
+ *     mix(s, i) = fmix32(fmix32(i + 0x9E3779B9) ^ s): u1 = ((mix(seed, 2e) >> 8) + 1) 2^-24, u2 = (mix(seed, 2e + 1) >> 8) 2^-24,
+ *     n = sqrtf(-2 logf(u1)) cosf(2 pi u2).
+ * op_codes / erase 4-byte, op_args 8-byte, an fp32 out 4-byte aligned. */
+enum { MAE_AUG_NONE = 0, MAE_AUG_AUTOCONTRAST, MAE_AUG_EQUALIZE, MAE_AUG_INVERT, MAE_AUG_POSTERIZE, MAE_AUG_SOLARIZE,
+       MAE_AUG_SOLARIZE_ADD, MAE_AUG_COLOR, MAE_AUG_CONTRAST, MAE_AUG_BRIGHTNESS, MAE_AUG_SHARPNESS, MAE_AUG_AFFINE };
+enum { MAE_AUG_GEOMETRIC = 0x100 /* or-ed into out_dtype */ };
+int mae_augment_ops_u8(const uint8_t* images, int32_t batch, int32_t in_chans, int32_t image_size, const int32_t* op_codes,
+                       const double* op_args, int32_t num_ops, const int32_t* erase, int32_t out_dtype, void* out, void* stream);
+
 /* The classifier's optimizer (Lightning gradient_clip_val = 1.0 + one-group torch AdamW over the requires_grad tensors,
  * scripts/training/train_mae.py:213, src/training/classifier.py:106-108) over buffers that are not the arena's trainable range:
  *   mae_engine_grad_sumsq_buffer       : sumsq_io[0] = (accumulate ? sumsq_io[0] : 0) + sum of grads[0 .. count)^2

@@ -16,6 +16,9 @@ per-epoch LR, one metrics line; best.ckpt on a new maximum of val_acc, last.ckpt
 The fine-tuning recipe of the MAE paper: --label_smoothing, --mixup, --cutmix and --layer_decay override the YAML keys
 train.label_smoothing / mixup_alpha / cutmix_alpha / layer_decay (configs/vits8_dec192_finetune.yaml sets 0.1, 0.8, 1.0, 0.75);
 --drop_path overrides train.drop_path (stochastic depth, default 0; the MAE recipe uses 0.1; ignored by a frozen encoder).
+--augment turns on the per-image augmentation in front of the mixing (train.augment: RandomResizedCrop + flip, RandAugment
+rand-m9-mstd0.5-inc1, random erasing 0.25; configs/vits8_dec192_finetune_aug.yaml); --crop_scale LO HI, --rand_augment N M and
+--random_erasing P override its keys.  Training batches only: validation and test images are never augmented.
 Under mixup / CutMix the metrics line's ``train_loss`` is the soft-target loss and ``train_acc`` counts argmax == the image's
 own label (the first of each mixed pair), so it reads lower than the accuracy on clean images; ``val_*`` stay hard-label.
 
@@ -42,7 +45,11 @@ IJEPA_LAYOUTS = ("ijepa_ckpt", "ijepa_pt")
 NO_CLS = "train_mae: I-JEPA encoders see no class token: --pool must be mean or mean_patches"
 
 
-def parse_args(argv=None):
+AUGMENT_RECIPE = {"crop_scale": [0.08, 1.0], "flip": 0.5, "interpolation": "bicubic",
+                  "rand_augment": {"num_ops": 2, "magnitude": 9.0, "mstd": 0.5, "prob": 0.5}, "random_erasing": 0.25, "fill": 128}
+
+
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Fine-tune / linear-probe the ViT classifier")
     parser.add_argument("--config", type=str, default="configs/mae.yaml")
     parser.add_argument("--encoder_ckpt", type=str, default=None, help="Path to a pretrained MAE or I-JEPA checkpoint (encoder weights)")
@@ -58,10 +65,40 @@ def parse_args(argv=None):
     parser.add_argument("--cutmix", type=float, default=None, help="overrides train.cutmix_alpha (0 = off)")
     parser.add_argument("--layer_decay", type=float, default=None, help="overrides train.layer_decay (1 = one learning rate)")
     parser.add_argument("--drop_path", type=float, default=None, help="overrides train.drop_path (stochastic depth rate, 0 = off)")
+    parser.add_argument("--augment", action="store_true",
+                        help="per-image augmentation with the recipe's defaults: RandomResizedCrop(0.08, 1) + flip, rand-m9-mstd0.5-inc1, random erasing 0.25")
+    parser.add_argument("--crop_scale", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="overrides train.augment.crop_scale")
+    parser.add_argument("--rand_augment", type=float, nargs=2, default=None, metavar=("N", "M"),
+                        help="overrides train.augment.rand_augment.num_ops / magnitude")
+    parser.add_argument("--random_erasing", type=float, default=None, help="overrides train.augment.random_erasing (probability, 0 = off)")
     parser.add_argument("--max_epochs", type=int, default=None)
     parser.add_argument("--max_steps_per_epoch", type=int, default=None)
     parser.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic labeled images instead of STL-10")
-    return parser.parse_args(argv)
+    return parser
+
+
+def parse_args(argv=None):
+    return build_parser().parse_args(argv)
+
+
+def augment_overrides(args, block):
+    """train.augment after --augment / --crop_scale / --rand_augment / --random_erasing: --augment fills in the recipe's defaults
+    under what the YAML sets, each other flag overrides its key; None when neither the YAML nor a flag asks for augmentation."""
+    import copy
+    block = copy.deepcopy(block) if block else {}
+    if getattr(args, "augment", False):
+        merged = copy.deepcopy(AUGMENT_RECIPE)
+        ra = dict(merged["rand_augment"], **(block.get("rand_augment") or {}))
+        merged.update(block)
+        merged["rand_augment"] = ra
+        block = merged
+    if getattr(args, "crop_scale", None) is not None:
+        block["crop_scale"] = [float(v) for v in args.crop_scale]
+    if getattr(args, "rand_augment", None) is not None:
+        block["rand_augment"] = dict(block.get("rand_augment") or {}, num_ops=int(args.rand_augment[0]), magnitude=float(args.rand_augment[1]))
+    if getattr(args, "random_erasing", None) is not None:
+        block["random_erasing"] = float(args.random_erasing)
+    return block or None
 
 
 def apply_recipe_flags(cfg: dict, args) -> None:
@@ -70,6 +107,9 @@ def apply_recipe_flags(cfg: dict, args) -> None:
                       ("drop_path", "drop_path")):
         if getattr(args, flag, None) is not None:
             cfg["train"][key] = float(getattr(args, flag))
+    block = augment_overrides(args, cfg["train"].get("augment"))
+    if block is not None:
+        cfg["train"]["augment"] = block
 
 
 def model_config(cfg: dict) -> dict:
@@ -171,7 +211,7 @@ def main(argv=None):
 
     train_batches, val_batches = get_train_batches(cfg, dev, synthetic_images=args.synthetic_images, seed=SEED)
     module = build_module(cfg, args.encoder_ckpt, args.classifier_ckpt, encoder=args.encoder, pool=args.pool).to(dev)
-    module.mix_seed = module.drop_seed = int(cfg.get("seed", SEED))  # the mixup / CutMix and the drop-path draw of a step are functions of (seed, epoch, step)
+    module.mix_seed = module.drop_seed = module.aug_seed = int(cfg.get("seed", SEED))  # the mixup / CutMix, drop-path and augmentation draws of a step are functions of (seed, epoch, step)
     total = int(train_cfg["total_epochs"]) if args.max_epochs is None else min(int(train_cfg["total_epochs"]), args.max_epochs)
     best_acc, log_path = -1.0, output_dir / "logs" / "metrics.jsonl"
     for epoch in range(total):

@@ -20,6 +20,10 @@ LOSS_MSE, LOSS_SMOOTH_L1 = 0, 1
 POOL_CLS, POOL_MEAN, POOL_MEAN_PATCHES = 0, 1, 2
 FEAT_NONE, FEAT_L2 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL, EPI_GELU_ACT = 0, 1, 2, 3, 4, 5, 6
+AUG_NONE, AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_INVERT, AUG_POSTERIZE, AUG_SOLARIZE, AUG_SOLARIZE_ADD, AUG_COLOR, AUG_CONTRAST, AUG_BRIGHTNESS, \
+    AUG_SHARPNESS, AUG_AFFINE = range(12)
+AUG_GEOMETRIC = 0x100  # MAE_AUG_GEOMETRIC, or-ed into out_dtype
+AUG_BILINEAR, AUG_BICUBIC, AUG_BILINEAR_ROUND, AUG_BICUBIC_ROUND = 0, 1, 2, 3  # AFFINE modes
 ABI_VERSION = 4
 NORM_PIX_EPS = 1e-6  # MAE_NORM_PIX_EPS
 
@@ -99,6 +103,7 @@ SIGNATURES = {
     "mae_engine_classifier_loss_and_grads_sd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i64,
                                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp]),
     "mae_mix_batch": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_augment_ops_u8": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
     "mae_engine_grad_sumsq_buffer": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "mae_engine_adamw_buffer": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _vp, _vp]),
     "mae_engine_refresh_transposed_range": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),

@@ -10,7 +10,9 @@ is set (Lightning ``gradient_clip_val=1.0``, scripts/training/train_mae.py:213; 
 The fine-tuning recipe of the MAE paper (not in the reference; every option off by default, and off means the calls above
 unchanged): ``train.label_smoothing``, ``train.mixup_alpha`` / ``train.cutmix_alpha`` (+ ``mix_prob``, ``mix_switch_prob``)
 mix each training batch on the device (``data.mix_batch``) and train on the soft targets inside the head kernel;
-``train.layer_decay`` scales the learning rate of layer l by ``layer_decay ** (depth + 1 - l)`` (BEiT / MAE numbering).
+``train.layer_decay`` scales the learning rate of layer l by ``layer_decay ** (depth + 1 - l)`` (BEiT / MAE numbering);
+``train.augment`` augments each image of a training batch before all that (``data.augment_finetune``: RandomResizedCrop + flip,
+RandAugment, random erasing, one kernel).
 """
 from __future__ import annotations
 
@@ -170,6 +172,46 @@ class ViTClassifier(nn.Module):
         return self.evaluate(x)[0]
 
 
+def parse_augment(block: Optional[Dict[str, Any]]) -> Optional[Dict[str, Any]]:
+    """``train.augment`` checked and turned into the keyword arguments of ``data.draw_finetune_augment``; None when the block is
+    absent or empty.  Keys: ``crop_scale`` [lo, hi] (absent: no crop), ``flip`` (probability, absent: 0), ``interpolation``
+    (bicubic | bilinear), ``rand_augment`` {num_ops, magnitude, mstd, prob} (absent: no ops), ``random_erasing`` (probability,
+    absent: 0), ``fill`` (a byte, or three)."""
+    if not block:
+        return None
+    if not isinstance(block, dict):
+        raise ValueError(f"train.augment must be a mapping, got {block!r}")
+    unknown = set(block) - {"crop_scale", "flip", "interpolation", "rand_augment", "random_erasing", "fill"}
+    if unknown:
+        raise ValueError(f"train.augment: unknown keys {sorted(unknown)}")
+    crop = block.get("crop_scale")
+    if crop is not None:
+        if not isinstance(crop, (list, tuple)) or len(crop) != 2 or not 0.0 < float(crop[0]) <= float(crop[1]) <= 1.0:
+            raise ValueError(f"train.augment.crop_scale must be [lo, hi] with 0 < lo <= hi <= 1, got {crop!r}")
+        crop = (float(crop[0]), float(crop[1]))
+    flip, erase = float(block.get("flip", 0.0) or 0.0), float(block.get("random_erasing", 0.0) or 0.0)
+    if not (0.0 <= flip <= 1.0 and 0.0 <= erase <= 1.0):
+        raise ValueError(f"train.augment.flip / random_erasing are probabilities, got {flip} / {erase}")
+    interpolation = block.get("interpolation", "bicubic")
+    if interpolation not in ("bicubic", "bilinear"):
+        raise ValueError(f"train.augment.interpolation must be bicubic or bilinear, got {interpolation!r}")
+    ra = block.get("rand_augment")
+    if ra is not None and not isinstance(ra, dict):
+        raise ValueError(f"train.augment.rand_augment must be a mapping, got {ra!r}")
+    if ra is not None and set(ra) - {"num_ops", "magnitude", "mstd", "prob"}:
+        raise ValueError(f"train.augment.rand_augment: unknown keys {sorted(set(ra) - {'num_ops', 'magnitude', 'mstd', 'prob'})}")
+    num_ops = int(ra.get("num_ops", 2)) if ra is not None else 0
+    magnitude, mstd, prob = (float((ra or {}).get(k, d)) for k, d in (("magnitude", 9.0), ("mstd", 0.5), ("prob", 0.5)))
+    if not (0 <= num_ops <= 7 and 0.0 <= magnitude <= 10.0 and mstd >= 0.0 and 0.0 <= prob <= 1.0):
+        raise ValueError("train.augment.rand_augment: num_ops in 0..7, magnitude in [0, 10], mstd >= 0, prob in [0, 1]")
+    fill = block.get("fill", 128)
+    fill = tuple(fill) if isinstance(fill, (list, tuple)) else (fill,) * 3
+    if len(fill) != 3 or not all(isinstance(v, int) and 0 <= v <= 255 for v in fill):
+        raise ValueError(f"train.augment.fill must be a byte or three, got {block.get('fill')!r}")
+    return dict(crop_scale=crop, flip=flip, interpolation=interpolation, num_ops=num_ops, magnitude=magnitude, mstd=mstd, op_prob=prob,
+                erase_prob=erase, fill=fill)
+
+
 def _group_of(name: str) -> str:
     if name.startswith("blocks."):
         return "blocks." + name.split(".")[1]
@@ -209,6 +251,14 @@ class ViTClassifierTrainModule(nn.Module):
         self.drop_path = float(self.training_cfg.get("drop_path", 0.0) or 0.0)
         if not 0.0 <= self.drop_path < 1.0:
             raise ValueError(f"train.drop_path must be in [0, 1), got {self.drop_path}")
+        self.augment = parse_augment(self.training_cfg.get("augment"))
+        general = self.model_cfg.get("general") or {}
+        if self.augment is not None and "image_size" in general:
+            need = 2 * int(general.get("in_chans", 3)) * int(general["image_size"]) ** 2 + 3200
+            if need > 160 * 1024:
+                raise ValueError(f"train.augment keeps two copies of an image in LDS: {need} bytes at image_size {general['image_size']}, more than 160 KiB")
+        self.aug_seed = 73
+        self._aug_step = 0
         self.mix_seed = 73
         self._mix_step = 0
         self.drop_seed = 73
@@ -275,6 +325,7 @@ class ViTClassifierTrainModule(nn.Module):
     def training_step(self, batch, batch_idx):
         """Loss + gradients of the trainable set (native); ``optimizer_step`` applies them."""
         imgs, labels = batch
+        imgs = self._augment(imgs)
         loss, correct = self.loss_and_grads(imgs, labels, branch_scale=self._draw_branch_scale(imgs.shape[0]))
         self.log("train_loss", loss[0])
         self.log("train_acc", correct[0].float() / imgs.shape[0])
@@ -450,6 +501,21 @@ class ViTClassifierTrainModule(nn.Module):
         self._last_mode = (tb, te)
         return loss, correct
 
+    def _augment(self, images: torch.Tensor) -> torch.Tensor:
+        """A training batch through ``train.augment`` (crop + flip, RandAugment, erasing: ``data.augment_finetune``), the draw a
+        function of (aug_seed, current_epoch, step); the batch itself, untouched, when the key is not set.  uint8 batches only:
+        the ops are those of PIL images."""
+        if self.augment is None:
+            return images
+        from .data import augment_finetune, draw_finetune_augment
+        m = self.model.mae
+        images = m._check_images(images).to(m._require_cuda())
+        if images.dtype != torch.uint8:
+            raise ValueError("train.augment works on uint8 pixels (the ops are those of PIL images): serve the batch as uint8")
+        params = draw_finetune_augment(images.shape[0], images.shape[-1], (self.aug_seed, self.current_epoch, self._aug_step), **self.augment)
+        self._aug_step += 1
+        return augment_finetune(images, params)
+
     def _draw_branch_scale(self, batch: int) -> Optional[torch.Tensor]:
         """This step's drop-path table (host), a function of (drop_seed, current_epoch, step); None with rate 0.  With a frozen
         encoder (the linear probe, whose encoder is in inference) the rate is ignored, and said so once."""
@@ -518,6 +584,7 @@ class ViTClassifierTrainModule(nn.Module):
         """training_step + clip + AdamW, all native; returns device (loss, correct).  With mixup / CutMix configured the batch
         is mixed first (the draw is a function of (mix_seed, current_epoch, step)), and ``correct`` -- so the logged
         train_acc -- is counted against the batch's own labels, the first of each mixed pair."""
+        images = self._augment(images)
         scale = self._draw_branch_scale(images.shape[0])
         if self.mixup_alpha > 0 or self.cutmix_alpha > 0:
             from .data import draw_mix_params, mix_batch

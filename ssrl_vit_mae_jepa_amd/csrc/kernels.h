@@ -137,6 +137,10 @@ int launch_reconstruct_compose(const void* images, int img_dt, const float* pred
 int launch_mix_batch(const void* images, int img_dt, const int32_t* partner, const float* lam, const int32_t* box, int B, int C, int S,
                      int out_dt, void* out, hipStream_t s);
 
+// ---- k_augment.hip: crop / flip, RandAugment ops and random erasing of one image per workgroup, the image held in LDS ----------
+int launch_augment_ops_u8(const uint8_t* images, int B, int C, int S, const int32_t* op_codes, const double* op_args, int num_ops,
+                          const int32_t* erase, int out_dt_flags, void* out, hipStream_t s);
+
 // ---- k_normpix.hip: targets standardised per patch (norm_pix_loss); idx is int64 when idx64 != 0, else int32 ---------------------
 // mae_mse_loss with the target (x - mean) * rstd of the image's patches, never materialised; stage-1 partials in scratch (1024+ floats)
 int launch_mse_norm_pix(const float* pred, const void* images, int img_dt, const void* idx, int idx64, int B, int m, int C, int img, int p,

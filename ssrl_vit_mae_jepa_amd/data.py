@@ -475,3 +475,232 @@ def draw_drop_path(depth: int, batch: int, rate: float, gen_or_seed: Union[np.ra
     p_rows = np.repeat(p, 2)[:, None]
     kept = (1.0 / (1.0 - p_rows)).astype(np.float32)
     return torch.from_numpy(np.where(u >= p_rows, kept, np.float32(0.0)).astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# per-image augmentation for fine-tuning (MAE main_finetune.py / timm create_transform: RandomResizedCrop + flip,
+# RandAugment rand-m9-mstd0.5-inc1, RandomErasing p 0.25 in `pixel` mode), applied by the kernel behind mae_augment_ops_u8
+# ---------------------------------------------------------------------------------------------------------------------
+RAND_AUGMENT_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness",
+                    "Sharpness", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")   # timm's _RAND_INCREASING_TRANSFORMS
+AUG_MAX_OPS = 8   # slots of one kernel call, the crop's included
+
+
+class AugParams(NamedTuple):
+    """One batch's draw, host tensors: ``op_codes`` (B, K, 2) int32 (op id, integer argument) and ``op_args`` (B, K, 6) fp64
+    (blend factor in [0], or the affine matrix) with slot 0 the crop + flip and slots 1.. RandAugment; ``erase`` (B, 5) int32
+    (y0, y1, x0, x1, seed; an empty box = not erased), None when the configuration erases nothing (probability 0); ``crop``
+    (B, 5) int32 (top, left, h, w, flip), the boxes slot 0 was made from."""
+    op_codes: torch.Tensor
+    op_args: torch.Tensor
+    erase: Optional[torch.Tensor]
+    crop: torch.Tensor
+
+
+def _fill_word(fill) -> int:
+    r, g, b = (int(v) for v in ((fill,) * 3 if isinstance(fill, (int, float)) else fill))
+    if not all(0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError(f"fill must be bytes, got {fill}")
+    return (r << 16) | (g << 8) | b
+
+
+def affine_arg(mode: int, fill=(128, 128, 128)) -> int:
+    """The integer argument of an AFFINE op, mode | fill << 8 with fill = 0xRRGGBB, as the int32 that holds those bits."""
+    v = (int(mode) & 0xff) | (_fill_word(fill) << 8)
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def rotate_matrix(deg: float, size: int) -> Tuple[float, ...]:
+    """The matrix ``Image.rotate(deg)`` hands to ``transform(AFFINE)``: cos / sin of -radians(deg) rounded to 15 places, the
+    centre (size / 2, size / 2) carried through."""
+    a = -math.radians(deg % 360.0)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    c = size / 2.0
+    m[2] = m[0] * -c + m[1] * -c + m[2]
+    m[5] = m[3] * -c + m[4] * -c + m[5]
+    m[2] += c
+    m[5] += c
+    return tuple(m)
+
+
+def crop_matrix(top: int, left: int, h: int, w: int, flip: bool, size: int) -> Tuple[float, ...]:
+    """The crop box resampled to the full frame as an affine map of output pixel centres (columns mirrored when flipped)."""
+    if flip:
+        return (-w / size, 0.0, float(left + w), 0.0, h / size, float(top))
+    return (w / size, 0.0, float(left), 0.0, h / size, float(top))
+
+
+def rand_augment_slots(which: np.ndarray, applied: np.ndarray, level: np.ndarray, positive: np.ndarray, size: int, fill=(128, 128, 128)):
+    """timm's level functions of the "increasing" transforms for arrays of draws of one shape (``which`` indexes
+    ``RAND_AUGMENT_OPS``, ``level`` in [0, 10]): (..., 2) int32 op ids / integer arguments and (..., 6) fp64 arguments, NONE where
+    ``applied`` is False.  With s = +-1: Rotate s 30 level / 10 degrees; ShearX / ShearY s 0.3 level / 10; TranslateXRel /
+    TranslateYRel s 0.45 level / 10 * size pixels; Posterize 4 - int(4 level / 10) bits; Solarize threshold 256 - int(256 level / 10);
+    SolarizeAdd min(128, int(110 level / 10)); Color / Contrast / Brightness / Sharpness factor max(0.1, 1 + s 0.9 level / 10).
+    Geometric ops resample bicubically (PIL's rounding) and fill with ``fill``.  Only the rotations, whose matrix goes through
+    Python's ``round``, are computed one by one."""
+    from . import _lib as L
+    idx = {n: i for i, n in enumerate(RAND_AUGMENT_OPS)}
+    codes = np.zeros(which.shape + (2,), dtype=np.int32)
+    args = np.zeros(which.shape + (6,), dtype=np.float64)
+    sign = np.where(positive, 1.0, -1.0)
+    geo = affine_arg(L.AUG_BICUBIC, fill)
+    def put(name, code, iarg=0):
+        m = applied & (which == idx[name])
+        codes[m, 0] = code
+        codes[m, 1] = iarg[m] if isinstance(iarg, np.ndarray) else iarg
+        return m
+    put("AutoContrast", L.AUG_AUTOCONTRAST); put("Equalize", L.AUG_EQUALIZE); put("Invert", L.AUG_INVERT)
+    put("Posterize", L.AUG_POSTERIZE, 4 - (4 * level / 10.0).astype(np.int64))
+    put("Solarize", L.AUG_SOLARIZE, 256 - (256 * level / 10.0).astype(np.int64))
+    put("SolarizeAdd", L.AUG_SOLARIZE_ADD, np.minimum(128, (110 * level / 10.0).astype(np.int64)))
+    factor = np.maximum(0.1, 1.0 + sign * 0.9 * level / 10.0)
+    for name, code in (("Color", L.AUG_COLOR), ("Contrast", L.AUG_CONTRAST), ("Brightness", L.AUG_BRIGHTNESS), ("Sharpness", L.AUG_SHARPNESS)):
+        m = put(name, code)
+        args[m, 0] = factor[m]
+    shear, shift = sign * 0.3 * level / 10.0, sign * 0.45 * level / 10.0 * size
+    for name, slot, value in (("ShearX", 1, shear), ("ShearY", 3, shear), ("TranslateXRel", 2, shift), ("TranslateYRel", 5, shift)):
+        m = put(name, L.AUG_AFFINE, geo)
+        args[m, 0] = 1.0; args[m, 4] = 1.0
+        args[m, slot] = value[m]
+    m = put("Rotate", L.AUG_AFFINE, geo)
+    for i in zip(*np.nonzero(m)):
+        args[i] = rotate_matrix(float(sign[i]) * 30.0 * float(level[i]) / 10.0, size)
+    return codes, args
+
+
+def rand_augment_op(name: str, level: float, positive: bool, size: int, fill=(128, 128, 128)):
+    """One RandAugment transform of the "increasing" set at ``level`` in [0, 10] as (op id, integer argument, six fp64 arguments):
+    one entry of ``rand_augment_slots``."""
+    if name not in RAND_AUGMENT_OPS:
+        raise ValueError(f"unknown RandAugment op {name!r}")
+    codes, args = rand_augment_slots(np.array([RAND_AUGMENT_OPS.index(name)]), np.array([True]), np.array([float(level)]),
+                                     np.array([bool(positive)]), size, fill)
+    return int(codes[0, 0]), int(codes[0, 1]), tuple(float(v) for v in args[0])
+
+
+def draw_finetune_augment(batch: int, size: int, gen_or_seed: Union[np.random.Generator, int, Sequence[int]],
+                          crop_scale: Optional[Sequence[float]] = (0.08, 1.0), crop_ratio: Sequence[float] = (3.0 / 4.0, 4.0 / 3.0),
+                          flip: float = 0.5, interpolation: str = "bicubic", num_ops: int = 2, magnitude: float = 9.0, mstd: float = 0.5,
+                          op_prob: float = 0.5, erase_prob: float = 0.25, erase_area: Sequence[float] = (0.02, 1.0 / 3.0),
+                          erase_aspect: Sequence[float] = (0.3, 1.0 / 0.3), fill=(128, 128, 128)) -> AugParams:
+    """One batch's per-image augmentation draw.  Per image:
+      crop   torchvision ``RandomResizedCrop.get_params``: up to ten draws of (area in ``crop_scale`` of the image, log-uniform
+             aspect in ``crop_ratio``), w = round(sqrt(area * aspect)), h = round(sqrt(area / aspect)); the first with
+             0 < w, h <= size is kept with a uniform integer top / left, else the whole image.  ``crop_scale`` None: no crop.
+      flip   with probability ``flip``.  The box is resampled by ``interpolation`` ("bicubic" | "bilinear"), rounded to nearest.
+      RandAugment  ``num_ops`` transforms drawn uniformly with replacement from ``RAND_AUGMENT_OPS``, each applied with
+             probability ``op_prob`` (else NONE) at level clip(N(magnitude, mstd), 0, 10) with a fair random sign
+             (``rand_augment_op``).
+      erase  timm ``RandomErasing``: with probability ``erase_prob`` up to ten draws of (area in ``erase_area`` of the image,
+             log-uniform aspect in ``erase_aspect``), h = round(sqrt(area * aspect)), w = round(sqrt(area / aspect)); the first
+             with h < size and w < size is kept with top in [0, size - h], left in [0, size - w], and one int32 noise seed.
+    ``gen_or_seed`` as in ``draw_mix_params``: the same entropy gives the same draw.  Host arithmetic only."""
+    from . import _lib as L
+    rng = gen_or_seed if isinstance(gen_or_seed, np.random.Generator) else np.random.default_rng(gen_or_seed)
+    B, S, K = int(batch), int(size), int(num_ops)
+    if interpolation not in ("bicubic", "bilinear"):
+        raise ValueError(f"interpolation must be 'bicubic' or 'bilinear', got {interpolation!r}")
+    if not 0 <= K <= AUG_MAX_OPS - 1:
+        raise ValueError(f"num_ops must be in 0..{AUG_MAX_OPS - 1}, got {K}")
+    if not all(0.0 <= p <= 1.0 for p in (flip, op_prob, erase_prob)):
+        raise ValueError("flip / op_prob / erase_prob are probabilities")
+    codes = np.zeros((B, 1 + K, 2), dtype=np.int32)
+    args = np.zeros((B, 1 + K, 6), dtype=np.float64)
+    rows = np.arange(B)
+
+    # crop box + flip -> slot 0
+    top = np.zeros(B, dtype=np.int64); left = np.zeros(B, dtype=np.int64)
+    h = np.full(B, S, dtype=np.int64); w = np.full(B, S, dtype=np.int64)
+    if crop_scale is not None:
+        lo, hi = float(crop_scale[0]), float(crop_scale[1])
+        if not 0.0 < lo <= hi:
+            raise ValueError(f"crop_scale must satisfy 0 < lo <= hi, got {tuple(crop_scale)}")
+        area = S * S * rng.uniform(lo, hi, (B, 10))
+        ar = np.exp(rng.uniform(math.log(crop_ratio[0]), math.log(crop_ratio[1]), (B, 10)))
+        cw = np.round(np.sqrt(area * ar)).astype(np.int64)
+        ch = np.round(np.sqrt(area / ar)).astype(np.int64)
+        ok = (cw > 0) & (cw <= S) & (ch > 0) & (ch <= S)
+        first = np.argmax(ok, axis=1)
+        found = ok.any(axis=1)
+        w = np.where(found, cw[rows, first], S); h = np.where(found, ch[rows, first], S)
+        top = np.floor(rng.random(B) * (S - h + 1)).astype(np.int64)    # randint(0, size - h + 1)
+        left = np.floor(rng.random(B) * (S - w + 1)).astype(np.int64)
+    flipped = rng.random(B) < flip
+    moved = flipped | (h != S) | (w != S)   # the identity box without a flip is the image: nothing to run
+    mode = L.AUG_BICUBIC_ROUND if interpolation == "bicubic" else L.AUG_BILINEAR_ROUND
+    codes[:, 0, 0] = np.where(moved, L.AUG_AFFINE, L.AUG_NONE)
+    codes[:, 0, 1] = np.where(moved, affine_arg(mode, fill), 0)
+    sx = w / S
+    args[:, 0, 0] = np.where(flipped, -sx, sx); args[:, 0, 2] = np.where(flipped, left + w, left).astype(np.float64)
+    args[:, 0, 4] = h / S; args[:, 0, 5] = top.astype(np.float64)
+    args[~moved, 0] = 0.0
+
+    # RandAugment -> slots 1..K
+    if K > 0:
+        which = rng.integers(0, len(RAND_AUGMENT_OPS), (B, K))
+        applied = rng.random((B, K)) < op_prob
+        level = np.clip(rng.normal(magnitude, mstd, (B, K)) if mstd > 0 else np.full((B, K), float(magnitude)), 0.0, 10.0)
+        positive = rng.random((B, K)) < 0.5
+        codes[:, 1:], args[:, 1:] = rand_augment_slots(which, applied, level, positive, S, fill)
+
+    # random erasing
+    erase = None
+    if erase_prob > 0.0:
+        erase = np.zeros((B, 5), dtype=np.int32)
+        chosen = rng.random(B) < erase_prob
+        area = S * S * rng.uniform(erase_area[0], erase_area[1], (B, 10))
+        ar = np.exp(rng.uniform(math.log(erase_aspect[0]), math.log(erase_aspect[1]), (B, 10)))
+        eh = np.round(np.sqrt(area * ar)).astype(np.int64)
+        ew = np.round(np.sqrt(area / ar)).astype(np.int64)
+        ok = (eh < S) & (ew < S) & (eh > 0) & (ew > 0)
+        first = np.argmax(ok, axis=1)
+        found = ok.any(axis=1) & chosen
+        eh, ew = eh[rows, first], ew[rows, first]
+        y0 = np.floor(rng.random(B) * (S - eh + 1)).astype(np.int64)    # randint(0, size - h), both ends included
+        x0 = np.floor(rng.random(B) * (S - ew + 1)).astype(np.int64)
+        seeds = rng.integers(-2 ** 31, 2 ** 31, B)
+        erase[:, 0] = np.where(found, y0, 0); erase[:, 1] = np.where(found, y0 + eh, 0)
+        erase[:, 2] = np.where(found, x0, 0); erase[:, 3] = np.where(found, x0 + ew, 0)
+        erase[:, 4] = np.where(found, seeds, 0)
+    crop = np.stack([top, left, h, w, flipped.astype(np.int64)], axis=1).astype(np.int32)
+    return AugParams(op_codes=torch.from_numpy(codes), op_args=torch.from_numpy(args),
+                     erase=None if erase is None else torch.from_numpy(erase), crop=torch.from_numpy(crop))
+
+
+def augment_finetune(images: torch.Tensor, params: AugParams, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """A uint8 device batch through its draw, by the HIP kernel behind ``mae_augment_ops_u8``: the ops of every image in slot
+    order, then -- with fp32 output -- normalisation and the erase noise.  Returns uint8 when the configuration erases nothing
+    (``params.erase`` is None), so that the batch stays 1 byte per pixel, and normalised fp32 otherwise; ``out_dtype``
+    overrides, except that erasing needs fp32 (normal noise has no byte form).  The draw reaches the device through pinned
+    memory: no host-device synchronisation.  No torch fallback."""
+    from . import _lib
+    from ._lib import check, lib, ptr
+    from .mae import _stream
+    if images.dtype != torch.uint8 or not images.is_cuda or images.dim() != 4 or images.shape[2] != images.shape[3]:
+        raise ValueError(f"augment_finetune needs a square (B, C, S, S) uint8 CUDA batch, got {tuple(images.shape)} {images.dtype} on {images.device}")
+    B, C, S, _ = images.shape
+    K = params.op_codes.shape[1] if params.op_codes.dim() == 3 else -1
+    if params.op_codes.shape != (B, K, 2) or params.op_args.shape != (B, K, 6) or (params.erase is not None and params.erase.shape != (B, 5)):
+        raise ValueError(f"augment_finetune: the parameters are not those of a batch of {B}")
+    if out_dtype is None:
+        out_dtype = torch.uint8 if params.erase is None else torch.float32
+    if out_dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"augment_finetune: out_dtype must be uint8 or float32, got {out_dtype}")
+    if params.erase is not None and out_dtype == torch.uint8:
+        raise ValueError("augment_finetune: random erasing writes normal noise in normalised space and needs float32 output")
+    dev = images.device
+    def up(t: torch.Tensor, dt: torch.dtype) -> torch.Tensor:  # a draw already on the device passes through
+        t = t.to(dt).contiguous()
+        return t.to(dev) if t.is_cuda else t.pin_memory().to(dev, non_blocking=True)
+    flags = _lib.MAE_U8 if out_dtype == torch.uint8 else _lib.MAE_F32
+    if C != 3 and K > 0 and not params.op_codes.is_cuda:
+        ids = params.op_codes[:, :, 0]
+        if bool(((ids == _lib.AUG_NONE) | (ids == _lib.AUG_AFFINE)).all()):
+            flags |= _lib.AUG_GEOMETRIC   # stated only where it is true: anything else is refused by the launcher
+    codes = up(params.op_codes, torch.int32) if K > 0 else None
+    args = up(params.op_args, torch.float64) if K > 0 else None
+    erase = up(params.erase, torch.int32) if params.erase is not None else None
+    images = images.contiguous()
+    out = torch.empty((B, C, S, S), dtype=out_dtype, device=dev)
+    check(lib.mae_augment_ops_u8(ptr(images), B, C, S, ptr(codes), ptr(args), K, ptr(erase), flags, ptr(out), _stream(dev)))
+    return out

@@ -14,11 +14,17 @@ step and the head takes soft targets) and also times `mae_mix_batch` alone (both
 `--drop_path X` trains with stochastic depth at rate X: every fused step of an unfrozen mode draws a (2 * depth, B) scale table on
 the host, uploads it and runs the scaled LayerNorm kernels (the frozen mode ignores the rate; the hand-off has no drop path and is
 not timed then).
+`--augment` trains with the per-image augmentation of the recipe in front (RandomResizedCrop(0.08, 1) + flip, rand-m9-mstd0.5-inc1, random
+erasing 0.25: a host draw and one `mae_augment_ops_u8` launch per step; no hand-off then) and also times that kernel alone on
+draws already on the device -- the crop + flip only (uint8 out) and the whole recipe (fp32 out) -- with the fp64 operations of
+their affine ops (counted from the draw: 12 per output pixel for the coordinates, 77 per channel bicubic, 11 bilinear), and the
+host's milliseconds per draw.
 
     python tools/classifier_bench.py --batch 2000 --steps 10 --warmup 3 --out profiles/r04_classifier_bench.json
     python tools/classifier_bench.py --models vits8 --patch_only --pool mean_patches --timers
     python tools/classifier_bench.py --models vits8 --no-handoff --mix --layer_decay 0.75
     python tools/classifier_bench.py --models vits8 --no-handoff --drop_path 0.1
+    python tools/classifier_bench.py --models vits8 --no-handoff --augment
 """
 from __future__ import annotations
 
@@ -26,6 +32,7 @@ import argparse
 import json
 import statistics
 import sys
+import time
 from pathlib import Path
 
 import torch
@@ -36,6 +43,10 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 from ssrl_vit_mae_jepa_amd.classifier import ViTClassifierTrainModule, encoder_mae  # noqa: E402
+
+
+AUGMENT_RECIPE = {"crop_scale": [0.08, 1.0], "flip": 0.5, "interpolation": "bicubic",
+                  "rand_augment": {"num_ops": 2, "magnitude": 9.0, "mstd": 0.5, "prob": 0.5}, "random_erasing": 0.25, "fill": 128}
 
 
 def timed(fn, steps: int, warmup: int) -> float:
@@ -62,7 +73,7 @@ def set_mode(mod, mode):
 
 def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repeats: int, modes=("frozen", "last1", "full"),
                 handoff: bool = True, patch_only: bool = False, pool=None, timers: bool = False, mix: bool = False,
-                layer_decay: float = 1.0, drop_path: float = 0.0) -> dict:
+                layer_decay: float = 1.0, drop_path: float = 0.0, augment: bool = False) -> dict:
     cfg = yaml.safe_load(cfg_path.read_text())
     mc = dict(cfg["model"], general=dict(cfg["model"]["general"], engine_precision=cfg.get("engine", {}).get("precision", "bf16")))
     if pool is not None:
@@ -72,7 +83,10 @@ def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repe
     mae.encoder.vit.with_cls = not patch_only
     handoff = handoff and not patch_only and mc.get("head", {}).get("pool", "cls") == "cls"  # the hand-off below pools the class token
     handoff = handoff and drop_path == 0.0  # the hand-off has no drop path: not comparable
+    handoff = handoff and not augment  # nor per-image augmentation
     recipe = dict(label_smoothing=0.1, mixup_alpha=0.8, cutmix_alpha=1.0) if mix else {}
+    if augment:
+        recipe["augment"] = AUGMENT_RECIPE
     mod = ViTClassifierTrainModule(pretrained_encoder=mae.encoder.vit, model_cfg=mc,
                                    training_cfg=dict(cfg.get("train", {}), layer_decay=layer_decay, drop_path=drop_path, **recipe)).to(dev)
     S = mc["general"]["image_size"]
@@ -83,7 +97,7 @@ def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repe
     ws_bytes = int(mod.model.workspace(B).numel())
     res = {"model": name, "config": str(cfg_path.relative_to(ROOT)), "batch": B, "precision": m.engine.precision,
            "with_cls": not patch_only, "pool": mod.model.pool_type, "workspace_gib": ws_bytes / 2 ** 30, "mix": mix, "layer_decay": layer_decay,
-           "drop_path": drop_path,
+           "drop_path": drop_path, "augment": augment,
            "ms": {}, "images_per_s": {}}
 
     def fused():
@@ -149,6 +163,35 @@ def bench_model(name: str, cfg_path: Path, B: int, steps: int, warmup: int, repe
         for _r in range(repeats):
             for key in boxes:
                 runs.setdefault(key, []).append(timed(raw(key), steps, warmup))
+    if augment:  # mae_augment_ops_u8 alone, draws already on the device: the crop + flip (uint8 out), then the whole recipe (fp32 out)
+        from ssrl_vit_mae_jepa_amd import _lib
+        from ssrl_vit_mae_jepa_amd.classifier import parse_augment
+        from ssrl_vit_mae_jepa_amd.data import draw_finetune_augment
+        kw = parse_augment(AUGMENT_RECIPE)
+        t0 = time.perf_counter()
+        for i in range(5):
+            full = draw_finetune_augment(B, S, (73, 0, i), **kw)
+        res["augment_host_draw_ms"] = (time.perf_counter() - t0) / 5 * 1e3
+        draws = {"augment_kernel_crop_flip": draw_finetune_augment(B, S, (73, 0, 0), **dict(kw, num_ops=0, erase_prob=0.0)),
+                 "augment_kernel_recipe": full}
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        res["augment_kernel_fp64_gflop"] = {}
+
+        def raw_aug(p):
+            codes, args = p.op_codes.to(dev), p.op_args.to(dev)
+            erase = p.erase.to(dev) if p.erase is not None else None
+            out = torch.empty(images.shape, dtype=torch.uint8 if erase is None else torch.float32, device=dev)
+            return lambda: _lib.check(_lib.lib.mae_augment_ops_u8(images.data_ptr(), B, images.shape[1], S, codes.data_ptr(), args.data_ptr(),
+                                                                  codes.shape[1], erase.data_ptr() if erase is not None else None,
+                                                                  _lib.MAE_U8 if erase is None else _lib.MAE_F32, out.data_ptr(), stream))
+        for key, p in draws.items():
+            affine = p.op_codes[:, :, 0] == _lib.AUG_AFFINE
+            cubic = affine & ((p.op_codes[:, :, 1] & 1) == 1)
+            C = images.shape[1]
+            res["augment_kernel_fp64_gflop"][key] = S * S * (int(affine.sum()) * 12 + int(cubic.sum()) * 77 * C + int((affine & ~cubic).sum()) * 11 * C) / 1e9
+            fn = raw_aug(p)
+            for _r in range(repeats):
+                runs.setdefault(key, []).append(timed(fn, steps, warmup))
     for key, v in runs.items():
         ms = statistics.median(v)
         res["ms"][key] = ms
@@ -174,6 +217,7 @@ def main(argv=None):
     ap.add_argument("--mix", action="store_true", help="mixup 0.8 + CutMix 1.0 + label smoothing 0.1 in the fused step; times the mix kernel too")
     ap.add_argument("--layer_decay", type=float, default=1.0, help="layer-wise learning-rate decay of the fused step (1 = off)")
     ap.add_argument("--drop_path", type=float, default=0.0, help="stochastic depth rate of the fused step (0 = off)")
+    ap.add_argument("--augment", action="store_true", help="crop + flip, RandAugment and random erasing in front of the fused step; times the kernel too")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -182,7 +226,7 @@ def main(argv=None):
     for name in args.models.split(","):
         out["results"].append(bench_model(name, cfgs[name], args.batch, args.steps, args.warmup, args.repeats,
                                               tuple(args.modes.split(",")), not args.no_handoff, args.patch_only, args.pool, args.timers, args.mix,
-                                              args.layer_decay, args.drop_path))
+                                              args.layer_decay, args.drop_path, args.augment))
         torch.cuda.empty_cache()
     text = json.dumps(out, indent=1)
     print(text)
