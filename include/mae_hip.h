@@ -583,6 +583,40 @@ int mae_classifier_head_soft(const void* feats, int32_t dtype, int32_t batch, in
                              float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
                              int64_t scratch_bytes, const int64_t* labels_b, const float* lam, float label_smoothing, void* stream);
 
+/* The linear probe of the MAE paper (A.1, Table 10; I-JEPA's probe is the same): BatchNorm1d(dim, affine=False, eps) over pooled
+ * feature rows, mae_classifier_head on the normalised rows (MAE_F32, seq_len = 1, MAE_POOL_CLS), then LARS on the head.  Additive in
+ * ABI v4; no reference counterpart.
+ *
+ * mae_batchnorm_fwd: x, y (rows, dim) fp32; y may be x itself (exactly in place), a partial overlap is refused.
+ *   training != 0 (torch BatchNorm1d in train mode):
+ *     mean[d] = sum_r x[r][d] / rows;  var[d] = sum_r (x[r][d] - mean[d])^2 / rows (biased);  rstd = 1 / sqrt(var + eps);
+ *     y = (x - mean) * rstd;  running_mean = (1 - momentum) * running_mean + momentum * mean;
+ *     running_var = (1 - momentum) * running_var + momentum * var * rows / (rows - 1) (the unbiased variance).
+ *     rows >= 2.  running_mean and running_var (dim) may both be NULL: statistics are then not tracked.
+ *   training == 0: y = (x - running_mean) / sqrt(running_var + eps); the running buffers are required and only read; rows >= 1;
+ *     scratch is not used and may be NULL.
+ *   mean_out / rstd_out (dim, may be NULL): the statistics y was formed with.
+ *   The variance is centred, in fp32, in two column reductions: sum_r (x - x[0]) gives the mean, sum_r (x - mean)^2 the variance, each
+ *   as row slices into partials that are added in a fixed order (no atomics): the order depends on (rows, dim) alone, so a call is
+ *   bit-identical from run to run.  A constant column gives var == 0 and y == 0 exactly.  x is read three times, y written once.
+ *   Limits, checked before any launch (a refused call launches nothing and writes nothing): dim % 4 == 0, 4 <= dim <= 1024;
+ *   rows * dim < 2^40; 0 <= momentum <= 1; eps >= 0; every buffer 16-byte aligned; scratch_bytes >= mae_batchnorm_scratch_bytes(rows, dim)
+ *   (-1 = rows / dim outside the limits).
+ * mae_lars_step: the LARS of the MAE code base on a plain fp32 buffer of count elements (a multiple of 4, as for
+ *   mae_engine_adamw_buffer; 0 is a no-op), 16-byte aligned:
+ *     adapt = 1 (a weight matrix): dp = grads + weight_decay * params; pn = ||params||_2, un = ||dp||_2;
+ *                                  q = (pn > 0 && un > 0) ? trust_coefficient * pn / un : 1;  dp *= q;
+ *     adapt = 0 (a 1-D tensor: neither weight decay nor the trust ratio): dp = grads;
+ *     then mu = momentum * mu + dp, params -= lr * mu.  No clip coefficient enters: the recipe trains unclipped.
+ *   The norms are two-stage sums in a fixed order (no atomics) and q is formed on the device: nothing synchronises with the host.
+ *   norms_out (2 floats, may be NULL) = pn, un before scaling (with adapt = 0: ||params||, ||grads||).  scratch: >= 4096 floats. */
+int64_t mae_batchnorm_scratch_bytes(int64_t rows, int32_t dim);
+int mae_batchnorm_fwd(const float* x, int64_t rows, int32_t dim, float eps, int32_t training, float momentum,
+                      float* running_mean, float* running_var, float* y, float* mean_out /* may be NULL */,
+                      float* rstd_out /* may be NULL */, void* scratch, int64_t scratch_bytes, void* stream);
+int mae_lars_step(float* params, const float* grads, float* mu, int64_t count, int32_t adapt, float lr, float momentum,
+                  float weight_decay, float trust_coefficient, float* norms_out /* may be NULL */, float* scratch, void* stream);
+
 /* Epilogues of the GEMM family. */
 enum {
   MAE_EPI_NONE  = 0,  /* out = acc (+bias)                                        */

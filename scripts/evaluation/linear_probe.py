@@ -1,0 +1,234 @@
+"""Linear probing of a frozen encoder on cached features: the protocol of the MAE paper (A.1, Table 10) and of I-JEPA --
+BatchNorm1d(affine=False) + Linear trained with LARS (no weight decay, momentum 0.9, no clipping), lr = base * batch / 256.
+
+The train, validation and test features are extracted ONCE (``representation.extract_split_features``); every epoch then runs
+over the cached features (shuffled by a permutation drawn from (seed, epoch), batches gathered on the device), so a 90-epoch
+probe pays one encoder pass instead of ninety.  ``--augment crop`` re-extracts the training features every step from
+RandomResizedCrop + flip images (``data.augment_batch_u8``, parameters drawn from (seed, epoch, step)); validation and test
+features stay cached.
+
+    python -m scripts.evaluation.linear_probe --config configs/vits8_dec192_linprobe.yaml --checkpoint outputs/pretrain/mae_pretrain/checkpoints/last.ckpt
+    python -m scripts.evaluation.linear_probe --config configs/ijepa_vits8.yaml --checkpoint outputs/pretrain/ijepa_pretrain/checkpoints/last.ckpt --encoder target
+    python -m scripts.evaluation.evaluate_classifier --config configs/vits8_dec192_linprobe.yaml --checkpoint outputs/probe/linprobe/checkpoints/best.ckpt
+
+Output tree ``outputs/probe/<suffix>/``: ``logs/metrics.jsonl`` (one line per epoch: train_loss, train_acc, val_loss, val_acc, lr,
+images_per_s), ``checkpoints/{best,last}.ckpt`` (classifier checkpoints with BatchNorm folded into the head, read by
+``train_mae.build_module(classifier_ckpt=...)`` and ``evaluate_classifier`` unchanged), ``checkpoints/probe_last.pt`` (the probe's own
+state: resume with --resume) and ``probe.json`` (test_acc / test_loss at the best validation epoch).  Every hyper-parameter flag
+overrides its ``probe.*`` YAML key.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+import yaml
+
+from ssrl_vit_mae_jepa_amd.data import STL10_DIR, augment_batch_u8, draw_augment_params, get_test_batches, get_train_batches
+from ssrl_vit_mae_jepa_amd.probe import AUGMENTS, PROBE_DEFAULTS, LinearProbe, classifier_pool, parse_probe, probe_lr
+from ssrl_vit_mae_jepa_amd.training import lr_lambda
+
+HYPER_FLAGS = ("total_epochs", "warmup_epochs", "batch_size", "base_learning_rate", "weight_decay", "momentum", "trust_coefficient", "bn_eps",
+               "bn_momentum", "head_init_std", "augment")
+EXTRACT_BATCH = 500   # images per encoder call while extracting
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Linear probe (BatchNorm + Linear, LARS) of a frozen MAE / I-JEPA encoder on cached features")
+    p.add_argument("--config", type=str, default="configs/vits8_dec192_linprobe.yaml")
+    p.add_argument("--checkpoint", type=str, required=True, help="checkpoint path (.ckpt / .pt) or 'random'")
+    p.add_argument("--encoder", type=str, choices=["target", "context"], default="target", help="I-JEPA encoder (default: the EMA target)")
+    p.add_argument("--pool", type=str, choices=["cls", "mean", "mean_all"], default=None, help="feature pool; MAE default cls, I-JEPA mean")
+    p.add_argument("--samples_per_class", type=int, default=None, help="training images per class (default: train.samples_per_class)")
+    p.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic labeled images instead of STL-10")
+    p.add_argument("--max_epochs", type=int, default=None, help="stop after this many epochs (the schedule keeps probe.total_epochs)")
+    p.add_argument("--output_dir_suffix", type=str, default="linprobe")
+    p.add_argument("--resume", type=str, default=None, help="a probe_last.pt to continue from")
+    for key in HYPER_FLAGS:
+        kind = type(PROBE_DEFAULTS[key])
+        if key == "augment":
+            p.add_argument("--augment", type=str, choices=list(AUGMENTS), default=None, help="overrides probe.augment")
+        else:
+            p.add_argument(f"--{key}", type=kind, default=None, help=f"overrides probe.{key} (default {PROBE_DEFAULTS[key]})")
+    return p
+
+
+def parse_args(argv=None):
+    return build_parser().parse_args(argv)
+
+
+def probe_config(cfg: dict, args) -> dict:
+    """``probe:`` of the YAML with every given flag on top, checked."""
+    block = dict(cfg.get("probe") or {})
+    for key in HYPER_FLAGS:
+        if getattr(args, key, None) is not None:
+            block[key] = getattr(args, key)
+    return parse_probe(block)
+
+
+def require_data(synthetic_images) -> None:
+    if synthetic_images is not None:
+        return
+    missing = [n for n in ("train_X.bin", "train_y.bin", "test_X.bin", "test_y.bin") if not (STL10_DIR / n).exists()]
+    if missing:
+        raise SystemExit(f"linear_probe: the labeled STL-10 files ({STL10_DIR}/train_*.bin, test_*.bin) are missing; "
+                         "pass --synthetic_images N to run on synthetic images")
+
+
+def epoch_order(n: int, seed: int, epoch: int) -> np.ndarray:
+    """The epoch's shuffle: a permutation of n drawn from (seed, epoch)."""
+    return np.random.default_rng([int(seed), int(epoch)]).permutation(n)
+
+
+def epoch_batches(n: int, batch: int, seed: int, epoch: int):
+    """Index arrays of the epoch's batches; the last partial batch is used only if it has at least 2 rows."""
+    order = epoch_order(n, seed, epoch)
+    return [order[i:i + batch] for i in range(0, n, batch) if len(order[i:i + batch]) >= 2]
+
+
+def save(path: Path, obj) -> None:
+    tmp = path.with_suffix(path.suffix + ".tmp")
+    torch.save(obj, tmp)
+    os.replace(tmp, path)
+
+
+def _features(enc, images: torch.Tensor, pool: str) -> torch.Tensor:
+    return torch.cat([enc.features(images[i:i + EXTRACT_BATCH], pool=pool, normalize="none") for i in range(0, images.shape[0], EXTRACT_BATCH)])
+
+
+def _evaluate(probe: LinearProbe, feats: torch.Tensor, labels: torch.Tensor, batch: int):
+    loss = torch.zeros((), dtype=torch.float64, device=feats.device)
+    correct = torch.zeros((), dtype=torch.int64, device=feats.device)
+    for i in range(0, feats.shape[0], batch):
+        _, l, c = probe.evaluate(feats[i:i + batch], labels[i:i + batch])
+        loss += l[0].double() * min(batch, feats.shape[0] - i)
+        correct += c[0]
+    n = feats.shape[0]
+    return float(loss) / n, int(correct) / n
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    with open(args.config, "r") as f:
+        cfg = yaml.safe_load(f)
+    try:
+        pcfg = probe_config(cfg, args)
+    except ValueError as exc:
+        raise SystemExit(f"linear_probe: {exc}")
+    model_cfg = cfg["model"]
+    is_ijepa = "predictor" in model_cfg
+    pool = args.pool or ("mean" if is_ijepa else "cls")
+    if is_ijepa and pool == "cls":
+        raise SystemExit("linear_probe: I-JEPA encoders see no class token: --pool must be mean or mean_all")
+    if args.max_epochs is not None and args.max_epochs < 1:
+        raise SystemExit("linear_probe: --max_epochs must be at least 1")
+    if args.checkpoint != "random" and not Path(args.checkpoint).exists():
+        raise SystemExit(f"linear_probe: checkpoint {args.checkpoint} not found")
+    if args.resume is not None and not Path(args.resume).exists():
+        raise SystemExit(f"linear_probe: --resume {args.resume} not found")
+    require_data(args.synthetic_images)
+    if not torch.cuda.is_available():
+        raise SystemExit("linear_probe: the MI355X engine has no CPU fallback")
+    from ssrl_vit_mae_jepa_amd.representation import extract_split_features, load_eval_encoder
+    dev = torch.device("cuda", 0)
+    seed = int(cfg.get("seed", 73))
+    batch = pcfg["batch_size"]
+
+    train_cfg = dict(cfg.get("train") or {}, batch_size=EXTRACT_BATCH)
+    if args.samples_per_class is not None:
+        train_cfg["samples_per_class"] = int(args.samples_per_class)
+    data_cfg = dict(cfg, train=train_cfg, test=dict(cfg.get("test") or {}, batch_size=EXTRACT_BATCH))
+    train_b, val_b = get_train_batches(data_cfg, dev, synthetic_images=args.synthetic_images)
+    train_b.shuffle = False   # the cache keeps the split's order; the probe shuffles the cached rows itself
+    test_b = get_test_batches(data_cfg, dev, synthetic_images=None if args.synthetic_images is None else max(1, args.synthetic_images * 2 // 5))
+
+    precision = cfg.get("engine", {}).get("precision")
+    enc = load_eval_encoder(args.checkpoint, model_cfg, encoder=args.encoder, precision=precision, device=dev)
+    try:
+        classifier_pool(pool, enc.with_cls)
+    except ValueError as exc:
+        raise SystemExit(f"linear_probe: {exc}")
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    crop = pcfg["augment"] == "crop"
+    if crop:   # the training features are re-extracted per step: only the images and labels are kept
+        train_images, train_f, train_y = train_b.images[train_b.idx], None, train_b.labels[train_b.idx]
+    else:
+        train_images, (train_f, train_y) = None, extract_split_features(enc, train_b, pool=pool, normalize="none")
+    val_f, val_y = extract_split_features(enc, val_b, pool=pool, normalize="none")
+    test_f, test_y = extract_split_features(enc, test_b, pool=pool, normalize="none")
+    torch.cuda.synchronize()
+    extract_s = time.perf_counter() - t0
+    n = int(train_y.shape[0])
+    if n < 2 or val_f.shape[0] < 1:
+        raise SystemExit(f"linear_probe: {n} training and {val_f.shape[0]} validation rows are too few")
+    num_classes = int(max(int(train_y.max()), int(val_y.max()), int(test_y.max()))) + 1
+
+    probe = LinearProbe(enc.embed_dim, num_classes, pcfg, seed=seed, device=dev)
+    start_epoch = 0
+    best = dict(val_acc=-1.0, epoch=-1, test_acc=None, test_loss=None)
+    if args.resume is not None:
+        state = torch.load(args.resume, map_location="cpu", weights_only=False)
+        probe.load_state_dict(state)
+        start_epoch = probe.epoch
+        best = dict(state.get("best") or best)   # best.ckpt is replaced only by a better epoch
+    out_dir = Path(cfg.get("logging", {}).get("output_dir_base", "outputs")) / "probe" / args.output_dir_suffix
+    (out_dir / "checkpoints").mkdir(parents=True, exist_ok=True)
+    (out_dir / "logs").mkdir(parents=True, exist_ok=True)
+    (out_dir / "config.yaml").write_text(yaml.safe_dump(dict(cfg, probe=pcfg)))
+    peak = probe_lr(pcfg)
+    end_epoch = pcfg["total_epochs"] if args.max_epochs is None else min(pcfg["total_epochs"], start_epoch + args.max_epochs)
+    metrics = (out_dir / "logs" / "metrics.jsonl").open("a" if args.resume else "w")
+    for epoch in range(start_epoch, end_epoch):
+        lr = peak * lr_lambda(epoch, pcfg["warmup_epochs"], pcfg["total_epochs"])
+        loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+        correct_sum = torch.zeros((), dtype=torch.int64, device=dev)
+        rows = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for step, idx in enumerate(epoch_batches(n, batch, seed, epoch)):
+            j = torch.from_numpy(idx).to(dev)
+            if crop:
+                imgs = train_images[j].contiguous()
+                g = torch.Generator().manual_seed(int(np.random.SeedSequence([seed, epoch, step]).generate_state(1)[0]))
+                feats = _features(enc, augment_batch_u8(imgs, params=draw_augment_params(imgs.shape[0], imgs.shape[2], g)), pool)
+            else:
+                feats = train_f[j]
+            loss, correct = probe.step(feats, train_y[j], lr)
+            loss_sum += loss[0].double() * len(idx)
+            correct_sum += correct[0]
+            rows += len(idx)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        probe.epoch = epoch + 1
+        val_loss, val_acc = _evaluate(probe, val_f, val_y, batch)
+        line = dict(epoch=epoch, train_loss=float(loss_sum) / max(rows, 1), train_acc=int(correct_sum) / max(rows, 1), val_loss=val_loss,
+                    val_acc=val_acc, lr=lr, images_per_s=rows / max(dt, 1e-9))
+        metrics.write(json.dumps(line) + "\n")
+        metrics.flush()
+        print(json.dumps(line))
+        ckpt = probe.classifier_checkpoint(enc, model_cfg, pool, epoch=epoch)
+        save(out_dir / "checkpoints" / "last.ckpt", ckpt)
+        if val_acc > best["val_acc"]:
+            test_loss, test_acc = _evaluate(probe, test_f, test_y, batch)
+            best = dict(val_acc=val_acc, epoch=epoch, test_acc=test_acc, test_loss=test_loss)
+            save(out_dir / "checkpoints" / "best.ckpt", ckpt)
+        save(out_dir / "checkpoints" / "probe_last.pt", dict(probe.state_dict(), best=best))
+    metrics.close()
+    res = dict(checkpoint=args.checkpoint, kind=enc.kind, encoder=enc.encoder, pool=pool, classifier_pool=classifier_pool(pool, enc.with_cls),
+               augment=pcfg["augment"], epochs=end_epoch, train_size=int(n), val_size=int(val_f.shape[0]), test_size=int(test_f.shape[0]),
+               best_epoch=best["epoch"], val_acc=best["val_acc"], test_acc=best["test_acc"], test_loss=best["test_loss"], peak_lr=peak,
+               extract_s=extract_s)
+    (out_dir / "probe.json").write_text(json.dumps(res) + "\n")
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main()

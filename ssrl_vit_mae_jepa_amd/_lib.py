@@ -132,6 +132,9 @@ SIGNATURES = {
     "mae_classifier_head_ex": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mae_classifier_head_soft": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                            _vp, _vp, _f32, _vp]),
+    "mae_batchnorm_scratch_bytes": (_i64, [_i64, _i32]),
+    "mae_batchnorm_fwd": (C.c_int, [_vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mae_lars_step": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "mae_linear_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mae_linear_wgrad_scratch_bytes": (_i64, [_i64, _i32, _i32]),
     "mae_linear_wgrad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

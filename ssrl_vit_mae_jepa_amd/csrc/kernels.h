@@ -152,6 +152,18 @@ int launch_patchify_gather_norm(const void* images, int img_dt, const void* idx,
 int launch_norm_pix_restore(const void* images, int img_dt, const float* pred, const void* idx, int idx64, int B, int m, int C, int img, int p,
                             float* out, hipStream_t s);
 
+// ---- k_probe.hip: the linear probe's BatchNorm1d(affine=False) over feature rows and the LARS step of its head --------------------
+// y = (x - mean) rsqrt(var + eps) per column: training != 0 takes the batch statistics (centred, two column reductions into
+// partials + launch_sum_partials) and updates the running buffers (may both be null); else the running buffers give them.
+// y may be x.  scratch >= batchnorm_scratch_bytes (-1 = outside the limits); mean_out / rstd_out (dim) may be null
+int64_t batchnorm_scratch_bytes(int64_t rows, int dim);
+int launch_batchnorm_fwd(const float* x, int64_t rows, int dim, float eps, int training, float momentum, float* running_mean,
+                         float* running_var, float* y, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, hipStream_t s);
+// dp = adapt ? (g + wd p) q : g, q = trust |p| / |g + wd p| (1 where a norm is 0); mu = momentum mu + dp; p -= lr mu.
+// norms_out (2 floats, may be null) = |p|, |g + wd p|.  scratch >= 4096 floats
+int launch_lars_step(float* p, const float* g, float* mu, int64_t n, int adapt, float lr, float momentum, float wd, float trust,
+                     float* norms_out, float* scratch, hipStream_t s);
+
 // ---- k_loss_optim.hip -----------------------------------------------------------------------------
 // loss[0] = mean((pred-target)^2); d_pred (dt, may be null) = grad_scale*2*(pred-target)/n.  scratch >= 1024+ floats
 int launch_mse(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,
