@@ -168,7 +168,8 @@ int mae_mse_loss_norm_pix(const float* pred, const void* images, int32_t image_d
                           void* d_pred /* may be NULL */, int32_t d_pred_dtype, float* scratch, void* stream);
 
 /* Backward of forward_decoder(forward_encoder(.)) given d_pred (batch, num_mask, P) fp32.
- * Writes (not accumulates) every trainable gradient into grads[0 .. trainable_elems).
+ * Writes (not accumulates) every trainable gradient into grads[0 .. trainable_elems); summing the gradients of several
+ * micro-batches is the caller's sweep with mae_engine_grad_accumulate (below).
  * Requires the workspace of the matching forward calls.  d_x_encoded_extra: optional extra
  * gradient (batch, num_keep, D) fp32 added at the encoder output (NULL on the MAE path): a second consumer of
  * x_encoded, e.g. a probe head trained next to the reconstruction loss. */
@@ -269,6 +270,20 @@ int mae_engine_clip_from_sumsq(mae_engine_t* e, const float* sumsq, float max_no
 int mae_engine_adamw_range(mae_engine_t* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* wcache,
                            float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, const float* stats,
                            int64_t lo, int64_t count, void* stream);
+
+/* Gradient accumulation over micro-batches (additive in ABI v4; Lightning's Trainer(accumulate_grad_batches=A), which the reference's
+ * scripts leave at 1).  Every *_loss_and_grads call WRITES its gradients, so a window of A micro-batches that feeds one optimizer
+ * step keeps a second buffer of the same layout (the stash) and sums into it between the calls:
+ *   dst[lo .. lo+count) = (overwrite ? 0 : dst[lo .. lo+count)) + src[lo .. lo+count)
+ * with exactly one fp32 add per element and no atomics (deterministic).  With overwrite the source is copied bit for bit and dst
+ * is not read.  lo, count: float offsets as in mae_engine_adamw_range, multiples of 4, but into the caller's own buffers (no engine
+ * range bounds them: a gradient arena with its loss slot, a head gradient, ...); count == 0 succeeds without a launch; dst + lo and
+ * src + lo must be 16-byte aligned and the two ranges must not overlap.  All of that is checked before any launch.  One streaming
+ * sweep of 12 bytes per element (8 with overwrite) on a grid of at most MAE_GRAD_ACC_BLOCKS blocks of 256 threads, 4 floats a thread.
+ * The optimizer calls are untouched: an accumulated step and a plain step share them. */
+enum { MAE_GRAD_ACC_BLOCKS = 2048 };
+int mae_engine_grad_accumulate(mae_engine_t* e, float* dst, const float* src, int64_t lo, int64_t count, int32_t overwrite,
+                               void* stream);
 
 /* Downstream classifier (additive in ABI v4): ViTClassifier + ViTClassifierTrainModule of the reference
  * (src/models/classifier.py:47-57, src/training/classifier.py:75-171), i.e. the encoder over EVERY token (timm

@@ -7,6 +7,12 @@ The Lightning Trainer is replaced by the plain loop below (Lightning is not inst
 ``unlabeled_X.bin`` file if present or synthetic 96x96x3 batches (there is no network for the download).
 
     python -m scripts.training.pretrain_mae --config configs/mae.yaml [--resume_from CKPT] [--output_dir_suffix NAME] [--norm_pix_loss]
+                                            [--accumulate_grad_batches N]
+
+--accumulate_grad_batches N (overrides pretrain.accumulate_grad_batches; Lightning's Trainer argument): N consecutive
+micro-batches of pretrain.batch_size feed one optimizer step, so the effective batch -- and the learning-rate scaling -- is
+batch_size x N (configs/vitb16_dec512_accum.yaml: 512 x 8 = 4096, the MAE recipe).  ``global_step``, --max_steps_per_epoch and
+the logged train_loss count optimizer steps; the noise of a window is drawn once for all its rows.
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 -m scripts.training.pretrain_mae ...
 """
 from __future__ import annotations
@@ -21,7 +27,7 @@ import torch
 import yaml
 
 from ssrl_vit_mae_jepa_amd import dist as mdist
-from ssrl_vit_mae_jepa_amd.data import get_pretrain_batches
+from ssrl_vit_mae_jepa_amd.data import accumulation_plan, accumulation_slots, get_pretrain_batches
 from ssrl_vit_mae_jepa_amd.training import MAEPretrainModule
 
 SEED = 73  # setup_reproducibility(seed=73), reference scripts/training/pretrain_mae.py:18
@@ -38,6 +44,8 @@ def parse_args(argv=None):
     parser.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic images instead of STL-10")
     parser.add_argument("--norm_pix_loss", action="store_true",
                         help="regress patches standardised by their own mean and variance (overrides model.general.norm_pix_loss)")
+    parser.add_argument("--accumulate_grad_batches", type=int, default=None,
+                        help="micro-batches per optimizer step (overrides pretrain.accumulate_grad_batches, default 1)")
     return parser.parse_args(argv)
 
 
@@ -47,7 +55,18 @@ def apply_overrides(cfg: dict, args) -> dict:
         model = dict(cfg["model"])
         model["general"] = dict(model.get("general", {}), norm_pix_loss=True)
         cfg = dict(cfg, model=model)
+    if getattr(args, "accumulate_grad_batches", None) is not None:
+        cfg = dict(cfg, pretrain=dict(cfg["pretrain"], accumulate_grad_batches=int(args.accumulate_grad_batches)))
     return cfg
+
+
+def epoch_slots(train_batches, module, max_steps=None):
+    """One epoch's micro-batches as (index in the window, micro-batches of the window, rows of the window over all ranks, rows
+    of the window before this micro-batch), ``max_steps`` windows at the most, and the number of windows (optimizer steps)."""
+    plan = accumulation_plan(train_batches.n_train, module.batch_size, module.accumulate_grad_batches)
+    if max_steps is not None:
+        plan = plan[:max_steps]
+    return accumulation_slots(plan), len(plan)
 
 
 def save_checkpoint(path: Path, module: MAEPretrainModule, epoch: int, weights_only: bool = False, extra=None) -> None:
@@ -107,16 +126,20 @@ def main(argv=None):
         module.current_epoch = epoch
         module.on_train_epoch_start()
         t0, seen, steps, loss_sum = time.perf_counter(), 0, 0, torch.zeros(1, device=dev)
-        for step, sb in enumerate(train_batches(epoch)):
-            if args.max_steps_per_epoch is not None and step >= args.max_steps_per_epoch:
-                break
+        slots, _windows = epoch_slots(train_batches, module, args.max_steps_per_epoch)
+        for (index, count, window_rows, before), sb in zip(slots, train_batches(epoch)):
             # this rank's rows of the global batch (fetched for these rows only) and of the global noise (drawn whole: 145 floats per
-            # image, so that W-GPU masks equal the one-GPU run); a ragged last batch is weighted by the rows each rank holds
-            noise = mdist.global_noise(sb.global_rows, L, SEED, module.global_step, dev)[sb.lo:sb.hi].contiguous()
-            loss = module.fused_training_step(sb.images, noise, global_rows=sb.global_rows)
-            loss_sum += loss  # already the global mean (it rides through the gradient all-reduce)
+            # image, so that W-GPU masks equal the one-GPU run); a ragged last batch is weighted by the rows each rank holds.  The noise
+            # is a function of global_step, which stands still inside a window: it is drawn once for the window's rows, so that a
+            # window is the same step as one batch of that many rows
+            if index == 0:
+                window_noise = mdist.global_noise(window_rows, L, SEED, module.global_step, dev)
+            noise = window_noise[before + sb.lo:before + sb.hi].contiguous()
+            loss = module.fused_training_step(sb.images, noise, global_rows=window_rows, accumulate=(index, count))
             seen += sb.global_rows
-            steps += 1
+            if index == count - 1:
+                loss_sum += loss  # already the window's global mean (it rides through the gradient all-reduce)
+                steps += 1
         # validation (masked-reconstruction MSE, no grad): every rank scores its rows of every batch, the sums are reduced
         val = torch.zeros(2, device=dev, dtype=torch.float64)  # [sum of per-image losses, images]
         with torch.no_grad():

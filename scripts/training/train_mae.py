@@ -23,6 +23,10 @@ Under mixup / CutMix the metrics line's ``train_loss`` is the soft-target loss a
 own label (the first of each mixed pair), so it reads lower than the accuracy on clean images; ``val_*`` stay hard-label.
 
     python -m scripts.training.train_mae --config configs/vits8_dec192_finetune.yaml --encoder_ckpt outputs/pretrain/mae_pretrain/checkpoints/last.ckpt
+
+--accumulate_grad_batches N overrides train.accumulate_grad_batches: N micro-batches of train.batch_size feed one optimizer
+step (the MAE fine-tuning recipe's batch of 1024 on a smaller memory budget); train.learning_rate stays absolute, the mixing,
+drop-path and augmentation draws stay per micro-batch, and --max_steps_per_epoch counts optimizer steps.
 """
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ import torch
 import yaml
 
 from ssrl_vit_mae_jepa_amd.classifier import ViTClassifierTrainModule, checkpoint_with_cls, encoder_mae, load_encoder_weights
-from ssrl_vit_mae_jepa_amd.data import get_train_batches
+from ssrl_vit_mae_jepa_amd.data import accumulation_plan, accumulation_slots, get_train_batches
 from ssrl_vit_mae_jepa_amd.representation import checkpoint_layout, load_ijepa_encoder
 
 SEED = 73
@@ -71,6 +75,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--rand_augment", type=float, nargs=2, default=None, metavar=("N", "M"),
                         help="overrides train.augment.rand_augment.num_ops / magnitude")
     parser.add_argument("--random_erasing", type=float, default=None, help="overrides train.augment.random_erasing (probability, 0 = off)")
+    parser.add_argument("--accumulate_grad_batches", type=int, default=None,
+                        help="micro-batches per optimizer step (overrides train.accumulate_grad_batches, default 1)")
     parser.add_argument("--max_epochs", type=int, default=None)
     parser.add_argument("--max_steps_per_epoch", type=int, default=None)
     parser.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic labeled images instead of STL-10")
@@ -102,11 +108,13 @@ def augment_overrides(args, block):
 
 
 def apply_recipe_flags(cfg: dict, args) -> None:
-    """--label_smoothing / --mixup / --cutmix / --layer_decay / --drop_path into cfg["train"]; a flag that was not given changes nothing."""
+    """--label_smoothing / --mixup / --cutmix / --layer_decay / --drop_path / --accumulate_grad_batches into cfg["train"]; a flag that was not given changes nothing."""
     for flag, key in (("label_smoothing", "label_smoothing"), ("mixup", "mixup_alpha"), ("cutmix", "cutmix_alpha"), ("layer_decay", "layer_decay"),
                       ("drop_path", "drop_path")):
         if getattr(args, flag, None) is not None:
             cfg["train"][key] = float(getattr(args, flag))
+    if getattr(args, "accumulate_grad_batches", None) is not None:
+        cfg["train"]["accumulate_grad_batches"] = int(args.accumulate_grad_batches)
     block = augment_overrides(args, cfg["train"].get("augment"))
     if block is not None:
         cfg["train"]["augment"] = block
@@ -219,13 +227,14 @@ def main(argv=None):
         lr = module.current_lr(epoch)
         t0, seen = time.perf_counter(), 0
         sums = torch.zeros(2, dtype=torch.float64, device=dev)  # [sum of batch-mean loss * rows, correct]
-        for step, (imgs, labels) in enumerate(train_batches(epoch)):
-            if args.max_steps_per_epoch is not None and step >= args.max_steps_per_epoch:
-                break
-            loss, correct = module.fused_training_step(imgs, labels, lr=lr)
-            sums[0] += loss[0].double() * imgs.shape[0]
-            sums[1] += correct[0].double()
-            seen += imgs.shape[0]
+        plan = accumulation_plan(train_batches.n, train_batches.batch, module.accumulate_grad_batches)
+        slots = accumulation_slots(plan if args.max_steps_per_epoch is None else plan[:args.max_steps_per_epoch])
+        for (index, count, window_rows, _before), (imgs, labels) in zip(slots, train_batches(epoch)):
+            loss, correct = module.fused_training_step(imgs, labels, lr=lr, accumulate=(index, count), window_rows=window_rows)
+            if index == count - 1:  # the window's mean loss and its correct count
+                sums[0] += loss[0].double() * window_rows
+                sums[1] += correct[0].double()
+                seen += window_rows
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         val = torch.zeros(2, dtype=torch.float64, device=dev)

@@ -26,6 +26,7 @@ AUG_GEOMETRIC = 0x100  # MAE_AUG_GEOMETRIC, or-ed into out_dtype
 AUG_BILINEAR, AUG_BICUBIC, AUG_BILINEAR_ROUND, AUG_BICUBIC_ROUND = 0, 1, 2, 3  # AFFINE modes
 ABI_VERSION = 4
 NORM_PIX_EPS = 1e-6  # MAE_NORM_PIX_EPS
+GRAD_ACC_BLOCKS = 2048  # MAE_GRAD_ACC_BLOCKS: grid cap of mae_engine_grad_accumulate (256 threads x 4 floats a block: one sweep covers 1024 x this many floats)
 
 
 class MaeConfig(C.Structure):
@@ -90,6 +91,7 @@ SIGNATURES = {
     "mae_engine_grad_sumsq_range": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "mae_engine_clip_from_sumsq": (C.c_int, [_vp, _vp, _f32, _vp, _vp]),
     "mae_engine_adamw_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i64, _vp, _i64, _i64, _vp]),
+    "mae_engine_grad_accumulate": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "mae_engine_classifier_workspace_bytes": (_i64, [_vp, _i32, _i32]),
     "mae_engine_classifier_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mae_engine_classifier_loss_and_grads": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i64,

@@ -27,7 +27,7 @@ from torch import nn
 from . import _lib
 from ._lib import check, lib
 from .mae import MaskedAutoencoder, _ptr, _stream, _ViT
-from .training import lr_lambda
+from .training import AccumulationWindow, lr_lambda
 
 POOLS = {"cls": _lib.POOL_CLS, "mean": _lib.POOL_MEAN, "mean_patches": _lib.POOL_MEAN_PATCHES}
 NO_CLS_POOL = "pool 'cls' needs a class token: I-JEPA encoders are trained on the patch tokens only (use 'mean' or 'mean_patches')"
@@ -264,6 +264,11 @@ class ViTClassifierTrainModule(nn.Module):
         self.drop_seed = 73
         self._drop_step = 0
         self._drop_ignored_said = False
+        self.accumulate_grad_batches = int(self.training_cfg.get("accumulate_grad_batches", 1))  # micro-batches per optimizer step; learning_rate stays absolute
+        if self.accumulate_grad_batches < 1:
+            raise ValueError(f"train.accumulate_grad_batches must be at least 1, got {self.accumulate_grad_batches}")
+        self._window = AccumulationWindow()
+        self._stashes: Dict[str, torch.Tensor] = {}
         self.current_epoch = 0
         self.logged: Dict[str, Any] = {}
         encoder = pretrained_encoder if pretrained_encoder is not None else build_baseline_encoder(self.model_cfg)
@@ -580,26 +585,70 @@ class ViTClassifierTrainModule(nn.Module):
         m.mark_weights_fresh()
         return stats[:2]
 
-    def fused_training_step(self, images: torch.Tensor, labels: torch.Tensor, lr: Optional[float] = None):
+    def _stash_grads(self, into_stash: bool, overwrite: bool = False) -> None:
+        """The window's running sums of the three gradient buffers the optimizer reads: the arena range of the trainable set,
+        ``head_grads`` and, when the embeddings train, ``pos_grads``.  ``into_stash``: stash (+)= live gradients; else live
+        gradients += stash (the micro-batch that closes the window)."""
+        tb, te = self._last_mode
+        m = self.model.mae
+        dev = m._require_cuda()
+        head_g, pos_g = self._grad_buffers()
+        lo, hi = self._arena_range(tb, te)
+        pairs = [("arena", m.flat_grads[lo:hi]), ("head", head_g)] + ([("pos", pos_g)] if te else [])
+        for key, live in pairs:
+            if live.numel() == 0:
+                continue
+            st = self._stashes.get(key)
+            if st is None or st.device != dev or st.numel() != live.numel():
+                if not into_stash:
+                    raise RuntimeError("the trainable set changed inside a window of micro-batches")
+                st = self._stashes[key] = torch.zeros(live.numel(), dtype=torch.float32, device=dev)
+            dst, src = (st, live) if into_stash else (live, st)
+            check(lib.mae_engine_grad_accumulate(m.engine.handle, _ptr(dst), _ptr(src), 0, live.numel(), int(overwrite), _stream(dev)))
+
+    def fused_training_step(self, images: torch.Tensor, labels: torch.Tensor, lr: Optional[float] = None,
+                            accumulate: Optional[Tuple[int, int]] = None, window_rows: Optional[int] = None):
         """training_step + clip + AdamW, all native; returns device (loss, correct).  With mixup / CutMix configured the batch
         is mixed first (the draw is a function of (mix_seed, current_epoch, step)), and ``correct`` -- so the logged
-        train_acc -- is counted against the batch's own labels, the first of each mixed pair."""
+        train_acc -- is counted against the batch's own labels, the first of each mixed pair.
+        ``accumulate=(index, count)`` with ``window_rows`` (the rows of all the window's micro-batches): this batch is
+        micro-batch ``index`` of a window that feeds ONE optimizer step.  Its loss gradient is weighted by rows / window_rows;
+        every micro-batch but the last adds its gradients to a stash and returns its own (loss, correct), the last one adds the
+        stash back, steps, logs train_loss / train_acc once for the window and returns the window's (mean loss, correct).  The
+        augmentation, mixup / CutMix and drop-path draws stay per micro-batch.  None or a count of 1: the plain step."""
+        window = self._window.enter(accumulate, window_rows)
         images = self._augment(images)
-        scale = self._draw_branch_scale(images.shape[0])
+        rows = int(images.shape[0])
+        weight = 1.0 if window is None else rows / float(window_rows)
+        scale = self._draw_branch_scale(rows)
         if self.mixup_alpha > 0 or self.cutmix_alpha > 0:
             from .data import draw_mix_params, mix_batch
-            params = draw_mix_params(images.shape[0], images.shape[-1], (self.mix_seed, self.current_epoch, self._mix_step),
+            params = draw_mix_params(rows, images.shape[-1], (self.mix_seed, self.current_epoch, self._mix_step),
                                      self.mixup_alpha, self.cutmix_alpha, self.mix_prob, self.mix_switch_prob)
             self._mix_step += 1
             m = self.model.mae
             images = m._check_images(images).to(m._require_cuda())
             images, labels, labels_b, lam = mix_batch(images, labels.to(images.device), params)
-            loss, correct = self.loss_and_grads(images, labels, labels_b=labels_b, lam=lam, branch_scale=scale)
+            loss, correct = self.loss_and_grads(images, labels, grad_scale=weight, labels_b=labels_b, lam=lam, branch_scale=scale)
         else:
-            loss, correct = self.loss_and_grads(images, labels, branch_scale=scale)
+            loss, correct = self.loss_and_grads(images, labels, grad_scale=weight, branch_scale=scale)
+        if window is not None:
+            index, count = window
+            if index == 0:  # the window's rows-weighted loss and summed correct, on the device
+                self._win_loss, self._win_correct = loss * weight, correct.clone()
+            else:
+                self._win_loss += loss * weight
+                self._win_correct += correct
+            if index < count - 1:
+                self._stash_grads(into_stash=True, overwrite=index == 0)
+                self._window.advance(index, count)
+                return loss, correct
+            self._stash_grads(into_stash=False)
+            self._window.advance(index, count)
+            loss, correct, rows = self._win_loss, self._win_correct, int(window_rows)
         self.optimizer_step(lr)
         self.log("train_loss", loss[0])
-        self.log("train_acc", correct[0].float() / images.shape[0])
+        self.log("train_acc", correct[0].float() / rows)
         return loss, correct
 
     # ---- checkpoints -------------------------------------------------------------------------------

@@ -1043,6 +1043,22 @@ extern "C" int mae_engine_adamw_range(mae_engine_t* e, float* params, const floa
   return 0;   // the bf16 operand copies of the OTHER ranks' shards and the transposes: mae_engine_refresh_weights after the all-gather
 }
 
+// ---- gradient accumulation over micro-batches (DESIGN section "Gradient accumulation") ---------------------------------------
+// The buffers are the caller's (a gradient arena with its tail, a head or position gradient): no range of the engine bounds them.
+extern "C" int mae_engine_grad_accumulate(mae_engine_t* e, float* dst, const float* src, int64_t lo, int64_t count, int32_t overwrite,
+                                          void* stream) {
+  MAE_REQUIRE(e && dst && src, "mae_engine_grad_accumulate: null argument");
+  MAE_REQUIRE(lo >= 0 && count >= 0 && lo % 4 == 0 && count % 4 == 0, "mae_engine_grad_accumulate: range [%lld, +%lld) is not a multiple of 4",
+              (long long)lo, (long long)count);
+  MAE_REQUIRE(((uintptr_t)(dst + lo) | (uintptr_t)(src + lo)) % 16 == 0, "mae_engine_grad_accumulate: dst + lo and src + lo must be 16-byte aligned");
+  if (count == 0) return 0;
+  MAE_REQUIRE((uintptr_t)(dst + lo + count) <= (uintptr_t)(src + lo) || (uintptr_t)(src + lo + count) <= (uintptr_t)(dst + lo),
+              "mae_engine_grad_accumulate: dst and src overlap");
+  hipStream_t s = (hipStream_t)stream;
+  RUN(TK_OPTIM, 0, count * (overwrite ? 8 : 12), launch_grad_accumulate(dst + lo, src + lo, count, overwrite != 0, s));
+  return 0;
+}
+
 extern "C" int mae_engine_optimizer_step_ema(mae_engine_t* e, float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* wcache,
                                              float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, int64_t step,
                                              float* stats_out, float* scratch, float* target_params, void* target_wcache,

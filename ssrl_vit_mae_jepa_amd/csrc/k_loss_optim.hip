@@ -250,6 +250,28 @@ int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float 
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// gradient accumulation over micro-batches: dst = (OVERWRITE ? 0 : dst) + src, one fp32 add per element, no atomics.
+// 12 bytes per element (8 with OVERWRITE, which never reads dst and copies src bit for bit).  The grid is capped at
+// GRAD_ACC_BLOCKS (256 CUs x 8 blocks of 256 threads) and strides over the rest, 16 bytes per lane.
+// ---------------------------------------------------------------------------------------------------
+template <bool OVERWRITE>
+__global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t n4) {
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const f32x4 s = load4(src + i * 4);
+    store4(dst + i * 4, OVERWRITE ? s : load4(dst + i * 4) + s);
+  }
+}
+
+int launch_grad_accumulate(float* dst, const float* src, int64_t n, bool overwrite, hipStream_t s) {
+  MAE_REQUIRE(dst && src && n > 0 && n % 4 == 0, "grad_accumulate: need n %% 4 == 0 and non-null buffers");
+  const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), GRAD_ACC_BLOCKS);
+  if (overwrite) hipLaunchKernelGGL((grad_accumulate_kernel<true>), dim3(grid), dim3(256), 0, s, dst, src, n / 4);
+  else           hipLaunchKernelGGL((grad_accumulate_kernel<false>), dim3(grid), dim3(256), 0, s, dst, src, n / 4);
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
+
 __global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restrict__ src, bf16* __restrict__ dst, int64_t n4) {
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) store4(dst + i * 4, load4(src + i * 4));
 }

@@ -190,6 +190,9 @@ int launch_clip_from_sumsq(const float* sumsq, float max_norm, float* stats, hip
 int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
                  float wd, float bc1, float bc2, const float* stats, bf16* wbf, hipStream_t s, float* ema_target = nullptr,
                  bf16* ema_wbf = nullptr, int64_t ema_n = 0, float ema_momentum = 0.f);
+// dst[0 .. n) = (overwrite ? 0 : dst) + src: one fp32 add per element, no atomics (gradient accumulation over micro-batches)
+constexpr int GRAD_ACC_BLOCKS = 2048;  // grid cap of the sweep; MAE_GRAD_ACC_BLOCKS of mae_hip.h and GRAD_ACC_BLOCKS of _lib.py
+int launch_grad_accumulate(float* dst, const float* src, int64_t n, bool overwrite, hipStream_t s);
 int launch_f32_to_bf16(const float* src, bf16* dst, int64_t n, hipStream_t s);
 // dst[c][r] = (bf16) src[r][c]
 int launch_transpose_to_bf16(const float* src, bf16* dst, int rows, int cols, hipStream_t s);

@@ -183,6 +183,24 @@ class ShardedBatch:
         self.images, self.global_rows, self.lo, self.hi = images, int(global_rows), int(lo), int(hi)
 
 
+def accumulation_plan(n_rows: int, batch: int, accumulate: int) -> List[List[int]]:
+    """The row counts of one epoch's micro-batches, grouped into the windows that feed one optimizer step each
+    (``accumulate_grad_batches``): ``n_rows`` rows in micro-batches of ``batch``, ``accumulate`` consecutive ones per window.
+    No batch is dropped (src/data.py:86-92) and no window spans epochs, so the last window may hold fewer micro-batches and a
+    short last one.  The loops read a window's row total from here instead of holding its batches back."""
+    n_rows, batch, accumulate = int(n_rows), int(batch), int(accumulate)
+    if n_rows < 0 or batch < 1 or accumulate < 1:
+        raise ValueError(f"accumulation_plan needs n_rows >= 0, batch >= 1 and accumulate >= 1, got {(n_rows, batch, accumulate)}")
+    micro = [min(batch, n_rows - i) for i in range(0, n_rows, batch)]
+    return [micro[i:i + accumulate] for i in range(0, len(micro), accumulate)]
+
+
+def accumulation_slots(plan: List[List[int]]) -> List[Tuple[int, int, int, int]]:
+    """``accumulation_plan`` per micro-batch, in the order a loader serves them: (index in its window, micro-batches of the
+    window, rows of the window, rows of the window before this micro-batch)."""
+    return [(i, len(w), sum(w), sum(w[:i])) for w in plan for i in range(len(w))]
+
+
 def get_pretrain_batches(cfg: dict, device: torch.device, synthetic_images: Optional[int] = None, seed: int = 73, rank: int = 0,
                          world: int = 1) -> Tuple[Callable[[int], Iterator["ShardedBatch"]], Callable[[], Iterator["ShardedBatch"]]]:
     """(train_batches(epoch), val_batches()): iterators of ``ShardedBatch``.  The order of the global batches and their

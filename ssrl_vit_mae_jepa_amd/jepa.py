@@ -332,9 +332,14 @@ class IJEPAPretrainModule(MAEPretrainModule):
 
     def fused_training_step(self, images: torch.Tensor, idx_context: Optional[torch.Tensor] = None, idx_target: Optional[torch.Tensor] = None,
                             lr: Optional[float] = None, momentum: Optional[float] = None, process_group=None,
-                            global_rows: Optional[int] = None) -> torch.Tensor:
+                            global_rows: Optional[int] = None, accumulate: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """``global_rows``: rows of the global batch this step belongs to (see MAEPretrainModule.fused_training_step): the rank's
-        mean loss and gradient are weighted by images.shape[0] / global_rows; a 0-row shard contributes zeros."""
+        mean loss and gradient are weighted by images.shape[0] / global_rows; a 0-row shard contributes zeros.
+        ``accumulate=(index, count)``: micro-batch ``index`` of a window of ``count`` (same semantics as the MAE module;
+        ``global_rows`` = the window's rows).  AdamW and the EMA sweep run once per window, with its last micro-batch.  Masks
+        drawn here are per micro-batch: a caller that wants the window to equal one batch draws them once for the window's rows
+        and passes the slices."""
+        window = self._window.enter(accumulate, global_rows)
         model = self.model
         rows = int(images.shape[0])
         weight = None if global_rows is None else rows / float(global_rows)
@@ -346,8 +351,17 @@ class IJEPAPretrainModule(MAEPretrainModule):
             if idx_context is None or idx_target is None:
                 idx_context, idx_target = model.sample_masks(rows, self.mask_generator)
             compute = lambda scale, events, out: model.loss_and_grads(images, idx_context, idx_target, grad_scale=scale, ready_events=events, loss_out=out)  # noqa: E731
-        loss = self._exchanged_loss_and_grads(compute, process_group, weight)
+        stash = None
+        if window is not None:
+            if window[0] < window[1] - 1:
+                loss = self._stash_micro_batch(compute, weight, window[0])
+                self._window.advance(*window)
+                return loss
+            stash = self._stash()
+        loss = self._exchanged_loss_and_grads(compute, process_group, weight, stash)
         self.optimizer_step(lr, momentum)
+        if window is not None:
+            self._window.advance(*window)
         self.global_step += 1
         self.log("train_loss", loss)
         return loss

@@ -37,6 +37,39 @@ def mask_ratio_at(epoch: int, start: float, end: float, ramp_epochs: int) -> flo
     return start + progress * (end - start)
 
 
+class AccumulationWindow:
+    """Where a training module stands inside a window: up to A consecutive micro-batches that feed one optimizer step
+    (Lightning's ``Trainer(accumulate_grad_batches=A)``).  ``enter`` checks the ``accumulate=(index, count)`` argument of a
+    fused step on the host, before anything is launched; ``advance`` moves on once the micro-batch is enqueued."""
+
+    def __init__(self) -> None:
+        self.next, self.count = 0, 1
+
+    def enter(self, accumulate: Optional[Tuple[int, int]], window_rows: Optional[int]) -> Optional[Tuple[int, int]]:
+        """None for a plain step (``accumulate`` None or a window of one), else (index, count)."""
+        if accumulate is None:
+            if self.next:
+                raise ValueError(f"a window of {self.count} micro-batches is open (next index {self.next}): pass accumulate=(index, count)")
+            return None
+        try:
+            index, count = (int(v) for v in accumulate)
+        except (TypeError, ValueError):
+            raise ValueError(f"accumulate must be (index, count), got {accumulate!r}") from None
+        if count < 1 or not 0 <= index < count:
+            raise ValueError(f"accumulate=(index, count) needs count >= 1 and 0 <= index < count, got {(index, count)}")
+        if index != self.next or (index > 0 and count != self.count):
+            raise ValueError(f"micro-batches of a window arrive in order: expected index {self.next}"
+                             + (f" of {self.count}" if self.next else "") + f", got {(index, count)}")
+        if count == 1:
+            return None
+        if window_rows is None or int(window_rows) < 1:
+            raise ValueError("a window of more than one micro-batch needs its row count (the rows of all its micro-batches, over all ranks)")
+        return index, count
+
+    def advance(self, index: int, count: int) -> None:
+        self.next, self.count = (index + 1) % count, count
+
+
 class MAEPretrainModule(nn.Module):
     """Self-supervised pretraining for Masked Autoencoder (reference API, no Lightning dependency)."""
 
@@ -55,7 +88,12 @@ class MAEPretrainModule(nn.Module):
         self.weight_decay = float(training_cfg.get("weight_decay", 0.05))
         self.warmup_epochs = int(training_cfg.get("warmup_epochs", 20))
         self.total_epochs = int(training_cfg.get("total_epochs", 200))
-        self.batch_size = int(training_cfg.get("batch_size", 512))
+        self.batch_size = int(training_cfg.get("batch_size", 512))  # one micro-batch
+        self.accumulate_grad_batches = int(training_cfg.get("accumulate_grad_batches", 1))  # micro-batches per optimizer step (Lightning's Trainer argument)
+        if self.accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be at least 1, got {self.accumulate_grad_batches}")
+        self._window = AccumulationWindow()
+        self._grad_stash: Optional[torch.Tensor] = None
         self.criterion = torch.nn.MSELoss()
         self.current_epoch = 0
         self.global_step = 0
@@ -96,7 +134,7 @@ class MAEPretrainModule(nn.Module):
 
     @property
     def effective_lr(self) -> float:
-        return self.lr * self.batch_size / 256
+        return self.lr * self.batch_size * self.accumulate_grad_batches / 256  # the batch of one optimizer step
 
     def configure_optimizers(self):
         from torch.optim import AdamW
@@ -168,24 +206,72 @@ class MAEPretrainModule(nn.Module):
             self._comm_stream = torch.cuda.Stream(device=dev)
         return self._bucket_events, self._comm_stream
 
-    def _exchanged_loss_and_grads(self, compute, process_group=None, weight: Optional[float] = None) -> torch.Tensor:
+    # ---- gradient accumulation over the micro-batches of a window ------------------------------------------------------------
+    def _stash(self) -> torch.Tensor:
+        """The window's running sum: a second buffer of ``grad_buffer``'s layout, loss slot included (4 bytes per trainable
+        element, allocated when the first window of more than one micro-batch starts)."""
+        buf = self.model.grad_buffer
+        if self._grad_stash is None or self._grad_stash.device != buf.device or self._grad_stash.numel() != buf.numel():
+            self._grad_stash = torch.zeros_like(buf)
+        return self._grad_stash
+
+    def _accumulate(self, dst: torch.Tensor, src: torch.Tensor, lo: int, hi: int, overwrite: bool = False) -> None:
+        """dst[lo:hi] = (0 if overwrite else dst[lo:hi]) + src[lo:hi] on the current stream.  ``hi`` is rounded up to 4 floats:
+        the range that carries the loss slot ends at n + 1, and the floats behind the slot are padding in both buffers."""
+        model = self.model
+        hi = (hi + 3) // 4 * 4
+        check(lib.mae_engine_grad_accumulate(model.engine.handle, _ptr(dst), _ptr(src), lo, hi - lo, int(overwrite), _stream(model._require_cuda())))
+
+    def _stash_micro_batch(self, compute, weight: float, index: int) -> torch.Tensor:
+        """A micro-batch that does not close its window: native loss + gradients weighted by ``weight`` (its rows / the
+        window's rows over all ranks), summed into the stash with the weighted loss in the stash's loss slot.  No collective, no
+        optimizer step.  Returns the micro-batch's own mean loss (zero from a rank that holds none of its rows)."""
+        model = self.model
+        dev = model._require_cuda()
+        n = model.engine.trainable_elems
+        buf, stash = model.grad_buffer, self._stash()
+        if compute is None:
+            if index == 0:
+                stash.zero_()
+            return torch.zeros(1, dtype=torch.float32, device=dev)
+        loss_slot = buf[n:n + 1]
+        compute(weight, None, loss_slot)
+        own = loss_slot * 1.0
+        loss_slot.mul_(weight)
+        self._accumulate(stash, buf, 0, n + 1, overwrite=index == 0)
+        return own
+
+    def _exchanged_loss_and_grads(self, compute, process_group=None, weight: Optional[float] = None,
+                                  stash: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Run ``compute(grad_scale, ready_events, loss_out)`` (a native loss+grads call) and, with torch.distributed
         initialised, sum the gradient buckets over the ranks as the backward pass finishes them.  Returns the GLOBAL mean
         loss as a device scalar (no host sync); afterwards ``model.flat_grads`` holds the reduced gradients.
         ``weight`` = this rank's share of the global batch (local rows / global rows; default 1 / world, equal shards): the
         local mean loss and its gradient are scaled by it before the sum, so a ragged last batch (the reference never drops
         one, src/data.py:86-92) still yields the global mean.  ``compute`` is None on a rank that holds no row of the batch:
-        it contributes zeros to the same sequence of collectives."""
+        it contributes zeros to the same sequence of collectives.
+        ``stash``: the sum over the earlier micro-batches of the window this call closes (``_stash_micro_batch``); it is added
+        into the buffer before the ranks exchange it -- bucket by bucket on the communication stream in the overlapped path --
+        and ``weight`` is then the share of the WINDOW's rows, applied in a single process too."""
         model = self.model
         dev = model._require_cuda()
         dist = torch.distributed
         world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
-        if world == 1 and not (dist.is_available() and dist.is_initialized() and os.environ.get("MAE_DP_FORCE_EXCHANGE") == "1"):
+        single = world == 1 and not (dist.is_available() and dist.is_initialized() and os.environ.get("MAE_DP_FORCE_EXCHANGE") == "1")
+        if single and stash is None:
             return compute(1.0, None, None)  # (MAE_DP_FORCE_EXCHANGE=1: rehearse the exchange on a one-rank RCCL group)
-        w = 1.0 / world if weight is None else float(weight)
         n = model.engine.trainable_elems
         buf = model.grad_buffer
         loss_slot = buf[n:n + 1]
+        if single:  # the last micro-batch of a window in one process: nothing to exchange, but the window's weight applies
+            if compute is None:
+                buf[:n + 1].zero_()
+            else:
+                compute(float(weight), None, loss_slot)
+                loss_slot.mul_(float(weight))
+            self._accumulate(buf, stash, 0, n + 1)
+            return loss_slot * 1.0
+        w = 1.0 / world if weight is None else float(weight)
         if self.overlap_exchange:
             events, comm = self._exchange_state(dev)
             main = torch.cuda.current_stream(dev)
@@ -202,6 +288,8 @@ class MAEPretrainModule(nn.Module):
                         comm.wait_event(events[j])
                     if compute is not None and b <= n < e:
                         loss_slot.mul_(w)  # the loss was written before this bucket's event (it opens the backward pass): weight it ahead of the sum
+                    if stash is not None:
+                        self._accumulate(buf, stash, b, e)  # the earlier micro-batches' share of this range (and, with the slot, their weighted losses)
                     works.append(dist.all_reduce(buf[b:e], op=dist.ReduceOp.SUM, group=process_group, async_op=True))
                 for wk in works:
                     wk.wait()
@@ -212,6 +300,8 @@ class MAEPretrainModule(nn.Module):
             else:
                 compute(w, None, loss_slot)
                 loss_slot.mul_(w)
+            if stash is not None:
+                self._accumulate(buf, stash, 0, n + 1)
             dist.all_reduce(buf[:n + 1], op=dist.ReduceOp.SUM, group=process_group)
         return loss_slot * 1.0  # sum over ranks of (share x local mean) = the global mean; a copy: the slot is rewritten next step
 
@@ -223,7 +313,8 @@ class MAEPretrainModule(nn.Module):
         world = dist.get_world_size(process_group)
         return world if world > 1 or os.environ.get("MAE_DP_FORCE_EXCHANGE") == "1" else 0
 
-    def _sharded_step(self, compute, process_group, weight: Optional[float], lr: Optional[float], world: int) -> torch.Tensor:
+    def _sharded_step(self, compute, process_group, weight: Optional[float], lr: Optional[float], world: int,
+                      stash: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The data-parallel step with the optimizer sharded over the ranks: every rank owns 1 / world of the
         trainable arena (64-float granules), receives only that slice of the summed gradient (reduce-scatter: half the bytes of
         an all-reduce), adds its slice's sum of squares to the others' (one scalar all-reduce: clip_grad_norm_ needs the norm of
@@ -247,6 +338,8 @@ class MAEPretrainModule(nn.Module):
         else:
             compute(w, None, loss_slot)
             loss_slot.mul_(w)
+        if stash is not None:               # the window's earlier micro-batches, weighted losses in the slot
+            self._accumulate(buf, stash, 0, n + 1)
         loss = loss_slot.clone()            # the slot lies inside the last rank's slice: the loss travels on its own
         dist.all_reduce(loss, op=dist.ReduceOp.SUM, group=process_group)
         loss_slot.zero_()                   # not a gradient: keep it out of the reduce-scatter's last slice
@@ -300,13 +393,20 @@ class MAEPretrainModule(nn.Module):
         self._moments_sharded = None
 
     def fused_training_step(self, images: torch.Tensor, noise: Optional[torch.Tensor] = None, lr: Optional[float] = None,
-                            process_group=None, global_rows: Optional[int] = None) -> torch.Tensor:
+                            process_group=None, global_rows: Optional[int] = None,
+                            accumulate: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """One whole pretrain step.  With torch.distributed initialised every rank computes its rows of the global batch
         with the loss gradient scaled by its share of the batch (``images.shape[0] / global_rows``; 1 / world when
         ``global_rows`` is not given: equal shards), the gradient buckets are summed over RCCL as the backward pass finishes
         them (on a side stream, behind the engine's gradient-ready events), and every rank then applies the same
         global-norm clip + AdamW.  A rank whose shard of a ragged last batch is empty passes a 0-row ``images``.
-        Returns the GLOBAL mean loss as a device scalar (no host sync)."""
+        Returns the GLOBAL mean loss as a device scalar (no host sync).
+        ``accumulate=(index, count)``: this call is micro-batch ``index`` of a window of ``count`` that feeds ONE optimizer step;
+        ``global_rows`` is then the rows of the whole window over all ranks, so the same weight yields the exact mean over the
+        window, ragged micro-batches included.  Every micro-batch but the last only adds its weighted gradients to a stash (no
+        collective, no optimizer step, ``global_step`` unchanged) and returns its own mean loss; the last one adds the stash to its
+        gradients, then exchanges and steps as ever and returns the window's mean loss.  None or a count of 1: the plain step."""
+        window = self._window.enter(accumulate, global_rows)
         model = self.model
         dev = model._require_cuda()
         rows = int(images.shape[0])
@@ -319,12 +419,21 @@ class MAEPretrainModule(nn.Module):
             if noise is None:
                 noise = torch.rand(rows, model.sequence_length, device=dev)
             compute = lambda scale, events, out: model.loss_and_grads(images, noise, grad_scale=scale, ready_events=events, loss_out=out)  # noqa: E731
+        stash = None
+        if window is not None:
+            if window[0] < window[1] - 1:
+                loss = self._stash_micro_batch(compute, weight, window[0])
+                self._window.advance(*window)
+                return loss
+            stash = self._stash()
         sharded = self._sharded_opt_world(process_group)
         if sharded:
-            loss = self._sharded_step(compute, process_group, weight, lr, sharded)
+            loss = self._sharded_step(compute, process_group, weight, lr, sharded, stash)
         else:
-            loss = self._exchanged_loss_and_grads(compute, process_group, weight)
+            loss = self._exchanged_loss_and_grads(compute, process_group, weight, stash)
             self.optimizer_step(lr)
+        if window is not None:
+            self._window.advance(*window)
         self.global_step += 1
         self.log("train_loss", loss)
         return loss
