@@ -736,6 +736,52 @@ int mae_rows_from_tokens(const int32_t* tok32, int32_t batch, int32_t per_image,
 int mae_smooth_l1_loss(const float* pred, const float* target, int64_t n, float grad_scale, float* loss,
                        void* d_pred /* may be NULL */, int32_t d_pred_dtype, float* scratch, void* stream);
 
+/* The kernels only the engine launches, on caller buffers (parity tests and reuse).  Additive in ABI v4.  Each call launches exactly
+ * what the engine launches for the same arguments.  Every check below is made before any launch: a refused call launches nothing
+ * and writes nothing.  dtype arguments are MAE_F32 or MAE_BF16, anything else (MAE_U8 included) is refused.
+ *
+ * mae_full_grad_split: the embedding gradient of a full sequence in one pass over dx (batch, seq_len, dim) fp32.
+ *   with_cls = 1 (row 0 of every image is the class token):
+ *     dtok (batch, seq_len, dim) in dtype = dx (MAE_BF16: rounded to nearest even), row 0 of every image +0.0;
+ *     dpos (seq_len, dim) fp32: dpos[t][d] = sum_b dx[b][t][d];  dcls (dim) fp32 = dpos[0], bit for bit.
+ *   with_cls = 0 (patch-only sequence: seq_len patch rows, row t is token t + 1): dtok = dx, no row zeroed;
+ *     dpos holds (seq_len + 1, dim) floats: dpos[t + 1][d] = sum_b dx[b][t][d], dpos[0] = +0.0;  dcls = +0.0.
+ *   The sum runs over S = mae_full_grad_split_partial_floats / (seq_len * dim) batch slices [batch * s / S, batch * (s + 1) / S),
+ *   each in ascending order, and the slices' partials are then added in a fixed order (no atomics): bit-identical from run to run.
+ *   S = max(1, min(batch, 64, ceil(2048 / ceil(seq_len * (dim / 4) / 256)))).
+ *   partial: scratch of >= mae_full_grad_split_partial_floats(batch, seq_len, dim) floats (-1 = arguments outside the limits).
+ *   Limits: dim % 4 == 0, 4 <= dim <= 1024, batch * seq_len < 2^31, no NULL buffer.  Buffers 16-byte aligned.
+ * mae_zero_token_rows: +0.0 in every row r of dres (fp32) and dres_c (dtype), both (rows, dim), with r % seq_len != 0; the rows
+ *   r % seq_len == 0 (the class tokens) keep their bits.  rows need not be a multiple of seq_len.  dim as above.
+ * mae_features_pool: out (batch, dim) fp32 from x_mid (fp32) and branch (branch_dtype), both (batch, seq_len, dim):
+ *     v = fl32(x_mid + branch);  y[t] = LayerNorm(v[t]; gamma, beta, eps) in fp32 (biased variance, 1 / sqrt(var + eps));
+ *     f = sum_{t in [row_lo, row_hi)} y[t] / (row_hi - row_lo);  normalize = MAE_FEAT_L2: out = f / (||f||_2 + 1e-8), else out = f.
+ *   One block per image; wave w of four adds rows row_lo + w, row_lo + w + 4, ... and the four sums are added in wave order, so an
+ *   image's result does not depend on batch.  Only the pooled rows are read.  Limits: dim as above, 0 <= row_lo < row_hi <= seq_len.
+ * mae_cast: dst[i] = src[i] converted, i < n: fp32 -> bf16 rounds to nearest even (a NaN stays a quiet NaN), bf16 -> fp32 is
+ *   exact, equal types copy.  n > 0.
+ * mae_add_rows_pos: out[r] = fl32(x[r] + pos[r % seq_len]) for r < rows; x, out (rows, dim), pos (seq_len, dim) fp32.
+ *   dim % 4 == 0, dim >= 4.
+ * mae_add_into: dst[i] (dst_dtype) = fl32(dst[i] + src[i]) (MAE_BF16: dst widened, the fp32 sum rounded to nearest even); src fp32.
+ * mae_linear_dgrad: out[M,K] = dY[M,N] * W[N,K] -- the input gradient of torch.nn.functional.linear -- by the exact-fp32 tiled
+ *   kernel for every dtype: one fmaf chain over n = 0 .. N - 1 in ascending order per output (bf16 operands widened), then
+ *     MAE_EPI_NONE: out = acc;  MAE_EPI_DGELU: out = acc * gelu_erf'(aux[m][k]);  MAE_EPI_MUL: out = acc * aux[m][k];
+ *   any other epilogue is refused.  dY, W in dtype; out and aux (M, K) in out_dtype; fp32 operands with a bf16 output are refused.
+ *   The engine launches it with fp32 operands only (bf16 dgrads go through mae_linear_fwd's kernels on a transposed weight copy).
+ *   M <= 64 * 65535. */
+int64_t mae_full_grad_split_partial_floats(int32_t batch, int32_t seq_len, int32_t dim);
+int mae_full_grad_split(const float* dx, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls, int32_t dtype, void* dtok,
+                        float* dpos, float* dcls, float* partial, void* stream);
+int mae_zero_token_rows(int64_t rows, int32_t seq_len, int32_t dim, int32_t dtype, float* dres, void* dres_c, void* stream);
+int mae_features_pool(const float* x_mid, const void* branch, int32_t branch_dtype, const float* gamma, const float* beta, float eps,
+                      int32_t batch, int32_t seq_len, int32_t dim, int32_t row_lo, int32_t row_hi, int32_t normalize, float* out,
+                      void* stream);
+int mae_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream);
+int mae_add_rows_pos(const float* x, const float* pos, int64_t rows, int32_t seq_len, int32_t dim, float* out, void* stream);
+int mae_add_into(const float* src, void* dst, int32_t dst_dtype, int64_t n, void* stream);
+int mae_linear_dgrad(const void* dY, const void* W, int64_t M, int32_t N, int32_t K, int32_t dtype, int32_t epilogue,
+                     int32_t out_dtype, void* out, const void* aux, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,14 @@ SIGNATURES = {
     "mae_build_tail_row_map": (C.c_int, [_i32, _i32, _i32, _vp, _vp]),
     "mae_rows_from_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "mae_smooth_l1_loss": (C.c_int, [_vp, _vp, _i64, _f32, _vp, _vp, _i32, _vp, _vp]),
+    "mae_full_grad_split": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mae_full_grad_split_partial_floats": (_i64, [_i32, _i32, _i32]),
+    "mae_zero_token_rows": (C.c_int, [_i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mae_features_pool": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_cast": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp]),
+    "mae_add_rows_pos": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "mae_add_into": (C.c_int, [_vp, _vp, _i32, _i64, _vp]),
+    "mae_linear_dgrad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

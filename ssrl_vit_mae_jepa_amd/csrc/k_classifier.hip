@@ -370,7 +370,9 @@ __global__ void __launch_bounds__(256) zero_token_rows_kernel(int64_t rows, int 
 }
 
 int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, void* dres_c, hipStream_t s) {
-  MAE_REQUIRE(dres && dres_c && rows > 0 && L > 0 && D % 4 == 0 && D <= 1024, "zero_token_rows: bad arguments");
+  MAE_REQUIRE(dres && dres_c && rows > 0 && L > 0, "zero_token_rows: bad arguments");
+  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "zero_token_rows: D = %d must be a multiple of 4 in [4, 1024]", D);
+  MAE_REQUIRE(act == MAE_F32 || act == MAE_BF16, "zero_token_rows: dtype must be MAE_F32 or MAE_BF16 (got %d)", act);
   const int rpb = D / 4 <= 64 ? 4 : 2;
   const int grid = (int)std::min<int64_t>(cdiv(rows, rpb), 8192);
   if (act == MAE_BF16)
@@ -423,7 +425,9 @@ int full_grad_split_slices(int B, int L, int D) {
 }
 
 int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s) {
-  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && L > 0 && D % 4 == 0 && D <= 1024, "full_grad_split: bad arguments");
+  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && L > 0, "full_grad_split: bad arguments");
+  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "full_grad_split: D = %d must be a multiple of 4 in [4, 1024]", D);
+  MAE_REQUIRE(dt == MAE_F32 || dt == MAE_BF16, "full_grad_split: dtype must be MAE_F32 or MAE_BF16 (got %d)", dt);
   MAE_REQUIRE((int64_t)B * L < (1ll << 31), "full_grad_split: B * L < 2^31");
   const int S = full_grad_split_slices(B, L, D);
   const dim3 grid((unsigned)cdiv((int64_t)L * (D / 4), 256), S);
@@ -440,7 +444,9 @@ int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* d
 // The patch-only sibling: dx is (B, N, D) with row t = patch token t + 1.  Same slices and summation order; the sums land in
 // rows 1..N of dpos ((N + 1) * D floats), and row 0 of dpos and dcls (D floats) -- no token carries them -- become exact zeros.
 int launch_patch_grad_split(const float* dx, int B, int N, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s) {
-  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && N > 0 && D % 4 == 0 && D <= 1024, "patch_grad_split: bad arguments");
+  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && N > 0, "patch_grad_split: bad arguments");
+  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "patch_grad_split: D = %d must be a multiple of 4 in [4, 1024]", D);
+  MAE_REQUIRE(dt == MAE_F32 || dt == MAE_BF16, "patch_grad_split: dtype must be MAE_F32 or MAE_BF16 (got %d)", dt);
   MAE_REQUIRE((int64_t)B * N < (1ll << 31), "patch_grad_split: B * N < 2^31");
   const int S = full_grad_split_slices(B, N, D);
   const dim3 grid((unsigned)cdiv((int64_t)N * (D / 4), 256), S);
@@ -558,4 +564,20 @@ extern "C" int mae_classifier_head_soft(const void* feats, int32_t dtype, int32_
   const mae::HeadSoft soft{labels_b, lam, label_smoothing};
   return mae::classifier_head_impl("mae_classifier_head_soft", true, feats, dtype, batch, seq_len, dim, with_cls, pool, head, num_classes, labels,
                                    grad_scale, logits, loss_out, correct_out, head_grads, d_feats, scratch, scratch_bytes, stream, &soft);
+}
+
+// single-kernel entries (parity tests): the engine-only kernels of this file, see mae_hip.h
+extern "C" int64_t mae_full_grad_split_partial_floats(int32_t batch, int32_t seq_len, int32_t dim) {
+  if (batch <= 0 || seq_len <= 0 || dim < 4 || dim > 1024 || dim % 4 != 0 || (int64_t)batch * seq_len >= (1ll << 31)) return -1;
+  return (int64_t)mae::full_grad_split_slices(batch, seq_len, dim) * seq_len * dim;
+}
+
+extern "C" int mae_full_grad_split(const float* dx, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls, int32_t dtype, void* dtok,
+                                   float* dpos, float* dcls, float* partial, void* stream) {
+  if (with_cls) return mae::launch_full_grad_split(dx, batch, seq_len, dim, dtype, dtok, dpos, dcls, partial, (hipStream_t)stream);
+  return mae::launch_patch_grad_split(dx, batch, seq_len, dim, dtype, dtok, dpos, dcls, partial, (hipStream_t)stream);
+}
+
+extern "C" int mae_zero_token_rows(int64_t rows, int32_t seq_len, int32_t dim, int32_t dtype, float* dres, void* dres_c, void* stream) {
+  return mae::launch_zero_token_rows(rows, seq_len, dim, dtype, dres, dres_c, (hipStream_t)stream);
 }

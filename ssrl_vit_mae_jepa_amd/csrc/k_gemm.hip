@@ -121,6 +121,7 @@ static int check_epi(const Epi& e, int dt, const char* who) {
   MAE_REQUIRE((e.mode != MAE_EPI_RESID && e.mode != MAE_EPI_DGELU && e.mode != MAE_EPI_MUL) || e.aux, "%s: epilogue needs aux", who);
   MAE_REQUIRE(e.mode != MAE_EPI_RESID || e.out_dt == MAE_F32, "%s: RESID epilogue writes fp32", who);
   MAE_REQUIRE(dt == MAE_F32 || dt == MAE_BF16, "%s: bad dtype %d", who, dt);
+  MAE_REQUIRE(e.out_dt == MAE_F32 || e.out_dt == MAE_BF16, "%s: bad output dtype %d", who, e.out_dt);
   MAE_REQUIRE(!(dt == MAE_F32 && e.out_dt == MAE_BF16), "%s: fp32 operands with bf16 output unsupported", who);
   return 0;
 }
@@ -280,6 +281,14 @@ extern "C" int mae_linear_fwd(const void* A, const void* W, const float* bias, i
   mae::Epi e;
   e.mode = epilogue; e.bias = bias; e.aux = aux_or_resid; e.out = out; e.out2 = out2; e.out_dt = out_dtype;
   return mae::launch_linear_fwd(A, W, M, N, K, dtype, e, (hipStream_t)stream);
+}
+
+// single-kernel entry (parity tests): the input gradient of a Linear as every engine backward launches it, see mae_hip.h
+extern "C" int mae_linear_dgrad(const void* dY, const void* W, int64_t M, int32_t N, int32_t K, int32_t dtype, int32_t epilogue,
+                                int32_t out_dtype, void* out, const void* aux, void* stream) {
+  mae::Epi e;
+  e.mode = epilogue; e.aux = aux; e.out = out; e.out_dt = out_dtype;
+  return mae::launch_linear_dgrad(dY, W, M, N, K, dtype, e, (hipStream_t)stream);
 }
 
 extern "C" int64_t mae_linear_wgrad_pair_scratch_bytes(int64_t M, int32_t N0, int32_t K0, int32_t N1, int32_t K1) {

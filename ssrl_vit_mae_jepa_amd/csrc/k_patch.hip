@@ -376,6 +376,8 @@ __global__ void __launch_bounds__(256) cast_kernel(const S* __restrict__ src, D_
 
 int launch_cast(const void* src, int src_dt, void* dst, int dst_dt, int64_t n, hipStream_t s) {
   MAE_REQUIRE(src && dst && n > 0, "cast: bad arguments");
+  MAE_REQUIRE((src_dt == MAE_F32 || src_dt == MAE_BF16) && (dst_dt == MAE_F32 || dst_dt == MAE_BF16),
+              "cast: dtypes must be MAE_F32 or MAE_BF16 (got %d -> %d)", src_dt, dst_dt);
   const int grid = (int)std::min<int64_t>(cdiv(n, 256), 256 * 16);
   if (src_dt == MAE_F32 && dst_dt == MAE_BF16)
     hipLaunchKernelGGL((cast_kernel<float, bf16>), dim3(grid), dim3(256), 0, s, (const float*)src, (bf16*)dst, n);
@@ -400,7 +402,8 @@ __global__ void add_rows_pos_kernel(const float* __restrict__ x, const float* __
   }
 }
 int launch_add_rows_pos(const float* x, const float* pos, int64_t rows, int L, int D, float* out, hipStream_t s) {
-  MAE_REQUIRE(x && pos && out && rows > 0 && L > 0 && D % 4 == 0, "add_rows_pos: bad arguments");
+  MAE_REQUIRE(x && pos && out && rows > 0 && L > 0, "add_rows_pos: bad arguments");
+  MAE_REQUIRE(D % 4 == 0 && D >= 4, "add_rows_pos: D = %d must be a positive multiple of 4", D);
   const int grid = (int)std::min<int64_t>(cdiv(rows * (D / 4), 256), 256 * 16);
   hipLaunchKernelGGL(add_rows_pos_kernel, dim3(grid), dim3(256), 0, s, x, pos, rows, L, D / 4, out);
   MAE_LAUNCH_CHECK();
@@ -415,6 +418,7 @@ __global__ void add_into_kernel(const float* __restrict__ src, T* __restrict__ d
 }
 int launch_add_into(const float* src, void* dst, int dst_dt, int64_t n, hipStream_t s) {
   MAE_REQUIRE(src && dst && n > 0, "add_into: bad arguments");
+  MAE_REQUIRE(dst_dt == MAE_F32 || dst_dt == MAE_BF16, "add_into: dtype must be MAE_F32 or MAE_BF16 (got %d)", dst_dt);
   const int grid = (int)std::min<int64_t>(cdiv(n, 256), 256 * 16);
   if (dst_dt == MAE_BF16) hipLaunchKernelGGL((add_into_kernel<bf16>), dim3(grid), dim3(256), 0, s, src, (bf16*)dst, n);
   else hipLaunchKernelGGL((add_into_kernel<float>), dim3(grid), dim3(256), 0, s, src, (float*)dst, n);
@@ -500,4 +504,17 @@ extern "C" int mae_decoder_assemble_bwd(const float* dx, const int32_t* inv, int
 extern "C" int mae_zero_unpredicted_rows(const int32_t* inv, int64_t rows, int32_t seq_len, int32_t num_pred, int32_t dim, int32_t dtype,
                                          float* dres, void* dres_c, void* stream) {
   return mae::launch_zero_unpredicted_rows(inv, rows, seq_len, num_pred, dim, dtype, dres, dres_c, (hipStream_t)stream);
+}
+
+// single-kernel entries (parity tests): the engine-only element kernels of this file, see mae_hip.h
+extern "C" int mae_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream) {
+  return mae::launch_cast(src, src_dtype, dst, dst_dtype, n, (hipStream_t)stream);
+}
+
+extern "C" int mae_add_rows_pos(const float* x, const float* pos, int64_t rows, int32_t seq_len, int32_t dim, float* out, void* stream) {
+  return mae::launch_add_rows_pos(x, pos, rows, seq_len, dim, out, (hipStream_t)stream);
+}
+
+extern "C" int mae_add_into(const float* src, void* dst, int32_t dst_dtype, int64_t n, void* stream) {
+  return mae::launch_add_into(src, dst, dst_dtype, n, (hipStream_t)stream);
 }

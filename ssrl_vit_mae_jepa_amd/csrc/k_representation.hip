@@ -79,6 +79,7 @@ int launch_features_pool(const float* x_mid, const void* branch, int branch_dt, 
   MAE_REQUIRE(x_mid && branch && gamma && beta && out && B > 0 && seq > 0, "features_pool: bad arguments");
   MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "features_pool: D = %d must be a multiple of 4 in [4, 1024]", D);
   MAE_REQUIRE(row_lo >= 0 && row_lo < row_hi && row_hi <= seq, "features_pool: rows [%d, %d) outside the sequence of %d", row_lo, row_hi, seq);
+  MAE_REQUIRE(branch_dt == MAE_F32 || branch_dt == MAE_BF16, "features_pool: branch dtype must be MAE_F32 or MAE_BF16 (got %d)", branch_dt);
   if (branch_dt == MAE_BF16)
     hipLaunchKernelGGL(features_pool_kernel<bf16>, dim3(B), dim3(256), 0, s, x_mid, (const bf16*)branch, gamma, beta, eps, seq, D, row_lo, row_hi, normalize, out);
   else
@@ -327,6 +328,15 @@ int launch_knn_vote(const float* sim, const int64_t* idx, int64_t Q, int k_strid
 }
 
 }  // namespace mae
+
+// single-kernel entry (parity tests): the pooling kernel of mae_engine_extract_features on caller buffers, see mae_hip.h
+extern "C" int mae_features_pool(const float* x_mid, const void* branch, int32_t branch_dtype, const float* gamma, const float* beta, float eps,
+                                 int32_t batch, int32_t seq_len, int32_t dim, int32_t row_lo, int32_t row_hi, int32_t normalize, float* out,
+                                 void* stream) {
+  MAE_REQUIRE(normalize == MAE_FEAT_NONE || normalize == MAE_FEAT_L2, "mae_features_pool: normalize must be MAE_FEAT_NONE or MAE_FEAT_L2 (got %d)", normalize);
+  return mae::launch_features_pool(x_mid, branch, branch_dtype, gamma, beta, eps, batch, seq_len, dim, row_lo, row_hi, normalize, out,
+                                   (hipStream_t)stream);
+}
 
 extern "C" int64_t mae_knn_scratch_bytes(int64_t num_queries, int64_t bank_size, int32_t dim, int32_t k) {
   return mae::knn_scratch_bytes(num_queries, bank_size, dim, k);
