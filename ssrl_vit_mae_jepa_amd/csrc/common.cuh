@@ -43,6 +43,13 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t round_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 inline size_t dtype_size(int dt) { return dt == MAE_BF16 ? 2 : 4; }
 
+// a kernel gets 64 KiB of dynamic LDS by default: a launch that asks for more raises the kernel's limit first
+template <class K>
+int allow_lds(K kernel, size_t lds) {
+  if (lds > 64 * 1024) MAE_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return 0;
+}
+
 // ---- device conversions --------------------------------------------------------------------
 __device__ __forceinline__ float to_f(float x) { return x; }
 __device__ __forceinline__ float to_f(bf16 x) { return (float)x; }
@@ -53,6 +60,9 @@ template <> __device__ __forceinline__ bf16 from_f<bf16>(float x) { return (bf16
 // uint8 pixel -> ToTensor + Normalize(.5, .5): (u8 / 255 - 0.5) / 0.5 with an IEEE-rounded division, bit-identical to the torch
 // fp32 expression (src/data.py:15-24); every kernel that reads raw pixels uses this one expression
 __device__ __forceinline__ float norm_u8(unsigned u) { return (__fdiv_rn((float)u, 255.0f) - 0.5f) / 0.5f; }
+// one pixel of either image format as the float the model sees
+__device__ __forceinline__ float px_value(const float* p) { return *p; }
+__device__ __forceinline__ float px_value(const uint8_t* p) { return norm_u8(*p); }
 
 // 4-wide vector load/store in either activation type
 __device__ __forceinline__ f32x4 load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }

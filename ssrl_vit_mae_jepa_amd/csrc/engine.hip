@@ -421,10 +421,9 @@ static int check_image_dtype(int dt, const char* who) {
 static int forward_encoder_impl(const Ctx& c, const Plan& pl, const void* images, int img_dt, float* x_encoded_out) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   const int32_t* keep32 = c.buf<int32_t>(pl.keep32);
-  if (img_dt == MAE_U8)  // whole image rows through LDS: every pixel byte is fetched once
-    RUN(TK_DATA, 0, (int64_t)pl.B * e->C * e->img * e->img + pl.Me * e->P * c.as, launch_gather_patches_u8((const uint8_t*)images, keep32, pl.B, pl.k, e->C, e->img, e->p, c.act, c.buf<>(pl.patchA), s));
-  else
-    RUN(TK_DATA, 0, pl.Me * e->P * (4 + c.as), launch_gather_patches((const float*)images, keep32, pl.B, pl.k, e->C, e->img, e->p, c.act, c.buf<>(pl.patchA), s));
+  // bytes read: uint8 images go whole through LDS (every pixel byte is fetched once), float images give up their kept patches only
+  const int64_t gather_read = img_dt == MAE_U8 ? (int64_t)pl.B * e->C * e->img * e->img : pl.Me * e->P * 4;
+  RUN(TK_DATA, 0, gather_read + pl.Me * e->P * c.as, launch_gather_patches(images, img_dt, keep32, pl.B, pl.k, e->C, e->img, e->p, c.act, c.buf<>(pl.patchA), s));
   MAE_TRY(linear(c, c.buf<>(pl.patchA), e->i_patch_w, e->i_patch_b, pl.Me, e->D, e->P, MAE_EPI_NONE, MAE_F32, c.buf<>(pl.enc_x[0]), nullptr, nullptr));
   RUN(TK_DATA, 0, pl.Me * e->D * 12, launch_assemble_visible(c.buf<float>(pl.enc_x[0]), keep32, c.P(e->i_cls), c.P(e->i_pos), pl.Me, e->D, s));
   for (int i = 0; i < e->depth; ++i)
@@ -832,10 +831,8 @@ static int loss_and_grads_impl(mae_engine_t* e, const float* params, const void*
   MAE_TRY(forward_decoder_impl(c, pl, nullptr));
   if (e->cfg.norm_pix_loss)
     RUN(TK_LOSS, 0, pl.Mp * e->P * (4 + c.as) + pl.Mp * e->P * (image_dtype == MAE_U8 ? 1 : 4), launch_mse_norm_pix(c.buf<float>(pl.pred), images, image_dtype, c.buf<int32_t>(pl.mask32), 0, batch, pl.m, e->C, e->img, e->p, grad_scale, loss_out, c.buf<>(pl.dpred), e->act, c.buf<float>(pl.loss_scratch), s));
-  else if (image_dtype == MAE_U8)
-    RUN(TK_LOSS, 0, pl.Mp * e->P * (4 + c.as) + (int64_t)batch * e->C * e->img * e->img, launch_mse_from_images_u8(c.buf<float>(pl.pred), (const uint8_t*)images, c.buf<int32_t>(pl.mask32), batch, pl.m, e->C, e->img, e->p, grad_scale, loss_out, c.buf<>(pl.dpred), e->act, c.buf<float>(pl.loss_scratch), s));
-  else
-    RUN(TK_LOSS, 0, pl.Mp * e->P * (8 + c.as), launch_mse_from_images(c.buf<float>(pl.pred), (const float*)images, c.buf<int32_t>(pl.mask32), batch, pl.m, e->C, e->img, e->p, grad_scale, loss_out, c.buf<>(pl.dpred), e->act, c.buf<float>(pl.loss_scratch), s));
+  else  // image bytes counted: the whole uint8 batch (band walk), the masked patches of a float one
+    RUN(TK_LOSS, 0, pl.Mp * e->P * (4 + c.as) + (image_dtype == MAE_U8 ? (int64_t)batch * e->C * e->img * e->img : pl.Mp * e->P * 4), launch_mse_from_images(c.buf<float>(pl.pred), images, image_dtype, c.buf<int32_t>(pl.mask32), batch, pl.m, e->C, e->img, e->p, grad_scale, loss_out, c.buf<>(pl.dpred), e->act, c.buf<float>(pl.loss_scratch), 0, s));
   return backward_impl(c, pl);
 }
 

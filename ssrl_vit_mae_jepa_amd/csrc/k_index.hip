@@ -47,22 +47,11 @@ __global__ void idx_to_i32_kernel(const int64_t* __restrict__ src, int32_t* __re
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     dst[i] = (int32_t)src[i];
 }
-__global__ void idx_to_i64_kernel(const int32_t* __restrict__ src, int64_t* __restrict__ dst, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = src[i];
-}
 
 int launch_idx_to_i32(const int64_t* src, int32_t* dst, int64_t n, hipStream_t s) {
   MAE_REQUIRE(src && dst && n > 0, "idx_to_i32: bad arguments");
   const int grid = (int)std::min<int64_t>(cdiv(n, 256), 2048);
   hipLaunchKernelGGL(idx_to_i32_kernel, dim3(grid), dim3(256), 0, s, src, dst, n);
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-int launch_idx_to_i64(const int32_t* src, int64_t* dst, int64_t n, hipStream_t s) {
-  MAE_REQUIRE(src && dst && n > 0, "idx_to_i64: bad arguments");
-  const int grid = (int)std::min<int64_t>(cdiv(n, 256), 2048);
-  hipLaunchKernelGGL(idx_to_i64_kernel, dim3(grid), dim3(256), 0, s, src, dst, n);
   MAE_LAUNCH_CHECK();
   return 0;
 }

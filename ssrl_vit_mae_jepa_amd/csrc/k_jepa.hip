@@ -168,25 +168,13 @@ __global__ void __launch_bounds__(256) smooth_l1_kernel(const float* __restrict_
   acc = block_sum_256(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
-__global__ void __launch_bounds__(256) mean_finalize_l1_kernel(const float* __restrict__ partial, int nb, float inv_n, float* __restrict__ out) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) acc += partial[i];
-  acc = block_sum_256(acc, red);
-  if (threadIdx.x == 0) out[0] = acc * inv_n;
-}
 int launch_smooth_l1(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred, int dpred_dt,
                      float* scratch, hipStream_t s) {
   MAE_REQUIRE(pred && target && loss && scratch && n > 0 && n % 4 == 0, "smooth_l1: need n %% 4 == 0 and non-null buffers");
   const int64_t n4 = n / 4;
   const int grid = (int)std::min<int64_t>(cdiv(n4, 256), 1024);
   const float gs = grad_scale / (float)n;
-  if (!d_pred) hipLaunchKernelGGL((smooth_l1_kernel<float, false>), dim3(grid), dim3(256), 0, s, pred, target, n4, gs, scratch, (float*)nullptr);
-  else if (dpred_dt == MAE_BF16) hipLaunchKernelGGL((smooth_l1_kernel<bf16, true>), dim3(grid), dim3(256), 0, s, pred, target, n4, gs, scratch, (bf16*)d_pred);
-  else hipLaunchKernelGGL((smooth_l1_kernel<float, true>), dim3(grid), dim3(256), 0, s, pred, target, n4, gs, scratch, (float*)d_pred);
-  MAE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mean_finalize_l1_kernel, dim3(1), dim3(256), 0, s, scratch, grid, 1.0f / (float)n, loss);
-  MAE_LAUNCH_CHECK();
+  MAE_LAUNCH_LOSS(smooth_l1_kernel, (), grid, 0, s, d_pred, dpred_dt, scratch, 1.0f / (float)n, loss, pred, target, n4, gs);
   return 0;
 }
 

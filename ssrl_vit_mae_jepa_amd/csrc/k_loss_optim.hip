@@ -1,11 +1,11 @@
-// Masked-pixel MSE loss (+ its gradient), global grad-norm clip and AdamW.  All HBM-bound streaming kernels.
+// MSE loss against a materialised target (+ its gradient; the loss read straight from the image is in k_pixels.hip), the second stage
+// of every loss, global grad-norm clip and AdamW.  All HBM-bound streaming kernels.
 // Reference behaviour:
 //   mse            == torch.nn.MSELoss() mean reduction                     (src/training/mae.py:40,48)
 //   grad_norm      == torch.nn.utils.clip_grad_norm_(params, 1.0, L2)       (scripts/training/pretrain_mae.py:124-125)
 //   adamw          == torch.optim.AdamW(lr, betas=(.9,.999), eps=1e-8, weight_decay) single group
 //                                                                          (src/training/mae.py:59-65)
 #include "kernels.h"
-#include <cstdlib>
 
 namespace mae {
 
@@ -24,38 +24,6 @@ __global__ void __launch_bounds__(256) mse_kernel(const float* __restrict__ pred
     const f32x4 d = load4(pred + i * 4) - load4(target + i * 4);
     acc += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
     if (HAS_GRAD) store4(dpred + i * 4, d * gscale);
-  }
-  acc = block_sum_256(acc, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-
-// target read straight from the image: element e of row r=(b,j) is (py, px, c) of patch mask[b][j]-1.
-// One thread per (row, py, px/VP): C-channel pixels for VP consecutive px.
-template <class T, bool HAS_GRAD>
-__global__ void __launch_bounds__(256) mse_images_kernel(const float* __restrict__ pred,
-                                                         const float* __restrict__ images,
-                                                         const int32_t* __restrict__ mask32, int64_t rows, int m, int C,
-                                                         int img, int p, float gscale, float* __restrict__ partial,
-                                                         T* __restrict__ dpred) {
-  __shared__ float red[4];
-  const int g = img / p, pp = p * p;
-  const int64_t total = rows * pp;
-  float acc = 0.f;
-  for (int64_t u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
-    const int64_t r = u / pp;
-    const int q = (int)(u - r * pp);
-    const int py = q / p, px = q - py * p;
-    const int64_t b = r / m;
-    int n = mask32[r] - 1;
-    n = n < 0 ? 0 : (n >= g * g ? g * g - 1 : n);   // the clamp of band_tokens and patchify_gather_kernel: the variants agree on every id
-    const int ph = n / g, pw = n - ph * g;
-    const float* src = images + (b * C * (int64_t)img + (ph * p + py)) * img + pw * p + px;
-    const int64_t o = r * (int64_t)(pp * C) + q * C;
-    for (int c = 0; c < C; ++c) {
-      const float d = pred[o + c] - src[(int64_t)c * img * img];
-      acc += d * d;
-      if (HAS_GRAD) dpred[o + c] = from_f<T>(d * gscale);
-    }
   }
   acc = block_sum_256(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
@@ -83,49 +51,8 @@ int launch_mse(const float* pred, const float* target, int64_t n, float grad_sca
   const int64_t n4 = n / 4;
   const int grid = (int)std::min<int64_t>(cdiv(n4, 256), RED_BLOCKS);
   const float gs = grad_scale * 2.0f / (float)n;
-  if (!d_pred)
-    hipLaunchKernelGGL((mse_kernel<float, false>), dim3(grid), dim3(256), 0, s, pred, target, n4, gs, scratch, (float*)nullptr);
-  else if (dpred_dt == MAE_BF16)
-    hipLaunchKernelGGL((mse_kernel<bf16, true>), dim3(grid), dim3(256), 0, s, pred, target, n4, gs, scratch, (bf16*)d_pred);
-  else
-    hipLaunchKernelGGL((mse_kernel<float, true>), dim3(grid), dim3(256), 0, s, pred, target, n4, gs, scratch, (float*)d_pred);
-  MAE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, s, scratch, grid, 1.0f / (float)n, loss);
-  MAE_LAUNCH_CHECK();
+  MAE_LAUNCH_LOSS(mse_kernel, (), grid, 0, s, d_pred, dpred_dt, scratch, 1.0f / (float)n, loss, pred, target, n4, gs);
   return 0;
-}
-
-// the per-pixel gather: any patch size, any alignment
-int launch_mse_from_images_gather(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img,
-                                  int p, float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch,
-                                  hipStream_t s) {
-  MAE_REQUIRE(pred && images && mask32 && loss && scratch && B > 0 && m > 0 && p > 0 && img % p == 0, "mse_from_images: bad arguments");
-  const int64_t rows = (int64_t)B * m;
-  const int64_t n = rows * p * p * C;
-  const int grid = (int)std::min<int64_t>(cdiv(rows * p * p, 256), RED_BLOCKS);
-  const float gs = grad_scale * 2.0f / (float)n;
-  if (!d_pred)
-    hipLaunchKernelGGL((mse_images_kernel<float, false>), dim3(grid), dim3(256), 0, s, pred, images, mask32, rows, m, C, img, p, gs, scratch, (float*)nullptr);
-  else if (dpred_dt == MAE_BF16)
-    hipLaunchKernelGGL((mse_images_kernel<bf16, true>), dim3(grid), dim3(256), 0, s, pred, images, mask32, rows, m, C, img, p, gs, scratch, (bf16*)d_pred);
-  else
-    hipLaunchKernelGGL((mse_images_kernel<float, true>), dim3(grid), dim3(256), 0, s, pred, images, mask32, rows, m, C, img, p, gs, scratch, (float*)d_pred);
-  MAE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, s, scratch, grid, 1.0f / (float)n, loss);
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_mse_from_images(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img,
-                           int p, float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch,
-                           hipStream_t s) {
-  MAE_REQUIRE(pred && images && mask32 && loss && scratch && B > 0 && m > 0 && p > 0 && img % p == 0, "mse_from_images: bad arguments");
-  {
-    static const bool band = [] { const char* v = getenv("MAE_MSE_BAND"); return !v || v[0] != '0'; }();   // MAE_MSE_BAND=0: the per-pixel gather (A/B)
-    const int r = band ? launch_mse_from_images_band_f32(pred, images, mask32, B, m, C, img, p, grad_scale, loss, d_pred, dpred_dt, scratch, s) : -1;
-    if (r >= 0) return r;
-  }
-  return launch_mse_from_images_gather(pred, images, mask32, B, m, C, img, p, grad_scale, loss, d_pred, dpred_dt, scratch, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -284,23 +211,6 @@ int launch_f32_to_bf16(const float* src, bf16* dst, int64_t n, hipStream_t s) {
   return 0;
 }
 
-// 32x32 LDS-tiled transpose + cast: dst[c][r] = src[r][c]
-__global__ void __launch_bounds__(256) transpose_bf16_kernel(const float* __restrict__ src, bf16* __restrict__ dst, int rows,
-                                                             int cols) {
-  __shared__ float tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-  for (int i = ty; i < 32; i += 8) {
-    const int r = r0 + i, c = c0 + tx;
-    tile[i][tx] = (r < rows && c < cols) ? src[(int64_t)r * cols + c] : 0.f;
-  }
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8) {
-    const int c = c0 + i, r = r0 + tx;
-    if (c < cols && r < rows) dst[(int64_t)c * rows + r] = (bf16)tile[tx][i];
-  }
-}
-
 // every GEMM weight in ONE launch: the matrix table travels as a kernel argument (<= 64 entries); block b finds its matrix
 // by a scan over the cumulative tile counts.  64 x 64 tiles (TransposeTable::TILE): rows are read as float4 (256 B per row of a tile)
 // and the transposed rows written as 4 bf16 per thread (128 B = one line per row of a tile); 32 x 32 tiles with 4-byte reads and
@@ -350,33 +260,9 @@ int launch_transpose_many(const float* params, bf16* tbase, const TransposeTable
   return 0;
 }
 
-int launch_transpose_to_bf16(const float* src, bf16* dst, int rows, int cols, hipStream_t s) {
-  MAE_REQUIRE(src && dst && rows > 0 && cols > 0, "transpose_to_bf16: bad arguments");
-  hipLaunchKernelGGL(transpose_bf16_kernel, dim3((int)cdiv(cols, 32), (int)cdiv(rows, 32)), dim3(256), 0, s, src, dst, rows, cols);
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
 }  // namespace mae
 
 extern "C" int mae_mse_loss(const float* pred, const float* target, int64_t n, float grad_scale, float* loss,
                             float* d_pred, float* scratch, void* stream) {
   return mae::launch_mse(pred, target, n, grad_scale, loss, d_pred, MAE_F32, scratch, (hipStream_t)stream);
-}
-
-extern "C" int mae_mse_loss_from_images(const float* pred, const void* images, int32_t image_dtype, const int32_t* mask32, int32_t batch,
-                                        int32_t num_mask, int32_t in_chans, int32_t image_size, int32_t patch_size, float grad_scale, float* loss,
-                                        void* d_pred, int32_t d_pred_dtype, float* scratch, int32_t path, void* stream) {
-  MAE_REQUIRE(image_dtype == MAE_F32 || image_dtype == MAE_U8, "mae_mse_loss_from_images: image_dtype must be MAE_F32 or MAE_U8 (got %d)", image_dtype);
-  MAE_REQUIRE(path == 0 || (path == 1 && image_dtype == MAE_F32), "mae_mse_loss_from_images: path must be 0, or 1 with MAE_F32 images (got %d)", path);
-  MAE_REQUIRE(in_chans > 0 && patch_size > 0, "mae_mse_loss_from_images: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  if (image_dtype == MAE_U8)
-    return mae::launch_mse_from_images_u8(pred, (const uint8_t*)images, mask32, batch, num_mask, in_chans, image_size, patch_size, grad_scale, loss,
-                                          d_pred, d_pred_dtype, scratch, s);
-  if (path == 1)
-    return mae::launch_mse_from_images_gather(pred, (const float*)images, mask32, batch, num_mask, in_chans, image_size, patch_size, grad_scale,
-                                              loss, d_pred, d_pred_dtype, scratch, s);
-  return mae::launch_mse_from_images(pred, (const float*)images, mask32, batch, num_mask, in_chans, image_size, patch_size, grad_scale, loss,
-                                     d_pred, d_pred_dtype, scratch, s);
 }

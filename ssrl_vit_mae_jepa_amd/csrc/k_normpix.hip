@@ -20,9 +20,6 @@ namespace {
 
 constexpr int NP_WAVES = 4;   // waves (= tokens in flight) per workgroup of 256
 
-__device__ __forceinline__ float px_value(const float* p) { return *p; }
-__device__ __forceinline__ float px_value(const uint8_t* p) { return norm_u8(*p); }
-
 // 1 / sqrt(v), v > 0, to within an ulp: IEEE sqrt and division, then one Newton step on the residual 1 - v r^2 formed without
 // rounding (the product v r is split into head and tail).  v = fp32(1e-6) gives exactly 1000.
 __device__ __forceinline__ float rsqrt_refined(float v) {
@@ -167,29 +164,6 @@ int check_geometry(const char* who, const void* images, int img_dt, const void* 
   return 0;
 }
 
-template <class K>
-int allow_lds(K kernel, size_t lds) {
-  if (lds > 64 * 1024) MAE_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return 0;
-}
-
-template <class IMG>
-int mse_norm_pix_typed(const float* pred, const IMG* images, const void* idx, int idx64, int64_t rows, int m, int C, int img, int p, float gs,
-                       void* d_pred, int dpred_dt, float* scratch, int grid, size_t lds, hipStream_t s) {
-  if (!d_pred) {
-    MAE_TRY(allow_lds(mse_norm_pix_kernel<IMG, float, false>, lds));
-    hipLaunchKernelGGL((mse_norm_pix_kernel<IMG, float, false>), dim3(grid), dim3(256), lds, s, pred, images, idx, idx64, rows, m, C, img, p, gs, scratch, (float*)nullptr);
-  } else if (dpred_dt == MAE_BF16) {
-    MAE_TRY(allow_lds(mse_norm_pix_kernel<IMG, bf16, true>, lds));
-    hipLaunchKernelGGL((mse_norm_pix_kernel<IMG, bf16, true>), dim3(grid), dim3(256), lds, s, pred, images, idx, idx64, rows, m, C, img, p, gs, scratch, (bf16*)d_pred);
-  } else {
-    MAE_TRY(allow_lds(mse_norm_pix_kernel<IMG, float, true>, lds));
-    hipLaunchKernelGGL((mse_norm_pix_kernel<IMG, float, true>), dim3(grid), dim3(256), lds, s, pred, images, idx, idx64, rows, m, C, img, p, gs, scratch, (float*)d_pred);
-  }
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
 }  // namespace
 
 int launch_mse_norm_pix(const float* pred, const void* images, int img_dt, const void* idx, int idx64, int B, int m, int C, int img, int p,
@@ -203,9 +177,13 @@ int launch_mse_norm_pix(const float* pred, const void* images, int img_dt, const
   const int grid = (int)std::min<int64_t>(cdiv(rows, NP_WAVES), 1024);  // stage-1 partials: scratch holds 1024 floats + 8
   const float gs = grad_scale * 2.0f / (float)n;
   const size_t lds = (size_t)C * p * p * 4 * NP_WAVES;
-  if (img_dt == MAE_U8) MAE_TRY(mse_norm_pix_typed(pred, (const uint8_t*)images, idx, idx64, rows, m, C, img, p, gs, d_pred, dpred_dt, scratch, grid, lds, s));
-  else MAE_TRY(mse_norm_pix_typed(pred, (const float*)images, idx, idx64, rows, m, C, img, p, gs, d_pred, dpred_dt, scratch, grid, lds, s));
-  return launch_mean_finalize(scratch, grid, 1.0f / (float)n, loss, s);
+  if (img_dt == MAE_U8)
+    MAE_LAUNCH_LOSS(mse_norm_pix_kernel, (uint8_t,), grid, lds, s, d_pred, dpred_dt, scratch, 1.0f / (float)n, loss, pred, (const uint8_t*)images, idx, idx64,
+                    rows, m, C, img, p, gs);
+  else
+    MAE_LAUNCH_LOSS(mse_norm_pix_kernel, (float,), grid, lds, s, d_pred, dpred_dt, scratch, 1.0f / (float)n, loss, pred, (const float*)images, idx, idx64,
+                    rows, m, C, img, p, gs);
+  return 0;
 }
 
 int launch_patchify_gather_norm(const void* images, int img_dt, const void* idx, int idx64, int B, int m, int C, int img, int p, float* target,

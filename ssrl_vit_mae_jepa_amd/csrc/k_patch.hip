@@ -1,67 +1,13 @@
-// Pixel <-> token data movement: visible-patch gather (im2col of the kept patches only), token assembly
-// (cls / position table), decoder scatter with mask tokens, target patchify-gather.  All HBM-bound.
+// Token-row data movement: token assembly (cls / position table), decoder scatter with mask tokens, and their adjoints.  All
+// HBM-bound.  (The kernels that read the image -- gather_patches, patchify_gather, the pixel loss -- are in k_pixels.hip.)
 // Reference behaviour:
 //   gather_patches + patch GEMM + assemble_visible == timm PatchEmbed conv (k = s = patch) -> cat(cls) -> +pos_embed
 //     -> gather(idx_keep)           (lightly MaskedVisionTransformerTIMM.preprocess, via src/models/mae.py:55)
 //   decoder_assemble == repeat_token(mask_token) -> set_at_index(idx_keep, x_decode) -> + decoder_pos_embed
 //                                   (src/models/mae.py:61-71)
-//   patchify_gather == utils.patchify + get_at_index(clamp(idx_mask-1, 0))   (src/models/mae.py:90-92)
 #include "kernels.h"
 
 namespace mae {
-
-// ---------------------------------------------------------------------------------------------------
-// visible-patch gather: row (b,j) <- patch tok[b][j]-1 in conv-weight order (c, py, px)
-// ---------------------------------------------------------------------------------------------------
-template <class T, int VEC>
-__global__ void __launch_bounds__(256) gather_patches_kernel(const float* __restrict__ images,
-                                                             const int32_t* __restrict__ tok, int64_t rows, int k,
-                                                             int C, int img, int p, T* __restrict__ out) {
-  const int g = img / p;
-  const int pv = p / VEC;                 // vector units per patch row
-  const int units_per_row = C * p * pv;   // per token row
-  const int64_t total = rows * units_per_row;
-  for (int64_t u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
-    const int64_t r = u / units_per_row;
-    int rem = (int)(u - r * units_per_row);
-    const int c = rem / (p * pv);
-    rem -= c * p * pv;
-    const int py = rem / pv;
-    const int px = (rem - py * pv) * VEC;
-    const int t = tok[r];
-    const int64_t b = r / k;
-    T* dst = out + r * (int64_t)(C * p * p) + (c * p + py) * p + px;
-    if (t <= 0) {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) dst[i] = from_f<T>(0.f);
-    } else {
-      const int n = t - 1, ph = n / g, pw = n - ph * g;
-      const float* src = images + ((b * C + c) * (int64_t)img + (ph * p + py)) * img + pw * p + px;
-      if (VEC == 4) {
-        store4(dst, load4(src));
-      } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) dst[i] = from_f<T>(src[i]);
-      }
-    }
-  }
-}
-
-int launch_gather_patches(const float* images, const int32_t* tok, int B, int k, int C, int img, int p, int dt,
-                          void* out, hipStream_t s) {
-  MAE_REQUIRE(images && tok && out && B > 0 && k > 0, "gather_patches: bad arguments");
-  MAE_REQUIRE(p > 0 && img % p == 0, "gather_patches: image_size %d not divisible by patch_size %d", img, p);
-  const int64_t rows = (int64_t)B * k;
-  const bool vec = (p % 4 == 0) && (img % 4 == 0);
-  const int64_t units = rows * C * p * (vec ? p / 4 : p);
-  const int grid = (int)std::min<int64_t>(cdiv(units, 256), 256 * 16);
-#define GP(T, V) hipLaunchKernelGGL((gather_patches_kernel<T, V>), dim3(grid), dim3(256), 0, s, images, tok, rows, k, C, img, p, (T*)out)
-  if (dt == MAE_BF16) { if (vec) GP(bf16, 4); else GP(bf16, 1); }
-  else                { if (vec) GP(float, 4); else GP(float, 1); }
-#undef GP
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
 
 // x[r] = (t == 0 ? cls : x[r]) + pos[t], fp32 in place, D % 4 == 0
 __global__ void __launch_bounds__(256) assemble_visible_kernel(float* __restrict__ x, const int32_t* __restrict__ tok,
@@ -323,52 +269,6 @@ int launch_decoder_assemble_bwd(const float* dx, const int32_t* inv, const int32
   return launch_sum_partials(partial, G, Dd, d_mask_token, nullptr, Dd, s);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// pixel targets: target[(b,j)][(py*p + px)*C + c] = images[b][c][ph*p+py][pw*p+px], patch = max(mask-1, 0)
-// one thread per (row, py, px): reads C strided pixels, writes C contiguous floats
-// ---------------------------------------------------------------------------------------------------
-template <class I>
-__global__ void __launch_bounds__(256) patchify_gather_kernel(const float* __restrict__ images,
-                                                              const I* __restrict__ mask32, int64_t rows, int m,
-                                                              int C, int img, int p, float* __restrict__ target) {
-  const int g = img / p, pp = p * p;
-  const int64_t total = rows * pp;
-  for (int64_t u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
-    const int64_t r = u / pp;
-    const int q = (int)(u - r * pp);
-    const int py = q / p, px = q - py * p;
-    const int64_t b = r / m;
-    int n = (int)mask32[r] - 1;
-    n = n < 0 ? 0 : (n >= g * g ? g * g - 1 : n);
-    const int ph = n / g, pw = n - ph * g;
-    const float* src = images + (b * C * (int64_t)img + (ph * p + py)) * img + pw * p + px;
-    float* dst = target + r * (int64_t)(pp * C) + q * C;
-    for (int c = 0; c < C; ++c) dst[c] = src[(int64_t)c * img * img];
-  }
-}
-
-int launch_patchify_gather(const float* images, const int32_t* mask32, int B, int m, int C, int img, int p,
-                           float* target, hipStream_t s) {
-  MAE_REQUIRE(images && mask32 && target && B > 0 && m > 0, "patchify_gather: bad arguments");
-  MAE_REQUIRE(p > 0 && img % p == 0, "patchify: image_size %d not divisible by patch_size %d", img, p);
-  const int64_t rows = (int64_t)B * m;
-  const int grid = (int)std::min<int64_t>(cdiv(rows * p * p, 256), 256 * 16);
-  hipLaunchKernelGGL((patchify_gather_kernel<int32_t>), dim3(grid), dim3(256), 0, s, images, mask32, rows, m, C, img, p, target);
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_patchify_gather_i64(const float* images, const int64_t* mask64, int B, int m, int C, int img, int p,
-                               float* target, hipStream_t s) {
-  MAE_REQUIRE(images && mask64 && target && B > 0 && m > 0, "patchify_gather: bad arguments");
-  MAE_REQUIRE(p > 0 && img % p == 0, "patchify: image_size %d not divisible by patch_size %d", img, p);
-  const int64_t rows = (int64_t)B * m;
-  const int grid = (int)std::min<int64_t>(cdiv(rows * p * p, 256), 256 * 16);
-  hipLaunchKernelGGL((patchify_gather_kernel<int64_t>), dim3(grid), dim3(256), 0, s, images, mask64, rows, m, C, img, p, target);
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
 template <class S, class D_>
 __global__ void __launch_bounds__(256) cast_kernel(const S* __restrict__ src, D_* __restrict__ dst, int64_t n) {
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dst[i] = from_f<D_>(to_f(src[i]));
@@ -457,27 +357,6 @@ int launch_zero_unpredicted_rows(const int32_t* inv, int64_t rows, int Tseq, int
 }
 
 }  // namespace mae
-
-extern "C" int mae_patchify_gather(const void* images, int32_t image_dtype, const int64_t* idx_mask, int32_t batch, int32_t in_chans,
-                                   int32_t image_size, int32_t patch_size, int32_t num_mask, float* target,
-                                   void* stream) {
-  MAE_REQUIRE(image_dtype == MAE_F32 || image_dtype == MAE_U8, "mae_patchify_gather: image_dtype must be MAE_F32 or MAE_U8 (got %d)", image_dtype);
-  if (image_dtype == MAE_U8)
-    return mae::launch_patchify_gather_u8_i64((const uint8_t*)images, idx_mask, batch, num_mask, in_chans, image_size, patch_size, target,
-                                              (hipStream_t)stream);
-  return mae::launch_patchify_gather_i64((const float*)images, idx_mask, batch, num_mask, in_chans, image_size, patch_size, target,
-                                         (hipStream_t)stream);
-}
-
-extern "C" int mae_gather_patches(const void* images, int32_t image_dtype, const int32_t* tok32, int32_t batch, int32_t num_keep, int32_t in_chans,
-                                  int32_t image_size, int32_t patch_size, int32_t out_dtype, void* out, void* stream) {
-  MAE_REQUIRE(image_dtype == MAE_F32 || image_dtype == MAE_U8, "mae_gather_patches: image_dtype must be MAE_F32 or MAE_U8 (got %d)", image_dtype);
-  if (image_dtype == MAE_U8)
-    return mae::launch_gather_patches_u8((const uint8_t*)images, tok32, batch, num_keep, in_chans, image_size, patch_size, out_dtype, out,
-                                         (hipStream_t)stream);
-  return mae::launch_gather_patches((const float*)images, tok32, batch, num_keep, in_chans, image_size, patch_size, out_dtype, out,
-                                    (hipStream_t)stream);
-}
 
 extern "C" int mae_assemble_visible(float* x, const int32_t* tok32, const float* cls, const float* pos, int64_t rows, int32_t dim, void* stream) {
   return mae::launch_assemble_visible(x, tok32, cls, pos, rows, dim, (hipStream_t)stream);

@@ -10,16 +10,12 @@ namespace mae {
 int launch_mask_from_noise(const float* noise, int B, int L, int k, int64_t* keep64, int64_t* mask64,
                            int32_t* keep32, int32_t* mask32, hipStream_t s);
 int launch_idx_to_i32(const int64_t* src, int32_t* dst, int64_t n, hipStream_t s);
-int launch_idx_to_i64(const int32_t* src, int64_t* dst, int64_t n, hipStream_t s);
 // inv[b][t] = j with keep[b][j] == t, else -1
 int launch_build_inverse(const int32_t* keep32, int B, int k, int L, int32_t* inv, hipStream_t s);
 // rows[b*m + j] = b*L + mask[b][j]  (row map of the masked tokens inside the (B*L) decoder matrix)
 int launch_build_row_map(const int32_t* idx32, int B, int n_per, int L, int32_t* rows, hipStream_t s);
 
-// ---- k_patch.hip: pixels <-> tokens ---------------------------------------------------------------
-// A[(b,j)][c*p*p + py*p + px] = images[b][c][ph*p+py][pw*p+px] for token t = tok[b][j] >= 1 (patch t-1), zeros for t == 0
-int launch_gather_patches(const float* images, const int32_t* tok, int B, int k, int C, int img, int p, int dt,
-                          void* out, hipStream_t s);
+// ---- k_patch.hip: token rows <-> sequences ----------------------------------------------------------
 // in place on x (B*k, D) fp32: x[r] = (t == 0 ? cls : x[r]) + pos[t]
 int launch_assemble_visible(float* x, const int32_t* tok, const float* cls, const float* pos, int64_t rows, int D,
                             hipStream_t s);
@@ -33,9 +29,14 @@ int launch_decoder_assemble(const void* xdec, int dt, const int32_t* inv, const 
 int launch_zero_unpredicted_rows(const int32_t* inv, int64_t rows, int Tseq, int m, int D, int act, float* dres, void* dres_c, hipStream_t s);
 int launch_decoder_assemble_bwd(const float* dx, const int32_t* inv, const int32_t* keep, int B, int k, int L, int Dd,
                                 int dt, void* d_xdec, float* d_mask_token, float* partial, hipStream_t s);
-// target (B*m, P) fp32 in (py, px, c) order for patch max(mask[b][j]-1, 0)
-int launch_patchify_gather(const float* images, const int32_t* mask32, int B, int m, int C, int img, int p,
-                           float* target, hipStream_t s);
+int launch_cast(const void* src, int src_dt, void* dst, int dst_dt, int64_t n, hipStream_t s);
+// out[r] = x[r] + pos[r mod L] (fp32 rows of D)
+int launch_add_rows_pos(const float* x, const float* pos, int64_t rows, int L, int D, float* out, hipStream_t s);
+// dst (dt) += src (fp32)
+int launch_add_into(const float* src, void* dst, int dst_dt, int64_t n, hipStream_t s);
+// out[c] = sum_{i<G} partial[i][c] in row order (deterministic); columns [0,split) go to out0, [split,C) to out1
+int launch_sum_partials(const float* partial, int G, int C, float* out0, float* out1, int split, hipStream_t s);
+
 // ---- k_jepa.hip: I-JEPA predictor input / target rows / latent loss (no reference code: spec in DESIGN.md) -----------------
 int launch_iota_tokens(int32_t* keep32, int B, int N, hipStream_t s);                 // keep[b][j] = j + 1
 int launch_fill(float* p, float v, int64_t n, hipStream_t s);
@@ -48,20 +49,20 @@ int launch_predictor_assemble_bwd(const float* dx, int B, int k, int nblk, int m
 int launch_smooth_l1(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred, int dpred_dt,
                      float* scratch, hipStream_t s);
 
-// ---- k_pixels_u8.hip: the same three pixel readers on uint8 images, ToTensor + Normalize(.5,.5) fused into the read -----
-int launch_gather_patches_u8(const uint8_t* images, const int32_t* tok, int B, int k, int C, int img, int p, int dt, void* out, hipStream_t s);
-int launch_mse_from_images_u8(const float* pred, const uint8_t* images, const int32_t* mask32, int B, int m, int C, int img, int p,
-                              float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch, hipStream_t s);
-int launch_patchify_gather_u8(const uint8_t* images, const int32_t* mask32, int B, int m, int C, int img, int p, float* target, hipStream_t s);
-int launch_patchify_gather_u8_i64(const uint8_t* images, const int64_t* mask64, int B, int m, int C, int img, int p, float* target, hipStream_t s);
+// ---- k_pixels.hip: the three readers of the image; images are fp32 (normalised) or uint8 (img_dt = MAE_F32 / MAE_U8), uint8 with
+// ToTensor + Normalize(.5,.5) fused into the read.  uint8 images, and the loss on float images where the geometry allows, go through
+// the band walk (one workgroup streams one row of patches into LDS); float images otherwise through per-pixel gathers ---------------
+// A[(b,j)][c*p*p + py*p + px] = images[b][c][ph*p+py][pw*p+px] for token t = tok[b][j] >= 1 (patch t-1), zeros for t == 0
+int launch_gather_patches(const void* images, int img_dt, const int32_t* tok, int B, int k, int C, int img, int p, int dt, void* out,
+                          hipStream_t s);
+// target (B*m, P) fp32 in (py, px, c) order for patch clamp(idx[b][j]-1, 0, g*g-1); idx is int64 when idx64 != 0, else int32
+int launch_patchify_gather(const void* images, int img_dt, const void* idx, int idx64, int B, int m, int C, int img, int p, float* target,
+                           hipStream_t s);
+// launch_mse with that target read straight from the image (never materialised).  Float images: path 0 = band walk where it applies
+// (MAE_MSE_BAND=0 switches it off), else the per-pixel gather; path 1 = the gather alone
+int launch_mse_from_images(const float* pred, const void* images, int img_dt, const int32_t* mask32, int B, int m, int C, int img, int p,
+                           float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch, int path, hipStream_t s);
 int launch_augment_crop_flip_u8(const uint8_t* in, const int32_t* params, int B, int C, int S, uint8_t* out, hipStream_t s);
-int launch_cast(const void* src, int src_dt, void* dst, int dst_dt, int64_t n, hipStream_t s);
-// out[r] = x[r] + pos[r mod L] (fp32 rows of D)
-int launch_add_rows_pos(const float* x, const float* pos, int64_t rows, int L, int D, float* out, hipStream_t s);
-// dst (dt) += src (fp32)
-int launch_add_into(const float* src, void* dst, int dst_dt, int64_t n, hipStream_t s);
-// out[c] = sum_{i<G} partial[i][c] in row order (deterministic); columns [0,split) go to out0, [split,C) to out1
-int launch_sum_partials(const float* partial, int G, int C, float* out0, float* out1, int split, hipStream_t s);
 
 // ---- k_classifier.hip: pooled linear head + cross-entropy, full-sequence embedding gradient ---------------------------------
 constexpr int HEAD_MAX_CLASSES = 128;   // classes held in LDS by the head kernel
@@ -168,19 +169,27 @@ int launch_lars_step(float* p, const float* g, float* mu, int64_t n, int adapt, 
 // loss[0] = mean((pred-target)^2); d_pred (dt, may be null) = grad_scale*2*(pred-target)/n.  scratch >= 1024+ floats
 int launch_mse(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,
                int dpred_dt, float* scratch, hipStream_t s);
-// same with the target read straight from the image (never materialised)
-// band walk for float images (k_pixels_u8.hip); -1 = geometry not covered
-int launch_mse_from_images_band_f32(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img, int p,
-                                    float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch, hipStream_t s);
-// the per-pixel gather alone (what launch_mse_from_images takes when the band walk declines)
-int launch_mse_from_images_gather(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img,
-                                  int p, float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch,
-                                  hipStream_t s);
-int launch_mse_from_images(const float* pred, const float* images, const int32_t* mask32, int B, int m, int C, int img,
-                           int p, float grad_scale, float* loss, void* d_pred, int dpred_dt, float* scratch,
-                           hipStream_t s);
 // out[0] = inv_n * sum of partial[0 .. nb): the second stage of the loss reductions
 int launch_mean_finalize(const float* partial, int nb, float inv_n, float* out, hipStream_t s);
+// Every loss runs in two stages.  Stage 1 is a kernel family K<.., T, HAS_GRAD> whose arguments end in (float* partial, T* dpred): the
+// instantiation that d_pred asks for (null: <float, false>, else <bf16, true> or <float, true>) leaves `grid` block sums in scratch
+// (1024+ floats); stage 2 is launch_mean_finalize.  PRE holds the family's leading template arguments with their comma, in
+// parentheses: () or (uint8_t,).  `...` are the kernel's arguments in front of (scratch, d_pred).
+template <class K, class T, class... A>
+int launch_loss_stage1(K kernel, int grid, size_t lds, hipStream_t s, T* dpred, A... args) {
+  MAE_TRY(allow_lds(kernel, lds));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, args..., dpred);
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
+#define MAE_UNPAREN(...) __VA_ARGS__
+#define MAE_LAUNCH_LOSS(K, PRE, grid, lds, s, d_pred, dpred_dt, scratch, inv_n, loss, ...)                                                     \
+  do {                                                                                                                                        \
+    if (!(d_pred)) MAE_TRY((launch_loss_stage1(K<MAE_UNPAREN PRE float, false>, grid, lds, s, (float*)nullptr, __VA_ARGS__, scratch)));       \
+    else if ((dpred_dt) == MAE_BF16) MAE_TRY((launch_loss_stage1(K<MAE_UNPAREN PRE bf16, true>, grid, lds, s, (bf16*)(d_pred), __VA_ARGS__, scratch))); \
+    else MAE_TRY((launch_loss_stage1(K<MAE_UNPAREN PRE float, true>, grid, lds, s, (float*)(d_pred), __VA_ARGS__, scratch)));                 \
+    MAE_TRY(launch_mean_finalize(scratch, grid, inv_n, loss, s));                                                                             \
+  } while (0)
 // stats[0] = ||g||_2, stats[1] = min(1, max_norm/(norm+1e-6)).  scratch >= 1024+ floats
 int launch_grad_norm(const float* g, int64_t n, float max_norm, float* stats, float* scratch, hipStream_t s);
 int launch_grad_sumsq(const float* g, int64_t n, float* out, float* scratch, hipStream_t s);
@@ -194,9 +203,7 @@ int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float 
 constexpr int GRAD_ACC_BLOCKS = 2048;  // grid cap of the sweep; MAE_GRAD_ACC_BLOCKS of mae_hip.h and GRAD_ACC_BLOCKS of _lib.py
 int launch_grad_accumulate(float* dst, const float* src, int64_t n, bool overwrite, hipStream_t s);
 int launch_f32_to_bf16(const float* src, bf16* dst, int64_t n, hipStream_t s);
-// dst[c][r] = (bf16) src[r][c]
-int launch_transpose_to_bf16(const float* src, bf16* dst, int rows, int cols, hipStream_t s);
-// the same for a whole list of matrices living in one arena (one launch); passed by value as a kernel argument
+// dst[c][r] = (bf16) src[r][c] for a whole list of matrices living in one arena (one launch); passed by value as a kernel argument
 struct TransposeTable {
   static constexpr int MAX = 64, TILE = 64;   // matrices per launch, tile edge
   int n = 0, total_tiles = 0;

@@ -3,7 +3,7 @@
 Mirrors what the reference's ``get_pretrain_dataloaders`` (src/data.py:45-106) hands the step, without torchvision
 (not installed): the STL-10 unlabeled split is read straight from its binary file (uint8, column-major images) and kept
 uint8 all the way INTO the engine (27.6 KB/image instead of 110.6 KB fp32): ToTensor + Normalize(.5,.5)
-(src/data.py:22-23) is applied by the kernels that read pixels (csrc/k_pixels_u8.hip), bit-identical to the torch
+(src/data.py:22-23) is applied by the kernels that read pixels (csrc/k_pixels.hip), bit-identical to the torch
 expression ``normalize_u8``.  The dataset lives either on the device (``engine.data_on_device: true``, the default:
 2.6 GB for STL-10 unlabeled) or in pinned host memory, streamed by ``PinnedBatchStream``: index gather on the host into
 a pinned staging buffer, H2D copy on a side stream into one of two device buffers, so batch i+1 crosses PCIe while
@@ -215,7 +215,7 @@ def get_pretrain_batches(cfg: dict, device: torch.device, synthetic_images: Opti
     on_device = bool(cfg.get("engine", {}).get("data_on_device", True))
     patch = int(cfg.get("model", {}).get("general", {}).get("patch_size", 8))
     img_size = int(cfg.get("model", {}).get("general", {}).get("image_size", 96))
-    # the uint8 pixel kernels take patch sizes that are multiples of 4 (csrc/k_pixels_u8.hip); other geometries (the reference
+    # the uint8 pixel kernels take patch sizes that are multiples of 4 (csrc/k_pixels.hip); other geometries (the reference
     # class's default patch_size 6, ViT-L/14) are served normalised fp32 batches, which every engine kernel accepts
     keep_u8 = patch % 4 == 0 and img_size // max(1, patch) <= 64
     stream: Optional[PinnedBatchStream] = None

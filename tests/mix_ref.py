@@ -8,7 +8,7 @@ lam CE(ya, label_smoothing=eps) + (1 - lam) CE(yb, label_smoothing=eps) of torch
 rounding points (features as stored, the pooled vector, W, d_logits).  lam enters as the fp32 value the kernel reads.
 
 Mixing.  out = n(partner) inside the box, lam n(own) + (1 - lam) n(partner) outside, where n() is ``normalize_u8`` evaluated
-in fp32 for uint8 images (the kernel's normalisation is bit-identical to it: the contract of k_pixels_u8.hip) and the identity
+in fp32 for uint8 images (the kernel's normalisation is bit-identical to it: the contract of k_pixels.hip) and the identity
 for fp32 images.  The reference mixes those fp32 values in fp64 with lam widened from fp32.
 Bound per outside pixel (the convention of tests/optim_ref.py, u = 2^-24, SECOND = 1 + 2^-16 for the second-order terms; the
 library is built with -ffp-contract=fast, and fusing only removes roundings):

@@ -126,7 +126,7 @@ def test_cutmix_u8_output_is_the_byte_select(dev, B, C, S):
 
 def test_mix_u8_normalisation_is_the_engines(dev):
     """lam = 1, empty boxes: the output is normalize_u8 (evaluated on the host, as the other pixel tests do) of every byte value,
-    bit for bit -- the contract of k_pixels_u8.hip."""
+    bit for bit -- the contract of k_pixels.hip."""
     from ssrl_vit_mae_jepa_amd.data import normalize_u8
     x = torch.arange(256, dtype=torch.uint8).repeat(3).reshape(1, 3, 16, 16)
     out = call_mix(dev, x, [0], [1.0], [(0, 0, 0, 0)], F32)

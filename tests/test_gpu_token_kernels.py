@@ -1,5 +1,5 @@
-"""The kernels that move tokens and pixels between the GEMMs, and the losses that read the image (k_patch.hip, k_pixels_u8.hip,
-k_index.hip, k_jepa.hip, mse_images_kernel), one by one through the C ABI against tests/token_ref.py (-m gpu).
+"""The kernels that move tokens and pixels between the GEMMs, and the losses that read the image (k_patch.hip, k_pixels.hip,
+k_index.hip, k_jepa.hip), one by one through the C ABI against tests/token_ref.py (-m gpu).
 
 Every case of token_ref's tables.  Copies, single fp32 additions, bf16 roundings, zeros, index maps and d_pred are compared bit
 for bit; column sums are bit-exact on the integer inputs and inside c u sum|x| on random ones; loss scalars inside
@@ -8,7 +8,7 @@ guard rows behind it and is compared as a whole, so nothing outside the specifie
 buffers must agree bit for bit.  Every kernel gets the reference's index maps, not another kernel's output, so each is judged
 on its own.  The last test prints the worst error / bound per kernel and output.
 
-The whole file (174 tests) takes about 6 s on an MI355X; the largest case (82 070 rows of 192) 0.35 s."""
+The whole file (200 tests) takes about 6 s on an MI355X; the largest case (82 070 rows of 192) 0.35 s."""
 import re
 
 import numpy as np
@@ -223,6 +223,26 @@ def test_mse_loss_from_images(dev, cid):
                 if dp:
                     assert np.array_equal(R.bits(got["mse.d_pred"]), R.bits(other["mse.d_pred"])), f"{cid}: d_pred of the two float variants differ"
                 assert abs(float(got["mse.loss"][0]) - float(other["mse.loss"][0])) <= exp.bound[0] + oexp.bound[0]
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("cid", list(LOSS))
+def test_patchify_gather(dev, cid):
+    """The target the loss never materialises, on the loss's token lists (ids as int64, as the ABI takes them): ids 0 and g*g + 1
+    (kind oor) copy patches 0 and g*g - 1 from either image dtype."""
+    c, s, fails = LOSS[cid], stream(dev), []
+    d = R.gen_pixels(c, False)
+    images, idx = {"f32": up(d["f32"], dev), "u8": up(d["u8"], dev)}, up(d["tok"].astype(np.int64), dev)
+    init, e = R.patchify_inits(c), R.expect_patchify(c, d)
+    for image_dtype in ("f32", "u8"):
+        def launch(b):
+            return lib.mae_patchify_gather(_ptr(images[image_dtype]), DT[image_dtype], _ptr(idx), c.B, c.C, c.img, c.p, c.n,
+                                           _ptr(b["patchify_gather.target"]), s)
+
+        if image_dtype == "u8" and not R.u8_supported(c.C, c.img, c.p, c.n):
+            assert rejected(launch, init, R.U8_LOSS_MESSAGE, dev), f"{cid}: a rejected geometry wrote to its output"
+            continue
+        settle(cid, image_dtype, e, run_twice(init, lambda b: check(launch(b)), dev, cid), init, fails)
     assert not fails, "\n".join(fails)
 
 

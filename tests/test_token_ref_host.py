@@ -130,6 +130,17 @@ def test_mse_reference_matches_torch(c):
         assert torch.all((got - grad).abs() <= 4 * R.U * grad.abs() + 1e-45)       # subtraction, two products, one division
 
 
+@pytest.mark.parametrize("cid", ["c3i32p8-oor", "c1i28p7-random"])
+def test_patchify_reference_matches_oracle(cid):
+    c = next(x for x in R.loss_cases() if x.id == cid)
+    d = R.gen_pixels(c, False)
+    patches = O.patchify(torch.from_numpy(d["f32"][:c.B]), c.p)
+    idx = (torch.from_numpy(d["tok"]).long() - 1).clamp(0, c.g * c.g - 1)
+    want = torch.gather(patches, 1, idx.unsqueeze(-1).expand(-1, -1, c.P)).reshape(-1, c.P)
+    got = R.expect_patchify(c, d)["patchify_gather.target"].want
+    assert got.dtype == np.float32 and np.array_equal(R.bits(got), R.bits(want.numpy()))
+
+
 @pytest.mark.parametrize("c", R.sl1_cases()[:3], ids=lambda c: c.id)
 def test_smooth_l1_reference_matches_torch(c):
     d = R.gen_sl1(c)
@@ -236,6 +247,7 @@ def _all_expectations():
             yield c.id, R.expect_zero(c, d), R.zero_inits(c, d)
     for c in SMALL_PIX:
         d = R.gen_pixels(c, False)
+        yield c.id, R.expect_patchify(c, d), R.patchify_inits(c)
         for variant in ("gather", "band"):
             for dp in ("", "f32", "bf16"):
                 yield c.id, R.expect_mse(c, d, variant, 1.0 / 3.0, dp), R.loss_inits(c, dp)

@@ -1,5 +1,5 @@
 """numpy restatement of the kernels that move tokens and pixels between the GEMMs, and of the losses that read the image
-(k_patch.hip, k_pixels_u8.hip, k_index.hip, k_jepa.hip, mse_images_kernel of k_loss_optim.hip), for the tests.
+(k_patch.hip, k_pixels.hip, k_index.hip, k_jepa.hip), for the tests.
 
 numpy on the CPU: no torch, no GPU.  One ``expect_*`` function per kernel family turns a case and its generated inputs into
 a dict  output name -> Exact | Bounded | Scratch;  ``judge`` compares what a kernel (or ``simulate``, the plain fp32 numpy
@@ -8,8 +8,8 @@ output buffer starts from ``init``: NaN-filled (or pattern-filled) with GUARD ro
 compared, so a guard row that was written, an untouched row that changed, or a NaN that turned into a number is a failure.
 
 What is exact (compared as integer views, NaN patterns included) and why:
-  copies          gather_patches (c, py, px), dtok, d_xdec of decoder_assemble_bwd: no arithmetic.  The uint8 gather and the
-                  uint8 loss read v = (fl(u / 255) - 0.5) / 0.5 evaluated in np.float32: the division is IEEE-rounded
+  copies          gather_patches (c, py, px), patchify_gather (py, px, c), dtok, d_xdec of decoder_assemble_bwd: no arithmetic.  The
+                  uint8 readers take v = (fl(u / 255) - 0.5) / 0.5 evaluated in np.float32: the division is IEEE-rounded
                   (__fdiv_rn), the subtraction rounds once, the division by 0.5 is exact.
   one fp32 add    assemble_visible, decoder_assemble, predictor_assemble: fl(a + b), which numpy's float32 addition returns.
   bf16 outputs    the round-to-nearest-even of that fp32 value (optim_ref.bf16_rne), a NaN keeps its quiet pattern.
@@ -664,11 +664,25 @@ def loss_inits(c: PixCase, dp: str) -> dict:
     return out
 
 
-def expect_mse(c: PixCase, d: dict, variant: str, grad_scale, dp: str) -> dict:
-    """dp: '' (d_pred NULL) | 'f32' | 'bf16'.  The target is patch clamp(id - 1, 0, g*g - 1) in (py, px, c) order."""
+def target_rows(c: PixCase, d: dict) -> np.ndarray:
+    """(B * n, P) fp32: patch clamp(id - 1, 0, g*g - 1) of every token in (py, px, c) order.  Both image dtypes give the same rows."""
     pat = patches_of(d["f32"][:c.B], c.p, "ppc")
     idx = np.clip(d["tok"] - 1, 0, c.g * c.g - 1)
-    t = pat[np.arange(c.B)[:, None], idx].reshape(-1, c.P)
+    return pat[np.arange(c.B)[:, None], idx].reshape(-1, c.P)
+
+
+def patchify_inits(c: PixCase) -> dict:
+    return {"patchify_gather.target": nan_buf(c.B * c.n, c.P)}
+
+
+def expect_patchify(c: PixCase, d: dict) -> dict:
+    """A copy: no arithmetic on float images, norm_u8 alone on uint8 ones."""
+    return {"patchify_gather.target": Exact(target_rows(c, d))}
+
+
+def expect_mse(c: PixCase, d: dict, variant: str, grad_scale, dp: str) -> dict:
+    """dp: '' (d_pred NULL) | 'f32' | 'bf16'.  The target is patch clamp(id - 1, 0, g*g - 1) in (py, px, c) order."""
+    t = target_rows(c, d)
     n = t.size
     diff = d["pred"] - t
     ref = float(((d["pred"].astype(np.float64) - t.astype(np.float64)) ** 2).sum() / n)
