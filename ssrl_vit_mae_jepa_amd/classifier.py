@@ -7,8 +7,11 @@ logged names, and adds the native step: one call for forward + pooled head + cro
 the trainable blocks end, then clip_grad_norm_(1.0) + one-group AdamW over exactly the tensors whose ``requires_grad``
 is set (Lightning ``gradient_clip_val=1.0``, scripts/training/train_mae.py:213; src/training/classifier.py:106-108).
 
-The fine-tuning recipe of the MAE paper (not in the reference; every option off by default, and off means the calls above
-unchanged): ``train.label_smoothing``, ``train.mixup_alpha`` / ``train.cutmix_alpha`` (+ ``mix_prob``, ``mix_switch_prob``)
+The native calls are the widest entry points of the C ABI (``mae_engine_classifier_forward_ex``, ``..._loss_and_grads_sd``), whatever
+the configuration: an option that is off is an argument left at None / 0, and the engine then issues the launches -- and the bits -- of
+the narrower entry points.
+
+The fine-tuning recipe of the MAE paper (not in the reference; every option off by default): ``train.label_smoothing``, ``train.mixup_alpha`` / ``train.cutmix_alpha`` (+ ``mix_prob``, ``mix_switch_prob``)
 mix each training batch on the device (``data.mix_batch``) and train on the soft targets inside the head kernel;
 ``train.layer_decay`` scales the learning rate of layer l by ``layer_decay ** (depth + 1 - l)`` (BEiT / MAE numbering);
 ``train.augment`` augments each image of a training batch before all that (``data.augment_finetune``: RandomResizedCrop + flip,
@@ -114,7 +117,8 @@ class ViTClassifier(nn.Module):
 
     @property
     def extended(self) -> bool:
-        """True when the call needs the ``_ex`` entry points: a patch-only sequence or the patch-row mean."""
+        """True for a patch-only sequence or the patch-row mean: what the first-generation entry points of the C ABI
+        (``with_cls = 1``, "cls" or "mean") cannot express.  Such a head pools through the row-range kernel."""
         return not self.with_cls or self.pool_type == "mean_patches"
 
     def _apply(self, fn, recurse=True):
@@ -127,10 +131,7 @@ class ViTClassifier(nn.Module):
         """The owner's workspace grown to the classifier's size.  It is shared with the MAE's forwards, so every saved
         activation of an earlier call is invalidated: a pending hand-off backward refuses to run."""
         m = self.mae
-        if self.extended:
-            need = lib.mae_engine_classifier_workspace_bytes_ex(m.engine.handle, batch, self.num_classes, int(self.with_cls))
-        else:
-            need = lib.mae_engine_classifier_workspace_bytes(m.engine.handle, batch, self.num_classes)
+        need = lib.mae_engine_classifier_workspace_bytes_ex(m.engine.handle, batch, self.num_classes, int(self.with_cls))
         if need < 0:
             raise ValueError(f"bad batch {batch} / num_classes {self.num_classes}")
         if m._workspace is None or m._workspace.numel() < need or m._workspace.device != m.flat_params.device:
@@ -159,12 +160,9 @@ class ViTClassifier(nn.Module):
             loss = torch.empty(1, dtype=torch.float32, device=dev)
             correct = torch.empty(1, dtype=torch.int32, device=dev)
         ws = self.workspace(B)
-        head = (m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(self.head.flat), _ptr(images), m._img_dt(images), _ptr(labels), B)
-        tail = (self.num_classes, _ptr(ws), ws.numel(), _ptr(out), _ptr(loss), _ptr(correct), _stream(dev))
-        if self.extended:
-            check(lib.mae_engine_classifier_forward_ex(*head, int(self.with_cls), POOLS[self.pool_type], *tail))
-        else:
-            check(lib.mae_engine_classifier_forward(*head, POOLS[self.pool_type], *tail))
+        check(lib.mae_engine_classifier_forward_ex(
+            m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(self.head.flat), _ptr(images), m._img_dt(images), _ptr(labels), B,
+            int(self.with_cls), POOLS[self.pool_type], self.num_classes, _ptr(ws), ws.numel(), _ptr(out), _ptr(loss), _ptr(correct), _stream(dev)))
         return out, loss, correct
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -458,7 +456,7 @@ class ViTClassifierTrainModule(nn.Module):
         ``head_grads`` (W then b) and ``pos_grads``.  Returns device tensors (loss[1], correct[1]); no host sync.
         Soft targets: ``labels_b`` (B) and ``lam`` (B, fp32) mix the labels as lam * labels + (1 - lam) * labels_b,
         ``label_smoothing`` (None: ``train.label_smoothing``) smooths them; ``correct`` counts argmax == labels.  With none
-        of the three active this is the hard-label call, unchanged.
+        of the three active the engine launches the hard-label kernels.
         Drop path: ``branch_scale`` (2 * depth, B) fp32, the table ``data.draw_drop_path`` returns (row 2i: the attention branch
         of blocks.i, 2i + 1: its MLP branch), scales each image's residual branches in the forward and their gradients in the
         backward.  A host table is uploaded through pinned memory (no synchronisation); a frozen encoder refuses one."""
@@ -474,9 +472,6 @@ class ViTClassifierTrainModule(nn.Module):
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         correct = torch.empty(1, dtype=torch.int32, device=dev)
         ws = clf.workspace(B)
-        head = (m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(clf.head.flat), _ptr(images), m._img_dt(images), _ptr(labels), B)
-        tail = (clf.num_classes, tb, te, float(grad_scale), _ptr(ws), ws.numel(), _ptr(m.flat_grads), _ptr(head_g), _ptr(pos_g), _ptr(logits_out),
-                _ptr(loss), _ptr(correct), _stream(dev))
         eps = self.label_smoothing if label_smoothing is None else float(label_smoothing)
         if branch_scale is not None:
             depth = len(clf.encoder.blocks)
@@ -486,23 +481,17 @@ class ViTClassifierTrainModule(nn.Module):
                 raise ValueError(f"branch_scale must be ({2 * depth}, {B}), got {tuple(branch_scale.shape)}")
             branch_scale = branch_scale.to(torch.float32).contiguous()
             branch_scale = branch_scale.to(dev) if branch_scale.is_cuda else branch_scale.pin_memory().to(dev, non_blocking=True)
-        if branch_scale is not None or labels_b is not None or lam is not None or eps != 0.0:
-            if labels_b is not None:
-                labels_b = labels_b.to(device=dev, dtype=torch.int64).contiguous()
-            if lam is not None:
-                lam = lam.to(device=dev, dtype=torch.float32).contiguous()
-            if any(t is not None and t.shape != (B,) for t in (labels_b, lam)):
-                raise ValueError(f"labels_b and lam must be ({B},)")
-            if branch_scale is not None:
-                check(lib.mae_engine_classifier_loss_and_grads_sd(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail[:-1], _ptr(labels_b),
-                                                                  _ptr(lam), eps, _ptr(branch_scale), tail[-1]))
-            else:
-                check(lib.mae_engine_classifier_loss_and_grads_soft(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail[:-1], _ptr(labels_b),
-                                                                    _ptr(lam), eps, tail[-1]))
-        elif clf.extended:
-            check(lib.mae_engine_classifier_loss_and_grads_ex(*head, int(clf.with_cls), POOLS[clf.pool_type], *tail))
-        else:
-            check(lib.mae_engine_classifier_loss_and_grads(*head, POOLS[clf.pool_type], *tail))
+        if labels_b is not None:
+            labels_b = labels_b.to(device=dev, dtype=torch.int64).contiguous()
+        if lam is not None:
+            lam = lam.to(device=dev, dtype=torch.float32).contiguous()
+        if any(t is not None and t.shape != (B,) for t in (labels_b, lam)):
+            raise ValueError(f"labels_b and lam must be ({B},)")
+        check(lib.mae_engine_classifier_loss_and_grads_sd(
+            m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(clf.head.flat), _ptr(images), m._img_dt(images), _ptr(labels), B,
+            int(clf.with_cls), POOLS[clf.pool_type], clf.num_classes, tb, te, float(grad_scale), _ptr(ws), ws.numel(), _ptr(m.flat_grads),
+            _ptr(head_g), _ptr(pos_g), _ptr(logits_out), _ptr(loss), _ptr(correct), _ptr(labels_b), _ptr(lam), eps, _ptr(branch_scale),
+            _stream(dev)))
         self._last_mode = (tb, te)
         return loss, correct
 

@@ -200,6 +200,9 @@ static Plan make_plan_ex(const mae_engine* e, int B, int k, int dec_B, int dec_T
   return pl;
 }
 static Plan make_plan(const mae_engine* e, int B, int k) { return make_plan_ex(e, B, k, B, e->L, e->L - k); }
+// The encoder alone over every token of every image -- [cls | patches], or the patches alone (what an I-JEPA encoder sees) -- with a
+// token-sized decoder stub: the I-JEPA target phase, the patch-only classifier and the frozen-encoder features.
+static Plan make_encoder_plan(const mae_engine* e, int B, bool with_cls) { return make_plan_ex(e, B, with_cls ? e->L : e->L - 1, 1, 1, 1); }
 
 // ---------------------------------------------------------------------------------------------------
 // timers
@@ -261,6 +264,11 @@ struct Ctx {
 // the one place a Ctx is built; `ready` / `fwd_only` / `skip_final_norm` are set by the few callers that need them
 static Ctx make_ctx(mae_engine* e, const float* params, const void* wcache, float* grads, void* ws, void* stream) {
   return Ctx{e, params, (const char*)wcache, grads, (char*)ws, (hipStream_t)stream, e->act, (int64_t)dtype_size(e->act)};
+}
+
+// keep32 of a plan over every token of every image: tokens 0 .. L-1, or 1 .. L-1 without the class token
+static int keep_every_token(const Ctx& c, const Plan& pl, bool with_cls) {
+  return launch_iota_tokens(c.buf<int32_t>(pl.keep32), pl.B, pl.k, with_cls ? 0 : 1, c.s);
 }
 
 // algorithmic HBM bytes of one Linear launch: both operands, every output (the GELU epilogues write two) and the (M,N) side input
@@ -897,7 +905,7 @@ static JepaPlan make_jepa_plan(const mae_engine* e, int B, int k, int nblk, int 
   jp.stat = take(2 * Mp * 4);
   jp.h = take(Mp * e->D * 4);
   jp.phase = off;
-  jp.tgt = make_plan_ex(e, B, N, 1, 1, 1);                       // encoder over every patch token; a token-sized decoder stub
+  jp.tgt = make_encoder_plan(e, B, false);                       // encoder over every patch token
   jp.xenc = round_up(jp.tgt.total, 256);
   const int64_t tgt_total = jp.xenc + round_up((int64_t)B * N * e->D * 4, 256);
   jp.ctx = make_plan_ex(e, B, k, B * nblk, k + m, m);
@@ -946,7 +954,7 @@ extern "C" int mae_engine_jepa_loss_and_grads(mae_engine_t* e, const float* para
     Ctx c = make_ctx(e, target_params, target_wcache, nullptr, ws + jp.phase, stream);
     c.fwd_only = true;
     float* xenc = reinterpret_cast<float*>(ws + jp.phase + jp.xenc);
-    MAE_TRY(launch_iota_tokens(c.buf<int32_t>(jp.tgt.keep32), batch, N, s));
+    MAE_TRY(keep_every_token(c, jp.tgt, false));
     MAE_TRY(forward_encoder_impl(c, jp.tgt, images, image_dtype, xenc));
     MAE_TRY(launch_rows_from_tokens(tgt32, batch, num_blocks * block_tokens, N, tgt_rows, s));
     MAE_TRY(launch_fill(reinterpret_cast<float*>(ws + jp.ones), 1.0f, e->D, s));
@@ -1072,8 +1080,9 @@ extern "C" int mae_engine_optimizer_step_ema(mae_engine_t* e, float* params, flo
 //   train_blocks = -1: linear probe -- the forward saves nothing for a backward, only the head gets gradients;
 //   train_blocks = n : final LayerNorm + blocks[depth-n:] (unfreeze_last_layers(n)); nothing below them runs;
 //   train_embed  = 1 : (n = depth only) also cls_token, the patch projection and pos_embed (unfreeze_encoder()).
-// The _ex entry points add the patch-only sequence (with_cls = 0: tokens 1..N, what an I-JEPA encoder was trained on) and
-// the patch-row mean (MAE_POOL_MEAN_PATCHES); both pool through the row-range head kernel.
+// Every entry point is one ClsCall handed to classifier_impl: the wider ones (_ex: the patch-only sequence, with_cls = 0, tokens
+// 1..N, what an I-JEPA encoder was trained on, and the patch-row mean MAE_POOL_MEAN_PATCHES; _soft: soft targets; _sd: drop path)
+// set more of its fields, and a field left at its default issues the narrower entry's launches.
 // =====================================================================================================
 namespace mae {
 
@@ -1084,8 +1093,8 @@ struct ClsPlan {
 
 static ClsPlan make_cls_plan(const mae_engine* e, int B, int C, bool with_cls = true) {
   ClsPlan cp;
-  const int T = with_cls ? e->L : e->L - 1;
-  cp.pl = with_cls ? make_plan(e, B, e->L) : make_plan_ex(e, B, T, 1, 1, 1);  // patch-only: a token-sized decoder stub, as the features plan
+  cp.pl = with_cls ? make_plan(e, B, e->L) : make_encoder_plan(e, B, false);
+  const int T = cp.pl.k;
   int64_t off = round_up(cp.pl.total, 256);
   auto take = [&](int64_t bytes) { const int64_t o = off; off += round_up(std::max<int64_t>(bytes, 4), 256); return o; };
   const int64_t D = e->D;
@@ -1104,68 +1113,85 @@ static ClsPlan make_cls_plan(const mae_engine* e, int B, int C, bool with_cls = 
   return cp;
 }
 
-static int classifier_impl(mae_engine* e, const float* params, const void* wcache, const float* head, const void* images, int32_t image_dtype,
-                           const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes, int32_t train_blocks, int32_t train_embed,
-                           float grad_scale, void* workspace, int64_t workspace_bytes, float* grads, float* head_grads, float* pos_grad,
-                           float* logits, float* loss_out, int32_t* correct_out, void* stream, const char* who, int32_t with_cls = 1,
-                           bool ex = false, const HeadSoft* soft = nullptr, const float* branch_scale = nullptr) {
-  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
-  MAE_REQUIRE(!branch_scale || (head_grads && train_blocks >= 0),
+// One classifier call: what the six entry points take, the defaults being the first entry's (forward over [cls | patches]).
+struct ClsCall {
+  const float *params = nullptr, *head = nullptr;
+  const void *wcache = nullptr, *images = nullptr;
+  const int64_t* labels = nullptr;
+  int32_t image_dtype = MAE_F32, batch = 0, with_cls = 1, pool = MAE_POOL_CLS, num_classes = 0, train_blocks = -1, train_embed = 0;
+  bool extended_pools = false;  // the entry takes with_cls = 0 and MAE_POOL_MEAN_PATCHES
+  bool training = false;        // a loss_and_grads entry: head_grads is required
+  float grad_scale = 1.f;
+  void *workspace = nullptr, *stream = nullptr;
+  int64_t workspace_bytes = 0;
+  float *grads = nullptr, *head_grads = nullptr, *pos_grad = nullptr, *logits = nullptr, *loss_out = nullptr;
+  int32_t* correct_out = nullptr;
+  HeadSoft soft = {nullptr, nullptr, 0.f};  // inactive: the hard-label kernels
+  const float* branch_scale = nullptr;      // drop path; null: none
+};
+// The six entry points name their parameters alike, so each fills its record from them with these: what every entry takes, and what
+// the four loss_and_grads entries add.
+#define CLS_CALL(k)                                                                                                                    \
+  ClsCall k;                                                                                                                           \
+  k.params = params; k.wcache = wcache; k.head = head; k.images = images; k.image_dtype = image_dtype; k.labels = labels;              \
+  k.batch = batch; k.pool = pool; k.num_classes = num_classes; k.workspace = workspace; k.workspace_bytes = workspace_bytes;           \
+  k.logits = logits; k.loss_out = loss_out; k.correct_out = correct_out; k.stream = stream
+#define CLS_CALL_TRAINING(k)                                                                                                           \
+  k.training = true; k.train_blocks = train_blocks; k.train_embed = train_embed; k.grad_scale = grad_scale;                            \
+  k.grads = grads; k.head_grads = head_grads; k.pos_grad = pos_grad
+
+static int classifier_impl(mae_engine* e, const ClsCall& k, const char* who) {
+  if (k.training) MAE_REQUIRE(k.head_grads, "%s: null head_grads", who);
+  else MAE_REQUIRE(k.labels || (!k.loss_out && !k.correct_out), "%s: loss / correct count need labels", who);
+  MAE_REQUIRE(k.soft.eps >= 0.f && k.soft.eps < 1.f, "%s: label_smoothing = %g outside [0, 1)", who, (double)k.soft.eps);
+  MAE_TRY(check_common(e, k.params, k.wcache, k.batch, k.workspace, who));
+  const int32_t train_blocks = k.train_blocks;
+  MAE_REQUIRE(!k.branch_scale || (k.head_grads && train_blocks >= 0),
               "%s: branch_scale needs a training encoder (train_blocks >= 0); the probe's encoder is in inference and never drops", who);
-  MAE_REQUIRE(batch > 0, "%s: batch %d out of range", who, batch);
-  MAE_REQUIRE(head && images, "%s: null head/images", who);
-  MAE_TRY(check_image_dtype(image_dtype, who));
-  MAE_REQUIRE(num_classes >= 2 && num_classes <= HEAD_MAX_CLASSES, "%s: num_classes = %d outside [2, %d]", who, num_classes, HEAD_MAX_CLASSES);
-  if (ex) {
-    MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
-    MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES,
-                "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
-    MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
-    MAE_REQUIRE(e->L >= 2 && e->D % 4 == 0 && e->D <= 1024, "%s: needs a patch row and embed_dim a multiple of 4 up to 1024", who);
-  } else {
-    MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN, "%s: pool must be MAE_POOL_CLS or MAE_POOL_MEAN (got %d)", who, pool);
-  }
-  const ClsPlan cp = make_cls_plan(e, batch, num_classes, with_cls != 0);
+  MAE_REQUIRE(k.batch > 0, "%s: batch %d out of range", who, k.batch);
+  MAE_REQUIRE(k.head && k.images, "%s: null head/images", who);
+  MAE_TRY(check_image_dtype(k.image_dtype, who));
+  MAE_REQUIRE(k.num_classes >= 2 && k.num_classes <= HEAD_MAX_CLASSES, "%s: num_classes = %d outside [2, %d]", who, k.num_classes, HEAD_MAX_CLASSES);
+  MAE_TRY(check_pool(k.with_cls, k.pool, k.extended_pools, who));
+  if (k.extended_pools) MAE_REQUIRE(e->L >= 2 && e->D % 4 == 0 && e->D <= 1024, "%s: needs a patch row and embed_dim a multiple of 4 up to 1024", who);
+  const bool with_cls = k.with_cls != 0;
+  const ClsPlan cp = make_cls_plan(e, k.batch, k.num_classes, with_cls);
   const Plan& pl = cp.pl;
-  MAE_REQUIRE(workspace_bytes >= cp.total, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)cp.total);
-  const bool train = head_grads != nullptr;
+  MAE_REQUIRE(k.workspace_bytes >= cp.total, "%s: workspace too small (%lld < %lld bytes)", who, (long long)k.workspace_bytes, (long long)cp.total);
+  const bool train = k.head_grads != nullptr;
   if (train) {
-    MAE_REQUIRE(labels && loss_out, "%s: training needs labels and loss_out", who);
+    MAE_REQUIRE(k.labels && k.loss_out, "%s: training needs labels and loss_out", who);
     MAE_REQUIRE(train_blocks >= -1 && train_blocks <= e->depth, "%s: train_blocks = %d outside [-1, %d]", who, train_blocks, e->depth);
-    MAE_REQUIRE(train_embed == 0 || (train_embed == 1 && train_blocks == e->depth),
+    MAE_REQUIRE(k.train_embed == 0 || (k.train_embed == 1 && train_blocks == e->depth),
                 "%s: train_embed = 1 needs train_blocks = depth (%d), got %d", who, e->depth, train_blocks);
-    MAE_REQUIRE(train_blocks < 0 || grads, "%s: train_blocks >= 0 needs the gradient arena", who);
-    MAE_REQUIRE(!train_embed || pos_grad, "%s: train_embed needs the pos_embed gradient buffer", who);
+    MAE_REQUIRE(train_blocks < 0 || k.grads, "%s: train_blocks >= 0 needs the gradient arena", who);
+    MAE_REQUIRE(!k.train_embed || k.pos_grad, "%s: train_embed needs the pos_embed gradient buffer", who);
   }
-  Ctx c = make_ctx(e, params, wcache, grads, workspace, stream);
+  Ctx c = make_ctx(e, k.params, k.wcache, k.grads, k.workspace, k.stream);
   hipStream_t s = c.s;
   const bool enc_bwd = train && train_blocks >= 0;
   c.fwd_only = !enc_bwd;  // the linear probe and evaluation save no GELU derivative
-  c.branch_scale = branch_scale;
-  const int B = batch, L = pl.k, D = e->D, C = num_classes;  // L rows per image: the class token (if any) and every patch
-  if (with_cls) MAE_TRY(launch_iota_rows(c.buf<int32_t>(pl.keep32), B, L, s));
-  else MAE_TRY(launch_iota_tokens(c.buf<int32_t>(pl.keep32), B, L, s));
-  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
-  const bool cls = pool == MAE_POOL_CLS;
-  const bool range = !with_cls || pool == MAE_POOL_MEAN_PATCHES;  // the mean over the patch rows [lo, L)
-  const int lo = with_cls ? 1 : 0;
-  void* dfeat = enc_bwd ? (cls ? c.buf<>(cp.dpooled) : c.buf<>(pl.d_ln)) : nullptr;
-  if (range) {
-    RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), (double)B * (L - lo) * D * c.as + (double)C * D * 4 + (enc_bwd ? (double)pl.Me * D * c.as : 0.0),
-        launch_classifier_head_range(c.buf<>(pl.enc_norm), e->act, B, L, D, lo, L, head, head + (int64_t)C * D, C, labels, grad_scale, logits,
-                                     c.buf<float>(cp.row_loss), c.buf<int32_t>(cp.row_correct), loss_out, correct_out,
-                                     train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat, s, soft));
-  } else {
-    RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), (cls ? (double)B * D : (double)pl.Me * D) * c.as + (double)C * D * 4 + (enc_bwd && !cls ? (double)pl.Me * D * c.as : 0.0),
-        launch_classifier_head(c.buf<>(pl.enc_norm), e->act, B, L, D, pool, head, head + (int64_t)C * D, C, labels, grad_scale, logits,
-                               c.buf<float>(cp.row_loss), c.buf<int32_t>(cp.row_correct), loss_out, correct_out,
-                               train ? c.buf<float>(cp.pooled) : nullptr, train ? c.buf<float>(cp.dlogits) : nullptr, dfeat,
-                               c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), c.buf<float>(cp.mean_c), c.buf<float>(cp.rstd_c),
-                               enc_bwd && cls ? c.buf<int32_t>(cp.cls_rows) : nullptr, s, soft));
-  }
+  c.branch_scale = k.branch_scale;
+  const int B = k.batch, L = pl.k, D = e->D, C = k.num_classes;  // L rows per image: the class token (if any) and every patch
+  MAE_TRY(keep_every_token(c, pl, with_cls));
+  MAE_TRY(forward_encoder_impl(c, pl, k.images, k.image_dtype, nullptr));
+  const bool cls = k.pool == MAE_POOL_CLS;
+  HeadCall h;
+  h.feats = c.buf<>(pl.enc_norm); h.dt = e->act; h.B = B; h.seq = L; h.D = D; h.with_cls = k.with_cls; h.pool = k.pool;
+  h.W = k.head; h.bias = k.head + (int64_t)C * D; h.C = C; h.labels = k.labels; h.soft = k.soft; h.grad_scale = k.grad_scale;
+  h.logits_out = k.logits; h.row_loss = c.buf<float>(cp.row_loss); h.row_correct = c.buf<int32_t>(cp.row_correct);
+  h.loss_out = k.loss_out; h.correct_out = k.correct_out;
+  h.pooled_out = train ? c.buf<float>(cp.pooled) : nullptr; h.dlogits_out = train ? c.buf<float>(cp.dlogits) : nullptr;
+  h.dfeat_out = enc_bwd ? (cls ? c.buf<>(cp.dpooled) : c.buf<>(pl.d_ln)) : nullptr;
+  h.mean_all = c.buf<float>(pl.enc_mean); h.rstd_all = c.buf<float>(pl.enc_rstd); h.mean_c = c.buf<float>(cp.mean_c); h.rstd_c = c.buf<float>(cp.rstd_c);
+  h.cls_rows = enc_bwd && cls ? c.buf<int32_t>(cp.cls_rows) : nullptr;
+  // bytes: the rows the head reads (the patch rows, the class row or every row), W, and the (B * L, D) feature gradient of a mean pool
+  const double rows_read = h.range() ? (double)B * (L - k.with_cls) : cls ? (double)B : (double)pl.Me;
+  RUN(TK_LOSS, 2.0 * B * C * D * (train ? 2 : 1), rows_read * D * c.as + (double)C * D * 4 + (enc_bwd && !cls ? (double)pl.Me * D * c.as : 0.0),
+      launch_classifier_head(h, s));
   if (!train) return 0;
   RUN(TK_WGRAD, 2.0 * B * C * D, (double)B * (C + D) * 4, launch_classifier_head_wgrad(c.buf<float>(cp.dlogits), c.buf<float>(cp.pooled), B, C, D,
-                                                                                    c.buf<float>(cp.head_partial), c.buf<float>(cp.head_sum), head_grads, s));
+                                                                                    c.buf<float>(cp.head_partial), c.buf<float>(cp.head_sum), k.head_grads, s));
   if (!enc_bwd) return 0;
   float* dres = c.buf<float>(pl.dres);
   backward_begin(c);
@@ -1181,12 +1207,11 @@ static int classifier_impl(mae_engine* e, const float* params, const void* wcach
   for (int i = e->depth - 1; i >= e->depth - train_blocks; --i)  // the trainable suffix only: the sweep stops below blocks[depth-n]
     MAE_TRY(block_backward(c, pl, e->enc[i], pl.enc[i], pl.Me, D, e->H, B, L, pl.enc_x[i], i ? c.scale_row(2 * i - 1, B) : nullptr,
                            c.scale_row(2 * i, B)));
-  if (train_embed) {
-    // token assembly: d pos_embed, d cls_token and the patch rows from one read of dres, then the patch projection
-    if (with_cls)
-      RUN(TK_DATA, 0, pl.Me * D * (4 + c.as), launch_full_grad_split(dres, B, L, D, e->act, c.buf<>(pl.dtok), pos_grad, c.Gp(e->i_cls), c.buf<float>(cp.pos_partial), s));
-    else  // no class row: every row feeds the patch projection; pos_embed[0] and cls_token get exact zeros
-      RUN(TK_DATA, 0, pl.Me * D * (4 + c.as), launch_patch_grad_split(dres, B, L, D, e->act, c.buf<>(pl.dtok), pos_grad, c.Gp(e->i_cls), c.buf<float>(cp.pos_partial), s));
+  if (k.train_embed) {
+    // token assembly: d pos_embed, d cls_token and the patch rows from one read of dres, then the patch projection.  Without a class
+    // row every row feeds the patch projection; pos_embed[0] and cls_token get exact zeros
+    RUN(TK_DATA, 0, pl.Me * D * (4 + c.as), launch_full_grad_split(dres, B, L, D, e->act, c.buf<>(pl.dtok), k.pos_grad, c.Gp(e->i_cls),
+                                                                  c.buf<float>(cp.pos_partial), with_cls, s));
     MAE_TRY(wgrad(c, pl, c.buf<>(pl.dtok), c.buf<>(pl.patchA), pl.Me, D, e->P, e->i_patch_w, e->i_patch_b));
   }
   return backward_end(c);
@@ -1203,9 +1228,8 @@ extern "C" int mae_engine_classifier_forward(mae_engine_t* e, const float* param
                                              int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes,
                                              void* workspace, int64_t workspace_bytes, float* logits, float* loss_out, int32_t* correct_out,
                                              void* stream) {
-  MAE_REQUIRE(labels || (!loss_out && !correct_out), "mae_engine_classifier_forward: loss / correct count need labels");
-  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, -1, 0, 1.f, workspace, workspace_bytes,
-                         nullptr, nullptr, nullptr, logits, loss_out, correct_out, stream, "mae_engine_classifier_forward");
+  CLS_CALL(k);
+  return classifier_impl(e, k, "mae_engine_classifier_forward");
 }
 
 extern "C" int mae_engine_classifier_loss_and_grads(mae_engine_t* e, const float* params, const void* wcache, const float* head,
@@ -1214,10 +1238,9 @@ extern "C" int mae_engine_classifier_loss_and_grads(mae_engine_t* e, const float
                                                     float grad_scale, void* workspace, int64_t workspace_bytes, float* grads,
                                                     float* head_grads, float* pos_grad, float* logits, float* loss_out,
                                                     int32_t* correct_out, void* stream) {
-  MAE_REQUIRE(head_grads, "mae_engine_classifier_loss_and_grads: null head_grads");
-  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
-                         workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
-                         "mae_engine_classifier_loss_and_grads");
+  CLS_CALL(k);
+  CLS_CALL_TRAINING(k);
+  return classifier_impl(e, k, "mae_engine_classifier_loss_and_grads");
 }
 
 extern "C" int64_t mae_engine_classifier_workspace_bytes_ex(const mae_engine_t* e, int32_t batch, int32_t num_classes, int32_t with_cls) {
@@ -1230,9 +1253,9 @@ extern "C" int mae_engine_classifier_forward_ex(mae_engine_t* e, const float* pa
                                                 int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t with_cls, int32_t pool,
                                                 int32_t num_classes, void* workspace, int64_t workspace_bytes, float* logits, float* loss_out,
                                                 int32_t* correct_out, void* stream) {
-  MAE_REQUIRE(labels || (!loss_out && !correct_out), "mae_engine_classifier_forward_ex: loss / correct count need labels");
-  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, -1, 0, 1.f, workspace, workspace_bytes,
-                         nullptr, nullptr, nullptr, logits, loss_out, correct_out, stream, "mae_engine_classifier_forward_ex", with_cls, true);
+  CLS_CALL(k);
+  k.with_cls = with_cls; k.extended_pools = true;
+  return classifier_impl(e, k, "mae_engine_classifier_forward_ex");
 }
 
 extern "C" int mae_engine_classifier_loss_and_grads_ex(mae_engine_t* e, const float* params, const void* wcache, const float* head,
@@ -1241,10 +1264,10 @@ extern "C" int mae_engine_classifier_loss_and_grads_ex(mae_engine_t* e, const fl
                                                        int32_t train_embed, float grad_scale, void* workspace, int64_t workspace_bytes,
                                                        float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
                                                        int32_t* correct_out, void* stream) {
-  MAE_REQUIRE(head_grads, "mae_engine_classifier_loss_and_grads_ex: null head_grads");
-  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
-                         workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
-                         "mae_engine_classifier_loss_and_grads_ex", with_cls, true);
+  CLS_CALL(k);
+  CLS_CALL_TRAINING(k);
+  k.with_cls = with_cls; k.extended_pools = true;
+  return classifier_impl(e, k, "mae_engine_classifier_loss_and_grads_ex");
 }
 
 // mae_engine_classifier_loss_and_grads_ex with the head's soft targets; with nothing soft asked for, the same launches and bits
@@ -1255,13 +1278,11 @@ extern "C" int mae_engine_classifier_loss_and_grads_soft(mae_engine_t* e, const 
                                                          float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
                                                          int32_t* correct_out, const int64_t* labels_b, const float* lam,
                                                          float label_smoothing, void* stream) {
-  MAE_REQUIRE(head_grads, "mae_engine_classifier_loss_and_grads_soft: null head_grads");
-  MAE_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "mae_engine_classifier_loss_and_grads_soft: label_smoothing = %g outside [0, 1)",
-              (double)label_smoothing);
-  const HeadSoft soft{labels_b, lam, label_smoothing};
-  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
-                         workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
-                         "mae_engine_classifier_loss_and_grads_soft", with_cls, true, soft.active() ? &soft : nullptr);
+  CLS_CALL(k);
+  CLS_CALL_TRAINING(k);
+  k.with_cls = with_cls; k.extended_pools = true;
+  k.soft = {labels_b, lam, label_smoothing};
+  return classifier_impl(e, k, "mae_engine_classifier_loss_and_grads_soft");
 }
 
 // mae_engine_classifier_loss_and_grads_soft with stochastic depth: branch_scale (2 * depth, batch) scales each image's residual branches
@@ -1272,14 +1293,16 @@ extern "C" int mae_engine_classifier_loss_and_grads_sd(mae_engine_t* e, const fl
                                                        float* grads, float* head_grads, float* pos_grad, float* logits, float* loss_out,
                                                        int32_t* correct_out, const int64_t* labels_b, const float* lam,
                                                        float label_smoothing, const float* branch_scale, void* stream) {
-  MAE_REQUIRE(head_grads, "mae_engine_classifier_loss_and_grads_sd: null head_grads");
-  MAE_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "mae_engine_classifier_loss_and_grads_sd: label_smoothing = %g outside [0, 1)",
-              (double)label_smoothing);
-  const HeadSoft soft{labels_b, lam, label_smoothing};
-  return classifier_impl(e, params, wcache, head, images, image_dtype, labels, batch, pool, num_classes, train_blocks, train_embed, grad_scale,
-                         workspace, workspace_bytes, grads, head_grads, pos_grad, logits, loss_out, correct_out, stream,
-                         "mae_engine_classifier_loss_and_grads_sd", with_cls, true, soft.active() ? &soft : nullptr, branch_scale);
+  CLS_CALL(k);
+  CLS_CALL_TRAINING(k);
+  k.with_cls = with_cls; k.extended_pools = true;
+  k.soft = {labels_b, lam, label_smoothing};
+  k.branch_scale = branch_scale;
+  return classifier_impl(e, k, "mae_engine_classifier_loss_and_grads_sd");
 }
+
+#undef CLS_CALL
+#undef CLS_CALL_TRAINING
 
 // =====================================================================================================
 // Frozen-encoder features (scripts/evaluation/visualize_representation.py:87-108): the encoder over [cls | patches] or the
@@ -1288,9 +1311,8 @@ extern "C" int mae_engine_classifier_loss_and_grads_sd(mae_engine_t* e, const fl
 // =====================================================================================================
 extern "C" int64_t mae_engine_features_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls) {
   if (!e || batch <= 0 || (with_cls != 0 && with_cls != 1) || e->D % 4 != 0 || e->D > 1024) return -1;  // the pool kernel's width limit
-  const int T = with_cls ? e->L : e->L - 1;
   if (!batch_in_bound(e, batch)) return -1;
-  return make_plan_ex(e, batch, T, 1, 1, 1).total;
+  return make_encoder_plan(e, batch, with_cls != 0).total;
 }
 
 extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
@@ -1299,23 +1321,20 @@ extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params,
   const char* who = "mae_engine_extract_features";
   MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
   MAE_REQUIRE(images && feats, "%s: null argument", who);
-  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+  MAE_TRY(check_pool(with_cls, pool, true, who));
   MAE_REQUIRE(e->D % 4 == 0 && e->D <= 1024, "%s: embed_dim = %d must be a multiple of 4 and at most 1024", who, e->D);
-  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES, "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
-  MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
   MAE_REQUIRE(normalize == MAE_FEAT_NONE || normalize == MAE_FEAT_L2, "%s: normalize must be MAE_FEAT_NONE or MAE_FEAT_L2 (got %d)", who, normalize);
   MAE_TRY(check_image_dtype(image_dtype, who));
   const int64_t need = mae_engine_features_workspace_bytes(e, batch, with_cls);
   MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
   MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
-  const int T = with_cls ? e->L : e->L - 1;
-  const Plan pl = make_plan_ex(e, batch, T, 1, 1, 1);
+  const Plan pl = make_encoder_plan(e, batch, with_cls != 0);
+  const int T = pl.k;
   Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
   hipStream_t s = c.s;
   c.fwd_only = true;
   c.skip_final_norm = true;
-  if (with_cls) MAE_TRY(launch_iota_rows(c.buf<int32_t>(pl.keep32), batch, T, s));
-  else MAE_TRY(launch_iota_tokens(c.buf<int32_t>(pl.keep32), batch, T, s));
+  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
   MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
   const int lo = pool == MAE_POOL_MEAN_PATCHES && with_cls ? 1 : 0, hi = pool == MAE_POOL_CLS ? 1 : T;
   RUN(TK_LN_FWD, 0, (double)batch * (hi - lo) * e->D * (4 + c.as) + (double)batch * e->D * 4,

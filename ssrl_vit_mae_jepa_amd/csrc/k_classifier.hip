@@ -12,26 +12,13 @@
 // Soft targets (SOFT = true: mixup / CutMix label pairs and label smoothing, the MAE / DeiT fine-tuning loss):
 //   t[b][c] = eps / C + (1 - eps) * (lam[b] * [c == ya[b]] + (1 - lam[b]) * [c == yb[b]]),  sum_c t = 1, so
 //   row_loss = lse - sum_c t[c] * logit[c]  and  d_logits = (softmax - t) * grad_scale / B, rounded at the same point (3).
-// SOFT = false is the hard-label head as it always was: the launchers pick it whenever no soft option is active.
+// SOFT = false is the hard-label head as it always was: the launcher picks it whenever no soft option is active.
 #include "kernels.h"
 
 namespace mae {
 
 template <class T> __device__ __forceinline__ float head_round(float x) { return x; }
 template <> __device__ __forceinline__ float head_round<bf16>(float x) { return (float)(bf16)x; }
-
-__global__ void iota_rows_kernel(int32_t* __restrict__ keep, int64_t n, int L) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) keep[i] = (int)(i % L);
-}
-
-int launch_iota_rows(int32_t* keep32, int B, int L, hipStream_t s) {
-  const int64_t n = (int64_t)B * L;
-  MAE_REQUIRE(keep32 && n > 0 && n < (1ll << 31), "iota_rows: bad arguments");
-  hipLaunchKernelGGL(iota_rows_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, keep32, n, L);
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
 
 // The phases both head kernels share once the pooled vector sits in sp[0 .. D): logits, row loss / correct flag, d_logits and
 // the pooled copy.  Wave w owns classes w, w+4, ...; returns false when the caller has nothing left to do (no backward asked).
@@ -263,56 +250,50 @@ __global__ void __launch_bounds__(256) classifier_reduce_kernel(const float* __r
   }
 }
 
-int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int pool, const float* W, const float* bias, int C,
-                           const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
-                           float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out,
-                           const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s,
-                           const HeadSoft* soft) {
-  MAE_REQUIRE(feats && W && bias && row_loss && row_correct && B > 0 && L > 0, "classifier_head: bad arguments");
-  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "classifier_head: D = %d must be a multiple of 4 in [4, 1024]", D);
-  MAE_REQUIRE(C >= 2 && C <= HEAD_MAX_CLASSES, "classifier_head: num_classes = %d outside [2, %d]", C, HEAD_MAX_CLASSES);
-  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN, "classifier_head: pool must be MAE_POOL_CLS or MAE_POOL_MEAN");
-  MAE_REQUIRE(!dlogits_out || pooled_out, "classifier_head: the backward needs the pooled-feature buffer");
-  MAE_REQUIRE(!dfeat_out || dlogits_out, "classifier_head: the feature gradient needs d_logits");
-  MAE_REQUIRE(!cls_rows || (mean_all && rstd_all && mean_c && rstd_c), "classifier_head: class-row statistics need every buffer");
-  const bool on = soft && soft->active();
-  MAE_REQUIRE(!on || (labels && soft->eps >= 0.f && soft->eps < 1.f), "classifier_head: soft targets need labels and label_smoothing in [0, 1)");
-  const HeadSoft hs = on ? *soft : HeadSoft{nullptr, nullptr, 0.f};
-#define HEAD(T, SOFT) hipLaunchKernelGGL((classifier_head_kernel<T, SOFT>), dim3(B), dim3(256), 0, s, (const T*)feats, L, D, pool, W, bias, C, labels, hs, \
-                                         grad_scale, B, logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out, mean_all, rstd_all,  \
-                                         mean_c, rstd_c, cls_rows)
-  if (on) { if (dt == MAE_BF16) HEAD(bf16, true); else HEAD(float, true); }
-  else    { if (dt == MAE_BF16) HEAD(bf16, false); else HEAD(float, false); }
-#undef HEAD
-  MAE_LAUNCH_CHECK();
-  if (loss_out || correct_out) {
-    hipLaunchKernelGGL(classifier_reduce_kernel, dim3(1), dim3(256), 0, s, row_loss, row_correct, B, loss_out, correct_out);
-    MAE_LAUNCH_CHECK();
+int check_pool(int with_cls, int pool, bool extended, const char* who) {
+  if (!extended) {
+    MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN, "%s: pool must be MAE_POOL_CLS or MAE_POOL_MEAN (got %d)", who, pool);
+    return 0;
   }
+  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES,
+              "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
+  MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
   return 0;
 }
 
-int launch_classifier_head_range(const void* feats, int dt, int B, int seq, int D, int lo, int hi, const float* W, const float* bias, int C,
-                                 const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
-                                 float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out, hipStream_t s,
-                                 const HeadSoft* soft) {
-  MAE_REQUIRE(feats && W && bias && row_loss && row_correct && B > 0 && seq > 0, "classifier_head_range: bad arguments");
-  MAE_REQUIRE(lo >= 0 && lo < hi && hi <= seq, "classifier_head_range: rows [%d, %d) outside the sequence of %d", lo, hi, seq);
-  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "classifier_head_range: D = %d must be a multiple of 4 in [4, 1024]", D);
-  MAE_REQUIRE(C >= 2 && C <= HEAD_MAX_CLASSES, "classifier_head_range: num_classes = %d outside [2, %d]", C, HEAD_MAX_CLASSES);
-  MAE_REQUIRE(!dlogits_out || pooled_out, "classifier_head_range: the backward needs the pooled-feature buffer");
-  MAE_REQUIRE(!dfeat_out || dlogits_out, "classifier_head_range: the feature gradient needs d_logits");
-  const bool on = soft && soft->active();
-  MAE_REQUIRE(!on || (labels && soft->eps >= 0.f && soft->eps < 1.f), "classifier_head_range: soft targets need labels and label_smoothing in [0, 1)");
-  const HeadSoft hs = on ? *soft : HeadSoft{nullptr, nullptr, 0.f};
-#define HEAD(T, SOFT) hipLaunchKernelGGL((classifier_head_range_kernel<T, SOFT>), dim3(B), dim3(256), 0, s, (const T*)feats, seq, D, lo, hi, W, bias, C, \
-                                         labels, hs, grad_scale, B, logits_out, row_loss, row_correct, pooled_out, dlogits_out, (T*)dfeat_out)
-  if (on) { if (dt == MAE_BF16) HEAD(bf16, true); else HEAD(float, true); }
-  else    { if (dt == MAE_BF16) HEAD(bf16, false); else HEAD(float, false); }
+int launch_classifier_head(const HeadCall& h, hipStream_t s) {
+  const bool range = h.range();  // the mean over the patch rows [lo, seq)
+  const char* who = range ? "classifier_head_range" : "classifier_head";
+  const int B = h.B, lo = h.with_cls ? 1 : 0;
+  MAE_REQUIRE(h.feats && h.W && h.bias && h.row_loss && h.row_correct && B > 0 && h.seq > 0, "%s: bad arguments", who);
+  MAE_TRY(check_pool(h.with_cls, h.pool, true, who));
+  MAE_REQUIRE(!range || lo < h.seq, "%s: rows [%d, %d) outside the sequence of %d", who, lo, h.seq, h.seq);
+  MAE_REQUIRE(h.D % 4 == 0 && h.D >= 4 && h.D <= 1024, "%s: D = %d must be a multiple of 4 in [4, 1024]", who, h.D);
+  MAE_REQUIRE(h.C >= 2 && h.C <= HEAD_MAX_CLASSES, "%s: num_classes = %d outside [2, %d]", who, h.C, HEAD_MAX_CLASSES);
+  MAE_REQUIRE(!h.dlogits_out || h.pooled_out, "%s: the backward needs the pooled-feature buffer", who);
+  MAE_REQUIRE(!h.dfeat_out || h.dlogits_out, "%s: the feature gradient needs d_logits", who);
+  MAE_REQUIRE(!h.cls_rows || (!range && h.mean_all && h.rstd_all && h.mean_c && h.rstd_c), "%s: class-row statistics need every buffer", who);
+  const bool on = h.soft.active();
+  MAE_REQUIRE(!on || (h.labels && h.soft.eps >= 0.f && h.soft.eps < 1.f), "%s: soft targets need labels and label_smoothing in [0, 1)", who);
+  const HeadSoft hs = on ? h.soft : HeadSoft{nullptr, nullptr, 0.f};
+#define HEAD(T, SOFT)                                                                                                                          \
+  do {                                                                                                                                         \
+    if (range)                                                                                                                                 \
+      hipLaunchKernelGGL((classifier_head_range_kernel<T, SOFT>), dim3(B), dim3(256), 0, s, (const T*)h.feats, h.seq, h.D, lo, h.seq, h.W,     \
+                         h.bias, h.C, h.labels, hs, h.grad_scale, B, h.logits_out, h.row_loss, h.row_correct, h.pooled_out, h.dlogits_out,     \
+                         (T*)h.dfeat_out);                                                                                                     \
+    else                                                                                                                                       \
+      hipLaunchKernelGGL((classifier_head_kernel<T, SOFT>), dim3(B), dim3(256), 0, s, (const T*)h.feats, h.seq, h.D, h.pool, h.W, h.bias, h.C, \
+                         h.labels, hs, h.grad_scale, B, h.logits_out, h.row_loss, h.row_correct, h.pooled_out, h.dlogits_out,                  \
+                         (T*)h.dfeat_out, h.mean_all, h.rstd_all, h.mean_c, h.rstd_c, h.cls_rows);                                             \
+  } while (0)
+  if (on) { if (h.dt == MAE_BF16) HEAD(bf16, true); else HEAD(float, true); }
+  else    { if (h.dt == MAE_BF16) HEAD(bf16, false); else HEAD(float, false); }
 #undef HEAD
   MAE_LAUNCH_CHECK();
-  if (loss_out || correct_out) {
-    hipLaunchKernelGGL(classifier_reduce_kernel, dim3(1), dim3(256), 0, s, row_loss, row_correct, B, loss_out, correct_out);
+  if (h.loss_out || h.correct_out) {
+    hipLaunchKernelGGL(classifier_reduce_kernel, dim3(1), dim3(256), 0, s, h.row_loss, h.row_correct, B, h.loss_out, h.correct_out);
     MAE_LAUNCH_CHECK();
   }
   return 0;
@@ -424,50 +405,29 @@ int full_grad_split_slices(int B, int L, int D) {
   return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)B, (int64_t)CLS_EMBED_SLICES, cdiv(2048, per_slice)}));
 }
 
-int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s) {
-  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && L > 0, "full_grad_split: bad arguments");
-  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "full_grad_split: D = %d must be a multiple of 4 in [4, 1024]", D);
-  MAE_REQUIRE(dt == MAE_F32 || dt == MAE_BF16, "full_grad_split: dtype must be MAE_F32 or MAE_BF16 (got %d)", dt);
-  MAE_REQUIRE((int64_t)B * L < (1ll << 31), "full_grad_split: B * L < 2^31");
+// has_cls = false is the patch-only sequence: the sums land in rows 1..L of dpos ((L + 1) * D floats), and row 0 of dpos and dcls
+// (D floats) -- no token carries them -- become exact zeros.  Same slices and summation order either way.
+int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, bool has_cls,
+                           hipStream_t s) {
+  const char* who = has_cls ? "full_grad_split" : "patch_grad_split";
+  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && L > 0, "%s: bad arguments", who);
+  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "%s: D = %d must be a multiple of 4 in [4, 1024]", who, D);
+  MAE_REQUIRE(dt == MAE_F32 || dt == MAE_BF16, "%s: dtype must be MAE_F32 or MAE_BF16 (got %d)", who, dt);
+  MAE_REQUIRE((int64_t)B * L < (1ll << 31), "%s: B * L < 2^31", who);
   const int S = full_grad_split_slices(B, L, D);
   const dim3 grid((unsigned)cdiv((int64_t)L * (D / 4), 256), S);
-  if (dt == MAE_BF16)
-    hipLaunchKernelGGL((full_grad_split_kernel<bf16, true>), grid, dim3(256), 0, s, dx, B, L, D, (bf16*)dtok, partial);
-  else
-    hipLaunchKernelGGL((full_grad_split_kernel<float, true>), grid, dim3(256), 0, s, dx, B, L, D, (float*)dtok, partial);
+#define SPLIT(T, HAS_CLS) hipLaunchKernelGGL((full_grad_split_kernel<T, HAS_CLS>), grid, dim3(256), 0, s, dx, B, L, D, (T*)dtok, partial)
+  if (has_cls) { if (dt == MAE_BF16) SPLIT(bf16, true); else SPLIT(float, true); }
+  else         { if (dt == MAE_BF16) SPLIT(bf16, false); else SPLIT(float, false); }
+#undef SPLIT
   MAE_LAUNCH_CHECK();
-  MAE_TRY(launch_sum_partials(partial, S, L * D, dpos, nullptr, L * D, s));
-  MAE_HIP(hipMemcpyAsync(dcls, dpos, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
-  return 0;
-}
-
-// The patch-only sibling: dx is (B, N, D) with row t = patch token t + 1.  Same slices and summation order; the sums land in
-// rows 1..N of dpos ((N + 1) * D floats), and row 0 of dpos and dcls (D floats) -- no token carries them -- become exact zeros.
-int launch_patch_grad_split(const float* dx, int B, int N, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s) {
-  MAE_REQUIRE(dx && dtok && dpos && dcls && partial && B > 0 && N > 0, "patch_grad_split: bad arguments");
-  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "patch_grad_split: D = %d must be a multiple of 4 in [4, 1024]", D);
-  MAE_REQUIRE(dt == MAE_F32 || dt == MAE_BF16, "patch_grad_split: dtype must be MAE_F32 or MAE_BF16 (got %d)", dt);
-  MAE_REQUIRE((int64_t)B * N < (1ll << 31), "patch_grad_split: B * N < 2^31");
-  const int S = full_grad_split_slices(B, N, D);
-  const dim3 grid((unsigned)cdiv((int64_t)N * (D / 4), 256), S);
-  if (dt == MAE_BF16)
-    hipLaunchKernelGGL((full_grad_split_kernel<bf16, false>), grid, dim3(256), 0, s, dx, B, N, D, (bf16*)dtok, partial);
-  else
-    hipLaunchKernelGGL((full_grad_split_kernel<float, false>), grid, dim3(256), 0, s, dx, B, N, D, (float*)dtok, partial);
-  MAE_LAUNCH_CHECK();
-  MAE_TRY(launch_sum_partials(partial, S, N * D, dpos + D, nullptr, N * D, s));
-  MAE_HIP(hipMemsetAsync(dpos, 0, (size_t)D * 4, s));
-  MAE_HIP(hipMemsetAsync(dcls, 0, (size_t)D * 4, s));
-  return 0;
-}
-
-// out[0] += out[1] (the buffer sum of squares folded into a running total)
-__global__ void add_slot_kernel(float* out) { out[0] += out[1]; }
-
-int launch_grad_sumsq_accumulate(const float* g, int64_t n, float* io, float* scratch, hipStream_t s) {
-  MAE_TRY(launch_grad_sumsq(g, n, io + 1, scratch, s));
-  hipLaunchKernelGGL(add_slot_kernel, dim3(1), dim3(1), 0, s, io);
-  MAE_LAUNCH_CHECK();
+  MAE_TRY(launch_sum_partials(partial, S, L * D, has_cls ? dpos : dpos + D, nullptr, L * D, s));
+  if (has_cls) {
+    MAE_HIP(hipMemcpyAsync(dcls, dpos, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
+  } else {
+    MAE_HIP(hipMemsetAsync(dpos, 0, (size_t)D * 4, s));
+    MAE_HIP(hipMemsetAsync(dcls, 0, (size_t)D * 4, s));
+  }
   return 0;
 }
 
@@ -494,77 +454,81 @@ static HeadScratch head_scratch(void* scratch, int64_t B, int64_t C, int64_t D) 
   h.hsum = h.partial + seg(classifier_wgrad_partial_floats((int)B, (int)C, (int)D));
   return h;
 }
-}  // namespace mae
 
-namespace mae {
-// The one body of mae_classifier_head / _ex / _soft.  ex = false is the first call (with_cls = 1, pool cls or mean); soft null or
-// inactive launches the hard-label kernels.
-static int classifier_head_impl(const char* who, bool ex, const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim,
-                                int32_t with_cls, int32_t pool, const float* head, int32_t num_classes, const int64_t* labels,
-                                float grad_scale, float* logits, float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats,
-                                void* scratch, int64_t scratch_bytes, void* stream, const HeadSoft* soft) {
-  if (ex) {
-    MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
-    MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pool == MAE_POOL_MEAN_PATCHES,
-                "%s: pool must be MAE_POOL_CLS, MAE_POOL_MEAN or MAE_POOL_MEAN_PATCHES (got %d)", who, pool);
-    MAE_REQUIRE(pool != MAE_POOL_CLS || with_cls, "%s: MAE_POOL_CLS needs with_cls = 1 (a patch-only sequence has no class token)", who);
-  }
-  const bool range = ex && (!with_cls || pool == MAE_POOL_MEAN_PATCHES);  // the mean over the patch rows [lo, seq_len)
-  const int lo = with_cls ? 1 : 0;
-  MAE_REQUIRE(dtype == MAE_F32 || dtype == MAE_BF16, "%s: dtype must be MAE_F32 or MAE_BF16", who);
-  MAE_REQUIRE(!range || seq_len > lo, "%s: seq_len = %d leaves no patch row to pool", who, seq_len);
-  const int64_t need = mae_classifier_head_scratch_bytes(batch, num_classes, dim);
-  MAE_REQUIRE(need > 0 && scratch && scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0,
+// What mae_classifier_head / _ex / _soft add to a HeadCall: the caller's scratch, the packed head (W then bias), the head gradient
+// and whether the entry accepts the patch-only sequence and the patch-row mean.  They fill feats .. dfeat_out of `h` themselves.
+struct HeadEntry {
+  HeadCall h;
+  const float* head;
+  float* head_grads;
+  void* scratch;
+  int64_t scratch_bytes;
+  bool extended_pools;
+};
+
+// The one body of mae_classifier_head / _ex / _soft; soft targets with nothing active launch the hard-label kernels.
+static int classifier_head_impl(HeadEntry c, void* stream, const char* who) {
+  HeadCall& h = c.h;
+  MAE_REQUIRE(h.soft.eps >= 0.f && h.soft.eps < 1.f, "%s: label_smoothing = %g outside [0, 1)", who, (double)h.soft.eps);
+  MAE_TRY(check_pool(h.with_cls, h.pool, c.extended_pools, who));
+  const bool range = h.range();
+  MAE_REQUIRE(h.dt == MAE_F32 || h.dt == MAE_BF16, "%s: dtype must be MAE_F32 or MAE_BF16", who);
+  MAE_REQUIRE(!range || h.seq > h.with_cls, "%s: seq_len = %d leaves no patch row to pool", who, h.seq);
+  const int64_t need = mae_classifier_head_scratch_bytes(h.B, h.C, h.D);
+  MAE_REQUIRE(need > 0 && c.scratch && c.scratch_bytes >= need && ((uintptr_t)c.scratch & 255) == 0,
               "%s: scratch must hold mae_classifier_head_scratch_bytes (%lld) bytes, 256-byte aligned", who, (long long)need);
-  MAE_REQUIRE(!d_feats || head_grads, "%s: d_feats needs head_grads", who);
-  MAE_REQUIRE(!head_grads || labels, "%s: gradients need labels", who);
-  MAE_REQUIRE(!range || (head && (labels || (!loss_out && !correct_out))), "%s: null head, or loss / correct count without labels", who);
+  MAE_REQUIRE(!h.dfeat_out || c.head_grads, "%s: d_feats needs head_grads", who);
+  MAE_REQUIRE(!c.head_grads || h.labels, "%s: gradients need labels", who);
+  MAE_REQUIRE(!range || (c.head && (h.labels || (!h.loss_out && !h.correct_out))), "%s: null head, or loss / correct count without labels", who);
   hipStream_t s = (hipStream_t)stream;
-  const HeadScratch hs = head_scratch(scratch, batch, num_classes, dim);
-  const float* bias = head + (int64_t)num_classes * dim;
-  float* pooled = head_grads ? hs.pooled : nullptr;
-  float* dlogits = head_grads ? hs.dlogits : nullptr;
-  if (range)
-    MAE_TRY(launch_classifier_head_range(feats, dtype, batch, seq_len, dim, lo, seq_len, head, bias, num_classes, labels, grad_scale, logits,
-                                         hs.row_loss, hs.row_correct, loss_out, correct_out, pooled, dlogits, d_feats, s, soft));
-  else
-    MAE_TRY(launch_classifier_head(feats, dtype, batch, seq_len, dim, pool, head, bias, num_classes, labels, grad_scale, logits, hs.row_loss,
-                                   hs.row_correct, loss_out, correct_out, pooled, dlogits, d_feats, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                   s, soft));
-  if (!head_grads) return 0;
-  return launch_classifier_head_wgrad(hs.dlogits, hs.pooled, batch, num_classes, dim, hs.partial, hs.hsum, head_grads, s);
+  const HeadScratch hs = head_scratch(c.scratch, h.B, h.C, h.D);
+  h.W = c.head;
+  h.bias = c.head + (int64_t)h.C * h.D;
+  h.row_loss = hs.row_loss;
+  h.row_correct = hs.row_correct;
+  h.pooled_out = c.head_grads ? hs.pooled : nullptr;
+  h.dlogits_out = c.head_grads ? hs.dlogits : nullptr;
+  MAE_TRY(launch_classifier_head(h, s));
+  if (!c.head_grads) return 0;
+  return launch_classifier_head_wgrad(hs.dlogits, hs.pooled, h.B, h.C, h.D, hs.partial, hs.hsum, c.head_grads, s);
 }
 }  // namespace mae
 
+// The three head entries (see mae_hip.h) fill one record each: the first is [cls | patches] with MAE_POOL_CLS or MAE_POOL_MEAN,
+// _ex adds with_cls and the patch-row mean, _soft adds the soft targets.  They name their parameters alike:
+#define HEAD_ENTRY(c, extended)                                                                                          \
+  mae::HeadEntry c{{}, head, head_grads, scratch, scratch_bytes, extended};                                              \
+  c.h.feats = feats; c.h.dt = dtype; c.h.B = batch; c.h.seq = seq_len; c.h.D = dim; c.h.pool = pool; c.h.C = num_classes; \
+  c.h.labels = labels; c.h.grad_scale = grad_scale; c.h.logits_out = logits; c.h.loss_out = loss_out;                    \
+  c.h.correct_out = correct_out; c.h.dfeat_out = d_feats
 extern "C" int mae_classifier_head(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t pool,
                                    const float* head, int32_t num_classes, const int64_t* labels, float grad_scale, float* logits,
                                    float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats, void* scratch,
                                    int64_t scratch_bytes, void* stream) {
-  return mae::classifier_head_impl("mae_classifier_head", false, feats, dtype, batch, seq_len, dim, 1, pool, head, num_classes, labels, grad_scale,
-                                   logits, loss_out, correct_out, head_grads, d_feats, scratch, scratch_bytes, stream, nullptr);
+  HEAD_ENTRY(c, false);
+  return mae::classifier_head_impl(c, stream, "mae_classifier_head");
 }
 
-// the same on a sequence with (with_cls = 1) or without (0) a class-token row, with the patch-row mean: see mae_hip.h
 extern "C" int mae_classifier_head_ex(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls,
                                       int32_t pool, const float* head, int32_t num_classes, const int64_t* labels, float grad_scale,
                                       float* logits, float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats,
                                       void* scratch, int64_t scratch_bytes, void* stream) {
-  return mae::classifier_head_impl("mae_classifier_head_ex", true, feats, dtype, batch, seq_len, dim, with_cls, pool, head, num_classes, labels,
-                                   grad_scale, logits, loss_out, correct_out, head_grads, d_feats, scratch, scratch_bytes, stream, nullptr);
+  HEAD_ENTRY(c, true);
+  c.h.with_cls = with_cls;
+  return mae::classifier_head_impl(c, stream, "mae_classifier_head_ex");
 }
 
-// mae_classifier_head_ex with soft targets (see mae_hip.h); with nothing soft asked for, the hard-label launches of _ex
 extern "C" int mae_classifier_head_soft(const void* feats, int32_t dtype, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls,
                                         int32_t pool, const float* head, int32_t num_classes, const int64_t* labels, float grad_scale,
                                         float* logits, float* loss_out, int32_t* correct_out, float* head_grads, void* d_feats,
                                         void* scratch, int64_t scratch_bytes, const int64_t* labels_b, const float* lam,
                                         float label_smoothing, void* stream) {
-  MAE_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "mae_classifier_head_soft: label_smoothing = %g outside [0, 1)",
-              (double)label_smoothing);
-  const mae::HeadSoft soft{labels_b, lam, label_smoothing};
-  return mae::classifier_head_impl("mae_classifier_head_soft", true, feats, dtype, batch, seq_len, dim, with_cls, pool, head, num_classes, labels,
-                                   grad_scale, logits, loss_out, correct_out, head_grads, d_feats, scratch, scratch_bytes, stream, &soft);
+  HEAD_ENTRY(c, true);
+  c.h.with_cls = with_cls;
+  c.h.soft = {labels_b, lam, label_smoothing};
+  return mae::classifier_head_impl(c, stream, "mae_classifier_head_soft");
 }
+#undef HEAD_ENTRY
 
 // single-kernel entries (parity tests): the engine-only kernels of this file, see mae_hip.h
 extern "C" int64_t mae_full_grad_split_partial_floats(int32_t batch, int32_t seq_len, int32_t dim) {
@@ -574,8 +538,7 @@ extern "C" int64_t mae_full_grad_split_partial_floats(int32_t batch, int32_t seq
 
 extern "C" int mae_full_grad_split(const float* dx, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls, int32_t dtype, void* dtok,
                                    float* dpos, float* dcls, float* partial, void* stream) {
-  if (with_cls) return mae::launch_full_grad_split(dx, batch, seq_len, dim, dtype, dtok, dpos, dcls, partial, (hipStream_t)stream);
-  return mae::launch_patch_grad_split(dx, batch, seq_len, dim, dtype, dtok, dpos, dcls, partial, (hipStream_t)stream);
+  return mae::launch_full_grad_split(dx, batch, seq_len, dim, dtype, dtok, dpos, dcls, partial, with_cls != 0, (hipStream_t)stream);
 }
 
 extern "C" int mae_zero_token_rows(int64_t rows, int32_t seq_len, int32_t dim, int32_t dtype, float* dres, void* dres_c, void* stream) {

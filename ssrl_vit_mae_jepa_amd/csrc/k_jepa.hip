@@ -12,14 +12,15 @@
 
 namespace mae {
 
-// keep[b][j] = j + 1: every patch token, no class token (the target encoder sees the whole image)
-__global__ void iota_tokens_kernel(int32_t* __restrict__ keep, int64_t n, int N) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) keep[i] = (int32_t)(i % N) + 1;
+// keep[b][j] = first + j: N tokens of every image.  first = 1: every patch token, no class token (what the I-JEPA encoders see);
+// first = 0: the class token and every patch
+__global__ void iota_tokens_kernel(int32_t* __restrict__ keep, int64_t n, int N, int first) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) keep[i] = (int32_t)(i % N) + first;
 }
-int launch_iota_tokens(int32_t* keep32, int B, int N, hipStream_t s) {
-  MAE_REQUIRE(keep32 && B > 0 && N > 0, "iota_tokens: bad arguments");
+int launch_iota_tokens(int32_t* keep32, int B, int N, int first, hipStream_t s) {
   const int64_t n = (int64_t)B * N;
-  hipLaunchKernelGGL(iota_tokens_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 2048)), dim3(256), 0, s, keep32, n, N);
+  MAE_REQUIRE(keep32 && B > 0 && N > 0 && n < (1ll << 31) && (first == 0 || first == 1), "iota_tokens: bad arguments");
+  hipLaunchKernelGGL(iota_tokens_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 2048)), dim3(256), 0, s, keep32, n, N, first);
   MAE_LAUNCH_CHECK();
   return 0;
 }

@@ -105,6 +105,14 @@ int launch_grad_sumsq(const float* g, int64_t n, float* out, float* scratch, hip
   MAE_LAUNCH_CHECK();
   return 0;
 }
+// out[0] += out[1] (the buffer sum of squares folded into a running total)
+__global__ void add_slot_kernel(float* out) { out[0] += out[1]; }
+int launch_grad_sumsq_accumulate(const float* g, int64_t n, float* io, float* scratch, hipStream_t s) {
+  MAE_TRY(launch_grad_sumsq(g, n, io + 1, scratch, s));
+  hipLaunchKernelGGL(add_slot_kernel, dim3(1), dim3(1), 0, s, io);
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
 int launch_clip_from_sumsq(const float* sumsq, float max_norm, float* stats, hipStream_t s) {
   MAE_REQUIRE(sumsq && stats, "clip_from_sumsq: null argument");
   hipLaunchKernelGGL(clip_from_sumsq_kernel, dim3(1), dim3(1), 0, s, sumsq, max_norm, stats);

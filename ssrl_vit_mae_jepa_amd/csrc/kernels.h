@@ -38,7 +38,7 @@ int launch_add_into(const float* src, void* dst, int dst_dt, int64_t n, hipStrea
 int launch_sum_partials(const float* partial, int G, int C, float* out0, float* out1, int split, hipStream_t s);
 
 // ---- k_jepa.hip: I-JEPA predictor input / target rows / latent loss (no reference code: spec in DESIGN.md) -----------------
-int launch_iota_tokens(int32_t* keep32, int B, int N, hipStream_t s);                 // keep[b][j] = j + 1
+int launch_iota_tokens(int32_t* keep32, int B, int N, int first, hipStream_t s);      // keep[b][j] = first + j: N tokens of every image
 int launch_fill(float* p, float v, int64_t n, hipStream_t s);
 int launch_build_tail_row_map(int seqs, int T, int m, int32_t* rows, hipStream_t s);  // last m rows of every sequence of T
 int launch_rows_from_tokens(const int32_t* tok, int B, int per_image, int N, int32_t* rows, hipStream_t s);  // b*N + tok-1
@@ -76,38 +76,45 @@ struct HeadSoft {
   float eps;
   bool active() const { return labels_b || lam || eps != 0.f; }
 };
-// keep[b*L + j] = j (every token of every image)
-int launch_iota_rows(int32_t* keep32, int B, int L, hipStream_t s);
-// one block per image: pooled = feats[b, 0] or mean over L rows; logits = pooled W^T + bias; row loss / correct flag;
-// with dlogits_out: d_logits (and pooled, both fp32, rounded at the bf16 points); with dfeat_out: cls -> (B, D) compact
-// d_pooled, mean -> (B*L, D) d_pooled / L; with cls_rows: class-row map and its LayerNorm statistics (compact).
-// loss_out = mean of the row losses, correct_out = number of correct rows (fixed-order reduction; either may be null)
-int launch_classifier_head(const void* feats, int dt, int B, int L, int D, int pool, const float* W, const float* bias, int C,
-                           const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
-                           float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out,
-                           const float* mean_all, const float* rstd_all, float* mean_c, float* rstd_c, int32_t* cls_rows, hipStream_t s,
-                           const HeadSoft* soft = nullptr);
-// the same head over the mean of rows [lo, hi) of each image's seq rows, four waves loading rows; dfeat_out (B*seq, D): d_pooled /
-// (hi - lo) on the pooled rows, exact zeros on the others
-int launch_classifier_head_range(const void* feats, int dt, int B, int seq, int D, int lo, int hi, const float* W, const float* bias, int C,
-                                 const int64_t* labels, float grad_scale, float* logits_out, float* row_loss, int32_t* row_correct,
-                                 float* loss_out, int32_t* correct_out, float* pooled_out, float* dlogits_out, void* dfeat_out, hipStream_t s,
-                                 const HeadSoft* soft = nullptr);
+// The pool rules every caller of the head shares: with_cls 0 or 1, a known pool, and MAE_POOL_CLS only on a sequence with a class
+// token.  extended = false is a first-generation entry point: [cls | patches] with MAE_POOL_CLS or MAE_POOL_MEAN, nothing else.
+int check_pool(int with_cls, int pool, bool extended, const char* who);
+// One head call.  feats is (B * seq, D) in dt; logits = pooled W^T + bias; row loss / correct flag per image; loss_out = mean of
+// the row losses, correct_out = number of correct rows (fixed-order reduction; either may be null).
+//   with dlogits_out: d_logits and pooled (both fp32, rounded at the bf16 points);
+//   with dfeat_out:   MAE_POOL_CLS -> (B, D) compact d_pooled, a mean -> (B * seq, D): d_pooled / rows on the pooled rows, exact
+//                     zeros on the others;
+//   with cls_rows:    (MAE_POOL_CLS) the class-row map and the rows' LayerNorm statistics, compact.
+// Two kernels, two summation orders: MAE_POOL_CLS and the all-row mean behind a class token take one block per image with each
+// thread walking the rows serially; a patch-only sequence or MAE_POOL_MEAN_PATCHES pools rows [with_cls, seq) with four waves
+// loading rows and their partial sums added through LDS.
+struct HeadCall {
+  const void* feats = nullptr;
+  int dt = MAE_F32, B = 0, seq = 0, D = 0, with_cls = 1, pool = MAE_POOL_CLS, C = 0;
+  const float *W = nullptr, *bias = nullptr;
+  const int64_t* labels = nullptr;
+  HeadSoft soft = {nullptr, nullptr, 0.f};
+  float grad_scale = 1.f;
+  float *logits_out = nullptr, *row_loss = nullptr, *loss_out = nullptr, *pooled_out = nullptr, *dlogits_out = nullptr;
+  int32_t *row_correct = nullptr, *correct_out = nullptr, *cls_rows = nullptr;
+  void* dfeat_out = nullptr;
+  const float *mean_all = nullptr, *rstd_all = nullptr;  // class-row statistics: every row's, read ...
+  float *mean_c = nullptr, *rstd_c = nullptr;            // ... and one per image, written
+  bool range() const { return !with_cls || pool == MAE_POOL_MEAN_PATCHES; }
+};
+int launch_classifier_head(const HeadCall& h, hipStream_t s);
 // head_grads[0 .. C*D) = dW, [C*D .. C*D+C) = db; partial >= classifier_wgrad_partial_floats, sum_out >= round_up(C*D+C, 4) floats
 int64_t classifier_wgrad_partial_floats(int B, int C, int D);
 int launch_classifier_head_wgrad(const float* dlogits, const float* pooled, int B, int C, int D, float* partial, float* sum_out,
                                  float* head_grads, hipStream_t s);
 // zero every row of dres / dres_c (B*L rows) whose token index is not 0
 int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, void* dres_c, hipStream_t s);
-// one read of dx (B, L, D): dtok = dx with class rows zeroed, dpos (L*D) = sum over images, dcls (D) = dpos[0].
-// partial >= full_grad_split_slices(B, L, D) * L * D floats
+// one read of dx (B, L, D), L rows per image.  has_cls: dtok = dx with class rows zeroed, dpos (L*D) = sum over images, dcls (D) =
+// dpos[0].  Patch-only (row t is patch token t + 1): dtok = dx, dpos ((L + 1) * D) rows 1..L = sum over images, dpos row 0 and
+// dcls = exact zeros.  partial >= full_grad_split_slices(B, L, D) * L * D floats
 int full_grad_split_slices(int B, int L, int D);
-int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s);
-// patch-only sequence, dx (B, N, D): dtok = dx, dpos rows 1..N = sum over images, dpos row 0 and dcls = exact zeros.
-// partial >= full_grad_split_slices(B, N, D) * N * D floats
-int launch_patch_grad_split(const float* dx, int B, int N, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, hipStream_t s);
-// io[0] += sum(g^2) (io[1] is a temporary)
-int launch_grad_sumsq_accumulate(const float* g, int64_t n, float* io, float* scratch, hipStream_t s);
+int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* dtok, float* dpos, float* dcls, float* partial, bool has_cls,
+                           hipStream_t s);
 
 // ---- k_representation.hip: frozen-encoder features and the k-NN probe -----------------------------------------------------
 // out[b] (fp32, D) = pool over rows [row_lo, row_hi) of LN(x_mid + branch) of image b (seq rows each), then f / (||f|| + 1e-8)
@@ -193,6 +200,8 @@ int launch_loss_stage1(K kernel, int grid, size_t lds, hipStream_t s, T* dpred, 
 // stats[0] = ||g||_2, stats[1] = min(1, max_norm/(norm+1e-6)).  scratch >= 1024+ floats
 int launch_grad_norm(const float* g, int64_t n, float max_norm, float* stats, float* scratch, hipStream_t s);
 int launch_grad_sumsq(const float* g, int64_t n, float* out, float* scratch, hipStream_t s);
+// io[0] += sum(g^2) (io[1] is a temporary)
+int launch_grad_sumsq_accumulate(const float* g, int64_t n, float* io, float* scratch, hipStream_t s);
 int launch_clip_from_sumsq(const float* sumsq, float max_norm, float* stats, hipStream_t s);
 // AdamW with g scaled by stats[1]; optionally refresh bf16 copy of the params (wbf may be null)
 // ema_target != null: target[0 .. ema_n) = ema_momentum * target + (1 - ema_momentum) * p_new in the same sweep (+ its bf16 copy)

@@ -323,6 +323,49 @@ def test_ex_with_cls_equals_old_entry_point(dev, pool):
     assert rc != 0 and b"class token" in lib.mae_last_error()
 
 
+@pytest.mark.parametrize("pool", ["cls", "mean"])
+def test_module_calls_equal_first_entry_points(dev, pool):
+    """The Python module always takes the widest entries (loss_and_grads -> _sd, evaluate -> forward_ex).  With nothing extended
+    asked for they issue the launches of the first entry points: every output has the bits of the direct narrow C call."""
+    from ssrl_vit_mae_jepa_amd._lib import check, lib
+    from ssrl_vit_mae_jepa_amd.mae import _ptr
+    mod, _ = TC.build_module(dev, "bf16", "full", pool)
+    clf, m = mod.model, mod.model.mae
+    assert not clf.extended and mod.label_smoothing == 0.0
+    B = 6
+    images = O.synthetic_images(B, MICRO, seed=8).to(dev)
+    labels = torch.tensor([0, 3, 9, 2, 2, 5], device=dev)
+    head_g, pos_g = mod._grad_buffers()
+    common = (m.engine.handle, _ptr(m.flat_params), _ptr(m._weights()), _ptr(clf.head.flat), _ptr(images), m._img_dt(images), _ptr(labels), B,
+              POOL[pool], 10)
+    outs = []
+    for through_module in (False, True):
+        m.flat_grads.zero_(); head_g.fill_(7.0); pos_g.fill_(7.0)
+        logits = torch.empty(B, 10, device=dev)
+        if through_module:
+            loss, correct = mod.loss_and_grads(images, labels, logits_out=logits)
+        else:
+            ws = clf.workspace(B)
+            loss, correct = torch.empty(1, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+            check(lib.mae_engine_classifier_loss_and_grads(*common, 2, 1, 1.0, _ptr(ws), ws.numel(), _ptr(m.flat_grads), _ptr(head_g), _ptr(pos_g),
+                                                           _ptr(logits), _ptr(loss), _ptr(correct), stream(dev)))
+        torch.cuda.synchronize()
+        outs.append([t.clone() for t in (m.flat_grads, head_g, pos_g, logits, loss, correct)])
+    for a, b in zip(*outs):
+        assert torch.isfinite(a.float()).all() and torch.equal(a, b)
+    assert float(outs[0][0].abs().max()) > 0 and not torch.equal(outs[0][1], torch.full_like(head_g, 7.0))  # the gradients were written
+    # evaluation: ViTClassifier.evaluate against mae_engine_classifier_forward
+    ws = clf.workspace(B)
+    logits, loss, correct = torch.empty(B, 10, device=dev), torch.empty(1, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib.mae_engine_classifier_forward(*common, _ptr(ws), ws.numel(), _ptr(logits), _ptr(loss), _ptr(correct), stream(dev)))
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        got = clf.evaluate(images, labels)
+    torch.cuda.synchronize()
+    for a, b in zip((logits, loss, correct), got):
+        assert torch.isfinite(a.float()).all() and torch.equal(a, b)
+
+
 def test_vits8_geometry_patch_only_full_mode(dev):
     """96 px, patch 8: 144 rows, depth 12, bf16 -- the MFMA attention and the NT / wgrad ring kernels at T = 144."""
     cfg = O.VIT_S8_YAMLDEC
