@@ -1,9 +1,12 @@
 """The per-element GEMM checker of tests/gemm_ref.py on the CPU: it accepts the output of a correct kernel, emulated as bf16
 operands with fp32 accumulation in 64-deep steps, and rejects each fault a wrong tile loop or epilogue would leave behind.
 Also on the CPU: the dispatch restatement's coverage of the -m gpu table, and the shipped ISA of the NT kernel against the
-gfx950 store-data hazard of bstore16 (k_gemm_nt3.hip)."""
+gfx950 store-data hazard of bstore16 (k_gemm_nt3.hip).  Second half: the kernels behind nt3 (tests/test_gpu_gemm_fallback.py):
+the restated dispatch chain against the table, an emulation of every route at every table shape (random data inside the bound,
+small integers bit-equal), and the faults those kernels can have, each injected at one of the table's own shapes."""
 import os
 import subprocess
+import zlib
 from pathlib import Path
 
 import pytest
@@ -200,3 +203,366 @@ def test_isa_scan_sees_a_scalar_soffset():
                      "\tbuffer_store_dwordx4 v[96:99], v104, s[8:11], s12 offen", ".Lfunc_end0:", "\tbuffer_store_dword v1, v2, s[0:3], s4 offen"])
     bad, count = R.scan_nt3_stores(asm)
     assert count == {"_ZN3mae15gemm_nt3_kernelILi0EEEv": 2} and len(bad["_ZN3mae15gemm_nt3_kernelILi0EEEv"]) == 1
+
+
+# ================================================================================================ the fallback kernels
+# (tests/test_gpu_gemm_fallback.py runs the same tables on the device)
+FWD_CASES = R.fallback_fwd_cases(256)
+WGRAD_CASES = R.fallback_wgrad_cases()
+
+
+# ------------------------------------------------------------------------------------------------ route restatement
+def test_fallback_routes_of_the_table():
+    """fwd_route / wgrad_route give the label each group of the table was written for (every case is named after it), the shape
+    lists of the table land where they were meant to, and the table has no gap."""
+    assert [c.id for c in FWD_CASES + WGRAD_CASES if c.route().label != c.name] == []
+    for shapes, lbl in ((R.RG_SHAPES, "nt1<2,RG>"), (R.NI2_SHAPES, "nt1<NI=2>"), (R.NI4_SHAPES, "nt1<NI=4>")):
+        assert {R.fwd_route(M, N, K, "bf16", R.NONE, False).label for M, N, K in shapes} == {lbl}
+    assert [R.fwd_route(M, N, K, "bf16", R.NONE, False, sel="v1").label for M, N, K in R.V1_SHAPES] == ["nt1<NI=4>", "nt1<NI=2>", "nt1<NI=2>"]
+    assert [R.fwd_route(M, N, K, "bf16", R.NONE, False).label for M, N, K in R.V1_SHAPES] == ["nt3", "nt3", "nt1<NI=2>"]
+    assert R.fwd_route(300, 384, 384, "bf16", R.NONE, False, sel="v2").label == "nt2" and R.fwd_route(300, 384, 384, "bf16", R.NONE, False, sel="v1x").label == "nt3"
+    for M, N, K in R.NT2_SHAPES + R.NT2_F32_SHAPES:
+        for mode in (R.GELU, R.RESID, R.DGELU):
+            assert R.fwd_route(M, N, K, "bf16", mode, True).label == "nt2"
+        for mode in (R.GELU_GRAD, R.GELU_ACT, R.MUL):
+            assert R.fwd_route(M, N, K, "bf16", mode, True).label == "nt2" and R.fwd_route(M, N, K, "bf16", mode, False).label == "nt3"
+    # the tile heights of gemm_nt2_kernel: 192 rows (NI, MI) = (6, 3), 256 rows (4, 4) and, once 192-row tiles need a second round, (6, 4)
+    assert R.fwd_route(300, 192, 192, "bf16", R.GELU, False).layout == (6, 3) and R.fwd_route(300, 128, 256, "bf16", R.GELU, False).layout == (4, 4)
+    assert R.fwd_route(*R.NT2_BM256, "bf16", R.GELU, False).layout == (6, 4) and R.fwd_route(*R.NT2_BM256, "bf16", R.GELU, False).tile == (256, 192)
+    assert R.fwd_route(70, 144, 144, "bf16", R.NONE, False).label == "nt1<2,RG>"
+    assert R.fwd_route(70, 144, 144, "bf16", R.NONE, False, aligned=False).label == "generic<bf16,bf16>"
+    assert R.fwd_route(31, 20, 24, "bf16", R.NONE, False).label == "generic<bf16,bf16>" and R.fwd_route(37, 12, 64, "bf16", R.NONE, True).label == "generic<bf16,f32>"
+    assert R.fwd_route(5000, 384, 384, "f32", R.NONE, True).label == "generic<f32,f32>"
+    for lbl, shapes in R.TN_SHAPES.items():
+        for N, K in shapes:
+            for M in R.TN_M + (3000,):
+                assert R.wgrad_route(M, N, K, "bf16", True).label == lbl, (lbl, M, N, K)
+    assert R.wgrad_route(700, 128, 128, "bf16", True).S == 1 and R.wgrad_route(1100, 128, 128, "bf16", True).S == 2
+    assert R.wgrad_route(1100, 128, 128, "bf16", True).m_chunk == 576 and R.wgrad_route(3000, 144, 144, "bf16", True).S == 5
+    assert R.fallback_coverage_gaps(FWD_CASES + WGRAD_CASES, 256) == []
+    assert R.fallback_coverage_gaps([c for c in FWD_CASES + WGRAD_CASES if (c.M, c.N, c.K) != (33000, 64, 64)], 256) != []
+
+
+def test_empty_chunk_splits_are_pinned():
+    r = R.wgrad_route(8200, 128, 128, "bf16", True)
+    assert (r.label, r.S, r.m_chunk) == ("tn<4,4>", 16, 576) and 15 * r.m_chunk > 8200 > 14 * r.m_chunk
+    r = R.wgrad_route(33000, 64, 64, "bf16", True)
+    assert (r.label, r.S, r.m_chunk) == ("tn<2,2>", 64, 576) and sum(1 for s in range(64) if s * 576 >= 33000) == 6
+    assert not R.ring_shape_ok(8200, 128, 128) and not R.ring_shape_ok(33000, 64, 64)
+    r = R.wgrad_route(4100, 192, 192, "bf16", True, sel="v1")
+    assert (r.label, r.S, r.m_chunk) == ("tn<2,2>", 8, 576)
+    assert R.wgrad_route(4100, 192, 192, "bf16", True).label == "ring" and R.wgrad_route(4100, 192, 192, "bf16", True, sel="v4").label == "ring"
+    assert R.wgrad_route(4095, 192, 192, "bf16", True).label == "tn<2,2>"
+    assert R.wgrad_route(8200, 128, 128, "bf16", False, has_scratch=False).label == "generic_tn_splitk"   # S > 1 without a slab
+
+
+def test_shipped_default_and_vitl14_patch_embed_routes():
+    """configs/mae.yaml (encoder width 144): every encoder launch is nt1<2,RG>, every encoder weight gradient tn<4,4,RG>; the ViT-L/14
+    patch embed (K = 588) is generic, its weight gradient at the engine's M split-K with atomics."""
+    rows = [r for r in R.engine_launches(R.MAE_YAML) if " enc " in r[0] or "embed" in r[0]]
+    assert len(rows) == 11 and all(R.fwd_route(M, N, K, "bf16", mode, f32).label == "nt1<2,RG>" for _, M, N, K, mode, f32, _ in rows)
+    assert {r[0] for r in R.dropped_engine_launches() if r[0].startswith("mae_yaml")} == {r[0] for r in rows}
+    for N, K in ((432, 144), (144, 144), (576, 144), (144, 576), (144, 192), (192, 144)):
+        assert R.wgrad_route(72000, N, K, "bf16", True).label == "tn<4,4,RG>"
+    for net in ("vitl14_target", "vitl14_ctx"):
+        (row,) = [r for r in R.dropped_engine_launches() if r[0] == f"{net} patch embed"]
+        assert R.fwd_route(row[1], 1024, 588, "bf16", R.NONE, True).label == "generic<bf16,f32>"
+    r = R.wgrad_route(25600, 1024, 588, "bf16", True)
+    assert (r.label, r.nz, r.ordered, r.colsum) == ("generic_tn_splitk", 13, False, True)
+    assert R.wgrad_route(4097, 384, 384, "f32", True).label == "generic_tn_splitk" and R.wgrad_route(4096, 384, 384, "f32", True).label == "generic_tn"
+    have = {(c.N, c.K, c.mode, c.f32, c.bias) for c in FWD_CASES if c.dt == "bf16" and c.sel is None and not c.misalign and c.M <= 1024}
+    assert all(row[2:] in have for row in R.dropped_engine_launches())
+    assert len(R.nt_cases(256)) == 156          # the nt3 table is what it was
+
+
+def test_erf_budget_is_the_engine_kernels_one():
+    from tests import engine_kernels_ref as E
+    x = torch.linspace(-7.5, 7.5, 301, dtype=torch.float64)
+    q, eq = E.gelu_slope64(x.numpy())
+    assert torch.allclose(R.gelu_slope64(x), torch.from_numpy(q), rtol=1e-12, atol=1e-15)
+    assert torch.allclose(R.erf_budget(x)[1], torch.from_numpy(eq), rtol=1e-9, atol=0)
+
+
+# ------------------------------------------------------------------------------------------------ emulations
+def _fma_chain(a, b):
+    """sum_k a[:, k] b[:, k]^T as one fmaf chain in ascending k per element (gemm_generic_kernel); a (m, k), b (n, k)."""
+    acc = torch.zeros(a.shape[0], b.shape[0], dtype=torch.float32)
+    ad, bd = a.double(), b.double()
+    for k in range(a.shape[1]):
+        acc = (ad[:, k:k + 1] * bd[None, :, k] + acc.double()).float()     # the product is exact in fp64, the sum rounded once more
+    return acc
+
+
+def _mfma_sum(a, b, acc=None):
+    """The same sum as 32-deep MFMAs: each step's products summed exactly, the step added to the fp32 accumulator."""
+    acc = torch.zeros(a.shape[0], b.shape[0], dtype=torch.float32) if acc is None else acc
+    for k0 in range(0, a.shape[1], 32):
+        acc = acc + (a[:, k0:k0 + 32].double() @ b[:, k0:k0 + 32].double().t()).float()
+    return acc
+
+
+def _cast(v, f32):
+    return v.float() if f32 else v.float().bfloat16()
+
+
+def emulate_fwd(case, route, A, W, bias, aux, fault=None, tile=(0, 0)):
+    """(out, out2) with R_GUARD NaN guard rows behind row M - 1, as a correct kernel of this route's order class computes them;
+    fault injects one of the mistakes these kernels can make into tile `tile` (route.tile units)."""
+    M, N, K, f32, mode = case.M, case.N, case.K, case.f32, case.mode
+    bm, bn = route.tile
+    rows, cols = slice(tile[0] * bm, min(M, (tile[0] + 1) * bm)), slice(tile[1] * bn, min(N, (tile[1] + 1) * bn))
+    summ = _fma_chain if route.label.startswith("generic") else _mfma_sum
+    acc = summ(A, W)
+    if fault == "ktail":       # the ragged K tail dropped for one tile column
+        k_full = K // 64 * 64
+        acc[:, cols] = summ(A[:, :k_full], W[cols, :k_full]) if k_full else 0
+    b2d = bias[None].expand(M, N).clone() if bias is not None else torch.zeros(M, N)
+    if fault == "bias":
+        b2d[rows, cols] = 0
+    v = acc + b2d
+    out2 = None
+    if mode == R.NONE:
+        out = _cast(v, f32)
+        if fault == "double_round":
+            out = (acc.bfloat16().float() + b2d).bfloat16()
+    elif mode == R.GELU:
+        out = _cast(v, f32)
+        out2 = _cast(R.gelu64(v.double() if fault == "gelu_unrounded" else out.double()), f32)
+    elif mode == R.RESID:
+        out = v + aux
+        if fault == "resid":
+            out[rows, cols] = v[rows, cols]
+    elif mode == R.DGELU:
+        out = _cast(v * R.gelu_slope64(aux.double()).float(), f32)
+    elif mode == R.MUL:
+        out = _cast(v * aux.float(), f32)
+    else:
+        c = _cast(v, f32).double()
+        act = _cast(R.gelu64(c), f32)
+        out, out2 = (_cast(R.gelu_slope64(c), f32), act) if mode == R.GELU_GRAD else (act, None)
+    if fault == "shift8":      # one 8-column group stored 8 columns to the left
+        c0 = cols.start
+        out[rows, c0:c0 + 8] = out[rows, c0 + 8:c0 + 16].clone()
+    full = [torch.cat([o, torch.full((R_GUARD, N), float("nan"), dtype=o.dtype)]) if o is not None else None for o in (out, out2)]
+    if fault == "row_ge_M":
+        full[0][M] = full[0][M - 1]
+    return full
+
+
+R_GUARD = 8
+
+
+def _host_operands(case, integer):
+    g = torch.Generator().manual_seed(zlib.crc32(f"{case.id}{integer}".encode()))
+    dt = torch.bfloat16 if case.dt == "bf16" else torch.float32
+    odt = torch.float32 if getattr(case, "f32", True) else torch.bfloat16
+
+    def op(shape, dtype, scale=1.0):
+        return torch.randint(-3, 4, shape, generator=g).to(dtype) if integer else (torch.randn(shape, generator=g) * scale).to(dtype)
+
+    if isinstance(case, R.WgradCase):
+        return [(op((case.M, N), dt), op((case.M, K), dt)) for N, K in [(case.N, case.K)] + ([case.pair] if case.pair else [])]
+    A, W = op((case.M, case.K), dt), op((case.N, case.K), dt, case.K ** -0.5)
+    bias = op((case.N,), torch.float32) if case.bias else None
+    aux = None
+    if case.mode == R.MUL:
+        aux = op((case.M, case.N), odt) if integer else (torch.rand(case.M, case.N, generator=g) * 4 - 2).to(odt)
+    elif case.mode == R.DGELU:
+        aux = op((case.M, case.N), odt, 1.5).clamp_(-7, 7)
+    elif case.mode == R.RESID:
+        aux = op((case.M, case.N), torch.float32)
+    return A, W, bias, aux
+
+
+def _judge_fwd(case, integer, fault=None, tile=(0, 0)):
+    """(ok, report, guard ok, exact ok): what the GPU module asserts of one launch, on the emulation."""
+    route = case.route()
+    A, W, bias, aux = _host_operands(case, integer)
+    out, out2 = emulate_fwd(case, route, A, W, bias, aux, fault, tile)
+    M = case.M
+    rep = R.check_nt(A, W, bias, aux, case.mode, out[:M], out2[:M] if out2 is not None else None, tile=route.tile, roundings=route.roundings,
+                     gelu=route.gelu, what=case.id, chunk_elems=1 << 22)
+    guard = R.guard_intact(out, M) and (out2 is None or R.guard_intact(out2, M))
+    want = R.exact_forward(A, W, bias, aux, case.mode, case.f32) if integer else None
+    exact = want is None or torch.equal(out[:M].double(), want)
+    return rep.ok and guard and exact, rep, guard, exact
+
+
+@pytest.mark.parametrize("case", FWD_CASES, ids=lambda c: c.id)
+def test_fallback_forward_emulation_passes(case):
+    """bf16 (or fp32) operands, fp32 accumulation in the route's order class (32-deep MFMA steps / one fmaf chain), its rounding
+    points: inside the bound on random data, bit-equal on integers."""
+    for integer in (False, True):
+        ok, rep, guard, exact = _judge_fwd(case, integer)
+        assert ok, (str(rep), guard, exact)
+        assert rep.n == case.M * case.N * (2 if case.mode in (R.GELU, R.GELU_GRAD) else 1)
+
+
+def emulate_wgrad(route, dY, A, want_db, fault=None, tile=(0, 0)):
+    """(dW, db) as the route's kernels compute them; fault: 'step' drops the rows of the second 64-row step of the last non-empty
+    M-split in tile `tile`, 'slab' leaves the last (empty) split's slab of that tile at the NaN fill."""
+    M, N = dY.shape
+    K = A.shape[1]
+    tn_, tk_ = route.tile
+    rows, cols = slice(tile[0] * tn_, min(N, (tile[0] + 1) * tn_)), slice(tile[1] * tk_, min(K, (tile[1] + 1) * tk_))
+    ones = torch.ones(M, 1, dtype=dY.dtype)
+    if route.label.startswith("tn<") or route.label == "ring":
+        S, mc = route.S, route.m_chunk if route.S > 1 else M
+        live = [s for s in range(S) if s * mc < M]
+        slabs, slabs_b = [], []
+        for s in range(S):
+            r0, r1 = min(M, s * mc), min(M, (s + 1) * mc)
+            w = _mfma_sum(dY[r0:r1].t(), A[r0:r1].t()) if r1 > r0 else torch.zeros(N, K)
+            b = _mfma_sum(dY[r0:r1].t(), ones[r0:r1].t())[:, 0] if r1 > r0 else torch.zeros(N)
+            if fault == "step" and s == live[-1]:
+                keep = torch.ones(r1 - r0, dtype=torch.bool)
+                keep[64:128] = False
+                w[rows, cols] = _mfma_sum(dY[r0:r1][keep].t(), A[r0:r1][keep].t())[rows, cols]
+            if fault == "slab" and s == S - 1:
+                assert r1 == r0, "the last split is not empty"
+                w[rows, cols] = float("nan")
+            slabs.append(w); slabs_b.append(b)
+
+        def reduce(parts):
+            if S == 1:
+                return parts[0]
+            red = []
+            for sl in range(8):   # slab_reduce_kernel: slice sl adds slabs sl, sl + 8, ..; the 8 slices are added in order
+                t = torch.zeros_like(parts[0])
+                for s in range(sl, S, 8):
+                    t = t + parts[s]
+                red.append(t)
+            t = red[0]
+            for k in range(1, 8):
+                t = t + red[k]
+            return t
+        return reduce(slabs), reduce(slabs_b) if want_db else None
+    chunk = M if M <= 4096 else 2048
+    parts = [_fma_chain(dY[r0:r0 + chunk].t(), A[r0:r0 + chunk].t()) for r0 in range(0, M, chunk)]
+    dW = torch.zeros(N, K)
+    for i in torch.randperm(len(parts), generator=torch.Generator().manual_seed(5)).tolist():    # atomicAdd: some order
+        dW = dW + parts[i]
+    db = None
+    if want_db:   # colsum_kernel + sum_partials_kernel
+        G = min(-(-M // 4), 256)
+        y = dY.float()
+        part = torch.zeros(G, N)
+        for bx in range(G):
+            wv = []
+            for wave in range(4):
+                t = torch.zeros(N)
+                for r in range(bx * 4 + wave, M, 4 * G):
+                    t = t + y[r]
+                wv.append(t)
+            part[bx] = ((wv[0] + wv[1]) + wv[2]) + wv[3]
+        red = []
+        for rl in range(32):
+            t = torch.zeros(N)
+            for i in range(rl, G, 32):
+                t = t + part[i]
+            red.append(t)
+        db = torch.zeros(N)
+        for j in range(32):
+            db = db + red[j]
+    return dW, db
+
+
+def _judge_wgrad(case, integer, fault=None, tile=(0, 0)):
+    reps, ok = [], True
+    probs = [(case.N, case.K)] + ([case.pair] if case.pair else [])
+    for (N, K), (dY, A) in zip(probs, _host_operands(case, integer)):
+        route = R.wgrad_route(case.M, N, K, case.dt, case.db, True, case.sel)
+        dW, db = emulate_wgrad(route, dY, A, case.db, fault, tile)
+        rep, repb = R.check_wgrad(dY, A, dW, db, what=case.id, roundings=route.roundings, db_roundings=route.db_roundings, tile=route.tile,
+                                  chunk_elems=1 << 22)
+        ok = ok and rep.ok and (repb is None or repb.ok)
+        if integer:
+            ok = ok and torch.equal(dW.double(), dY.double().t() @ A.double()) and (db is None or torch.equal(db.double(), dY.double().sum(0)))
+        reps.append(rep)
+    return ok, reps[0]
+
+
+@pytest.mark.parametrize("case", WGRAD_CASES, ids=lambda c: c.id)
+def test_fallback_wgrad_emulation_passes(case):
+    """Per-split 32-deep MFMA steps and the slab reduction in its slice order; fmaf chains per split-K chunk added in a shuffled
+    order; the two-stage column sums in their order: inside the bound on random data, bit-equal on integers."""
+    for integer in (False, True):
+        ok, rep = _judge_wgrad(case, integer)
+        assert ok, str(rep)
+
+
+# ------------------------------------------------------------------------------------------------ injected faults
+def _fwd_case(label, M, N, K, mode=R.NONE, f32=False, bias=True):
+    (c,) = [c for c in FWD_CASES if (c.name, c.M, c.N, c.K, c.mode, c.f32, c.bias, c.sel, c.misalign) == (label, M, N, K, mode, f32, bias, None, False)]
+    return c
+
+
+# fault -> (the table's case it is injected into, the tile, the runs that must report it).  Which run catches which:
+#   ktail, bias, shift8, resid, step, slab   far outside the bound on random data, and not bit-equal on integers: both runs
+#   row_ge_M                                 neither bound sees it (every element inside is right): the guard rows do, on both runs
+#   double_round  (the sum rounded to bf16 before the bias add and again after it, K = 576: sums beyond 256, where bf16 no longer
+#                 holds every integer)       both runs; on integers only 37 of 37 008 elements move, each by one bf16 ulp: the
+#                                            bit-equality is what sees them (error / bound 1.98 there, 157 on random data)
+#   gelu_unrounded (out2 = GELU of the fp32 sum instead of the stored bf16 value)   the random run only, against the half-ulp bound
+#                 around f(out): out2 is off by up to one bf16 ulp; on integers most pre-activations are bf16 values themselves and
+#                 the bound holds, so this fault rests on the random run
+FWD_FAULTS = {
+    "ktail": (("nt1<2,RG>", 129, 144, 144, R.NONE, False, True), (0, 2), ("random", "int")),
+    "ktail_f32": (("nt1<2,RG>", 129, 144, 144, R.NONE, True, True), (0, 2), ("random", "int")),
+    "bias": (("nt1<2,RG>", 129, 144, 144, R.NONE, False, True), (1, 1), ("random", "int")),
+    "bias_generic": (("generic<bf16,f32>", 65, 68, 24, R.NONE, True, True), (1, 1), ("random", "int")),
+    "shift8": (("nt1<2,RG>", 300, 200, 64, R.NONE, True, True), (2, 2), ("random", "int")),
+    "shift8_nt2": (("nt2", 300, 192, 192, R.GELU, False, True), (1, 0), ("random", "int")),
+    "row_ge_M": (("nt1<NI=2>", 200, 192, 128, R.NONE, False, True), (1, 0), ("random", "int")),
+    "resid": (("nt2", 300, 192, 192, R.RESID, True, True), (1, 0), ("random", "int")),
+    "gelu_unrounded": (("nt1<2,RG>", 129, 144, 144, R.GELU, False, True), (0, 0), ("random",)),
+    "double_round": (("nt1<2,RG>", 257, 144, 576, R.NONE, False, True), (0, 0), ("random", "int")),
+}
+
+
+@pytest.mark.parametrize("name", FWD_FAULTS)
+def test_fallback_forward_fault_is_caught(name):
+    key, tile, must = FWD_FAULTS[name]
+    case = _fwd_case(*key)
+    fault = name.split("_")[0] if name.split("_")[0] in ("ktail", "bias", "shift8") else name
+    caught = []
+    for integer in (False, True):
+        ok, rep, guard, exact = _judge_fwd(case, integer, fault, tile)
+        if not ok:
+            caught.append("int" if integer else "random")
+            if fault == "row_ge_M":
+                assert not guard and rep.ok
+            elif rep.first_bad:      # the first failing element lies in the faulty tile
+                bm, bn = case.route().tile
+                first = rep.first_bad
+                if fault in ("gelu_unrounded", "double_round"):
+                    continue         # these faults are injected everywhere
+                assert (first[0] // bm, first[1] // bn) == tile, str(rep)
+        print(name, "int" if integer else "random", "caught" if not ok else "not caught", rep, "exact" if exact else "not exact")
+    assert set(must) <= set(caught), (name, caught)
+
+
+WGRAD_FAULTS = {
+    # rows 64 .. 127 of the second M-split (S = 2, a ragged second chunk) dropped in the last tile
+    "step": (("tn<4,4,RG>", 1100, 144, 144), (1, 1), ("random", "int")),
+    "step_tn22": (("tn<2,2>", 1100, 192, 192), (2, 1), ("random", "int")),
+    # chunk 15 of 16 is empty: its slab left at the fill value
+    "slab": (("tn<4,4>", 8200, 128, 128), (0, 0), ("random", "int")),
+    "slab_64": (("tn<2,2>", 33000, 64, 64), (0, 0), ("random", "int")),
+}
+
+
+@pytest.mark.parametrize("name", WGRAD_FAULTS)
+def test_fallback_wgrad_fault_is_caught(name):
+    key, tile, must = WGRAD_FAULTS[name]
+    (case,) = [c for c in WGRAD_CASES if (c.name, c.M, c.N, c.K) == key and c.db and not c.sel and not c.pair]
+    caught = []
+    for integer in (False, True):
+        ok, rep = _judge_wgrad(case, integer, name.split("_")[0], tile)
+        if not ok:
+            caught.append("int" if integer else "random")
+            if rep.first_bad:
+                tn_, tk_ = case.route().tile
+                assert (rep.first_bad[0] // tn_, rep.first_bad[1] // tk_) == tile, str(rep)
+        print(name, "int" if integer else "random", "caught" if not ok else "not caught", rep)
+    assert set(must) <= set(caught), (name, caught)
