@@ -153,6 +153,30 @@ int mae_norm_pix_restore(const void* images, int32_t image_dtype, const float* p
 int mae_augment_crop_flip_u8(const uint8_t* images, const int32_t* params, int32_t batch, int32_t in_chans,
                              int32_t image_size, uint8_t* out, void* stream);
 
+/* The same step to another size (additive in ABI v4): the box of every image resampled to out_size x out_size, so that a dataset
+ * resident at one resolution feeds a model of another -- RandomResizedCrop(size) + RandomHorizontalFlip() for training,
+ * Resize(size) for evaluation (src/data.py:15-34) -- in one pass.
+ *   images : (batch, C, in_size, in_size), MAE_U8 raw pixels or MAE_F32 values;   out: (batch, C, out_size, out_size);
+ *   params : (batch, 5) int32 = (top, left, height, width, flip) in source pixels; NULL = the whole image, not flipped.
+ * Per axis (x shown; ox' = out_size - 1 - ox when flip != 0), with s = width / out_size and
+ * c = left + width (2 ox' + 1) / (2 out_size) - 0.5 (the convention of mae_augment_crop_flip_u8):
+ *   width <= out_size: c clamped to [0, in_size - 1]; taps floor(c), min(floor(c) + 1, in_size - 1), weights (1 - a, a);
+ *   width >  out_size: the antialiasing triangle filter: taps j with |j - c| < s, those outside the image dropped, weight
+ *                      1 - |j - c| / s divided by the sum of the kept weights.
+ * The axes decide independently; the pixel is the separable weighted sum in fp32 (F.interpolate(mode="bilinear",
+ * antialias=True, align_corners=False) for a whole-image box).  The border is the image edge, not the box edge.
+ *   MAE_U8 -> MAE_U8 : rounded to nearest even and clamped to [0, 255];
+ *   MAE_U8 -> MAE_F32: that byte through (v / 255 - 0.5) / 0.5, bit-identical to the engine's pixel kernels;
+ *   MAE_F32 -> MAE_F32: the sum as it is;   MAE_F32 -> MAE_U8 is an error.
+ * An output pixel whose centre falls on a source pixel copies it bit for bit (the identity box, a flip alone).
+ * Errors before any launch: NULL images / out, a non-positive batch / in_chans / size, a size above 8192,
+ * in_size > 8 * out_size (at most 17 taps an axis), an unknown dtype, out overlapping images, a float buffer or params not
+ * 4-byte aligned.  The boxes are device data and are not checked: the kernel clamps top / left to [-in_size, 2 in_size],
+ * height / width to [0, 2 in_size] and every tap index into the image, so no value reads outside the batch; the caller
+ * validates 0 <= top, top + height <= in_size, height >= 1 (and the columns) if it wants the definition above. */
+int mae_resize_crop_flip(const void* images, int32_t in_dtype, int32_t batch, int32_t in_chans, int32_t in_size,
+                         const int32_t* params, int32_t out_size, int32_t out_dtype, void* out, void* stream);
+
 /* torch.nn.MSELoss() (src/training/mae.py:40,48) over n elements, and its gradient w.r.t. pred
  * scaled by grad_scale: loss[0] = mean((pred-target)^2); d_pred = grad_scale*2*(pred-target)/n.
  * scratch: >= 4096 floats. */

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch
 import yaml
 
-from ssrl_vit_mae_jepa_amd.data import STL10_DIR, LabeledBatches, _load_stl10_labeled, get_test_batches, split_per_class, synthetic_labeled
+from ssrl_vit_mae_jepa_amd.data import STL10_DIR, LabeledBatches, _load_stl10_labeled, get_test_batches, labeled_serving, split_per_class, synthetic_labeled
 from ssrl_vit_mae_jepa_amd.representation import extract_split_features, knn_topk, knn_vote, load_eval_encoder, parse_ks
 
 
@@ -72,7 +72,8 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("knn_eval: the MI355X engine has no CPU fallback")
     dev = torch.device("cuda", 0)
-    bank = LabeledBatches(imgs.to(dev), torch.from_numpy(labels).to(dev), bank_idx, args.batch_size, False, int(cfg.get("seed", 73)))
+    bank = LabeledBatches(imgs.to(dev), torch.from_numpy(labels).to(dev), bank_idx, args.batch_size, False, int(cfg.get("seed", 73)),
+                          *labeled_serving(cfg))   # the bank at the model's size, as the queries
     precision = cfg.get("engine", {}).get("precision")
     enc = load_eval_encoder(args.checkpoint, model_cfg, encoder=args.encoder, precision=precision, device=dev)
     if not enc.with_cls and pool != "mean":

@@ -4,8 +4,8 @@ BatchNorm1d(affine=False) + Linear trained with LARS (no weight decay, momentum 
 The train, validation and test features are extracted ONCE (``representation.extract_split_features``); every epoch then runs
 over the cached features (shuffled by a permutation drawn from (seed, epoch), batches gathered on the device), so a 90-epoch
 probe pays one encoder pass instead of ninety.  ``--augment crop`` re-extracts the training features every step from
-RandomResizedCrop + flip images (``data.augment_batch_u8``, parameters drawn from (seed, epoch, step)); validation and test
-features stay cached.
+RandomResizedCrop + flip images (``data.augment_to_size``: the box is drawn on the stored image and resampled straight to the
+model's size, parameters drawn from (seed, epoch, step)); validation and test features stay cached.
 
     python -m scripts.evaluation.linear_probe --config configs/vits8_dec192_linprobe.yaml --checkpoint outputs/pretrain/mae_pretrain/checkpoints/last.ckpt
     python -m scripts.evaluation.linear_probe --config configs/ijepa_vits8.yaml --checkpoint outputs/pretrain/ijepa_pretrain/checkpoints/last.ckpt --encoder target
@@ -29,7 +29,7 @@ import numpy as np
 import torch
 import yaml
 
-from ssrl_vit_mae_jepa_amd.data import STL10_DIR, augment_batch_u8, draw_augment_params, get_test_batches, get_train_batches
+from ssrl_vit_mae_jepa_amd.data import STL10_DIR, augment_to_size, draw_augment_params, get_test_batches, get_train_batches, labeled_serving
 from ssrl_vit_mae_jepa_amd.probe import AUGMENTS, PROBE_DEFAULTS, LinearProbe, classifier_pool, parse_probe, probe_lr
 from ssrl_vit_mae_jepa_amd.training import lr_lambda
 
@@ -157,7 +157,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     crop = pcfg["augment"] == "crop"
-    if crop:   # the training features are re-extracted per step: only the images and labels are kept
+    crop_size, crop_dtype = labeled_serving(data_cfg)   # the model's size: the crop is resampled straight to it (None: the stored size)
+    if crop:   # the training features are re-extracted per step: only the images and labels are kept, at the stored resolution
         train_images, train_f, train_y = train_b.images[train_b.idx], None, train_b.labels[train_b.idx]
     else:
         train_images, (train_f, train_y) = None, extract_split_features(enc, train_b, pool=pool, normalize="none")
@@ -197,7 +198,7 @@ def main(argv=None):
             if crop:
                 imgs = train_images[j].contiguous()
                 g = torch.Generator().manual_seed(int(np.random.SeedSequence([seed, epoch, step]).generate_state(1)[0]))
-                feats = _features(enc, augment_batch_u8(imgs, params=draw_augment_params(imgs.shape[0], imgs.shape[2], g)), pool)
+                feats = _features(enc, augment_to_size(imgs, crop_size, draw_augment_params(imgs.shape[0], imgs.shape[2], g), crop_dtype), pool)
             else:
                 feats = train_f[j]
             loss, correct = probe.step(feats, train_y[j], lr)

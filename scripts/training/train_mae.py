@@ -18,7 +18,9 @@ train.label_smoothing / mixup_alpha / cutmix_alpha / layer_decay (configs/vits8_
 --drop_path overrides train.drop_path (stochastic depth, default 0; the MAE recipe uses 0.1; ignored by a frozen encoder).
 --augment turns on the per-image augmentation in front of the mixing (train.augment: RandomResizedCrop + flip, RandAugment
 rand-m9-mstd0.5-inc1, random erasing 0.25; configs/vits8_dec192_finetune_aug.yaml); --crop_scale LO HI, --rand_augment N M and
---random_erasing P override its keys.  Training batches only: validation and test images are never augmented.
+--random_erasing P override its keys.  Training batches only: validation and test images are never augmented.  A model of
+another size than the 96 px dataset (model.general.image_size) gets its batches resized on the device; with train.augment the ops run
+on the dataset's own pixels first (the kernel holds an image in LDS), then the resize, then the mixing at the model's size.
 Under mixup / CutMix the metrics line's ``train_loss`` is the soft-target loss and ``train_acc`` counts argmax == the image's
 own label (the first of each mixed pair), so it reads lower than the accuracy on clean images; ``val_*`` stay hard-label.
 
@@ -217,7 +219,9 @@ def main(argv=None):
     with open(output_dir / "config.yaml", "w") as f_out:
         yaml.safe_dump(cfg, f_out)
 
-    train_batches, val_batches = get_train_batches(cfg, dev, synthetic_images=args.synthetic_images, seed=SEED)
+    # train.augment runs on the dataset's own pixels and the module resizes afterwards: its training batches leave the loader as stored
+    train_batches, val_batches = get_train_batches(cfg, dev, synthetic_images=args.synthetic_images, seed=SEED,
+                                                   train_at_dataset_size=bool(train_cfg.get("augment")))
     module = build_module(cfg, args.encoder_ckpt, args.classifier_ckpt, encoder=args.encoder, pool=args.pool).to(dev)
     module.mix_seed = module.drop_seed = module.aug_seed = int(cfg.get("seed", SEED))  # the mixup / CutMix, drop-path and augmentation draws of a step are functions of (seed, epoch, step)
     total = int(train_cfg["total_epochs"]) if args.max_epochs is None else min(int(train_cfg["total_epochs"]), args.max_epochs)

@@ -75,6 +75,7 @@ SIGNATURES = {
     "mae_norm_pix_restore": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mae_mse_loss_norm_pix": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp]),
     "mae_augment_crop_flip_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "mae_resize_crop_flip": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "mae_mse_loss": (C.c_int, [_vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "mae_engine_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "mae_engine_loss_and_grads": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),

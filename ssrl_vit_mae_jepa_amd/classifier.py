@@ -15,7 +15,8 @@ The fine-tuning recipe of the MAE paper (not in the reference; every option off 
 mix each training batch on the device (``data.mix_batch``) and train on the soft targets inside the head kernel;
 ``train.layer_decay`` scales the learning rate of layer l by ``layer_decay ** (depth + 1 - l)`` (BEiT / MAE numbering);
 ``train.augment`` augments each image of a training batch before all that (``data.augment_finetune``: RandomResizedCrop + flip,
-RandAugment, random erasing, one kernel).
+RandAugment, random erasing, one kernel).  With a model of another size than the dataset the order is: the ops at the dataset's
+resolution, then the resize to ``image_size`` (``data.resize_batch``), then mixup / CutMix at the model's size.
 """
 from __future__ import annotations
 
@@ -174,7 +175,9 @@ def parse_augment(block: Optional[Dict[str, Any]]) -> Optional[Dict[str, Any]]:
     """``train.augment`` checked and turned into the keyword arguments of ``data.draw_finetune_augment``; None when the block is
     absent or empty.  Keys: ``crop_scale`` [lo, hi] (absent: no crop), ``flip`` (probability, absent: 0), ``interpolation``
     (bicubic | bilinear), ``rand_augment`` {num_ops, magnitude, mstd, prob} (absent: no ops), ``random_erasing`` (probability,
-    absent: 0), ``fill`` (a byte, or three)."""
+    absent: 0), ``fill`` (a byte, or three).  The ops run at the resolution the training batch arrives in: for a model of another
+    size than the dataset that is the dataset's (``get_train_batches(train_at_dataset_size=True)``), and the resize to the model's size
+    follows them -- uint8 -> uint8 / fp32 without erasing, fp32 -> fp32 with it -- before mixup / CutMix."""
     if not block:
         return None
     if not isinstance(block, dict):
@@ -252,9 +255,11 @@ class ViTClassifierTrainModule(nn.Module):
         self.augment = parse_augment(self.training_cfg.get("augment"))
         general = self.model_cfg.get("general") or {}
         if self.augment is not None and "image_size" in general:
-            need = 2 * int(general.get("in_chans", 3)) * int(general["image_size"]) ** 2 + 3200
+            from .data import DATASET_SIZE
+            ops_size = min(int(general["image_size"]), DATASET_SIZE)  # a larger model is fed through the resize: the ops run on the dataset's own pixels
+            need = 2 * int(general.get("in_chans", 3)) * ops_size ** 2 + 3200
             if need > 160 * 1024:
-                raise ValueError(f"train.augment keeps two copies of an image in LDS: {need} bytes at image_size {general['image_size']}, more than 160 KiB")
+                raise ValueError(f"train.augment keeps two copies of an image in LDS: {need} bytes at image size {ops_size}, more than 160 KiB")
         self.aug_seed = 73
         self._aug_step = 0
         self.mix_seed = 73
@@ -498,17 +503,25 @@ class ViTClassifierTrainModule(nn.Module):
     def _augment(self, images: torch.Tensor) -> torch.Tensor:
         """A training batch through ``train.augment`` (crop + flip, RandAugment, erasing: ``data.augment_finetune``), the draw a
         function of (aug_seed, current_epoch, step); the batch itself, untouched, when the key is not set.  uint8 batches only:
-        the ops are those of PIL images."""
+        the ops are those of PIL images.  A batch of another size than the model's (the dataset's own resolution, what
+        ``get_train_batches(train_at_dataset_size=True)`` serves) is augmented at ITS size -- the kernel holds an image in LDS and
+        takes none above 160 x 160 -- and resized to the model's afterwards (``data.resize_batch``): uint8 -> uint8, or normalised
+        fp32 where the engine reads no bytes; the fp32 batch that erasing leaves -> fp32.  mixup / CutMix then see model-size images."""
         if self.augment is None:
             return images
-        from .data import augment_finetune, draw_finetune_augment
+        from .data import augment_finetune, draw_finetune_augment, resize_batch
         m = self.model.mae
-        images = m._check_images(images).to(m._require_cuda())
+        resize = images.dim() == 4 and images.shape[2] == images.shape[3] and images.shape[1] == m.in_chans and images.shape[-1] != m.image_size
+        images = (images.contiguous() if resize else m._check_images(images)).to(m._require_cuda())
         if images.dtype != torch.uint8:
             raise ValueError("train.augment works on uint8 pixels (the ops are those of PIL images): serve the batch as uint8")
         params = draw_finetune_augment(images.shape[0], images.shape[-1], (self.aug_seed, self.current_epoch, self._aug_step), **self.augment)
         self._aug_step += 1
-        return augment_finetune(images, params)
+        images = augment_finetune(images, params)
+        if resize:
+            reads_u8 = m.patch_size % 4 == 0 and m.image_size // m.patch_size <= 64
+            images = resize_batch(images, m.image_size, out_dtype=None if (reads_u8 or images.dtype != torch.uint8) else torch.float32)
+        return images
 
     def _draw_branch_scale(self, batch: int) -> Optional[torch.Tensor]:
         """This step's drop-path table (host), a function of (drop_seed, current_epoch, step); None with rate 0.  With a frozen

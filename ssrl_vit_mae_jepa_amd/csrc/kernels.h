@@ -149,6 +149,11 @@ int launch_mix_batch(const void* images, int img_dt, const int32_t* partner, con
 int launch_augment_ops_u8(const uint8_t* images, int B, int C, int S, const int32_t* op_codes, const double* op_args, int num_ops,
                           const int32_t* erase, int out_dt_flags, void* out, hipStream_t s);
 
+// ---- k_resize.hip: (B, C, Si, Si) -> (B, C, So, So) through a crop box and a flip per image (params (B, 5) or null: whole image) ----
+// bilinear where an axis keeps or gains pixels, the antialiasing triangle filter where it loses them; u8 -> u8 | f32, f32 -> f32
+int launch_resize_crop_flip(const void* images, int in_dt, int B, int C, int Si, const int32_t* params, int So, int out_dt, void* out,
+                            hipStream_t s);
+
 // ---- k_normpix.hip: targets standardised per patch (norm_pix_loss); idx is int64 when idx64 != 0, else int32 ---------------------
 // mae_mse_loss with the target (x - mean) * rstd of the image's patches, never materialised; stage-1 partials in scratch (1024+ floats)
 int launch_mse_norm_pix(const float* pred, const void* images, int img_dt, const void* idx, int idx64, int B, int m, int C, int img, int p,

@@ -1,4 +1,4 @@
-"""Input step before the hot path: batches of (B, 3, 96, 96) images, uint8 as the dataset stores them, on the GPU.
+"""Input step before the hot path: batches of (B, 3, S, S) images at the model's size S, uint8 as the dataset stores them, on the GPU.
 
 Mirrors what the reference's ``get_pretrain_dataloaders`` (src/data.py:45-106) hands the step, without torchvision
 (not installed): the STL-10 unlabeled split is read straight from its binary file (uint8, column-major images) and kept
@@ -17,6 +17,14 @@ and BOTH loaders keep the training transform RandomResizedCrop(96, scale=(0.8, 1
 ``get_params``, bilinear resampling through an affine grid, flip by sign of the x scale); it cannot be bit-identical to
 PIL's fixed-point resize nor share its RNG stream, so it is the same distribution, not the same pixels.
 Without the dataset file (no network here) it serves seeded synthetic uniform[-1,1] images of the same shape.
+A model of another size than the dataset (``model.general.image_size`` != 96: ViT-B/16 and ViT-L/14 at 224 px) is fed through
+``resize_batch`` (csrc/k_resize.hip, ``mae_resize_crop_flip``): the dataset stays resident at 96 px uint8 -- on the device or in
+pinned memory -- and every batch takes ONE pass that crops, flips and resamples it to the model's size, the reference's
+RandomResizedCrop(size) for training and Resize(size) + CenterCrop(size) for evaluation (src/data.py:15-34; a square image has
+nothing to centre-crop).  The crop box is drawn at the source size by the unchanged ``draw_augment_params``, so data-parallel
+ranks still agree; the batch leaves as uint8 where the engine reads bytes and as normalised fp32 otherwise (``serves_u8``).
+The labeled loaders do the same with the plain whole-image resize (``LabeledBatches(image_size=...)``); a configuration of
+the dataset's own size, or one without a model block, takes none of this: the old kernel, the old path, the old bits.
 """
 from __future__ import annotations
 
@@ -115,6 +123,83 @@ def augment_batch_u8(x: torch.Tensor, gen: Optional[torch.Generator] = None, par
     out = torch.empty_like(x)
     check(lib.mae_augment_crop_flip_u8(ptr(x), ptr(params), B, C, S, ptr(out), _stream(x.device)))
     return out
+
+
+DATASET_SIZE = 96   # STL-10 and its synthetic stand-ins: the resolution every loader keeps the dataset at
+
+
+def model_image_size(cfg: dict) -> int:
+    """``model.general.image_size`` of a configuration; one without a model block serves the dataset's own resolution."""
+    return int((cfg.get("model") or {}).get("general", {}).get("image_size", DATASET_SIZE))
+
+
+def serves_u8(cfg: dict) -> bool:
+    """Whether the model of a configuration reads raw bytes: the uint8 pixel kernels take patch sizes that are multiples of 4
+    on grids up to 64 x 64 (csrc/k_pixels.hip); other geometries (the reference class's default patch_size 6, ViT-L/14) are
+    served normalised fp32 batches, which every engine kernel accepts."""
+    general = (cfg.get("model") or {}).get("general", {})
+    patch = int(general.get("patch_size", 8))
+    return patch % 4 == 0 and model_image_size(cfg) // max(1, patch) <= 64
+
+
+def check_boxes(params: torch.Tensor, size: int) -> None:
+    """ValueError unless every row (top, left, h, w, flip) of a host tensor is a box inside a size x size image."""
+    if params.dim() != 2 or params.shape[1] != 5:
+        raise ValueError(f"crop parameters must be (B, 5) rows of (top, left, h, w, flip), got {tuple(params.shape)}")
+    p = params.to(torch.int64)
+    top, left, h, w = p[:, 0], p[:, 1], p[:, 2], p[:, 3]
+    bad = (top < 0) | (left < 0) | (h < 1) | (w < 1) | (top + h > size) | (left + w > size)
+    if bool(bad.any()):
+        b = int(bad.nonzero()[0])
+        raise ValueError(f"crop box {p[b, :4].tolist()} of image {b} does not lie inside a {size} x {size} image")
+
+
+def resize_batch(x: torch.Tensor, out_size: int, params=None, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """A square (B, C, S, S) uint8 or float32 device batch resampled to (B, C, out_size, out_size) by the HIP kernel behind
+    ``mae_resize_crop_flip``: bilinear where an axis keeps or gains pixels, the antialiasing triangle filter where it loses
+    them (``F.interpolate(mode="bilinear", antialias=True)`` for the whole image).  ``params``: None (the whole image), the
+    (top, left, h, w, flip) tuple of ``draw_augment_params`` sliced to the batch's rows, or a (B, 5) integer tensor -- boxes in
+    source pixels, resampled straight to ``out_size`` with the columns mirrored under a flip.  Host boxes are validated here
+    (a box outside the image is a ValueError); device boxes are clamped by the kernel, never read out of bounds.
+    ``out_dtype``: uint8 input gives uint8 (default) or normalised float32, bit-identical to ``normalize_u8`` of the uint8
+    result; float32 input gives float32, not normalised.  No torch fallback: a missing extension fails loudly."""
+    from . import _lib
+    from ._lib import check, lib, ptr
+    from .mae import _stream
+    if x.dtype not in (torch.uint8, torch.float32) or not x.is_cuda or x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError(f"resize_batch needs a square (B, C, S, S) uint8 or float32 CUDA batch, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    B, C, S, _ = x.shape
+    out_size = int(out_size)
+    if out_dtype is None:
+        out_dtype = x.dtype
+    if out_dtype not in (torch.uint8, torch.float32) or (out_dtype == torch.uint8 and x.dtype != torch.uint8):
+        raise ValueError(f"resize_batch: {x.dtype} input cannot leave as {out_dtype}")
+    if out_size < 1 or S > 8 * out_size:
+        raise ValueError(f"resize_batch: out_size {out_size} must be positive and at least an eighth of the input size {S}")
+    if params is not None:
+        if not torch.is_tensor(params):
+            top, left, h, w, flip = params
+            params = torch.stack([top, left, h, w, flip.to(top.dtype)], dim=1)
+        if params.shape[0] != B:
+            raise ValueError(f"resize_batch: {params.shape[0]} crop boxes for a batch of {B}")
+        if not params.is_cuda:
+            check_boxes(params, S)
+        params = params.to(device=x.device, dtype=torch.int32).contiguous()
+    x = x.contiguous()
+    out = torch.empty((B, C, out_size, out_size), dtype=out_dtype, device=x.device)
+    if B == 0:
+        return out
+    dt = lambda d: _lib.MAE_U8 if d == torch.uint8 else _lib.MAE_F32  # noqa: E731
+    check(lib.mae_resize_crop_flip(ptr(x), dt(x.dtype), B, C, S, ptr(params), out_size, dt(out_dtype), ptr(out), _stream(x.device)))
+    return out
+
+
+def augment_to_size(x: torch.Tensor, out_size: Optional[int], params, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """RandomResizedCrop(out_size) + flip of a uint8 device batch with boxes drawn at ITS size: ``augment_batch_u8`` (the same
+    bits as ever) when the size stays (``out_size`` None or the batch's own), one ``resize_batch`` pass when it changes."""
+    if out_size is None or (out_size == x.shape[-1] and out_dtype in (None, torch.uint8)):
+        return augment_batch_u8(x, params=params)
+    return resize_batch(x, out_size, params=params, out_dtype=out_dtype)
 
 
 class PinnedBatchStream:
@@ -246,6 +331,13 @@ def get_pretrain_batches(cfg: dict, device: torch.device, synthetic_images: Opti
 
     def finish(x: torch.Tensor, lo: int, hi: int, gb: int) -> torch.Tensor:
         params = None
+        if img_size != x.shape[-1]:
+            # a model of another size than the dataset: the box is drawn at the SOURCE size by the same rule and generator (so the
+            # ranks still agree) and resampled straight to the model's size, in the one pass that also resizes
+            if augment:
+                params = tuple(t[lo:hi] for t in draw_augment_params(gb, x.shape[-1], aug_gen))
+            out_dt = torch.uint8 if (x.dtype == torch.uint8 and keep_u8) else torch.float32
+            return resize_batch(x, img_size, params=params, out_dtype=out_dt)
         if hi == lo:   # this rank holds no row of a short last batch (the generator still advances below, in step with the other ranks)
             if augment:
                 draw_augment_params(gb, x.shape[-1], aug_gen)
@@ -332,10 +424,15 @@ def synthetic_labeled(n: int, num_classes: int = 10, seed: int = 73) -> Tuple[to
 
 class LabeledBatches:
     """(images uint8 on the device, labels int64 on the device) batches of a fixed index list; ``shuffle`` reorders the
-    list every epoch from a generator seeded with (seed, epoch) (DataLoader(shuffle=True)); no batch is dropped."""
+    list every epoch from a generator seeded with (seed, epoch) (DataLoader(shuffle=True)); no batch is dropped.
+    ``image_size`` other than the stored resolution: the split stays resident as stored and every batch leaves through the plain
+    whole-image ``resize_batch`` (Resize(size) + CenterCrop(size) of a square image, src/data.py:25-34), as ``out_dtype``
+    (None: uint8)."""
 
-    def __init__(self, images: torch.Tensor, labels: torch.Tensor, idx: List[int], batch: int, shuffle: bool, seed: int):
+    def __init__(self, images: torch.Tensor, labels: torch.Tensor, idx: List[int], batch: int, shuffle: bool, seed: int,
+                 image_size: Optional[int] = None, out_dtype: Optional[torch.dtype] = None):
         self.images, self.labels = images, labels
+        self.image_size, self.out_dtype = (None if image_size is None else int(image_size)), out_dtype
         self.idx = torch.as_tensor(idx, dtype=torch.int64, device=images.device)
         self.batch, self.shuffle, self.seed = int(batch), shuffle, seed
         self.n = len(idx)
@@ -348,15 +445,31 @@ class LabeledBatches:
             order = order[torch.randperm(self.n, generator=g).to(order.device)]
         for i in range(0, self.n, self.batch):
             j = order[i:i + self.batch]
-            yield self.images[j].contiguous(), self.labels[j].contiguous()
+            x = self.images[j].contiguous()
+            if self.image_size is not None and self.image_size != x.shape[-1]:
+                x = resize_batch(x, self.image_size, out_dtype=self.out_dtype)
+            yield x, self.labels[j].contiguous()
 
 
-def get_train_batches(cfg: dict, device: torch.device, synthetic_images: Optional[int] = None, seed: int = 73):
+def labeled_serving(cfg: dict):
+    """(image_size, out_dtype) the labeled loaders serve for a configuration: the model's size, uint8 where its engine reads
+    bytes; (None, None) -- batches as stored -- for the dataset's own size or a configuration without a model block."""
+    size = model_image_size(cfg)
+    if size == DATASET_SIZE:
+        return None, None
+    return size, (torch.uint8 if serves_u8(cfg) else torch.float32)
+
+
+def get_train_batches(cfg: dict, device: torch.device, synthetic_images: Optional[int] = None, seed: int = 73,
+                      train_at_dataset_size: bool = False):
     """(train_batches(epoch), val_batches()) over the labeled STL-10 train split (``train_X.bin`` / ``train_y.bin``),
     split per class as src/data.py:126-138 does.  Neither split is augmented: the reference assigns the eval transform to
     ``val_dataset.dataset`` (src/data.py:139), which is the STL10 object BOTH subsets share, so its training images are only
     normalised too; the same holds here (uint8 on the device, normalised inside the engine's pixel kernels).  Without the
-    files: ``synthetic_labeled`` images (default 5000), with samples_per_class capped at 80 % of a class."""
+    files: ``synthetic_labeled`` images (default 5000), with samples_per_class capped at 80 % of a class.
+    Both loaders serve batches of ``model.general.image_size`` (resized on the device, see ``LabeledBatches``).
+    ``train_at_dataset_size``: the TRAINING loader alone keeps the dataset's resolution, for a consumer that resizes itself after
+    its own per-image augmentation (``train.augment``: the ops run on the stored bytes, the resize follows)."""
     train_cfg = cfg["train"]
     seed = int(cfg.get("seed", seed))
     spc = int(train_cfg.get("samples_per_class", 400))
@@ -372,19 +485,22 @@ def get_train_batches(cfg: dict, device: torch.device, synthetic_images: Optiona
     images = imgs.to(device)
     lab = torch.from_numpy(labels).to(device)
     bs = int(train_cfg.get("batch_size", 64))
-    return (LabeledBatches(images, lab, train_idx, bs, True, seed), LabeledBatches(images, lab, val_idx, bs, False, seed))
+    size, out_dt = labeled_serving(cfg)
+    return (LabeledBatches(images, lab, train_idx, bs, True, seed, None if train_at_dataset_size else size, out_dt),
+            LabeledBatches(images, lab, val_idx, bs, False, seed, size, out_dt))
 
 
 def get_test_batches(cfg: dict, device: torch.device, synthetic_images: Optional[int] = None, seed: int = 73) -> LabeledBatches:
     """The labeled STL-10 test split (``test_X.bin`` / ``test_y.bin``) in file order (src/data.py:157-176); without the
-    files, ``synthetic_labeled`` images drawn with another seed than the training split's."""
+    files, ``synthetic_labeled`` images drawn with another seed than the training split's.  Batches of
+    ``model.general.image_size``, as ``get_train_batches`` serves them."""
     loaded = None if synthetic_images is not None else _load_stl10_labeled("test")
     if loaded is None:
         imgs, labels = synthetic_labeled(int(synthetic_images or 2000), seed=int(cfg.get("seed", seed)) + 1)
     else:
         imgs, labels = loaded
     bs = int(cfg.get("test", {}).get("batch_size", 64))
-    return LabeledBatches(imgs.to(device), torch.from_numpy(labels).to(device), list(range(len(labels))), bs, False, seed)
+    return LabeledBatches(imgs.to(device), torch.from_numpy(labels).to(device), list(range(len(labels))), bs, False, seed, *labeled_serving(cfg))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
