@@ -43,6 +43,13 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t round_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 inline size_t dtype_size(int dt) { return dt == MAE_BF16 ? 2 : 4; }
 
+// The dtype pick of a launch site: f(T{}) with T = bf16 for MAE_BF16, else float, so that the site states its kernel and its
+// argument list once:  with_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL(K<T>, .., (T*)p); });
+template <class F>
+void with_dtype(int dt, F&& f) {
+  if (dt == MAE_BF16) f(bf16{}); else f(float{});
+}
+
 // a kernel gets 64 KiB of dynamic LDS by default: a launch that asks for more raises the kernel's limit first
 template <class K>
 int allow_lds(K kernel, size_t lds) {

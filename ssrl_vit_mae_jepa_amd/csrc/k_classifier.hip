@@ -336,34 +336,6 @@ int launch_classifier_head_wgrad(const float* dlogits, const float* pooled, int 
   return 0;
 }
 
-// cls pooling: every row of dres / dres_c except the class-token row of each image is zero before the blocks' backward
-template <class T>
-__global__ void __launch_bounds__(256) zero_token_rows_kernel(int64_t rows, int L, int D4, float* __restrict__ dres, T* __restrict__ dres_c) {
-  const int lanes = D4 <= 64 ? 64 : 128;
-  const int rpb = 256 / lanes, sub = threadIdx.x / lanes, l = threadIdx.x % lanes;
-  for (int64_t row = (int64_t)blockIdx.x * rpb + sub; row < rows; row += (int64_t)gridDim.x * rpb) {
-    if (row % L == 0) continue;
-    for (int c = l; c < D4; c += lanes) {
-      store4(dres + row * (int64_t)D4 * 4 + c * 4, f32x4{0.f, 0.f, 0.f, 0.f});
-      store4(dres_c + row * (int64_t)D4 * 4 + c * 4, f32x4{0.f, 0.f, 0.f, 0.f});
-    }
-  }
-}
-
-int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, void* dres_c, hipStream_t s) {
-  MAE_REQUIRE(dres && dres_c && rows > 0 && L > 0, "zero_token_rows: bad arguments");
-  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "zero_token_rows: D = %d must be a multiple of 4 in [4, 1024]", D);
-  MAE_REQUIRE(act == MAE_F32 || act == MAE_BF16, "zero_token_rows: dtype must be MAE_F32 or MAE_BF16 (got %d)", act);
-  const int rpb = D / 4 <= 64 ? 4 : 2;
-  const int grid = (int)std::min<int64_t>(cdiv(rows, rpb), 8192);
-  if (act == MAE_BF16)
-    hipLaunchKernelGGL(zero_token_rows_kernel<bf16>, dim3(grid), dim3(256), 0, s, rows, L, D / 4, dres, reinterpret_cast<bf16*>(dres_c));
-  else
-    hipLaunchKernelGGL(zero_token_rows_kernel<float>, dim3(grid), dim3(256), 0, s, rows, L, D / 4, dres, reinterpret_cast<float*>(dres_c));
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
 // Full-sequence embedding gradient in ONE pass over dres (B, L, D) fp32:
 //   dtok (act dtype) = dres with the class-token rows zeroed (the patch-projection weight gradient reads it),
 //   partial[slice][t][d] = sum of dres[b, t, d] over the slice's images in ascending order.
@@ -416,10 +388,10 @@ int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* d
   MAE_REQUIRE((int64_t)B * L < (1ll << 31), "%s: B * L < 2^31", who);
   const int S = full_grad_split_slices(B, L, D);
   const dim3 grid((unsigned)cdiv((int64_t)L * (D / 4), 256), S);
-#define SPLIT(T, HAS_CLS) hipLaunchKernelGGL((full_grad_split_kernel<T, HAS_CLS>), grid, dim3(256), 0, s, dx, B, L, D, (T*)dtok, partial)
-  if (has_cls) { if (dt == MAE_BF16) SPLIT(bf16, true); else SPLIT(float, true); }
-  else         { if (dt == MAE_BF16) SPLIT(bf16, false); else SPLIT(float, false); }
-#undef SPLIT
+  with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((has_cls ? full_grad_split_kernel<T, true> : full_grad_split_kernel<T, false>), grid, dim3(256), 0, s, dx, B, L, D, (T*)dtok, partial);
+  });
   MAE_LAUNCH_CHECK();
   MAE_TRY(launch_sum_partials(partial, S, L * D, has_cls ? dpos : dpos + D, nullptr, L * D, s));
   if (has_cls) {
@@ -539,8 +511,4 @@ extern "C" int64_t mae_full_grad_split_partial_floats(int32_t batch, int32_t seq
 extern "C" int mae_full_grad_split(const float* dx, int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls, int32_t dtype, void* dtok,
                                    float* dpos, float* dcls, float* partial, void* stream) {
   return mae::launch_full_grad_split(dx, batch, seq_len, dim, dtype, dtok, dpos, dcls, partial, with_cls != 0, (hipStream_t)stream);
-}
-
-extern "C" int mae_zero_token_rows(int64_t rows, int32_t seq_len, int32_t dim, int32_t dtype, float* dres, void* dres_c, void* stream) {
-  return mae::launch_zero_token_rows(rows, seq_len, dim, dtype, dres, dres_c, (hipStream_t)stream);
 }

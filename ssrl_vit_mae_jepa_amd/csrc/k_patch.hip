@@ -35,35 +35,9 @@ int launch_assemble_visible(float* x, const int32_t* tok, const float* cls, cons
 }
 
 // Second stage of every two-stage column reduction: 32 columns per block (8 lanes x float4), 32 row lanes, fixed order.
-__global__ void __launch_bounds__(256) sum_partials_kernel(const float* __restrict__ partial, int G, int C,
-                                                           float* __restrict__ out0, float* __restrict__ out1, int split) {
+__device__ __forceinline__ void sum_partials_block(const float* __restrict__ partial, int G, int C, float* __restrict__ out0,
+                                                   float* __restrict__ out1, int split, int blk) {
   __shared__ __attribute__((aligned(16))) float red[32][36];
-  const int cl = threadIdx.x & 7, rl = threadIdx.x >> 3;
-  const int c = blockIdx.x * 32 + cl * 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (c < C)
-    for (int i = rl; i < G; i += 32) acc += load4(partial + (int64_t)i * C + c);
-  store4(&red[rl][cl * 4], acc);
-  __syncthreads();
-  if (threadIdx.x < 32) {
-    const int cc = blockIdx.x * 32 + threadIdx.x;
-    if (cc < C) {
-      float v = 0.f;
-#pragma unroll
-      for (int j = 0; j < 32; ++j) v += red[j][threadIdx.x];
-      if (cc < split) out0[cc] = v; else out1[cc - split] = v;
-    }
-  }
-}
-
-// the same for a table of reductions: block -> (entry, 32-column group)
-__global__ void __launch_bounds__(256) sum_partials_many_kernel(const PartialsTable tab) {
-  __shared__ __attribute__((aligned(16))) float red[32][36];
-  int e = 0;
-  while (e + 1 < tab.n && (int)blockIdx.x >= tab.block_begin[e + 1]) ++e;
-  const int blk = blockIdx.x - tab.block_begin[e];
-  const float* __restrict__ partial = tab.partial[e];
-  const int G = tab.G[e], C = tab.C[e], split = tab.split[e];
   const int cl = threadIdx.x & 7, rl = threadIdx.x >> 3;
   const int c = blk * 32 + cl * 4;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -77,9 +51,21 @@ __global__ void __launch_bounds__(256) sum_partials_many_kernel(const PartialsTa
       float v = 0.f;
 #pragma unroll
       for (int j = 0; j < 32; ++j) v += red[j][threadIdx.x];
-      if (cc < split) tab.out0[e][cc] = v; else tab.out1[e][cc - split] = v;
+      if (cc < split) out0[cc] = v; else out1[cc - split] = v;
     }
   }
+}
+
+__global__ void __launch_bounds__(256) sum_partials_kernel(const float* __restrict__ partial, int G, int C,
+                                                           float* __restrict__ out0, float* __restrict__ out1, int split) {
+  sum_partials_block(partial, G, C, out0, out1, split, blockIdx.x);
+}
+
+// the same for a table of reductions: block -> (entry, 32-column group)
+__global__ void __launch_bounds__(256) sum_partials_many_kernel(const PartialsTable tab) {
+  int e = 0;
+  while (e + 1 < tab.n && (int)blockIdx.x >= tab.block_begin[e + 1]) ++e;
+  sum_partials_block(tab.partial[e], tab.G[e], tab.C[e], tab.out0[e], tab.out1[e], tab.split[e], blockIdx.x - tab.block_begin[e]);
 }
 
 int launch_sum_partials_many(const PartialsTable& tab, hipStream_t s) {
@@ -97,62 +83,49 @@ int launch_sum_partials(const float* partial, int G, int C, float* out0, float* 
   return 0;
 }
 
-// Row-walk helper shared by the two "split" kernels: thread (ro, c4) owns 4 columns of row offset ro; a block
-// covers RPI = 256 / (D/4) rows per iteration and G blocks stride the matrix.  Column sums of the selected rows
-// are reduced over ro in LDS and written to partial[block][D].
-constexpr int SPLIT_BLOCKS = 512;
-
-template <class T>
-__global__ void __launch_bounds__(256) visible_grad_split_kernel(const float* __restrict__ dx,
-                                                                 const int32_t* __restrict__ tok, int64_t rows, int D,
-                                                                 T* __restrict__ dtok, float* __restrict__ partial) {
-  extern __shared__ __attribute__((aligned(16))) float red[];  // [RPI][D]
-  const int D4 = D / 4, RPI = 256 / D4;
-  const int ro = threadIdx.x / D4, d0 = (threadIdx.x - ro * D4) * 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (ro < RPI) {
-    constexpr int U = 4;   // rows in flight per thread (see decoder_assemble_bwd_kernel); same summation order
+// The row walk of the two split kernels of this file (layout, fold and launcher tail: kernels.h).  U rows per thread and trip are
+// in flight (512 blocks x one 16-byte load per thread ran at 2.6 TB/s).  A row r < rows has the key key(r); a row past the end
+// has key -1 and reads as zeros.  fate(r, key, v, d0, acc) adds the row to the column sum, or stores it wherever it goes, or both;
+// u ascending inside a trip = r ascending, which fixes the order of the additions.
+template <int U, class Key, class Fate>
+__device__ __forceinline__ void split_walk(const float* __restrict__ dx, int64_t rows, int D, float* __restrict__ partial, Key key, Fate fate) {
+  split_block(D, partial, [&](int RPI, int ro, int d0, f32x4& acc) {
     const int64_t stride = (int64_t)gridDim.x * RPI;
     for (int64_t r0 = (int64_t)blockIdx.x * RPI + ro; r0 < rows; r0 += U * stride) {
       f32x4 v[U];
-      bool is_cls[U];
+      int j[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t r = r0 + u * stride;
         const bool live = r < rows;
         v[u] = live ? load4(dx + r * D + d0) : f32x4{0.f, 0.f, 0.f, 0.f};
-        is_cls[u] = live && tok[r] == 0;
+        j[u] = live ? key(r) : -1;
       }
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t r = r0 + u * stride;
-        if (is_cls[u]) acc += v[u];
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        if (r < rows) store4(dtok + r * D + d0, is_cls[u] ? z : v[u]);
-      }
+      for (int u = 0; u < U; ++u) fate(r0 + u * stride, j[u], v[u], d0, acc);
     }
-    store4(red + ro * D + d0, acc);
-  }
-  __syncthreads();
-  if (ro == 0) {
-    for (int i = 1; i < RPI; ++i) acc += load4(red + i * D + d0);
-    store4(partial + (int64_t)blockIdx.x * D + d0, acc);
-  }
+  });
+}
+
+// dtok = dx with the class-token rows (tok == 0) zeroed; partial = column sums of those rows
+template <class T>
+__global__ void __launch_bounds__(256) visible_grad_split_kernel(const float* __restrict__ dx,
+                                                                 const int32_t* __restrict__ tok, int64_t rows, int D,
+                                                                 T* __restrict__ dtok, float* __restrict__ partial) {
+  split_walk<4>(dx, rows, D, partial, [&](int64_t r) { return tok[r]; }, [&](int64_t r, int t, f32x4 v, int d0, f32x4& acc) {
+    if (t == 0) acc += v;
+    if (r < rows) store4(dtok + r * D + d0, t == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : v);
+  });
 }
 
 int launch_visible_grad_split(const float* dx, const int32_t* tok, int64_t rows, int D, int dt, void* dtok, float* dcls,
                               float* partial, hipStream_t s) {
   MAE_REQUIRE(dx && tok && dtok && dcls && partial && rows > 0 && D % 4 == 0 && D <= 1024,
               "visible_grad_split: bad arguments (need D %% 4 == 0, D <= 1024)");
-  const int RPI = 256 / (D / 4);
-  const int G = (int)std::min<int64_t>(cdiv(rows, RPI), SPLIT_BLOCKS);
-  const size_t lds = (size_t)RPI * D * sizeof(float);
-  if (dt == MAE_BF16)
-    hipLaunchKernelGGL((visible_grad_split_kernel<bf16>), dim3(G), dim3(256), lds, s, dx, tok, rows, D, (bf16*)dtok, partial);
-  else
-    hipLaunchKernelGGL((visible_grad_split_kernel<float>), dim3(G), dim3(256), lds, s, dx, tok, rows, D, (float*)dtok, partial);
-  MAE_LAUNCH_CHECK();
-  return launch_sum_partials(partial, G, D, dcls, nullptr, D, s);
+  return launch_split(rows, D, dt, partial, dcls, s, [&](auto t, dim3 grid, size_t lds) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(visible_grad_split_kernel<T>, grid, dim3(256), lds, s, dx, tok, rows, D, (T*)dtok, partial);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -199,74 +172,41 @@ int launch_decoder_assemble(const void* xdec, int dt, const int32_t* inv, const 
   const int64_t rows = (int64_t)B * L;
   MAE_REQUIRE(Dd / 4 <= 256 && rows < (1ll << 31), "decoder_assemble: Dd <= 1024 and B * L < 2^31");
   const int grid = (int)std::min<int64_t>(cdiv(rows, 256 / (Dd / 4)), 256 * 16);
-  if (dt == MAE_BF16)
-    hipLaunchKernelGGL((decoder_assemble_kernel<bf16>), dim3(grid), dim3(256), 0, s, (const bf16*)xdec, inv, mask_token, pos, rows, k, L, Dd / 4, out);
-  else
-    hipLaunchKernelGGL((decoder_assemble_kernel<float>), dim3(grid), dim3(256), 0, s, (const float*)xdec, inv, mask_token, pos, rows, k, L, Dd / 4, out);
+  with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(decoder_assemble_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)xdec, inv, mask_token, pos, rows, k, L, Dd / 4, out);
+  });
   MAE_LAUNCH_CHECK();
   return 0;
 }
 
+// d_xdec[b*k + inv[r]] = dx[r] for the visible rows; partial = column sums of the masked rows (inv[r] < 0), rows past the end
+// joining them as zeros
 template <class T>
 __global__ void __launch_bounds__(256) decoder_assemble_bwd_kernel(const float* __restrict__ dx,
                                                                    const int32_t* __restrict__ inv, int64_t rows, int k,
                                                                    int L, int D, T* __restrict__ d_xdec,
                                                                    float* __restrict__ partial) {
-  extern __shared__ __attribute__((aligned(16))) float red[];  // [RPI][D]
-  const int D4 = D / 4, RPI = 256 / D4;
-  const int ro = threadIdx.x / D4, d0 = (threadIdx.x - ro * D4) * 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (ro < RPI) {
-    // four rows per thread and pass in flight (512 blocks x one 16-byte load per thread ran at 2.6 TB/s); the masked rows are added in
-    // the same order as before (u ascending inside a pass = r ascending)
-    constexpr int U = 4;
-    const int64_t stride = (int64_t)gridDim.x * RPI;
-    for (int64_t r0 = (int64_t)blockIdx.x * RPI + ro; r0 < rows; r0 += U * stride) {
-      f32x4 v[U];
-      int j[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t r = r0 + u * stride;
-        const bool live = r < rows;
-        v[u] = live ? load4(dx + r * D + d0) : f32x4{0.f, 0.f, 0.f, 0.f};
-        j[u] = live ? inv[r] : -1;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t r = r0 + u * stride;
-        if (j[u] < 0) {
-          acc += v[u];   // rows past the end contribute zeros
-        } else {
-          const int64_t b = (uint32_t)r / (uint32_t)L;  // rows < 2^31 (checked by the launcher)
-          store4(d_xdec + (b * k + j[u]) * (int64_t)D + d0, v[u]);
-        }
-      }
+  split_walk<4>(dx, rows, D, partial, [&](int64_t r) { return inv[r]; }, [&](int64_t r, int j, f32x4 v, int d0, f32x4& acc) {
+    if (j < 0) {
+      acc += v;
+    } else {
+      const int64_t b = (uint32_t)r / (uint32_t)L;  // rows < 2^31 (checked by the launcher)
+      store4(d_xdec + (b * k + j) * (int64_t)D + d0, v);
     }
-    store4(red + ro * D + d0, acc);
-  }
-  __syncthreads();
-  if (ro == 0) {
-    for (int i = 1; i < RPI; ++i) acc += load4(red + i * D + d0);
-    store4(partial + (int64_t)blockIdx.x * D + d0, acc);
-  }
+  });
 }
 
-int launch_decoder_assemble_bwd(const float* dx, const int32_t* inv, const int32_t* keep, int B, int k, int L, int Dd,
-                                int dt, void* d_xdec, float* d_mask_token, float* partial, hipStream_t s) {
-  (void)keep;
+int launch_decoder_assemble_bwd(const float* dx, const int32_t* inv, int B, int k, int L, int Dd, int dt, void* d_xdec,
+                                float* d_mask_token, float* partial, hipStream_t s) {
   MAE_REQUIRE(dx && inv && d_xdec && d_mask_token && partial && Dd % 4 == 0 && Dd <= 1024,
               "decoder_assemble_bwd: bad arguments (need Dd %% 4 == 0, Dd <= 1024)");
   const int64_t rows = (int64_t)B * L;
   MAE_REQUIRE(rows < (1ll << 31), "decoder_assemble_bwd: B * L < 2^31");
-  const int RPI = 256 / (Dd / 4);
-  const int G = (int)std::min<int64_t>(cdiv(rows, RPI), SPLIT_BLOCKS);
-  const size_t lds = (size_t)RPI * Dd * sizeof(float);
-  if (dt == MAE_BF16)
-    hipLaunchKernelGGL((decoder_assemble_bwd_kernel<bf16>), dim3(G), dim3(256), lds, s, dx, inv, rows, k, L, Dd, (bf16*)d_xdec, partial);
-  else
-    hipLaunchKernelGGL((decoder_assemble_bwd_kernel<float>), dim3(G), dim3(256), lds, s, dx, inv, rows, k, L, Dd, (float*)d_xdec, partial);
-  MAE_LAUNCH_CHECK();
-  return launch_sum_partials(partial, G, Dd, d_mask_token, nullptr, Dd, s);
+  return launch_split(rows, Dd, dt, partial, d_mask_token, s, [&](auto t, dim3 grid, size_t lds) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(decoder_assemble_bwd_kernel<T>, grid, dim3(256), lds, s, dx, inv, rows, k, L, Dd, (T*)d_xdec, partial);
+  });
 }
 
 template <class S, class D_>
@@ -279,14 +219,13 @@ int launch_cast(const void* src, int src_dt, void* dst, int dst_dt, int64_t n, h
   MAE_REQUIRE((src_dt == MAE_F32 || src_dt == MAE_BF16) && (dst_dt == MAE_F32 || dst_dt == MAE_BF16),
               "cast: dtypes must be MAE_F32 or MAE_BF16 (got %d -> %d)", src_dt, dst_dt);
   const int grid = (int)std::min<int64_t>(cdiv(n, 256), 256 * 16);
-  if (src_dt == MAE_F32 && dst_dt == MAE_BF16)
-    hipLaunchKernelGGL((cast_kernel<float, bf16>), dim3(grid), dim3(256), 0, s, (const float*)src, (bf16*)dst, n);
-  else if (src_dt == MAE_BF16 && dst_dt == MAE_F32)
-    hipLaunchKernelGGL((cast_kernel<bf16, float>), dim3(grid), dim3(256), 0, s, (const bf16*)src, (float*)dst, n);
-  else if (src_dt == MAE_F32 && dst_dt == MAE_F32)
-    hipLaunchKernelGGL((cast_kernel<float, float>), dim3(grid), dim3(256), 0, s, (const float*)src, (float*)dst, n);
-  else
-    hipLaunchKernelGGL((cast_kernel<bf16, bf16>), dim3(grid), dim3(256), 0, s, (const bf16*)src, (bf16*)dst, n);
+  with_dtype(src_dt, [&](auto a) {
+    with_dtype(dst_dt, [&](auto b) {
+      using S = decltype(a);
+      using D_ = decltype(b);
+      hipLaunchKernelGGL((cast_kernel<S, D_>), dim3(grid), dim3(256), 0, s, (const S*)src, (D_*)dst, n);
+    });
+  });
   MAE_LAUNCH_CHECK();
   return 0;
 }
@@ -320,23 +259,24 @@ int launch_add_into(const float* src, void* dst, int dst_dt, int64_t n, hipStrea
   MAE_REQUIRE(src && dst && n > 0, "add_into: bad arguments");
   MAE_REQUIRE(dst_dt == MAE_F32 || dst_dt == MAE_BF16, "add_into: dtype must be MAE_F32 or MAE_BF16 (got %d)", dst_dt);
   const int grid = (int)std::min<int64_t>(cdiv(n, 256), 256 * 16);
-  if (dst_dt == MAE_BF16) hipLaunchKernelGGL((add_into_kernel<bf16>), dim3(grid), dim3(256), 0, s, src, (bf16*)dst, n);
-  else hipLaunchKernelGGL((add_into_kernel<float>), dim3(grid), dim3(256), 0, s, src, (float*)dst, n);
+  with_dtype(dst_dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL(add_into_kernel<T>, dim3(grid), dim3(256), 0, s, src, (T*)dst, n); });
   MAE_LAUNCH_CHECK();
   return 0;
 }
 
-// The backward pass of the decoder starts from a residual gradient that is zero on every row the prediction head never saw: the
-// visible rows (inv[row] >= 0, MAE) or the first T - m rows of every sequence (inv == nullptr, I-JEPA's predictor).  Only those
-// rows are cleared here (a quarter of the rows at mask ratio 0.75); the decoder_norm backward then writes the others.
+// The row clear.  The backward pass of the decoder starts from a residual gradient that is zero on every row the prediction head
+// never saw: the visible rows (inv[row] >= 0, MAE) or the first T - m rows of every sequence (I-JEPA's predictor); the classifier's
+// with cls pooling is zero on every row but the class token's.  Only those rows are cleared here (a quarter of the rows at mask
+// ratio 0.75); the norm backward then writes the others.  A row is kept when inv[row] < 0, or without inv when row % Tseq lies in
+// [lo, hi).
 template <class T>
-__global__ void __launch_bounds__(256) zero_unpredicted_rows_kernel(const int32_t* __restrict__ inv, int64_t rows, int Tseq, int m, int D4,
-                                                                    float* __restrict__ dres, T* __restrict__ dres_c) {
+__global__ void __launch_bounds__(256) zero_rows_kernel(const int32_t* __restrict__ inv, int64_t rows, int Tseq, int lo, int hi, int D4,
+                                                        float* __restrict__ dres, T* __restrict__ dres_c) {
   const int lanes = D4 <= 64 ? 64 : 128;   // threads per row: one float4 each, two passes at most for D <= 1024
   const int rpb = 256 / lanes, sub = threadIdx.x / lanes, l = threadIdx.x % lanes;
   for (int64_t row = (int64_t)blockIdx.x * rpb + sub; row < rows; row += (int64_t)gridDim.x * rpb) {
-    const bool clear = inv ? inv[row] >= 0 : (int)(row % Tseq) < Tseq - m;
-    if (!clear) continue;
+    const int t = (int)(row % Tseq);
+    if (inv ? inv[row] < 0 : t >= lo && t < hi) continue;
     for (int c = l; c < D4; c += lanes) {
       store4(dres + row * (int64_t)D4 * 4 + c * 4, f32x4{0.f, 0.f, 0.f, 0.f});
       store4(dres_c + row * (int64_t)D4 * 4 + c * 4, f32x4{0.f, 0.f, 0.f, 0.f});
@@ -344,16 +284,28 @@ __global__ void __launch_bounds__(256) zero_unpredicted_rows_kernel(const int32_
   }
 }
 
-int launch_zero_unpredicted_rows(const int32_t* inv, int64_t rows, int Tseq, int m, int D, int act, float* dres, void* dres_c, hipStream_t s) {
-  MAE_REQUIRE(dres && dres_c && rows > 0 && D % 4 == 0 && Tseq > 0 && m >= 0 && m <= Tseq, "zero_unpredicted_rows: bad arguments");
+static int launch_zero_rows(const int32_t* inv, int64_t rows, int Tseq, int lo, int hi, int D, int act, float* dres, void* dres_c, hipStream_t s) {
   const int rpb = D / 4 <= 64 ? 4 : 2;
   const int grid = (int)std::min<int64_t>(cdiv(rows, rpb), 8192);
-  if (act == MAE_BF16)
-    hipLaunchKernelGGL(zero_unpredicted_rows_kernel<bf16>, dim3(grid), dim3(256), 0, s, inv, rows, Tseq, m, D / 4, dres, reinterpret_cast<bf16*>(dres_c));
-  else
-    hipLaunchKernelGGL(zero_unpredicted_rows_kernel<float>, dim3(grid), dim3(256), 0, s, inv, rows, Tseq, m, D / 4, dres, reinterpret_cast<float*>(dres_c));
+  with_dtype(act, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(zero_rows_kernel<T>, dim3(grid), dim3(256), 0, s, inv, rows, Tseq, lo, hi, D / 4, dres, (T*)dres_c);
+  });
   MAE_LAUNCH_CHECK();
   return 0;
+}
+
+int launch_zero_unpredicted_rows(const int32_t* inv, int64_t rows, int Tseq, int m, int D, int act, float* dres, void* dres_c, hipStream_t s) {
+  MAE_REQUIRE(dres && dres_c && rows > 0 && D % 4 == 0 && Tseq > 0 && m >= 0 && m <= Tseq, "zero_unpredicted_rows: bad arguments");
+  return launch_zero_rows(inv, rows, Tseq, Tseq - m, Tseq, D, act, dres, dres_c, s);
+}
+
+// cls pooling: every row of dres / dres_c except the class-token row of each image is zero before the blocks' backward
+int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, void* dres_c, hipStream_t s) {
+  MAE_REQUIRE(dres && dres_c && rows > 0 && L > 0, "zero_token_rows: bad arguments");
+  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "zero_token_rows: D = %d must be a multiple of 4 in [4, 1024]", D);
+  MAE_REQUIRE(act == MAE_F32 || act == MAE_BF16, "zero_token_rows: dtype must be MAE_F32 or MAE_BF16 (got %d)", act);
+  return launch_zero_rows(nullptr, rows, L, 0, 1, D, act, dres, dres_c, s);
 }
 
 }  // namespace mae
@@ -376,13 +328,16 @@ extern "C" int mae_decoder_assemble(const void* xdec, int32_t dtype, const int32
 extern "C" int mae_decoder_assemble_bwd(const float* dx, const int32_t* inv, int32_t batch, int32_t num_keep, int32_t seq_len, int32_t dim,
                                         int32_t dtype, void* d_xdec, float* d_mask_token, float* partial, void* stream) {
   MAE_REQUIRE(batch > 0 && num_keep > 0 && num_keep <= seq_len, "mae_decoder_assemble_bwd: bad arguments");
-  return mae::launch_decoder_assemble_bwd(dx, inv, nullptr, batch, num_keep, seq_len, dim, dtype, d_xdec, d_mask_token, partial,
-                                          (hipStream_t)stream);
+  return mae::launch_decoder_assemble_bwd(dx, inv, batch, num_keep, seq_len, dim, dtype, d_xdec, d_mask_token, partial, (hipStream_t)stream);
 }
 
 extern "C" int mae_zero_unpredicted_rows(const int32_t* inv, int64_t rows, int32_t seq_len, int32_t num_pred, int32_t dim, int32_t dtype,
                                          float* dres, void* dres_c, void* stream) {
   return mae::launch_zero_unpredicted_rows(inv, rows, seq_len, num_pred, dim, dtype, dres, dres_c, (hipStream_t)stream);
+}
+
+extern "C" int mae_zero_token_rows(int64_t rows, int32_t seq_len, int32_t dim, int32_t dtype, float* dres, void* dres_c, void* stream) {
+  return mae::launch_zero_token_rows(rows, seq_len, dim, dtype, dres, dres_c, (hipStream_t)stream);
 }
 
 // single-kernel entries (parity tests): the engine-only element kernels of this file, see mae_hip.h

@@ -14,6 +14,10 @@ int launch_idx_to_i32(const int64_t* src, int32_t* dst, int64_t n, hipStream_t s
 int launch_build_inverse(const int32_t* keep32, int B, int k, int L, int32_t* inv, hipStream_t s);
 // rows[b*m + j] = b*L + mask[b][j]  (row map of the masked tokens inside the (B*L) decoder matrix)
 int launch_build_row_map(const int32_t* idx32, int B, int n_per, int L, int32_t* rows, hipStream_t s);
+int launch_iota_tokens(int32_t* keep32, int B, int N, int first, hipStream_t s);      // keep[b][j] = first + j: N tokens of every image
+int launch_fill(float* p, float v, int64_t n, hipStream_t s);
+int launch_build_tail_row_map(int seqs, int T, int m, int32_t* rows, hipStream_t s);  // last m rows of every sequence of T
+int launch_rows_from_tokens(const int32_t* tok, int B, int per_image, int N, int32_t* rows, hipStream_t s);  // b*N + tok-1
 
 // ---- k_patch.hip: token rows <-> sequences ----------------------------------------------------------
 // in place on x (B*k, D) fp32: x[r] = (t == 0 ? cls : x[r]) + pos[t]
@@ -26,9 +30,12 @@ int launch_visible_grad_split(const float* dx, const int32_t* tok, int64_t rows,
 int launch_decoder_assemble(const void* xdec, int dt, const int32_t* inv, const float* mask_token, const float* pos,
                             int B, int k, int L, int Dd, float* out, hipStream_t s);
 // d_xdec[b*k+j] (dt) = dx[b][keep[b][j]];  d_mask_token[Dd] = sum over rows with inv < 0.  partial: >= 512*Dd floats
+int launch_decoder_assemble_bwd(const float* dx, const int32_t* inv, int B, int k, int L, int Dd, int dt, void* d_xdec,
+                                float* d_mask_token, float* partial, hipStream_t s);
+// The row clear: +0.0 in every row of dres (fp32) / dres_c (act) that is not kept.  zero_unpredicted_rows keeps the rows with
+// inv[row] < 0, or (inv == nullptr) the last m rows of every sequence of Tseq; zero_token_rows keeps row 0 of every sequence of L
 int launch_zero_unpredicted_rows(const int32_t* inv, int64_t rows, int Tseq, int m, int D, int act, float* dres, void* dres_c, hipStream_t s);
-int launch_decoder_assemble_bwd(const float* dx, const int32_t* inv, const int32_t* keep, int B, int k, int L, int Dd,
-                                int dt, void* d_xdec, float* d_mask_token, float* partial, hipStream_t s);
+int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, void* dres_c, hipStream_t s);
 int launch_cast(const void* src, int src_dt, void* dst, int dst_dt, int64_t n, hipStream_t s);
 // out[r] = x[r] + pos[r mod L] (fp32 rows of D)
 int launch_add_rows_pos(const float* x, const float* pos, int64_t rows, int L, int D, float* out, hipStream_t s);
@@ -37,11 +44,39 @@ int launch_add_into(const float* src, void* dst, int dst_dt, int64_t n, hipStrea
 // out[c] = sum_{i<G} partial[i][c] in row order (deterministic); columns [0,split) go to out0, [split,C) to out1
 int launch_sum_partials(const float* partial, int G, int C, float* out0, float* out1, int split, hipStream_t s);
 
-// ---- k_jepa.hip: I-JEPA predictor input / target rows / latent loss (no reference code: spec in DESIGN.md) -----------------
-int launch_iota_tokens(int32_t* keep32, int B, int N, int first, hipStream_t s);      // keep[b][j] = first + j: N tokens of every image
-int launch_fill(float* p, float v, int64_t n, hipStream_t s);
-int launch_build_tail_row_map(int seqs, int T, int m, int32_t* rows, hipStream_t s);  // last m rows of every sequence of T
-int launch_rows_from_tokens(const int32_t* tok, int B, int per_image, int N, int32_t* rows, hipStream_t s);  // b*N + tok-1
+// The "split" kernels (visible_grad_split, decoder_assemble_bwd; predictor_assemble_bwd of k_jepa.hip) walk a (rows, D) fp32 matrix
+// alike: thread (ro, d0) owns 4 columns of row offset ro, a block covers RPI = 256 / (D/4) rows per trip and at most SPLIT_BLOCKS
+// blocks stride the matrix.  walk(RPI, ro, d0, acc) is the kernel's own part: it adds the rows it selects into the thread's column
+// sum.  The sums are then added over ro through LDS ([RPI][D] floats, dynamic) into partial[block][D]; launch_sum_partials adds
+// the blocks.
+constexpr int SPLIT_BLOCKS = 512;
+template <class Walk>
+__device__ __forceinline__ void split_block(int D, float* __restrict__ partial, Walk walk) {
+  extern __shared__ __attribute__((aligned(16))) float red[];  // [RPI][D]
+  const int D4 = D / 4, RPI = 256 / D4;
+  const int ro = threadIdx.x / D4, d0 = (threadIdx.x - ro * D4) * 4;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (ro < RPI) {
+    walk(RPI, ro, d0, acc);
+    store4(red + ro * D + d0, acc);
+  }
+  __syncthreads();
+  if (ro == 0) {
+    for (int i = 1; i < RPI; ++i) acc += load4(red + i * D + d0);
+    store4(partial + (int64_t)blockIdx.x * D + d0, acc);
+  }
+}
+// launcher tail of a split kernel over `rows` rows: launch(T{}, grid, lds) launches it on s, then out[D] = sum of the partials
+template <class L>
+int launch_split(int64_t rows, int D, int dt, float* partial, float* out, hipStream_t s, L launch) {
+  const int RPI = 256 / (D / 4);
+  const int G = (int)std::min<int64_t>(cdiv(rows, RPI), SPLIT_BLOCKS);
+  with_dtype(dt, [&](auto t) { launch(t, dim3(G), (size_t)RPI * D * sizeof(float)); });
+  MAE_LAUNCH_CHECK();
+  return launch_sum_partials(partial, G, D, out, nullptr, D, s);
+}
+
+// ---- k_jepa.hip: I-JEPA predictor input, its adjoint and the latent loss (no reference code: spec in DESIGN.md) ---------------
 int launch_predictor_assemble(const void* xdec, int dt, const int32_t* ctx32, const int32_t* tgt32, const float* mask_token, const float* pos,
                               int B, int k, int nblk, int m, int L, int Dd, float* out, hipStream_t s);
 int launch_predictor_assemble_bwd(const float* dx, int B, int k, int nblk, int m, int Dd, int dt, void* d_xdec, float* d_mask_token,
@@ -107,8 +142,6 @@ int launch_classifier_head(const HeadCall& h, hipStream_t s);
 int64_t classifier_wgrad_partial_floats(int B, int C, int D);
 int launch_classifier_head_wgrad(const float* dlogits, const float* pooled, int B, int C, int D, float* partial, float* sum_out,
                                  float* head_grads, hipStream_t s);
-// zero every row of dres / dres_c (B*L rows) whose token index is not 0
-int launch_zero_token_rows(int64_t rows, int L, int D, int act, float* dres, void* dres_c, hipStream_t s);
 // one read of dx (B, L, D), L rows per image.  has_cls: dtok = dx with class rows zeroed, dpos (L*D) = sum over images, dcls (D) =
 // dpos[0].  Patch-only (row t is patch token t + 1): dtok = dx, dpos ((L + 1) * D) rows 1..L = sum over images, dpos row 0 and
 // dcls = exact zeros.  partial >= full_grad_split_slices(B, L, D) * L * D floats
