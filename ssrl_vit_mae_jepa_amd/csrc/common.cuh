@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <algorithm>
+#include <type_traits>
 #include "../../include/mae_hip.h"
 
 typedef __bf16 bf16;
@@ -48,6 +49,11 @@ inline size_t dtype_size(int dt) { return dt == MAE_BF16 ? 2 : 4; }
 template <class F>
 void with_dtype(int dt, F&& f) {
   if (dt == MAE_BF16) f(bf16{}); else f(float{});
+}
+// the same for a kernel's bool template argument: f(std::true_type{}) or f(std::false_type{}), read as decltype(b)::value
+template <class F>
+void with_bool(bool flag, F&& f) {
+  if (flag) f(std::true_type{}); else f(std::false_type{});
 }
 
 // a kernel gets 64 KiB of dynamic LDS by default: a launch that asks for more raises the kernel's limit first
@@ -97,6 +103,8 @@ __device__ __forceinline__ f32x4 load4_nt(const bf16* p) {
 }
 
 // ---- reductions ------------------------------------------------------------------------------
+// sum of the squares of a float4, left to right: the one association of every scalar sum of squares
+__device__ __forceinline__ float sumsq4(f32x4 v) { return v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -104,7 +104,7 @@ int launch_smooth_l1(const float* pred, const float* target, int64_t n, float gr
                      float* scratch, hipStream_t s) {
   MAE_REQUIRE(pred && target && loss && scratch && n > 0 && n % 4 == 0, "smooth_l1: need n %% 4 == 0 and non-null buffers");
   const int64_t n4 = n / 4;
-  const int grid = (int)std::min<int64_t>(cdiv(n4, 256), 1024);
+  const int grid = (int)std::min<int64_t>(cdiv(n4, 256), RED_BLOCKS);
   const float gs = grad_scale / (float)n;
   MAE_LAUNCH_LOSS(smooth_l1_kernel, (), grid, 0, s, d_pred, dpred_dt, scratch, 1.0f / (float)n, loss, pred, target, n4, gs);
   return 0;

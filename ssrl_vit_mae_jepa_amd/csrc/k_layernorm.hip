@@ -1,29 +1,11 @@
 // LayerNorm(eps) forward / backward over fp32 residual-stream rows; LPR lanes per row (64, 32 or 16: a wave walks 1, 2 or 4
 // rows at a time so that 384- and 192-wide rows = 96 / 48 float4 fill every lane; at 64 lanes per row a quarter of the lanes
 // idled), the row held in registers, mean/variance by shuffles inside the lane group.  HBM-bound: fwd reads 4*D B/row,
-// writes sizeof(T)*D.
+// writes sizeof(T)*D.  Cache policy as measured on the step: store4_nt for the fp32 residual-stream and dx stores (-0.4 ms), load4_nt
+// for the read-once x, branch and dy (-0.2 ms, mostly in the GEMMs that follow), plain store4 for the y / dx_copy copies (no gain).
 // Reference behaviour: torch.nn.LayerNorm(dim, eps=1e-6) as timm VisionTransformer / lightly MAEDecoderTIMM
 // instantiate it (norm1/norm2/norm/decoder_norm), computed in fp32 (autocast keeps layer_norm in fp32).
 #include "kernels.h"
-
-#ifndef MAE_LN_NT
-#define MAE_LN_NT 5  // bit 0: fp32 residual-stream / dx stores stream (measured -0.4 ms per step); bit 1: the bf16 operand copies too (no gain); bit 2: the read-once inputs (x, branch, dy) are loaded non-temporally (-0.2 ms, mostly in the GEMMs that follow)
-#endif
-#if MAE_LN_NT & 1
-#define LN_ST_A store4_nt
-#else
-#define LN_ST_A store4
-#endif
-#if MAE_LN_NT & 2
-#define LN_ST_B store4_nt
-#else
-#define LN_ST_B store4
-#endif
-#if MAE_LN_NT & 4
-#define LN_LD load4_nt
-#else
-#define LN_LD load4
-#endif
 
 namespace mae {
 
@@ -43,6 +25,24 @@ static int ln_lanes_per_row(int d4) {
     if (fill > best_fill + 1e-9) { best_fill = fill; best = lpr; }
   }
   return best;
+}
+// The eight (lanes per row, float4 per lane) pairs that ln_lanes_per_row gives for dim 4..1024, and the only ones compiled:
+// f(integral_constant<LPR>, integral_constant<NV>) for the pair (lpr, nv)
+template <int N> using int_c = std::integral_constant<int, N>;
+template <class F>
+static int with_ln_shape(int lpr, int nv, F&& f) {
+  switch (lpr * 8 + nv) {
+    case 16 * 8 + 1: f(int_c<16>{}, int_c<1>{}); break;
+    case 32 * 8 + 1: f(int_c<32>{}, int_c<1>{}); break;
+    case 16 * 8 + 3: f(int_c<16>{}, int_c<3>{}); break;
+    case 64 * 8 + 1: f(int_c<64>{}, int_c<1>{}); break;
+    case 32 * 8 + 3: f(int_c<32>{}, int_c<3>{}); break;
+    case 64 * 8 + 2: f(int_c<64>{}, int_c<2>{}); break;
+    case 64 * 8 + 3: f(int_c<64>{}, int_c<3>{}); break;
+    case 64 * 8 + 4: f(int_c<64>{}, int_c<4>{}); break;
+    default: MAE_REQUIRE(false, "layernorm: no kernel for lpr = %d lanes per row with nv = %d float4 per lane", lpr, nv);
+  }
+  return 0;
 }
 
 // NV = float4 vectors per lane: covers dim <= 4*LPR*NV
@@ -83,11 +83,11 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
     for (int i = 0; i < NV; ++i) {
       const int c = li + LPR * i;
       if (c < D4) {
-        v[i] = LN_LD(px + c * 4);
+        v[i] = load4_nt(px + c * 4);
         if (ADD) {
-          if (!SCALE) v[i] += LN_LD(branch + src * dim + c * 4);
-          else if (sc != 0.f) v[i] += LN_LD(branch + src * dim + c * 4) * sc;
-          if (live) LN_ST_A(x_out + src * dim + c * 4, v[i]);
+          if (!SCALE) v[i] += load4_nt(branch + src * dim + c * 4);
+          else if (sc != 0.f) v[i] += load4_nt(branch + src * dim + c * 4) * sc;
+          if (live) store4_nt(x_out + src * dim + c * 4, v[i]);
         }
         sum += v[i][0] + v[i][1] + v[i][2] + v[i][3];
       } else {
@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
       const int c = li + LPR * i;
       if (c < D4) {
         const f32x4 d = v[i] - mean;
-        sq += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
+        sq += sumsq4(d);
       }
     }
     const float var = group_sum<LPR>(sq) * inv_d;
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
       const int c = li + LPR * i;
       if (c < D4 && live) {
         const f32x4 o = (v[i] - mean) * rstd * load4(gamma + c * 4) + load4(beta + c * 4);
-        LN_ST_B(py + c * 4, o);
+        store4(py + c * 4, o);
       }
     }
     if (li == 0 && live) {
@@ -132,21 +132,20 @@ int launch_layernorm_fwd(const float* x, const void* branch, float* x_out, const
   MAE_REQUIRE(dim % 4 == 0 && dim >= 4 && dim <= 1024, "layernorm: dim %d must be a multiple of 4 in [4, 1024]", dim);
   const int lpr = ln_lanes_per_row(dim / 4), nv = (int)cdiv(dim / 4, lpr);
   const int grid = (int)std::min<int64_t>(cdiv(rows, 4 * (64 / lpr)), 256 * 32);
-#define LN(T, NV, ADD, LPR) hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV, ADD, LPR>), dim3(grid), dim3(256), 0, s, x, (const T*)branch, x_out, row_map, gamma, beta, eps, rows, dim, (T*)y, mean, rstd)
-#define LN_NV(T, ADD, LPR) switch (nv) { case 1: LN(T, 1, ADD, LPR); break; case 2: LN(T, 2, ADD, LPR); break; case 3: LN(T, 3, ADD, LPR); break; default: LN(T, 4, ADD, LPR); }
-#define LN_LPR(T, ADD) switch (lpr) { case 16: LN_NV(T, ADD, 16) break; case 32: LN_NV(T, ADD, 32) break; default: LN_NV(T, ADD, 64) }
-#define LNS(T, NV, LPR) hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV, true, LPR, const float*, int>), dim3(grid), dim3(256), 0, s, x, (const T*)branch, x_out, row_map, gamma, beta, eps, rows, dim, (T*)y, mean, rstd, image_scale, rows_per_image)
-#define LNS_NV(T, LPR) switch (nv) { case 1: LNS(T, 1, LPR); break; case 2: LNS(T, 2, LPR); break; case 3: LNS(T, 3, LPR); break; default: LNS(T, 4, LPR); }
-#define LNS_LPR(T) switch (lpr) { case 16: LNS_NV(T, 16) break; case 32: LNS_NV(T, 32) break; default: LNS_NV(T, 64) }
-  if (image_scale) { if (y_dt == MAE_BF16) { LNS_LPR(bf16) } else { LNS_LPR(float) } }
-  else if (y_dt == MAE_BF16) { if (branch) { LN_LPR(bf16, true) } else { LN_LPR(bf16, false) } }
-  else { if (branch) { LN_LPR(float, true) } else { LN_LPR(float, false) } }
-#undef LNS_LPR
-#undef LNS_NV
-#undef LNS
-#undef LN_LPR
-#undef LN_NV
-#undef LN
+  const auto launch = [&](auto add, auto... scale) {  // scale: () or (image_scale, rows_per_image)
+    int rc = 0;
+    with_dtype(y_dt, [&](auto t) {
+      using T = decltype(t);
+      rc = with_ln_shape(lpr, nv, [&](auto L, auto N) {
+        hipLaunchKernelGGL((layernorm_fwd_kernel<T, decltype(N)::value, decltype(add)::value, decltype(L)::value, decltype(scale)...>), dim3(grid),
+                           dim3(256), 0, s, x, (const T*)branch, x_out, row_map, gamma, beta, eps, rows, dim, (T*)y, mean, rstd, scale...);
+      });
+    });
+    return rc;
+  };
+  if (image_scale) MAE_TRY(launch(std::true_type{}, image_scale, rows_per_image));
+  else if (branch) MAE_TRY(launch(std::true_type{}));
+  else MAE_TRY(launch(std::false_type{}));
   MAE_LAUNCH_CHECK();
   return 0;
 }
@@ -192,8 +191,8 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict_
     for (int i = 0; i < NV; ++i) {
       const int c = li + LPR * i;
       if (c < D4) {
-        const f32x4 d = LN_LD(dy + r * dim + c * 4);
-        xh[i] = (LN_LD(x + src * dim + c * 4) - mu) * rs;
+        const f32x4 d = load4_nt(dy + r * dim + c * 4);
+        xh[i] = (load4_nt(x + src * dim + c * 4) - mu) * rs;
         g[i] = d * gam[i];
         if (live) {
           dg[i] += d * xh[i];
@@ -212,9 +211,9 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const T* __restrict_
         f32x4 d = (g[i] - s1 - xh[i] * s2) * rs;
         float* pd = dx_io + src * dim + c * 4;
         if (accumulate) d += load4(pd);
-        LN_ST_A(pd, d);
-        if (SCALE) LN_ST_B(dx_copy + src * dim + c * 4, d * sc);
-        else if (dx_copy) LN_ST_B(dx_copy + src * dim + c * 4, d);
+        store4_nt(pd, d);
+        if (SCALE) store4(dx_copy + src * dim + c * 4, d * sc);
+        else if (dx_copy) store4(dx_copy + src * dim + c * 4, d);
       }
     }
   }
@@ -250,20 +249,18 @@ int launch_layernorm_bwd(const void* dy, int dy_dt, const float* x, const int32_
   const int lpr = ln_lanes_per_row(dim / 4), nv = (int)cdiv(dim / 4, lpr);
   const int grid = (int)std::min<int64_t>(cdiv(rows, 4 * (64 / lpr)), LN_BWD_MAX_BLOCKS);
   const size_t lds = (size_t)8 * (64 / lpr) * dim * sizeof(float);
-#define LNB(T, NV, LPR) hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV, LPR>), dim3(grid), dim3(256), lds, s, (const T*)dy, x, row_map, gamma, mean, rstd, rows, dim, accumulate, dx_io, (T*)dx_copy, partial)
-#define LNB_NV(T, LPR) switch (nv) { case 1: LNB(T, 1, LPR); break; case 2: LNB(T, 2, LPR); break; case 3: LNB(T, 3, LPR); break; default: LNB(T, 4, LPR); }
-#define LNB_LPR(T) switch (lpr) { case 16: LNB_NV(T, 16) break; case 32: LNB_NV(T, 32) break; default: LNB_NV(T, 64) }
-#define LNBS(T, NV, LPR) hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV, LPR, const float*, int>), dim3(grid), dim3(256), lds, s, (const T*)dy, x, row_map, gamma, mean, rstd, rows, dim, accumulate, dx_io, (T*)dx_copy, partial, copy_scale, rows_per_image)
-#define LNBS_NV(T, LPR) switch (nv) { case 1: LNBS(T, 1, LPR); break; case 2: LNBS(T, 2, LPR); break; case 3: LNBS(T, 3, LPR); break; default: LNBS(T, 4, LPR); }
-#define LNBS_LPR(T) switch (lpr) { case 16: LNBS_NV(T, 16) break; case 32: LNBS_NV(T, 32) break; default: LNBS_NV(T, 64) }
-  if (copy_scale) { if (dy_dt == MAE_BF16) { LNBS_LPR(bf16) } else { LNBS_LPR(float) } }
-  else if (dy_dt == MAE_BF16) { LNB_LPR(bf16) } else { LNB_LPR(float) }
-#undef LNBS_LPR
-#undef LNBS_NV
-#undef LNBS
-#undef LNB_LPR
-#undef LNB_NV
-#undef LNB
+  const auto launch = [&](auto... scale) {  // scale: () or (copy_scale, rows_per_image)
+    int rc = 0;
+    with_dtype(dy_dt, [&](auto t) {
+      using T = decltype(t);
+      rc = with_ln_shape(lpr, nv, [&](auto L, auto N) {
+        hipLaunchKernelGGL((layernorm_bwd_kernel<T, decltype(N)::value, decltype(L)::value, decltype(scale)...>), dim3(grid), dim3(256), lds, s,
+                           (const T*)dy, x, row_map, gamma, mean, rstd, rows, dim, accumulate, dx_io, (T*)dx_copy, partial, scale...);
+      });
+    });
+    return rc;
+  };
+  MAE_TRY(copy_scale ? launch(copy_scale, rows_per_image) : launch());
   MAE_LAUNCH_CHECK();
   if (defer) {
     const int i = defer->n++;

@@ -9,8 +9,6 @@
 
 namespace mae {
 
-constexpr int RED_BLOCKS = 1024;  // stage-1 partial count upper bound (scratch holds RED_BLOCKS floats + 8)
-
 // ---------------------------------------------------------------------------------------------------
 // MSE
 // ---------------------------------------------------------------------------------------------------
@@ -22,27 +20,42 @@ __global__ void __launch_bounds__(256) mse_kernel(const float* __restrict__ pred
   float acc = 0.f;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const f32x4 d = load4(pred + i * 4) - load4(target + i * 4);
-    acc += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
+    acc += sumsq4(d);
     if (HAS_GRAD) store4(dpred + i * 4, d * gscale);
   }
   acc = block_sum_256(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
-__global__ void __launch_bounds__(256) mean_finalize_kernel(const float* __restrict__ partial, int nb, float inv_n,
-                                                            float* __restrict__ out) {
+// Stage 2 of every scalar sum: one block adds partial[0 .. nb) in a fixed order and thread 0 hands the total to `tail`
+template <class Tail>
+__global__ void __launch_bounds__(256) finalize_kernel(const float* __restrict__ partial, int nb, Tail tail) {
   __shared__ float red[4];
   float acc = 0.f;
   for (int i = threadIdx.x; i < nb; i += 256) acc += partial[i];
   acc = block_sum_256(acc, red);
-  if (threadIdx.x == 0) out[0] = acc * inv_n;
+  if (threadIdx.x == 0) tail(acc);
 }
+template <class Tail>
+static int launch_finalize(const float* partial, int nb, Tail tail, hipStream_t s) {
+  hipLaunchKernelGGL(finalize_kernel<Tail>, dim3(1), dim3(256), 0, s, partial, nb, tail);
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
+// stats[0] = the norm, stats[1] = clip_grad_norm_'s coefficient clamp(max_norm / (total + 1e-6), max = 1)
+__device__ __forceinline__ void clip_from_sumsq(float sumsq, float max_norm, float* stats) {
+  const float total = sqrtf(sumsq);
+  stats[0] = total;
+  stats[1] = fminf(max_norm / (total + 1e-6f), 1.0f);
+}
+// the three tails: the mean of a loss, the sum itself, the gradient norm with its clip coefficient
+struct MeanTail  { float inv_n; float* out;      __device__ void operator()(float acc) const { out[0] = acc * inv_n; } };
+struct StoreTail { float* out;                   __device__ void operator()(float acc) const { out[0] = acc; } };
+struct ClipTail  { float max_norm; float* stats; __device__ void operator()(float acc) const { clip_from_sumsq(acc, max_norm, stats); } };
 
 int launch_mean_finalize(const float* partial, int nb, float inv_n, float* out, hipStream_t s) {
   MAE_REQUIRE(partial && out && nb > 0, "mean_finalize: bad arguments");
-  hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, s, partial, nb, inv_n, out);
-  MAE_LAUNCH_CHECK();
-  return 0;
+  return launch_finalize(partial, nb, MeanTail{inv_n, out}, s);
 }
 
 int launch_mse(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, void* d_pred,
@@ -63,47 +76,28 @@ __global__ void __launch_bounds__(256) sumsq_kernel(const float* __restrict__ g,
   float acc = 0.f;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const f32x4 v = load4(g + i * 4);
-    acc += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    acc += sumsq4(v);
   }
   acc = block_sum_256(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
-
-__global__ void __launch_bounds__(256) norm_finalize_kernel(const float* __restrict__ partial, int nb, float max_norm,
-                                                            float* __restrict__ stats) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) acc += partial[i];
-  acc = block_sum_256(acc, red);
-  if (threadIdx.x == 0) {
-    const float total = sqrtf(acc);
-    stats[0] = total;
-    stats[1] = fminf(max_norm / (total + 1e-6f), 1.0f);  // clip_grad_norm_: clamp(max_norm/(total+1e-6), max=1)
-  }
+// both stages: the block sums of g's squares into scratch, then tail(their sum)
+template <class Tail>
+static int launch_sumsq(const float* g, int64_t n, float* scratch, Tail tail, hipStream_t s) {
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n / 4, 256), RED_BLOCKS));
+  hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, s, g, n / 4, scratch);   // n == 0: every partial is zero
+  MAE_LAUNCH_CHECK();
+  return launch_finalize(scratch, grid, tail, s);
 }
 
 // the two halves of launch_grad_norm for a gradient that is sharded over ranks: sum of squares of a range, then (after the ranks'
 // sums were added) norm + clip coefficient from the total
-__global__ void __launch_bounds__(256) sumsq_finalize_kernel(const float* __restrict__ partial, int nb, float* __restrict__ out) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) acc += partial[i];
-  acc = block_sum_256(acc, red);
-  if (threadIdx.x == 0) out[0] = acc;
-}
 __global__ void clip_from_sumsq_kernel(const float* __restrict__ sumsq, float max_norm, float* __restrict__ stats) {
-  const float total = sqrtf(sumsq[0]);
-  stats[0] = total;
-  stats[1] = fminf(max_norm / (total + 1e-6f), 1.0f);
+  clip_from_sumsq(sumsq[0], max_norm, stats);
 }
 int launch_grad_sumsq(const float* g, int64_t n, float* out, float* scratch, hipStream_t s) {
   MAE_REQUIRE(g && out && scratch && n >= 0 && n % 4 == 0, "grad_sumsq: need n %% 4 == 0 and non-null buffers");
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n / 4, 256), RED_BLOCKS));
-  hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, s, g, n / 4, scratch);   // n == 0: every partial is zero
-  MAE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sumsq_finalize_kernel, dim3(1), dim3(256), 0, s, scratch, grid, out);
-  MAE_LAUNCH_CHECK();
-  return 0;
+  return launch_sumsq(g, n, scratch, StoreTail{out}, s);
 }
 // out[0] += out[1] (the buffer sum of squares folded into a running total)
 __global__ void add_slot_kernel(float* out) { out[0] += out[1]; }
@@ -122,12 +116,7 @@ int launch_clip_from_sumsq(const float* sumsq, float max_norm, float* stats, hip
 
 int launch_grad_norm(const float* g, int64_t n, float max_norm, float* stats, float* scratch, hipStream_t s) {
   MAE_REQUIRE(g && stats && scratch && n > 0 && n % 4 == 0, "grad_norm: need n %% 4 == 0 and non-null buffers");
-  const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), RED_BLOCKS);
-  hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, s, g, n / 4, scratch);
-  MAE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(256), 0, s, scratch, grid, max_norm, stats);
-  MAE_LAUNCH_CHECK();
-  return 0;
+  return launch_sumsq(g, n, scratch, ClipTail{max_norm, stats}, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -177,10 +166,10 @@ int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float 
   const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), 256 * 16);
   const float inv_bc1 = 1.0f / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
   MAE_REQUIRE(!ema_target || (ema_n > 0 && ema_n % 4 == 0 && ema_n <= n && (!wbf || ema_wbf)), "adamw: bad EMA range");
-#define ADAMW(W, E) hipLaunchKernelGGL((adamw_kernel<W, E>), dim3(grid), dim3(256), 0, s, p, g, m, v, n / 4, lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, stats, wbf, ema_target, ema_wbf, ema_n / 4, ema_momentum)
-  if (wbf) { if (ema_target) ADAMW(true, true); else ADAMW(true, false); }
-  else     { if (ema_target) ADAMW(false, true); else ADAMW(false, false); }
-#undef ADAMW
+  with_bool(wbf != nullptr, [&](auto W) { with_bool(ema_target != nullptr, [&](auto E) {
+    hipLaunchKernelGGL((adamw_kernel<decltype(W)::value, decltype(E)::value>), dim3(grid), dim3(256), 0, s, p, g, m, v, n / 4, lr, b1, b2, eps, wd,
+                       inv_bc1, inv_sqrt_bc2, stats, wbf, ema_target, ema_wbf, ema_n / 4, ema_momentum);
+  }); });
   MAE_LAUNCH_CHECK();
   return 0;
 }
@@ -201,8 +190,7 @@ __global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict_
 int launch_grad_accumulate(float* dst, const float* src, int64_t n, bool overwrite, hipStream_t s) {
   MAE_REQUIRE(dst && src && n > 0 && n % 4 == 0, "grad_accumulate: need n %% 4 == 0 and non-null buffers");
   const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), GRAD_ACC_BLOCKS);
-  if (overwrite) hipLaunchKernelGGL((grad_accumulate_kernel<true>), dim3(grid), dim3(256), 0, s, dst, src, n / 4);
-  else           hipLaunchKernelGGL((grad_accumulate_kernel<false>), dim3(grid), dim3(256), 0, s, dst, src, n / 4);
+  with_bool(overwrite, [&](auto O) { hipLaunchKernelGGL((grad_accumulate_kernel<decltype(O)::value>), dim3(grid), dim3(256), 0, s, dst, src, n / 4); });
   MAE_LAUNCH_CHECK();
   return 0;
 }

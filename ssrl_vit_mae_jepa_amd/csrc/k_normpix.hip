@@ -174,7 +174,7 @@ int launch_mse_norm_pix(const float* pred, const void* images, int img_dt, const
   MAE_REQUIRE((((uintptr_t)pred | (uintptr_t)loss | (uintptr_t)scratch) & 3) == 0 && ((uintptr_t)d_pred & (dpred_dt == MAE_BF16 ? 1 : 3)) == 0,
               "mse_norm_pix: misaligned buffer");
   const int64_t rows = (int64_t)B * m, n = rows * p * p * C;
-  const int grid = (int)std::min<int64_t>(cdiv(rows, NP_WAVES), 1024);  // stage-1 partials: scratch holds 1024 floats + 8
+  const int grid = (int)std::min<int64_t>(cdiv(rows, NP_WAVES), RED_BLOCKS);
   const float gs = grad_scale * 2.0f / (float)n;
   const size_t lds = (size_t)C * p * p * 4 * NP_WAVES;
   if (img_dt == MAE_U8)

@@ -247,7 +247,7 @@ template <class PX>
 static int mse_from_images_band(const float* pred, const PX* images, const int32_t* mask32, int B, int m, int C, int img, int p, float grad_scale,
                          float* loss, void* d_pred, int dpred_dt, float* scratch, hipStream_t s) {
   const int64_t n = (int64_t)B * m * p * p * C;
-  const int grid = (int)std::min<int64_t>((int64_t)B * (img / p), 1024);  // stage-1 partials: scratch holds 1024 floats + 8
+  const int grid = (int)std::min<int64_t>((int64_t)B * (img / p), RED_BLOCKS);
   const float gs = grad_scale * 2.0f / (float)n;
   const size_t lds = (size_t)C * p * img * sizeof(PX) + (size_t)m * 8;   // band + token list + its sorted copy: up to 96 + 64 KiB
   MAE_LAUNCH_LOSS(mse_images_band_kernel, (PX,), grid, lds, s, d_pred, dpred_dt, scratch, 1.0f / (float)n, loss, pred, images, mask32, B, m, C, img,
@@ -385,7 +385,7 @@ int launch_mse_from_images(const float* pred, const void* images, int img_dt, co
     return mse_from_images_band(pred, (const float*)images, mask32, B, m, C, img, p, grad_scale, loss, d_pred, dpred_dt, scratch, s);
   const int64_t rows = (int64_t)B * m;
   const int64_t n = rows * p * p * C;
-  const int grid = (int)std::min<int64_t>(cdiv(rows * p * p, 256), 1024);  // stage-1 partials: scratch holds 1024 floats + 8
+  const int grid = (int)std::min<int64_t>(cdiv(rows * p * p, 256), RED_BLOCKS);
   const float gs = grad_scale * 2.0f / (float)n;
   MAE_LAUNCH_LOSS(mse_images_kernel, (), grid, 0, s, d_pred, dpred_dt, scratch, 1.0f / (float)n, loss, pred, (const float*)images, mask32, rows, m, C,
                   img, p, gs);

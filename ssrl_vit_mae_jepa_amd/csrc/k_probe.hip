@@ -159,8 +159,8 @@ __global__ void __launch_bounds__(256) lars_sumsq_kernel(const float* __restrict
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const f32x4 v = load4(p + i * 4);
     const f32x4 d = load4(g + i * 4) + v * wd;
-    ap += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-    au += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
+    ap += sumsq4(v);
+    au += sumsq4(d);
   }
   ap = block_sum_256(ap, red);
   au = block_sum_256(au, red);
@@ -223,10 +223,9 @@ int launch_lars_step(float* p, const float* g, float* mu, int64_t n, int adapt, 
     MAE_LAUNCH_CHECK();
   }
   const int grid = (int)std::min<int64_t>(cdiv(n4, 256), 256 * 16);
-  if (adapt)
-    hipLaunchKernelGGL((lars_update_kernel<true>), dim3(grid), dim3(256), 0, s, p, g, mu, n4, lr, momentum, wd, scratch + 2 * LARS_BLOCKS);
-  else
-    hipLaunchKernelGGL((lars_update_kernel<false>), dim3(grid), dim3(256), 0, s, p, g, mu, n4, lr, momentum, 0.f, (const float*)nullptr);
+  with_bool(adapt != 0, [&](auto A) {  // without ADAPT the kernel reads neither wd nor the stats
+    hipLaunchKernelGGL((lars_update_kernel<decltype(A)::value>), dim3(grid), dim3(256), 0, s, p, g, mu, n4, lr, momentum, wd, scratch + 2 * LARS_BLOCKS);
+  });
   MAE_LAUNCH_CHECK();
   return 0;
 }

@@ -217,9 +217,10 @@ int launch_mse(const float* pred, const float* target, int64_t n, float grad_sca
 // out[0] = inv_n * sum of partial[0 .. nb): the second stage of the loss reductions
 int launch_mean_finalize(const float* partial, int nb, float inv_n, float* out, hipStream_t s);
 // Every loss runs in two stages.  Stage 1 is a kernel family K<.., T, HAS_GRAD> whose arguments end in (float* partial, T* dpred): the
-// instantiation that d_pred asks for (null: <float, false>, else <bf16, true> or <float, true>) leaves `grid` block sums in scratch
-// (1024+ floats); stage 2 is launch_mean_finalize.  PRE holds the family's leading template arguments with their comma, in
-// parentheses: () or (uint8_t,).  `...` are the kernel's arguments in front of (scratch, d_pred).
+// instantiation that d_pred asks for (null: <float, false>, else <bf16, true> or <float, true>) leaves `grid` <= RED_BLOCKS block sums
+// in scratch (RED_BLOCKS floats + 8); stage 2 is launch_mean_finalize.  PRE holds the family's leading template arguments with their
+// comma, in parentheses: () or (uint8_t,).  `...` are the kernel's arguments in front of (scratch, d_pred).
+constexpr int RED_BLOCKS = 1024;  // stage-1 partial count upper bound of every scalar sum (the losses, the gradient's sum of squares)
 template <class K, class T, class... A>
 int launch_loss_stage1(K kernel, int grid, size_t lds, hipStream_t s, T* dpred, A... args) {
   MAE_TRY(allow_lds(kernel, lds));

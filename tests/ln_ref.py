@@ -74,7 +74,7 @@ F = np.float32
 # (lanes per row, NV, smallest dim, largest dim) of the eight instantiations ln_lanes_per_row can select
 PAIRS = [(16, 1, 4, 64), (32, 1, 68, 128), (16, 3, 132, 192), (64, 1, 196, 256), (32, 3, 260, 384), (64, 2, 388, 512),
          (64, 3, 516, 768), (64, 4, 772, 1024)]
-UNREACHABLE = [(16, 2), (16, 4), (32, 2), (32, 4)]   # compiled and never selected: ties in the fill go to the wider group
+UNREACHABLE = [(16, 2), (16, 4), (32, 2), (32, 4)]   # never selected, not compiled: ties in the fill go to the wider group
 
 
 def f32(x) -> float:
