@@ -1,5 +1,6 @@
 // Device helpers shared by the MFMA GEMM files (k_gemm_nt1.hip, k_gemm_nt2.hip, k_gemm_nt3.hip, k_gemm_tn.hip): the block
-// remap, the counted wait, the transposed LDS read, the LDS-DMA issue forms and the value pieces of the NT epilogues.
+// remap, the counted wait, the transposed LDS read, the LDS-DMA issue forms, the value pieces of the NT epilogues and the one
+// value step that nt1 and nt2 build from them (epi_values8).
 #pragma once
 #include "gemm_mfma.h"
 
@@ -60,7 +61,8 @@ __device__ __forceinline__ i32x4 make_rsrc(const void* p, uint32_t bytes) {
 }
 
 // ---- pieces of the NT epilogues (k_gemm_nt1 / nt2 / nt3.hip).  The store forms are NOT here: they differ per kernel on purpose
-// (nt1 plain, nt2 non-temporal, nt3 buffer stores with a per-piece cache policy), each measured.
+// (nt1 plain, nt2 non-temporal, nt3 buffer stores with a per-piece cache policy), each measured.  nt3 keeps its own mode switch
+// over the same pieces (three modes; its register allocation is as sensitive as the note on MAE_REGROUP8 says).
 
 // 8 consecutive outputs of one row as two f32x4: load (fp32 / bf16 side inputs), unpack and pack
 __device__ __forceinline__ void unpack8(const bf16x8& v, f32x4& a, f32x4& b) {
@@ -90,6 +92,29 @@ __device__ __forceinline__ void gelu_rounded(f32x4& v0, f32x4& v1, f32x4& a0, f3
   }
   gelu_fast_pair(v0, a0, g0);
   gelu_fast_pair(v1, a1, g1);
+}
+// The value step of nt1's and nt2's epilogues, every mode in both output types.  In: v = a lane's 8 accumulators with the bias added,
+// q = the (m, n) side input of RESID / DGELU / MUL, loaded or prefetched by the caller (unread in the other modes).  Out: v = the 8
+// values for `out`, w = the 8 for `out2` (GELU and GELU_GRAD only).  Loads, stores and the accumulator zeroing stay with the kernel.
+constexpr bool epi_side_input(int mode) { return mode == MAE_EPI_RESID || mode == MAE_EPI_DGELU || mode == MAE_EPI_MUL; }
+constexpr bool epi_two_outputs(int mode) { return mode == MAE_EPI_GELU || mode == MAE_EPI_GELU_GRAD; }
+template <int MODE, class TO>
+__device__ __forceinline__ void epi_values8(f32x4& v0, f32x4& v1, const f32x4& q0, const f32x4& q1, f32x4& w0, f32x4& w1) {
+  if constexpr (MODE == MAE_EPI_GELU || MODE == MAE_EPI_GELU_GRAD || MODE == MAE_EPI_GELU_ACT) {
+    f32x4 a0, a1, g0, g1;
+    gelu_rounded<TO>(v0, v1, a0, a1, g0, g1);
+    if (MODE == MAE_EPI_GELU) { w0 = a0; w1 = a1; }
+    else if (MODE == MAE_EPI_GELU_GRAD) { v0 = g0; v1 = g1; w0 = a0; w1 = a1; }
+    else { v0 = a0; v1 = a1; }
+  } else if constexpr (MODE == MAE_EPI_RESID) {
+    v0 += q0; v1 += q1;
+  } else if constexpr (MODE == MAE_EPI_DGELU) {
+    f32x4 a_, g_;
+    gelu_fast_pair(q0, a_, g_); v0 *= g_;
+    gelu_fast_pair(q1, a_, g_); v1 *= g_;
+  } else if constexpr (MODE == MAE_EPI_MUL) {
+    v0 *= q0; v1 *= q1;
+  }
 }
 
 // After the MFMAs lane (fq, fr) holds, per 16x16 tile ni, 4 consecutive columns (4 fq ..) of row fr.  One v_permlane16_swap per

@@ -1,6 +1,7 @@
 // bf16 MFMA GEMM kernels (k_gemm_nt1 / nt2 / nt3.hip, k_gemm_tn.hip, k_attention_mfma.hip): entry points used by the dispatch in
 // k_gemm.hip, and the host pieces the three NT files share.  Each entry point returns MFMA_UNSUPPORTED when the shape or the
-// epilogue is outside what its kernel takes; the caller then tries the next kernel.
+// epilogue is outside what its kernel takes; the caller then tries the next kernel, and last the generic kernel (launch_generic,
+// k_gemm.hip).  The device pieces, the 8-column epilogue value step of v1 and v2 among them, are in gemm_dev.cuh.
 #pragma once
 #include "kernels.h"
 #include <type_traits>

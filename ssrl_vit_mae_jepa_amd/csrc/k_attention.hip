@@ -165,21 +165,32 @@ __global__ void __launch_bounds__(256) attn_bwd_generic_kernel(const T* __restri
 
 static int attn_block(int T) { return (int)std::min<int64_t>(round_up(T, 64), 256); }
 
+// the head-dimension pick of both launchers: f(std::integral_constant<int, HD>{}) for the five compiled sizes
+template <class F>
+static int with_head_dim(int hd, F&& f) {
+  switch (hd) {
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 24: return f(std::integral_constant<int, 24>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 48: return f(std::integral_constant<int, 48>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    default: set_error("attention: head_dim %d unsupported (16, 24, 32, 48, 64)", hd); return 1;
+  }
+}
+
 template <class T>
 static int run_attn_fwd(const void* qkv, int B, int Tn, int H, int hd, void* out, float* lse, hipStream_t s) {
   const int KB = (int)std::min<int64_t>(Tn, (160 * 1024) / (2 * hd * (int)sizeof(float)));   // rows of K and V per LDS block
   const size_t lds = (size_t)2 * KB * hd * sizeof(float);
   const float scale = 1.0f / sqrtf((float)hd);
   const dim3 grid((unsigned)B * H), block(attn_block(Tn));
-#define AF(HD) { MAE_HIP(hipFuncSetAttribute((const void*)attn_fwd_generic_kernel<T, HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((attn_fwd_generic_kernel<T, HD>), grid, block, lds, s, (const T*)qkv, Tn, H, scale, (T*)out, lse, KB); }
-  switch (hd) {
-    case 16: AF(16) break; case 24: AF(24) break; case 32: AF(32) break; case 48: AF(48) break; case 64: AF(64) break;
-    default: set_error("attention: head_dim %d unsupported (16, 24, 32, 48, 64)", hd); return 1;
-  }
-#undef AF
-  MAE_LAUNCH_CHECK();
-  return 0;
+  return with_head_dim(hd, [&](auto d) -> int {
+    auto kern = attn_fwd_generic_kernel<T, decltype(d)::value>;
+    MAE_TRY(allow_lds(kern, lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, s, (const T*)qkv, Tn, H, scale, (T*)out, lse, KB);
+    MAE_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 template <class T>
@@ -190,15 +201,13 @@ static int run_attn_bwd(const void* qkv, const void* out, const void* d_out, con
   const size_t lds = ((size_t)2 * KB * hd + 2 * Tn) * sizeof(float);
   const float scale = 1.0f / sqrtf((float)hd);
   const dim3 grid((unsigned)B * H), block(attn_block(Tn));
-#define AB(HD) { MAE_HIP(hipFuncSetAttribute((const void*)attn_bwd_generic_kernel<T, HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((attn_bwd_generic_kernel<T, HD>), grid, block, lds, s, (const T*)qkv, (const T*)out, (const T*)d_out, lse, Tn, H, scale, (T*)d_qkv, KB); }
-  switch (hd) {
-    case 16: AB(16) break; case 24: AB(24) break; case 32: AB(32) break; case 48: AB(48) break; case 64: AB(64) break;
-    default: set_error("attention: head_dim %d unsupported (16, 24, 32, 48, 64)", hd); return 1;
-  }
-#undef AB
-  MAE_LAUNCH_CHECK();
-  return 0;
+  return with_head_dim(hd, [&](auto d) -> int {
+    auto kern = attn_bwd_generic_kernel<T, decltype(d)::value>;
+    MAE_TRY(allow_lds(kern, lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, s, (const T*)qkv, (const T*)out, (const T*)d_out, lse, Tn, H, scale, (T*)d_qkv, KB);
+    MAE_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_attention_fwd(const void* qkv, int B, int T, int H, int hd, int dt, void* out, float* lse, hipStream_t s) {

@@ -11,7 +11,8 @@
 namespace mae {
 
 // ---------------------------------------------------------------------------------------------------
-// epilogue shared by every GEMM kernel: (m, n, acc) -> stores
+// epilogue of the generic kernel, one output at a time: (m, n, acc) -> stores.  Scalar, exact erff GELU: the parity path's
+// definition of every mode.  (The MFMA kernels' 8-column value step with the fast GELU is epi_values8, gemm_dev.cuh.)
 // ---------------------------------------------------------------------------------------------------
 template <class TO>
 struct EpiDev {
@@ -102,14 +103,26 @@ __global__ void __launch_bounds__(256) gemm_generic_kernel(const TI* __restrict_
   }
 }
 
-template <class TI, class TO>
-static int run_generic(const void* A, int64_t sam, int64_t sak, const void* Bm, int64_t sbk, int64_t sbn, int64_t M, int N,
-                       int64_t K, const Epi& e, hipStream_t s) {
-  EpiDev<TO> d{e.mode, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, (int64_t)N};
+// One launch of gemm_generic_kernel.  dt: operand type; e: the epilogue and its output type, ld = N; atomic: split-K over nz chunks
+// of k_chunk, added into a zeroed fp32 `out`.  bf16 outputs exist with bf16 operands and without split-K only: check_epi refuses
+// fp32 operands with them before any launch, and the atomics add into fp32.
+static int launch_generic(int dt, bool atomic, const void* A, int64_t sam, int64_t sak, const void* Bm, int64_t sbk, int64_t sbn,
+                          int64_t M, int N, int64_t K, int64_t k_chunk, int nz, const Epi& e, hipStream_t s) {
   MAE_REQUIRE(cdiv(M, 64) <= 65535, "gemm: M too large for the fallback kernel grid");
-  dim3 grid((unsigned)cdiv(N, 64), (unsigned)cdiv(M, 64), 1);
-  hipLaunchKernelGGL((gemm_generic_kernel<TI, TO, false>), grid, dim3(256), 0, s, (const TI*)A, sam, sak, (const TI*)Bm, sbk,
-                     sbn, M, N, K, K, d);
+  const dim3 grid((unsigned)cdiv(N, 64), (unsigned)cdiv(M, 64), (unsigned)nz);
+  with_dtype(dt, [&](auto ti) {
+    using TI = decltype(ti);
+    auto go = [&](auto to, auto at) {
+      using TO = decltype(to);
+      const EpiDev<TO> d{e.mode, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, (int64_t)N};
+      hipLaunchKernelGGL((gemm_generic_kernel<TI, TO, decltype(at)::value>), grid, dim3(256), 0, s, (const TI*)A, sam, sak,
+                         (const TI*)Bm, sbk, sbn, M, N, K, k_chunk, d);
+    };
+    if constexpr (std::is_same<TI, bf16>::value) {
+      if (e.out_dt == MAE_BF16) return go(bf16{}, std::false_type{});
+    }
+    with_bool(atomic, [&](auto at) { go(float{}, at); });
+  });
   MAE_LAUNCH_CHECK();
   return 0;
 }
@@ -171,10 +184,8 @@ int launch_linear_fwd(const void* A, const void* W, int64_t M, int N, int K, int
     }
     const int r = mfma_linear_fwd((const bf16*)A, (const bf16*)W, M, N, K, e, s);
     if (r != MFMA_UNSUPPORTED) return r;
-    if (e.out_dt == MAE_BF16) return run_generic<bf16, bf16>(A, K, 1, W, 1, K, M, N, K, e, s);
-    return run_generic<bf16, float>(A, K, 1, W, 1, K, M, N, K, e, s);
   }
-  return run_generic<float, float>(A, K, 1, W, 1, K, M, N, K, e, s);
+  return launch_generic(dt, false, A, K, 1, W, 1, K, M, N, K, K, 1, e, s);
 }
 
 int launch_linear_dgrad(const void* dY, const void* W, int64_t M, int N, int K, int dt, const Epi& e, hipStream_t s) {
@@ -182,11 +193,7 @@ int launch_linear_dgrad(const void* dY, const void* W, int64_t M, int N, int K, 
   MAE_TRY(check_epi(e, dt, "linear_dgrad"));
   MAE_REQUIRE(e.mode == MAE_EPI_NONE || e.mode == MAE_EPI_DGELU || e.mode == MAE_EPI_MUL, "linear_dgrad: epilogue must be NONE, DGELU or MUL");
   // dX[m][k] = sum_n dY[m][n] W[n][k]: reduction length N, output width K
-  if (dt == MAE_BF16) {
-    if (e.out_dt == MAE_BF16) return run_generic<bf16, bf16>(dY, N, 1, W, K, 1, M, K, N, e, s);
-    return run_generic<bf16, float>(dY, N, 1, W, K, 1, M, K, N, e, s);
-  }
-  return run_generic<float, float>(dY, N, 1, W, K, 1, M, K, N, e, s);
+  return launch_generic(dt, false, dY, N, 1, W, K, 1, M, K, N, N, 1, e, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -246,8 +253,10 @@ int launch_linear_wgrad(const void* dY, const void* A, int64_t M, int N, int K, 
   if (db) {
     const int G = (int)std::min<int64_t>(cdiv(M, 4), COLSUM_BLOCKS);
     dim3 grid(G, (unsigned)cdiv(N, 256));
-    if (dt == MAE_BF16) hipLaunchKernelGGL((colsum_kernel<bf16>), grid, dim3(256), 0, s, (const bf16*)dY, M, N, (float*)scratch);
-    else hipLaunchKernelGGL((colsum_kernel<float>), grid, dim3(256), 0, s, (const float*)dY, M, N, (float*)scratch);
+    with_dtype(dt, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((colsum_kernel<T>), grid, dim3(256), 0, s, (const T*)dY, M, N, (float*)scratch);
+    });
     MAE_LAUNCH_CHECK();
     MAE_TRY(launch_sum_partials((const float*)scratch, G, N, db, nullptr, N, s));
   }
@@ -255,22 +264,10 @@ int launch_linear_wgrad(const void* dY, const void* A, int64_t M, int N, int K, 
   const int64_t chunk = M <= 4096 ? M : 2048;
   const int nz = (int)cdiv(M, chunk);
   MAE_REQUIRE(nz <= 65535, "linear_wgrad: reduction too long for the fallback kernel");
-  EpiDev<float> d{MAE_EPI_NONE, nullptr, nullptr, dW, nullptr, (int64_t)K};
-  dim3 grid((unsigned)cdiv(K, 64), (unsigned)cdiv(N, 64), nz);
-  if (nz == 1) {
-    if (dt == MAE_BF16)
-      hipLaunchKernelGGL((gemm_generic_kernel<bf16, float, false>), grid, dim3(256), 0, s, (const bf16*)dY, (int64_t)1, (int64_t)N, (const bf16*)A, (int64_t)K, (int64_t)1, (int64_t)N, K, M, chunk, d);
-    else
-      hipLaunchKernelGGL((gemm_generic_kernel<float, float, false>), grid, dim3(256), 0, s, (const float*)dY, (int64_t)1, (int64_t)N, (const float*)A, (int64_t)K, (int64_t)1, (int64_t)N, K, M, chunk, d);
-  } else {
-    MAE_HIP(hipMemsetAsync(dW, 0, (size_t)N * K * sizeof(float), s));
-    if (dt == MAE_BF16)
-      hipLaunchKernelGGL((gemm_generic_kernel<bf16, float, true>), grid, dim3(256), 0, s, (const bf16*)dY, (int64_t)1, (int64_t)N, (const bf16*)A, (int64_t)K, (int64_t)1, (int64_t)N, K, M, chunk, d);
-    else
-      hipLaunchKernelGGL((gemm_generic_kernel<float, float, true>), grid, dim3(256), 0, s, (const float*)dY, (int64_t)1, (int64_t)N, (const float*)A, (int64_t)K, (int64_t)1, (int64_t)N, K, M, chunk, d);
-  }
-  MAE_LAUNCH_CHECK();
-  return 0;
+  if (nz > 1) MAE_HIP(hipMemsetAsync(dW, 0, (size_t)N * K * sizeof(float), s));
+  Epi e;   // NONE, fp32
+  e.out = dW;
+  return launch_generic(dt, nz > 1, dY, 1, N, A, K, 1, N, K, M, chunk, nz, e, s);
 }
 
 }  // namespace mae

@@ -18,19 +18,13 @@ namespace mae {
 __device__ __forceinline__ void store8(float* p, const f32x4& a, const f32x4& b) { store4(p, a); store4(p + 4, b); }
 __device__ __forceinline__ void store8(bf16* p, const f32x4& a, const f32x4& b) { *reinterpret_cast<bf16x8*>(p) = pk8(a, b); }
 
-struct EpiArgs {
-  const float* bias;
-  const void* aux;
-  void* out;
-  void* out2;
-};
-
 // RG ("ragged"): N and K only have to be multiples of 8 (16-byte rows): the last tile column and the last K-step are
 // zero-filled on load (predicated, nothing is read out of bounds) and the stores are guarded by column.  This is the
 // MFMA path of the reference's shipped tiny config (D = 144: K = 144 / 576, N = 432 / 144 / 576).
 template <int MODE, class TO, int NI, bool RG>
 __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W, int64_t M,
-                                                         int N, int K, EpiArgs ep, int tiles_n) {
+                                                         int N, int K, const float* bias, const void* aux, TO* out, TO* out2,
+                                                         int tiles_n) {
   constexpr int BM = 128, BN = 32 * NI, BK = 64;
   constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
   constexpr int NB = BN / 32;  // 16-byte chunks of the W tile per thread
@@ -59,30 +53,30 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const bf16* __restrict_
   const bool wok2 = !RG || n0 + srow + 64 < N, wok3 = !RG || n0 + srow + 96 < N;
   uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2 = uint4{0, 0, 0, 0}, rb3 = uint4{0, 0, 0, 0};
   const int soff = srow * 128 + ((skc ^ (srow & 7)) << 4);  // (srow + 32 i) & 7 == srow & 7
-#define LD16(p, k0) (*reinterpret_cast<const uint4*>((p) + (k0)))
-#define LD16P(p, k0, ok) ((ok) ? LD16(p, k0) : uint4{0, 0, 0, 0})
-#define NT_G_LOAD(k0)                                                                 \
-  {                                                                                   \
-    if (RG) {                                                                         \
-      const bool kok = (k0) + skc * 8 < K;                                            \
-      ra0 = LD16P(pa0, k0, kok); ra1 = LD16P(pa1, k0, kok); ra2 = LD16P(pa2, k0, kok); ra3 = LD16P(pa3, k0, kok); \
-      rb0 = LD16P(pb0, k0, kok && wok0); rb1 = LD16P(pb1, k0, kok && wok1);           \
-      if (NB > 2) { rb2 = LD16P(pb2, k0, kok && wok2); rb3 = LD16P(pb3, k0, kok && wok3); } \
-    } else {                                                                          \
-      ra0 = LD16(pa0, k0); ra1 = LD16(pa1, k0); ra2 = LD16(pa2, k0); ra3 = LD16(pa3, k0); \
-      rb0 = LD16(pb0, k0); rb1 = LD16(pb1, k0);                                       \
-      if (NB > 2) { rb2 = LD16(pb2, k0); rb3 = LD16(pb3, k0); }                       \
-    }                                                                                 \
-  }
-#define ST16(base, i, v) (*reinterpret_cast<uint4*>((base) + soff + (i) * 32 * 128) = (v))
-#define NT_S_STORE(buf)                                                               \
-  {                                                                                   \
-    char* _a = sA + (buf) * A_BYTES;                                                  \
-    char* _b = sB + (buf) * B_BYTES;                                                  \
-    ST16(_a, 0, ra0); ST16(_a, 1, ra1); ST16(_a, 2, ra2); ST16(_a, 3, ra3);           \
-    ST16(_b, 0, rb0); ST16(_b, 1, rb1);                                               \
-    if (NB > 2) { ST16(_b, 2, rb2); ST16(_b, 3, rb3); }                               \
-  }
+  // One 16-byte chunk; ld16p: zero where the ragged form says it does not exist.  The two forms stay two branches: one branch with
+  // `ok` a constant true in the plain form cost every plain instantiation a VGPR (profiles/r25_gemm_fallback_refactor_ab.txt).
+  auto ld16 = [](const bf16* p, int k0) { return *reinterpret_cast<const uint4*>(p + k0); };
+  auto ld16p = [](const bf16* p, int k0, bool ok) { return ok ? *reinterpret_cast<const uint4*>(p + k0) : uint4{0, 0, 0, 0}; };
+  auto stage_load = [&](int k0) {
+    if (RG) {
+      const bool kok = k0 + skc * 8 < K;
+      ra0 = ld16p(pa0, k0, kok); ra1 = ld16p(pa1, k0, kok); ra2 = ld16p(pa2, k0, kok); ra3 = ld16p(pa3, k0, kok);
+      rb0 = ld16p(pb0, k0, kok && wok0); rb1 = ld16p(pb1, k0, kok && wok1);
+      if (NB > 2) { rb2 = ld16p(pb2, k0, kok && wok2); rb3 = ld16p(pb3, k0, kok && wok3); }
+    } else {
+      ra0 = ld16(pa0, k0); ra1 = ld16(pa1, k0); ra2 = ld16(pa2, k0); ra3 = ld16(pa3, k0);
+      rb0 = ld16(pb0, k0); rb1 = ld16(pb1, k0);
+      if (NB > 2) { rb2 = ld16(pb2, k0); rb3 = ld16(pb3, k0); }
+    }
+  };
+  auto lds_store = [&](int buf) {
+    auto st16 = [&](char* base, int i, const uint4& v) { *reinterpret_cast<uint4*>(base + soff + i * 32 * 128) = v; };
+    char* a = sA + buf * A_BYTES;
+    char* b = sB + buf * B_BYTES;
+    st16(a, 0, ra0); st16(a, 1, ra1); st16(a, 2, ra2); st16(a, 3, ra3);
+    st16(b, 0, rb0); st16(b, 1, rb1);
+    if (NB > 2) { st16(b, 2, rb2); st16(b, 3, rb3); }
+  };
 
   f32x4 acc[4][NI];
 #pragma unroll
@@ -92,12 +86,12 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const bf16* __restrict_
 
   const int nk = RG ? (K + BK - 1) / BK : K / BK;
   const int fr = lane & 15, fq = lane >> 4;
-  NT_G_LOAD(0)
+  stage_load(0);
   for (int kt = 0; kt < nk; ++kt) {
     const int buf = kt & 1;
-    NT_S_STORE(buf)
+    lds_store(buf);
     __syncthreads();
-    if (kt + 1 < nk) NT_G_LOAD((kt + 1) * BK)
+    if (kt + 1 < nk) stage_load((kt + 1) * BK);
     const char* a_base = sA + buf * A_BYTES + (wm * 64 + fr) * 128;
     const char* b_base = sB + buf * B_BYTES + (wn * (NI * 16) + fr) * 128;
 #pragma unroll
@@ -128,56 +122,12 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const bf16* __restrict_
       const int n = n0 + wn * (NI * 16) + 32 * j + 4 * gb;
       if (RG && n >= N) continue;  // N % 8 == 0: a lane's 8 columns are all inside or all outside
       const int64_t o = m * N + n;
-      f32x4 v0 = acc[mi][2 * j], v1 = acc[mi][2 * j + 1];
-      if (ep.bias) { v0 += load4(ep.bias + n); v1 += load4(ep.bias + n + 4); }
-      if (MODE == MAE_EPI_NONE) {
-        store8(reinterpret_cast<TO*>(ep.out) + o, v0, v1);
-      } else if (MODE == MAE_EPI_GELU) {
-        f32x4 a0, a1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v0[r] = to_f(from_f<TO>(v0[r]));
-          v1[r] = to_f(from_f<TO>(v1[r]));
-          a0[r] = gelu_fast(v0[r]);
-          a1[r] = gelu_fast(v1[r]);
-        }
-        store8(reinterpret_cast<TO*>(ep.out) + o, v0, v1);
-        store8(reinterpret_cast<TO*>(ep.out2) + o, a0, a1);
-      } else if (MODE == MAE_EPI_RESID) {
-        v0 += load4(reinterpret_cast<const float*>(ep.aux) + o);
-        v1 += load4(reinterpret_cast<const float*>(ep.aux) + o + 4);
-        store8(reinterpret_cast<TO*>(ep.out) + o, v0, v1);
-      } else if (MODE == MAE_EPI_DGELU) {
-        f32x4 p0, p1;
-        ld8(reinterpret_cast<const TO*>(ep.aux) + o, p0, p1);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v0[r] *= gelu_grad_fast(p0[r]);
-          v1[r] *= gelu_grad_fast(p1[r]);
-        }
-        store8(reinterpret_cast<TO*>(ep.out) + o, v0, v1);
-      } else if (MODE == MAE_EPI_GELU_GRAD) {
-        f32x4 a0, a1, g0, g1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          { float _a, _g; gelu_fast_pair(to_f(from_f<TO>(v0[r])), _a, _g); a0[r] = _a; g0[r] = _g; }
-          { float _a, _g; gelu_fast_pair(to_f(from_f<TO>(v1[r])), _a, _g); a1[r] = _a; g1[r] = _g; }
-        }
-        store8(reinterpret_cast<TO*>(ep.out) + o, g0, g1);
-        store8(reinterpret_cast<TO*>(ep.out2) + o, a0, a1);
-      } else if (MODE == MAE_EPI_GELU_ACT) {
-        f32x4 a0, a1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          a0[r] = gelu_fast(to_f(from_f<TO>(v0[r])));
-          a1[r] = gelu_fast(to_f(from_f<TO>(v1[r])));
-        }
-        store8(reinterpret_cast<TO*>(ep.out) + o, a0, a1);
-      } else {  // MAE_EPI_MUL
-        f32x4 p0, p1;
-        ld8(reinterpret_cast<const TO*>(ep.aux) + o, p0, p1);
-        store8(reinterpret_cast<TO*>(ep.out) + o, v0 * p0, v1 * p1);
-      }
+      f32x4 v0 = acc[mi][2 * j], v1 = acc[mi][2 * j + 1], q0 = {0.f, 0.f, 0.f, 0.f}, q1 = q0, w0, w1;
+      if (bias) { v0 += load4(bias + n); v1 += load4(bias + n + 4); }
+      if (epi_side_input(MODE)) ld8(reinterpret_cast<const TO*>(aux) + o, q0, q1);  // RESID's fp32 residual: TO is float there (EpiAll)
+      epi_values8<MODE, TO>(v0, v1, q0, q1, w0, w1);
+      store8(out + o, v0, v1);
+      if (epi_two_outputs(MODE)) store8(out2 + o, w0, w1);
     }
   }
 }
@@ -190,9 +140,8 @@ static int launch_nt(const bf16* A, const bf16* W, int64_t M, int N, int K, cons
   MAE_REQUIRE(tiles < (1ll << 31), "gemm: grid too large");
   const size_t lds = 2 * (128 * 64 * 2) + 2 * (BN * 64 * 2);
   auto kern = gemm_nt_kernel<MODE, TO, NI, RG>;
-  MAE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  EpiArgs ea{e.bias, e.aux, e.out, e.out2};
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, s, A, W, M, N, K, ea, tiles_n);
+  MAE_TRY(allow_lds(kern, lds));   // 48 or 64 KiB: inside the default limit
+  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, s, A, W, M, N, K, e.bias, e.aux, (TO*)e.out, (TO*)e.out2, tiles_n);
   MAE_LAUNCH_CHECK();
   return 0;
 }

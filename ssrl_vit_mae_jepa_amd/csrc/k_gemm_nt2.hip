@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
   constexpr int BN = G_::BN, STAGE = G_::STAGE, NSTAGE = G_::NSTAGE, AHEAD = G_::AHEAD, GPW = G_::GPW;
   constexpr int NB = HAS_BIAS ? G_::NBIAS : 0;
   constexpr int STORE8 = sizeof(TO) == 2 ? 1 : 2;                                // store instructions per 8 outputs
-  constexpr int E = MI * (NI / 2) * STORE8 * ((MODE == MAE_EPI_GELU || MODE == MAE_EPI_GELU_GRAD) ? 2 : 1);      // epilogue stores per wave (full tile)
+  constexpr int E = MI * (NI / 2) * STORE8 * (epi_two_outputs(MODE) ? 2 : 1);   // epilogue stores per wave (full tile)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -97,10 +97,14 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
     }
     return W + (int64_t)(n0 + (g - BM2 / 8) * 8 + r8) * K + src_chunk;
   };
-  auto set_tile = [&](int ord) {
+  // first row and column of this workgroup's tile number `ord`
+  struct Origin { int64_t m0; int n0; };
+  auto tile_origin = [&](int ord) {
     const int t = vb + ord * G;
-    const int64_t m0 = (int64_t)(t / tiles_n) * BM2;
-    const int n0 = (t % tiles_n) * BN;
+    return Origin{(int64_t)(t / tiles_n) * BM2, (t % tiles_n) * BN};
+  };
+  auto set_tile = [&](int ord) {
+    const auto [m0, n0] = tile_origin(ord);
     p0 = src_ptr(0, m0, n0); p1 = src_ptr(1, m0, n0); p2 = src_ptr(2, m0, n0);
     p3 = src_ptr(3, m0, n0); p4 = src_ptr(4, m0, n0);
     if (GPW > 5) p5 = src_ptr(5, m0, n0);
@@ -163,9 +167,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (PREF && ck == nk - 1) {
-      const int t = vb + ct * G;
-      const int64_t m0 = (int64_t)(t / tiles_n) * BM2;
-      const int n0 = (t % tiles_n) * BN;
+      const auto [m0, n0] = tile_origin(ct);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
         int64_t m = m0 + wm * WROWS + mi * 16 + fr;
@@ -199,10 +201,8 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
     cs = cs == NSTAGE - 1 ? 0 : cs + 1;
 
     if (++ck == nk) {
-      // ---- epilogue of tile `ct`: regroup to 8 consecutive columns per lane (gemm_dev.cuh), store
-      const int t = vb + ct * G;
-      const int64_t m0 = (int64_t)(t / tiles_n) * BM2;
-      const int n0 = (t % tiles_n) * BN;
+      // ---- epilogue of tile `ct`: regroup to 8 consecutive columns per lane, the value step (both gemm_dev.cuh), store
+      const auto [m0, n0] = tile_origin(ct);
       MAE_REGROUP8(acc, MI, NI)
       const float* sbias = reinterpret_cast<const float*>(smem + G_::BIAS_OFF + (ct & 1) * (BN * 4)) + wn * (NI * 16);
       if constexpr (sizeof(TO) == 2) {
@@ -215,7 +215,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
         // a line and a half: the wave with the even column offset pairs groups (0, 1), the other one (1, 2); the group left
         // over shares its line with the neighbouring wave and goes out as before.  NI = 4: one pair, nothing left over.
         constexpr int NJ = NI / 2;
-        constexpr bool TWO = MODE == MAE_EPI_GELU || MODE == MAE_EPI_GELU_GRAD;
+        constexpr bool TWO = epi_two_outputs(MODE);
         const bool lo8 = fr < 8;
         const int colw = n0 + wn * (NI * 16) + 4 * gb;      // this lane's column inside group 0
 #pragma unroll
@@ -228,22 +228,11 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
             const int nl = 32 * j + 4 * gb;
             f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
             if (HAS_BIAS) { b0 = load4(sbias + nl); b1 = load4(sbias + nl + 4); }
-            f32x4 v0 = acc[mi][2 * j] + b0, v1 = acc[mi][2 * j + 1] + b1;
-            if (MODE == MAE_EPI_GELU || MODE == MAE_EPI_GELU_GRAD || MODE == MAE_EPI_GELU_ACT) {
-              f32x4 a0, a1, g0, g1;
-              gelu_rounded<TO>(v0, v1, a0, a1, g0, g1);
-              if (MODE == MAE_EPI_GELU) { pa[j] = pk8(v0, v1); pb[TWO ? j : 0] = pk8(a0, a1); }
-              else if (MODE == MAE_EPI_GELU_GRAD) { pa[j] = pk8(g0, g1); pb[TWO ? j : 0] = pk8(a0, a1); }
-              else pa[j] = pk8(a0, a1);
-            } else if (PREF) {   // DGELU / MUL: the side input fetched during the last K-step
-              f32x4 q0, q1;
-              unpack8(qa[PREF ? j : 0][PREF ? mi : 0], q0, q1);
-              if (MODE == MAE_EPI_DGELU) { f32x4 a_, g_; gelu_fast_pair(q0, a_, g_); v0 *= g_; gelu_fast_pair(q1, a_, g_); v1 *= g_; }
-              else { v0 *= q0; v1 *= q1; }
-              pa[j] = pk8(v0, v1);
-            } else {
-              pa[j] = pk8(v0, v1);
-            }
+            f32x4 v0 = acc[mi][2 * j] + b0, v1 = acc[mi][2 * j + 1] + b1, q0 = {0.f, 0.f, 0.f, 0.f}, q1 = q0, w0, w1;
+            if (PREF) unpack8(qa[PREF ? j : 0][PREF ? mi : 0], q0, q1);   // DGELU / MUL: the side input fetched during the last K-step
+            epi_values8<MODE, TO>(v0, v1, q0, q1, w0, w1);
+            pa[j] = pk8(v0, v1);
+            if (TWO) pb[TWO ? j : 0] = pk8(w0, w1);
             acc[mi][2 * j] = f32x4{0.f, 0.f, 0.f, 0.f};
             acc[mi][2 * j + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
           }
@@ -282,26 +271,11 @@ __global__ void __launch_bounds__(512, 2) gemm_nt2_kernel(const bf16* __restrict
             const int64_t m = m0 + wm * WROWS + mi * 16 + fr;
             if (m < M) {
               const int64_t o = m * N + n0 + wn * (NI * 16) + nl;
-              f32x4 v0 = acc[mi][2 * j] + b0, v1 = acc[mi][2 * j + 1] + b1;
-              if (MODE == MAE_EPI_GELU || MODE == MAE_EPI_GELU_GRAD || MODE == MAE_EPI_GELU_ACT) {
-                f32x4 a0, a1, g0, g1;
-                gelu_rounded<TO>(v0, v1, a0, a1, g0, g1);
-                if (MODE == MAE_EPI_GELU) { st8(out + o, v0, v1); st8(out2 + o, a0, a1); }
-                else if (MODE == MAE_EPI_GELU_GRAD) { st8(out + o, g0, g1); st8(out2 + o, a0, a1); }
-                else st8(out + o, a0, a1);
-              } else if (MODE == MAE_EPI_RESID) {
-                v0 += load4(reinterpret_cast<const float*>(aux) + o);
-                v1 += load4(reinterpret_cast<const float*>(aux) + o + 4);
-                st8(out + o, v0, v1);
-              } else if (MODE == MAE_EPI_DGELU || MODE == MAE_EPI_MUL) {
-                f32x4 q0, q1;
-                ld8(reinterpret_cast<const TO*>(aux) + o, q0, q1);
-                if (MODE == MAE_EPI_DGELU) { f32x4 a_, g_; gelu_fast_pair(q0, a_, g_); v0 *= g_; gelu_fast_pair(q1, a_, g_); v1 *= g_; }
-                else { v0 *= q0; v1 *= q1; }
-                st8(out + o, v0, v1);
-              } else {
-                st8(out + o, v0, v1);
-              }
+              f32x4 v0 = acc[mi][2 * j] + b0, v1 = acc[mi][2 * j + 1] + b1, q0 = {0.f, 0.f, 0.f, 0.f}, q1 = q0, w0, w1;
+              if (epi_side_input(MODE)) ld8(reinterpret_cast<const TO*>(aux) + o, q0, q1);
+              epi_values8<MODE, TO>(v0, v1, q0, q1, w0, w1);
+              st8(out + o, v0, v1);
+              if (epi_two_outputs(MODE)) st8(out2 + o, w0, w1);
             }
             acc[mi][2 * j] = f32x4{0.f, 0.f, 0.f, 0.f};
             acc[mi][2 * j + 1] = f32x4{0.f, 0.f, 0.f, 0.f};

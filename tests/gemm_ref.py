@@ -683,8 +683,10 @@ def makefile_cxxflags(makefile: Path):
 # ------------------------------------------------------------------------------------------------ the whole dispatch
 # Restated from the C++ (ssrl_vit_mae_jepa_amd/csrc): launch_linear_fwd and nt_sel (k_gemm.hip, the chain v3 -> v2 -> v1 -> generic and
 # the whole-string MAE_GEMM_NT match), mfma_linear_fwd_v2 / launch_nt2_ni (k_gemm_nt2.hip, shape test and tile choice), prefer_bm192
-# (k_gemm.hip), mfma_linear_fwd / launch_nt_ni (k_gemm_nt1.hip, shape and 16-byte alignment test, NI), launch_linear_wgrad (k_gemm.hip,
-# the `M <= 4096 ? M : 2048` split-K rule and the colsum grid), mfma_linear_wgrad, wgrad_splits, ring_shape_ok, ring_splits and
+# (k_gemm.hip), mfma_linear_fwd / launch_nt_ni (k_gemm_nt1.hip, shape and 16-byte alignment test, NI), launch_generic (k_gemm.hip, the
+# operand type x output type x split-K pick of the generic kernel), launch_linear_wgrad (k_gemm.hip, the `M <= 4096 ? M : 2048`
+# split-K rule and the colsum grid), epi_values8 (gemm_dev.cuh, the fast-GELU value step of the nt1 and nt2 epilogues; EpiDev in
+# k_gemm.hip is the generic kernel's exact-erf one), mfma_linear_wgrad, wgrad_splits, ring_shape_ok, ring_splits and
 # env_sel (k_gemm_tn.hip, `m_chunk = round_up(cdiv(M, S), 64)`, the instantiation switch and the whole-string MAE_WGRAD match).
 @dataclass(frozen=True)
 class KRoute:
