@@ -487,6 +487,17 @@ int mae_engine_extract_features(mae_engine_t* e, const float* params, const void
                                 int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, void* workspace,
                                 int64_t workspace_bytes, float* feats, void* stream);
 
+/* Frozen-encoder tokens (additive in ABI v4): the call above without the pool.  The encoder forward with nothing saved, the last
+ * residual add and the final LayerNorm in fp32 (the step of the fused add + LayerNorm kernel, a bf16 branch widened first), written as
+ * tokens (batch, T_out, embed_dim) fp32 in the sequence's order.
+ *   with_cls as above: T = N + 1 rows [cls | patches], or the N patch rows;
+ *   drop_cls = 1 (with_cls = 1 only): the class row is left out, T_out = N; else T_out = T.
+ * Same limits, workspace rules and determinism; the workspace query returns what the features call asks for. */
+int64_t mae_engine_tokens_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls);
+int mae_engine_extract_tokens(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                              int32_t batch, int32_t with_cls, int32_t drop_cls, void* workspace, int64_t workspace_bytes,
+                              float* tokens, void* stream);
+
 /* MAE reconstruction (additive in ABI v4; scripts/evaluation/visualize_reconstruction.py of the reference, MAEReconstructor):
  * the inverse of mae_patchify_gather, fused with the whole-image error sums.  One pass over the OUTPUT pixels produces up to
  * three results from images (batch, C, S, S) in image_dtype (MAE_F32 normalised | MAE_U8 raw pixels, normalised in the read),
@@ -655,6 +666,49 @@ int mae_batchnorm_fwd(const float* x, int64_t rows, int32_t dim, float eps, int3
                       float* rstd_out /* may be NULL */, void* scratch, int64_t scratch_bytes, void* stream);
 int mae_lars_step(float* params, const float* grads, float* mu, int64_t count, int32_t adapt, float lr, float momentum,
                   float weight_decay, float trust_coefficient, float* norms_out /* may be NULL */, float* scratch, void* stream);
+
+/* The statistics half of mae_batchnorm_fwd (additive in ABI v4): the same two centred column reductions and the same running-buffer
+ * update by the same device code, so mean_out, rstd_out, running_mean and running_var get the bits mae_batchnorm_fwd gives them on
+ * the same input; no normalising sweep and no y (x is read twice).  training == 0: mean_out = running_mean,
+ * rstd_out = 1 / sqrt(running_var + eps).  mean_out and rstd_out are required; every other rule is mae_batchnorm_fwd's. */
+int mae_batchnorm_stats(const float* x, int64_t rows, int32_t dim, float eps, int32_t training, float momentum, float* running_mean,
+                        float* running_var, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* The attentive probe on cached tokens (additive in ABI v4; no reference counterpart).  x (batch, tokens, dim) fp32 is
+ * the frozen encoder's output, heads | dim, hd = dim / heads; q (dim), Wk, Wv (dim, dim), no bias.  Behind BatchNorm1d(affine=False)
+ * with statistics mean / rstd (dim) the definition is
+ *     xh = (x - mean) rstd;  k, v = xh Wk^T, xh Wv^T;  s[b,t,h] = hd^-1/2 q[h] . k[b,t,h];  a = softmax over t;  p[b,h] = sum_t a v[b,t,h]
+ * and the folded form below computes it without writing anything of the size of x, reading x once per pass:
+ *   mae_attn_probe_fold       : uq[h][d] = rstd[d] * (hd^-1/2 * sum_j q[h hd + j] Wk[h hd + j][d])                        (heads, dim)
+ *   mae_attn_pool_fwd         : s = (x - mean) . uq[h]; lse[b][h] = log sum_t exp s; a = exp(s - lse);
+ *                               ybar[b][h][:] = sum_t a (x[b][t][:] - mean).  mean may be NULL (= 0).  One pass over x with a running
+ *                               maximum and sum over token chunks; an image's ybar and lse do not depend on the batch it is part of
+ *   mae_attn_probe_project    : p[b][h hd + j] = sum_d (Wv[h hd + j][d] rstd[d]) ybar[b][h][d]                             (batch, dim)
+ *   mae_attn_probe_project_bwd: g[b][h][d] = rstd[d] * sum_j dp[b][h hd + j] Wv[h hd + j][d]                        (batch, heads, dim)
+ *                               dwv[h hd + j][d] = rstd[d] * sum_b dp[b][h hd + j] ybar[b][h][d]
+ *   mae_attn_pool_bwd         : delta = ybar[b][h] . g[b][h]; da = (x - mean) . g[b][h]; ds = exp(s - lse) (da - delta);
+ *                               duq[h][:] = sum_{b,t} ds (x[b][t][:] - mean)                                              (heads, dim)
+ *   mae_attn_probe_fold_bwd   : du = rstd duq[h]; dwk[h hd + j][:] = hd^-1/2 q[h hd + j] du; dq[h hd + j] = hd^-1/2 Wk[h hd + j] . du
+ * No gradient flows to x or to the statistics.  The head on p is mae_classifier_head (MAE_F32, seq_len 1, MAE_POOL_CLS), whose d_feats
+ * is dp.  Every sum has a fixed order that depends on the shape alone (image and batch slices into scratch, added in order; no
+ * atomics), so a call is bit-identical from run to run.
+ * Limits, checked before any launch (a refused call launches nothing and writes nothing): dim % 4 == 0, 4 <= dim <= 1024,
+ * 1 <= heads <= 16, dim % heads == 0, batch >= 1, tokens >= 1, batch * tokens < 2^31; every buffer 16-byte aligned;
+ * scratch_bytes >= the call's ..._scratch_bytes query (-1 = outside the limits). */
+int mae_attn_pool_fwd(const float* x, const float* mean /* may be NULL */, const float* uq, int64_t batch, int64_t tokens, int32_t dim,
+                      int32_t heads, float* ybar, float* lse, void* stream);
+int64_t mae_attn_pool_bwd_scratch_bytes(int64_t batch, int64_t tokens, int32_t dim, int32_t heads);
+int mae_attn_pool_bwd(const float* x, const float* mean /* may be NULL */, const float* uq, const float* lse, const float* ybar,
+                      const float* g, int64_t batch, int64_t tokens, int32_t dim, int32_t heads, float* duq, void* scratch,
+                      int64_t scratch_bytes, void* stream);
+int mae_attn_probe_fold(const float* q, const float* wk, const float* rstd, int32_t dim, int32_t heads, float* uq, void* stream);
+int mae_attn_probe_fold_bwd(const float* duq, const float* q, const float* wk, const float* rstd, int32_t dim, int32_t heads, float* dq,
+                            float* dwk, void* stream);
+int mae_attn_probe_project(const float* ybar, const float* rstd, const float* wv, int64_t batch, int32_t dim, int32_t heads, float* p,
+                           void* stream);
+int64_t mae_attn_probe_project_bwd_scratch_bytes(int64_t batch, int32_t dim, int32_t heads);
+int mae_attn_probe_project_bwd(const float* dp, const float* ybar, const float* rstd, const float* wv, int64_t batch, int32_t dim,
+                               int32_t heads, float* g, float* dwv, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* Epilogues of the GEMM family. */
 enum {

@@ -138,6 +138,17 @@ SIGNATURES = {
     "mae_batchnorm_scratch_bytes": (_i64, [_i64, _i32]),
     "mae_batchnorm_fwd": (C.c_int, [_vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mae_lars_step": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
+    "mae_batchnorm_stats": (C.c_int, [_vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mae_attn_pool_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "mae_attn_pool_bwd_scratch_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "mae_attn_pool_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "mae_attn_probe_fold": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "mae_attn_probe_fold_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "mae_attn_probe_project": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "mae_attn_probe_project_bwd_scratch_bytes": (_i64, [_i64, _i32, _i32]),
+    "mae_attn_probe_project_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "mae_engine_tokens_workspace_bytes": (_i64, [_vp, _i32, _i32]),
+    "mae_engine_extract_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "mae_linear_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mae_linear_wgrad_scratch_bytes": (_i64, [_i64, _i32, _i32]),
     "mae_linear_wgrad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -1343,6 +1343,53 @@ extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params,
   return 0;
 }
 
+// mae_engine_extract_features without the pool: the same encoder forward, then the last residual add and the final LayerNorm in fp32
+// (launch_layernorm_fwd with an fp32 branch: a bf16 branch is widened first, which is what the fused add does with it) written as
+// (batch, T_out, D) fp32 tokens.  drop_cls maps the output rows onto the patch rows of [cls | patches].  The plan's backward
+// buffers are free in a forward-only call: dres takes the widened branch, keep32 (read by the forward alone) the row map.
+extern "C" int64_t mae_engine_tokens_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls) {
+  return mae_engine_features_workspace_bytes(e, batch, with_cls);
+}
+
+extern "C" int mae_engine_extract_tokens(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                         int32_t batch, int32_t with_cls, int32_t drop_cls, void* workspace, int64_t workspace_bytes,
+                                         float* tokens, void* stream) {
+  const char* who = "mae_engine_extract_tokens";
+  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
+  MAE_REQUIRE(images && tokens, "%s: null argument", who);
+  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+  MAE_REQUIRE(drop_cls == 0 || (drop_cls == 1 && with_cls == 1), "%s: drop_cls = %d needs a sequence with a class row (with_cls = 1)", who, drop_cls);
+  MAE_REQUIRE(e->D % 4 == 0 && e->D <= 1024, "%s: embed_dim = %d must be a multiple of 4 and at most 1024", who, e->D);
+  MAE_TRY(check_image_dtype(image_dtype, who));
+  const int64_t need = mae_engine_tokens_workspace_bytes(e, batch, with_cls);
+  MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
+  MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
+  const Plan pl = make_encoder_plan(e, batch, with_cls != 0);
+  const int T = pl.k, T_out = T - drop_cls;
+  MAE_REQUIRE(T_out >= 1, "%s: no token row is left", who);
+  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  hipStream_t s = c.s;
+  c.fwd_only = true;
+  c.skip_final_norm = true;
+  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
+  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
+  const void* branch = c.buf<>(pl.branch_b);
+  if (e->act != MAE_F32) {
+    MAE_TRY(launch_cast(branch, e->act, c.buf<>(pl.dres), MAE_F32, pl.Me * e->D, s));
+    branch = c.buf<>(pl.dres);
+  }
+  const int32_t* row_map = nullptr;
+  if (drop_cls) {
+    MAE_TRY(launch_build_tail_row_map(batch, T, T_out, c.buf<int32_t>(pl.keep32), s));
+    row_map = c.buf<int32_t>(pl.keep32);
+  }
+  const int64_t rows = (int64_t)batch * T_out;
+  RUN(TK_LN_FWD, 0, (double)rows * e->D * 16,
+      launch_layernorm_fwd(c.buf<float>(pl.enc[e->depth - 1].x_mid), branch, c.buf<float>(pl.enc_x[e->depth]), row_map, c.P(e->i_norm_w),
+                           c.P(e->i_norm_b), 1e-6f, rows, e->D, MAE_F32, tokens, c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd), s));
+  return 0;
+}
+
 extern "C" int mae_engine_grad_sumsq_buffer(mae_engine_t* e, const float* grads, int64_t count, int32_t accumulate, float* sumsq_io,
                                             float* scratch, void* stream) {
   MAE_REQUIRE(e && grads && sumsq_io && scratch, "mae_engine_grad_sumsq_buffer: null argument");

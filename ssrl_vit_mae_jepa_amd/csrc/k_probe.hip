@@ -71,7 +71,8 @@ __global__ void __launch_bounds__(256) bn_colsum_kernel(const float* __restrict_
 
 // TRAIN: mean / m2 are the scratch's statistics; else the running buffers.  Block 0 writes the statistics out and, when tracked, the
 // running buffers: rm' = (1 - mom) rm + mom mean, rv' = (1 - mom) rv + mom m2 / (rows - 1).  x and y may be the same buffer.
-template <bool TRAIN>
+// SWEEP = false (mae_batchnorm_stats) is the same statistics code without the normalising sweep: one block, x and y unread.
+template <bool TRAIN, bool SWEEP = true>
 __global__ void __launch_bounds__(256) bn_normalize_kernel(const float* x, const float* __restrict__ mean, const float* __restrict__ m2_or_var,
                                                            int64_t rows, int dim, int rp, float eps, float momentum,
                                                            float* __restrict__ running_mean, float* __restrict__ running_var, float* y,
@@ -94,6 +95,7 @@ __global__ void __launch_bounds__(256) bn_normalize_kernel(const float* x, const
       store4(running_var + c * 4, load4(running_var + c * 4) * keep + (m2 / (float)(rows - 1)) * momentum);
     }
   }
+  if (!SWEEP) return;
   for (int64_t r = (int64_t)blockIdx.x * rp + rs; r < rows; r += (int64_t)gridDim.x * rp) {
     const int64_t o = r * dim + c * 4;
     store4(y + o, (load4(x + o) - mu) * rstd);
@@ -107,12 +109,15 @@ int64_t batchnorm_scratch_bytes(int64_t rows, int dim) {
   return ((int64_t)bn_geometry(rows, dim).grid + 3) * dim * (int64_t)sizeof(float);
 }
 
-int launch_batchnorm_fwd(const float* x, int64_t rows, int dim, float eps, int training, float momentum, float* running_mean,
-                         float* running_var, float* y, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, hipStream_t s) {
+// SWEEP = false: launch_batchnorm_stats, the statistics half (y is null and stays unread)
+template <bool SWEEP>
+static int batchnorm_impl(const float* x, int64_t rows, int dim, float eps, int training, float momentum, float* running_mean,
+                          float* running_var, float* y, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, hipStream_t s) {
   MAE_REQUIRE(dim % 4 == 0 && dim >= 4 && dim <= 1024, "batchnorm: dim %d must be a multiple of 4 in [4, 1024]", dim);
   MAE_REQUIRE(rows >= (training ? 2 : 1), "batchnorm: rows = %lld: training needs at least 2 rows, evaluation 1", (long long)rows);
   MAE_REQUIRE(rows < ((int64_t)1 << 40) / dim, "batchnorm: rows * dim = %lld * %d must stay below 2^40", (long long)rows, dim);
-  MAE_REQUIRE(x && y, "batchnorm: x / y is null");
+  MAE_REQUIRE(x && (y || !SWEEP), "batchnorm: x / y is null");
+  MAE_REQUIRE(SWEEP || (mean_out && rstd_out), "batchnorm: the statistics call needs mean_out and rstd_out");
   MAE_REQUIRE(eps >= 0.f, "batchnorm: eps = %g must not be negative", (double)eps);
   MAE_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "batchnorm: running_mean and running_var come together");
   MAE_REQUIRE(training || running_mean, "batchnorm: evaluation needs running_mean / running_var");
@@ -120,11 +125,11 @@ int launch_batchnorm_fwd(const float* x, int64_t rows, int dim, float eps, int t
               aligned16(scratch), "batchnorm: every buffer must be 16-byte aligned");
   const int64_t bytes = rows * dim * (int64_t)sizeof(float);
   const char *xb = (const char*)x, *yb = (const char*)y;
-  MAE_REQUIRE(xb == yb || xb + bytes <= yb || yb + bytes <= xb, "batchnorm: y overlaps x partly (it may be x itself, or apart)");
+  MAE_REQUIRE(!SWEEP || xb == yb || xb + bytes <= yb || yb + bytes <= xb, "batchnorm: y overlaps x partly (it may be x itself, or apart)");
   const BnGeo g = bn_geometry(rows, dim);
-  const int ngrid = (int)std::min<int64_t>(cdiv(rows, (int64_t)g.rp * BN_MIN_TRIPS), BN_NORM_BLOCKS);
+  const int ngrid = SWEEP ? (int)std::min<int64_t>(cdiv(rows, (int64_t)g.rp * BN_MIN_TRIPS), BN_NORM_BLOCKS) : 1;
   if (!training) {
-    hipLaunchKernelGGL((bn_normalize_kernel<false>), dim3(ngrid), dim3(256), 0, s, x, running_mean, running_var, rows, dim, g.rp, eps, 0.f,
+    hipLaunchKernelGGL((bn_normalize_kernel<false, SWEEP>), dim3(ngrid), dim3(256), 0, s, x, running_mean, running_var, rows, dim, g.rp, eps, 0.f,
                        (float*)nullptr, (float*)nullptr, y, mean_out, rstd_out);
     MAE_LAUNCH_CHECK();
     return 0;
@@ -143,10 +148,21 @@ int launch_batchnorm_fwd(const float* x, int64_t rows, int dim, float eps, int t
   hipLaunchKernelGGL((bn_colsum_kernel<1>), dim3(g.grid), dim3(256), 0, s, x, (const float*)s0, rows, dim, g.rp, g.slice, mean, partial);
   MAE_LAUNCH_CHECK();
   MAE_TRY(launch_sum_partials(partial, g.grid, dim, m2, nullptr, dim, s));
-  hipLaunchKernelGGL((bn_normalize_kernel<true>), dim3(ngrid), dim3(256), 0, s, x, (const float*)mean, (const float*)m2, rows, dim, g.rp, eps,
+  hipLaunchKernelGGL((bn_normalize_kernel<true, SWEEP>), dim3(ngrid), dim3(256), 0, s, x, (const float*)mean, (const float*)m2, rows, dim, g.rp, eps,
                      momentum, running_mean, running_var, y, mean_out, rstd_out);
   MAE_LAUNCH_CHECK();
   return 0;
+}
+
+int launch_batchnorm_fwd(const float* x, int64_t rows, int dim, float eps, int training, float momentum, float* running_mean,
+                         float* running_var, float* y, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, hipStream_t s) {
+  return batchnorm_impl<true>(x, rows, dim, eps, training, momentum, running_mean, running_var, y, mean_out, rstd_out, scratch, scratch_bytes, s);
+}
+
+int launch_batchnorm_stats(const float* x, int64_t rows, int dim, float eps, int training, float momentum, float* running_mean,
+                           float* running_var, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, hipStream_t s) {
+  return batchnorm_impl<false>(x, rows, dim, eps, training, momentum, running_mean, running_var, nullptr, mean_out, rstd_out, scratch,
+                               scratch_bytes, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -239,6 +255,12 @@ extern "C" int mae_batchnorm_fwd(const float* x, int64_t rows, int32_t dim, floa
                                  void* stream) {
   return mae::launch_batchnorm_fwd(x, rows, dim, eps, training, momentum, running_mean, running_var, y, mean_out, rstd_out, scratch,
                                    scratch_bytes, (hipStream_t)stream);
+}
+
+extern "C" int mae_batchnorm_stats(const float* x, int64_t rows, int32_t dim, float eps, int32_t training, float momentum, float* running_mean,
+                                   float* running_var, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, void* stream) {
+  return mae::launch_batchnorm_stats(x, rows, dim, eps, training, momentum, running_mean, running_var, mean_out, rstd_out, scratch,
+                                     scratch_bytes, (hipStream_t)stream);
 }
 
 extern "C" int mae_lars_step(float* params, const float* grads, float* mu, int64_t count, int32_t adapt, float lr, float momentum,

@@ -205,10 +205,35 @@ int launch_norm_pix_restore(const void* images, int img_dt, const float* pred, c
 int64_t batchnorm_scratch_bytes(int64_t rows, int dim);
 int launch_batchnorm_fwd(const float* x, int64_t rows, int dim, float eps, int training, float momentum, float* running_mean,
                          float* running_var, float* y, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, hipStream_t s);
+// the statistics half of launch_batchnorm_fwd: the same device code, so mean_out / rstd_out / the running buffers get the same bits;
+// no normalising sweep and no y.  mean_out and rstd_out are required
+int launch_batchnorm_stats(const float* x, int64_t rows, int dim, float eps, int training, float momentum, float* running_mean,
+                           float* running_var, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, hipStream_t s);
 // dp = adapt ? (g + wd p) q : g, q = trust |p| / |g + wd p| (1 where a norm is 0); mu = momentum mu + dp; p -= lr mu.
 // norms_out (2 floats, may be null) = |p|, |g + wd p|.  scratch >= 4096 floats
 int launch_lars_step(float* p, const float* g, float* mu, int64_t n, int adapt, float lr, float momentum, float wd, float trust,
                      float* norms_out, float* scratch, hipStream_t s);
+
+// ---- k_attnpool.hip: the attentive probe's pool over cached tokens and the small products around it -------------
+// x (B, T, D) fp32 tokens, centred on load with mean (D, null = 0); uq (H, D).  ybar[b][h] = sum_t a (x - mean), a = softmax_t of
+// (x - mean) . uq[h]; lse (B, H) = the log of the softmax denominator.  One workgroup per image, online softmax over token chunks
+int launch_attn_pool_fwd(const float* x, const float* mean, const float* uq, int64_t B, int64_t T, int D, int H, float* ybar, float* lse,
+                         hipStream_t s);
+// duq[h] = sum_{b,t} a (da - delta) (x - mean), da = (x - mean) . g[b][h], delta = ybar[b][h] . g[b][h]; image slices into scratch
+// (attn_pool_bwd_scratch_bytes, -1 outside the limits), added by launch_sum_partials
+int64_t attn_pool_bwd_scratch_bytes(int64_t B, int64_t T, int D, int H);
+int launch_attn_pool_bwd(const float* x, const float* mean, const float* uq, const float* lse, const float* ybar, const float* g, int64_t B,
+                         int64_t T, int D, int H, float* duq, void* scratch, int64_t scratch_bytes, hipStream_t s);
+// uq = rstd * (hd^-1/2 Wk[h]^T q[h]) and its adjoint: dwk[n] = hd^-1/2 q[n] (rstd duq[h]), dq[n] = hd^-1/2 Wk[n] . (rstd duq[h])
+int launch_attn_probe_fold(const float* q, const float* wk, const float* rstd, int D, int H, float* uq, hipStream_t s);
+int launch_attn_probe_fold_bwd(const float* duq, const float* q, const float* wk, const float* rstd, int D, int H, float* dq, float* dwk,
+                               hipStream_t s);
+// p[b][n] = sum_d (Wv[n][d] rstd[d]) ybar[b][h(n)][d] and its adjoints: g[b][h] = rstd * (Wv[h]^T dp[b][h]),
+// dwv[n] = rstd * sum_b dp[b][n] ybar[b][h(n)] (batch slices into scratch, added by launch_sum_partials)
+int launch_attn_probe_project(const float* ybar, const float* rstd, const float* wv, int64_t B, int D, int H, float* p, hipStream_t s);
+int64_t attn_probe_project_bwd_scratch_bytes(int64_t B, int D, int H);
+int launch_attn_probe_project_bwd(const float* dp, const float* ybar, const float* rstd, const float* wv, int64_t B, int D, int H, float* g,
+                                  float* dwv, void* scratch, int64_t scratch_bytes, hipStream_t s);
 
 // ---- k_loss_optim.hip -----------------------------------------------------------------------------
 // loss[0] = mean((pred-target)^2); d_pred (dt, may be null) = grad_scale*2*(pred-target)/n.  scratch >= 1024+ floats

@@ -251,6 +251,17 @@ class IJEPA(nn.Module):
         return net._extract(images, net.flat_params, net._weights(), pool, normalize, with_cls=False)
 
     @torch.no_grad()
+    def extract_tokens(self, images: torch.Tensor, encoder: str = "target") -> torch.Tensor:
+        """The patch tokens of the EMA target encoder (``encoder="target"``) or the context encoder after the final LayerNorm:
+        (B, N, D) fp32 -- ``extract_features`` without the pool."""
+        if encoder not in ("target", "context"):
+            raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
+        net = self.net
+        if encoder == "target":
+            return net._extract_tokens(images, self.target_arena, self._target_weights(), False, False)
+        return net._extract_tokens(images, net.flat_params, net._weights(), False, False)
+
+    @torch.no_grad()
     def target_features(self, images: torch.Tensor, idx_target: torch.Tensor) -> torch.Tensor:
         """layer_norm(target_encoder(images))[target blocks]: (B, nblk, m, D) fp32 (no gradient, nothing else computed)."""
         net = self.net

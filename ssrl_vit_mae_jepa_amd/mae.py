@@ -202,6 +202,10 @@ class _ViT(_Node):
         """Pooled features of the frozen encoder: ``MaskedAutoencoder.extract_features``."""
         return self._owner().extract_features(images, pool=pool, normalize=normalize, with_cls=with_cls)
 
+    def extract_tokens(self, images: torch.Tensor, with_cls: bool = True, drop_cls: bool = True) -> torch.Tensor:
+        """Every token of the frozen encoder: ``MaskedAutoencoder.extract_tokens``."""
+        return self._owner().extract_tokens(images, with_cls=with_cls, drop_cls=drop_cls)
+
 
 # extract_features pool names: "mean" averages the patch tokens (visualize_representation.py:94), "mean_all" every token (the classifier)
 FEATURE_POOLS = {"cls": _lib.POOL_CLS, "mean": _lib.POOL_MEAN_PATCHES, "mean_all": _lib.POOL_MEAN}
@@ -634,6 +638,33 @@ class MaskedAutoencoder(nn.Module):
         check(lib.mae_engine_extract_features(self._engine.handle, _ptr(params), _ptr(wcache), _ptr(images), self._img_dt(images), B,
                                               int(bool(with_cls)), FEATURE_POOLS[pool], FEATURE_NORMS[normalize], _ptr(self._workspace),
                                               self._workspace.numel(), _ptr(out), _stream(dev)))
+        return out
+
+    @torch.no_grad()
+    def extract_tokens(self, images: torch.Tensor, with_cls: bool = True, drop_cls: bool = True) -> torch.Tensor:
+        """Every token of the frozen encoder after its final LayerNorm: (B, T, D) fp32, no autograd graph -- ``extract_features`` without
+        the pool.  with_cls=False runs the encoder over the patch tokens only (T = N); with the class token, drop_cls leaves its row
+        out of the result (T = N, the patch rows) or keeps it (T = N + 1)."""
+        return self._extract_tokens(images, self._arena, self._weights(), with_cls, drop_cls)
+
+    def _extract_tokens(self, images: torch.Tensor, params: torch.Tensor, wcache: Optional[torch.Tensor], with_cls: bool, drop_cls: bool) -> torch.Tensor:
+        dev = self._require_cuda()
+        images = self._check_images(images.to(dev))
+        B = images.shape[0]
+        with_cls = bool(with_cls)
+        drop = with_cls and bool(drop_cls)
+        need = lib.mae_engine_tokens_workspace_bytes(self._engine.handle, B, int(with_cls))
+        if need < 0:
+            raise ValueError(f"bad batch {B}")
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._plan = None
+        self._gen_enc += 1; self._gen_dec += 1
+        T = self.sequence_length - (0 if with_cls and not drop else 1)
+        out = torch.empty(B, T, self._dims["embed_dim"], dtype=torch.float32, device=dev)
+        check(lib.mae_engine_extract_tokens(self._engine.handle, _ptr(params), _ptr(wcache), _ptr(images), self._img_dt(images), B, int(with_cls),
+                                            int(drop), _ptr(self._workspace), self._workspace.numel(), _ptr(out), _stream(dev)))
         return out
 
     def _run_decoder(self, x_encoded: torch.Tensor, idx_keep: torch.Tensor, idx_mask: torch.Tensor) -> torch.Tensor:
