@@ -330,7 +330,8 @@ int mae_engine_grad_accumulate(mae_engine_t* e, float* dst, const float* src, in
  *   train_embed = 1   : n = depth only -- also cls_token, patch_embed.proj.* (in `grads`) and pos_embed, whose gradient
  *                       goes to pos_grad (L * embed_dim floats, it lies outside the trainable range) (unfreeze_encoder(), :134).
  *   head_grads: dW then db, same layout as head.  grad_scale multiplies every gradient (not the loss). */
-enum { MAE_POOL_CLS = 0, MAE_POOL_MEAN = 1, MAE_POOL_MEAN_PATCHES = 2 /* features and the _ex classifier calls; the three calls below reject it */ };
+enum { MAE_POOL_CLS = 0, MAE_POOL_MEAN = 1, MAE_POOL_MEAN_PATCHES = 2 /* features and the _ex classifier calls; the three calls below reject it */,
+       MAE_POOL_CLS_MEAN_PATCHES = 3 /* [class row | patch mean], 2 * dim wide: mae_engine_extract_layer_features and mae_features_tap only */ };
 int64_t mae_engine_classifier_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t num_classes);
 int mae_engine_classifier_forward(mae_engine_t* e, const float* params, const void* wcache, const float* head, const void* images,
                                   int32_t image_dtype, const int64_t* labels, int32_t batch, int32_t pool, int32_t num_classes,
@@ -487,7 +488,22 @@ int mae_engine_extract_features(mae_engine_t* e, const float* params, const void
                                 int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, void* workspace,
                                 int64_t workspace_bytes, float* feats, void* stream);
 
-/* Frozen-encoder tokens (additive in ABI v4): the call above without the pool.  The encoder forward with nothing saved, the last
+/* Features after any encoder block (additive in ABI v4): ONE forward pass, and after every block layers[i] the fused step of
+ * mae_engine_extract_features on the residual stream x_mid + mlp branch of that block, through the encoder's own final LayerNorm
+ * (encoder.vit.norm, eps 1e-6: DINO's get_intermediate_layers, the I-JEPA last-n-layers probe), written to feats[:, i, :].
+ *   layers: HOST array of num_layers 0-based block indices, strictly ascending, each in [0, depth); 1 <= num_layers <= depth.
+ *           The forward stops after block layers[num_layers - 1].  Block depth - 1 gives mae_engine_extract_features' bits.
+ *   pool: the three pools above (W = embed_dim), or MAE_POOL_CLS_MEAN_PATCHES (with_cls = 1 only): W = 2 embed_dim,
+ *         feats[b][i] = [class row | mean over the patch rows], equal bit for bit to MAE_POOL_CLS and MAE_POOL_MEAN_PATCHES.
+ *   normalize: MAE_FEAT_L2 normalises every embed_dim-wide slice (layer, and half of pool 3) on its own.
+ *   feats: (batch, num_layers, W) fp32, 16-byte aligned.
+ * Same limits, workspace (mae_engine_features_workspace_bytes) and determinism as the call above; every refusal comes before
+ * any launch. */
+int mae_engine_extract_layer_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                      int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, const int32_t* layers,
+                                      int32_t num_layers, void* workspace, int64_t workspace_bytes, float* feats, void* stream);
+
+/* Frozen-encoder tokens (additive in ABI v4): mae_engine_extract_features without the pool.  The encoder forward with nothing saved, the last
  * residual add and the final LayerNorm in fp32 (the step of the fused add + LayerNorm kernel, a bf16 branch widened first), written as
  * tokens (batch, T_out, embed_dim) fp32 in the sequence's order.
  *   with_cls as above: T = N + 1 rows [cls | patches], or the N patch rows;
@@ -836,6 +852,14 @@ int mae_smooth_l1_loss(const float* pred, const float* target, int64_t n, float 
  *     f = sum_{t in [row_lo, row_hi)} y[t] / (row_hi - row_lo);  normalize = MAE_FEAT_L2: out = f / (||f||_2 + 1e-8), else out = f.
  *   One block per image; wave w of four adds rows row_lo + w, row_lo + w + 4, ... and the four sums are added in wave order, so an
  *   image's result does not depend on batch.  Only the pooled rows are read.  Limits: dim as above, 0 <= row_lo < row_hi <= seq_len.
+ * mae_features_tap: mae_features_pool by (with_cls, pool) with a row stride on the output: image b's feature goes to
+ *     out + b * out_row_stride (floats).  Rows pooled: MAE_POOL_CLS row 0; MAE_POOL_MEAN every row; MAE_POOL_MEAN_PATCHES rows
+ *     [with_cls, seq_len); each with mae_features_pool's arithmetic order, so the slice holds its bits.  MAE_POOL_CLS_MEAN_PATCHES:
+ *     W = 2 dim, out[0, dim) = the MAE_POOL_CLS result, out[dim, 2 dim) = the MAE_POOL_MEAN_PATCHES result, bit for bit, from one
+ *     pass over the rows; MAE_FEAT_L2 normalises each half on its own.  Nothing outside [0, W) of a slice is written.
+ *   Limits (checked before the launch): dim as above; MAE_POOL_CLS and MAE_POOL_CLS_MEAN_PATCHES need with_cls = 1;
+ *   MAE_POOL_CLS_MEAN_PATCHES, and MAE_POOL_MEAN_PATCHES with with_cls = 1, need seq_len >= 2; out_row_stride >= W and a multiple
+ *   of 4; out 16-byte aligned.
  * mae_cast: dst[i] = src[i] converted, i < n: fp32 -> bf16 rounds to nearest even (a NaN stays a quiet NaN), bf16 -> fp32 is
  *   exact, equal types copy.  n > 0.
  * mae_add_rows_pos: out[r] = fl32(x[r] + pos[r % seq_len]) for r < rows; x, out (rows, dim), pos (seq_len, dim) fp32.
@@ -854,6 +878,9 @@ int mae_zero_token_rows(int64_t rows, int32_t seq_len, int32_t dim, int32_t dtyp
 int mae_features_pool(const float* x_mid, const void* branch, int32_t branch_dtype, const float* gamma, const float* beta, float eps,
                       int32_t batch, int32_t seq_len, int32_t dim, int32_t row_lo, int32_t row_hi, int32_t normalize, float* out,
                       void* stream);
+int mae_features_tap(const float* x_mid, const void* branch, int32_t branch_dtype, const float* gamma, const float* beta, float eps,
+                     int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls, int32_t pool, int32_t normalize, float* out,
+                     int64_t out_row_stride, void* stream);
 int mae_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream);
 int mae_add_rows_pos(const float* x, const float* pos, int64_t rows, int32_t seq_len, int32_t dim, float* out, void* stream);
 int mae_add_into(const float* src, void* dst, int32_t dst_dtype, int64_t n, void* stream);

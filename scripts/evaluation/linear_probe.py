@@ -16,6 +16,11 @@ images_per_s), ``checkpoints/{best,last}.ckpt`` (classifier checkpoints with Bat
 ``train_mae.build_module(classifier_ckpt=...)`` and ``evaluate_classifier`` unchanged), ``checkpoints/probe_last.pt`` (the probe's own
 state: resume with --resume) and ``probe.json`` (test_acc / test_loss at the best validation epoch).  Every hyper-parameter flag
 overrides its ``probe.*`` YAML key.
+
+``--layers SPEC`` (last | lastN | each | 2,5,-1) probes the concatenated features of those encoder blocks, each through the encoder's final
+LayerNorm (DINO's and I-JEPA's last-n-blocks probe), from one forward pass per batch; ``--pool cls_mean`` then gives [class token |
+patch mean] per block.  The concatenation must fit the probe kernels' 1024 columns (ViT-S: two blocks).  Such a head reads no single
+encoder output, so no classifier checkpoint is written: ``probe_last.pt`` and ``probe.json`` carry ``layers`` instead.
 """
 from __future__ import annotations
 
@@ -36,6 +41,7 @@ from ssrl_vit_mae_jepa_amd.training import lr_lambda
 HYPER_FLAGS = ("total_epochs", "warmup_epochs", "batch_size", "base_learning_rate", "weight_decay", "momentum", "trust_coefficient", "bn_eps",
                "bn_momentum", "head_init_std", "augment")
 EXTRACT_BATCH = 500   # images per encoder call while extracting
+PROBE_MAX_DIM = 1024  # columns the probe kernels take (probe.ProbeHead)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -43,7 +49,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--config", type=str, default="configs/vits8_dec192_linprobe.yaml")
     p.add_argument("--checkpoint", type=str, required=True, help="checkpoint path (.ckpt / .pt) or 'random'")
     p.add_argument("--encoder", type=str, choices=["target", "context"], default="target", help="I-JEPA encoder (default: the EMA target)")
-    p.add_argument("--pool", type=str, choices=["cls", "mean", "mean_all"], default=None, help="feature pool; MAE default cls, I-JEPA mean")
+    p.add_argument("--pool", type=str, choices=["cls", "mean", "mean_all", "cls_mean"], default=None,
+                   help="feature pool; MAE default cls, I-JEPA mean; cls_mean = [class token | patch mean], with --layers only")
+    p.add_argument("--layers", type=str, default=None,
+                   help="probe the concatenated features of these encoder blocks: last | lastN | each | comma-separated indices")
     p.add_argument("--samples_per_class", type=int, default=None, help="training images per class (default: train.samples_per_class)")
     p.add_argument("--synthetic_images", type=int, default=None, help="use N synthetic labeled images instead of STL-10")
     p.add_argument("--max_epochs", type=int, default=None, help="stop after this many epochs (the schedule keeps probe.total_epochs)")
@@ -97,8 +106,29 @@ def save(path: Path, obj) -> None:
     os.replace(tmp, path)
 
 
-def _features(enc, images: torch.Tensor, pool: str) -> torch.Tensor:
-    return torch.cat([enc.features(images[i:i + EXTRACT_BATCH], pool=pool, normalize="none") for i in range(0, images.shape[0], EXTRACT_BATCH)])
+def _features(enc, images: torch.Tensor, pool: str, layers=None) -> torch.Tensor:
+    return torch.cat([enc.features(images[i:i + EXTRACT_BATCH], pool=pool, normalize="none", layers=layers).flatten(1)
+                      for i in range(0, images.shape[0], EXTRACT_BATCH)])
+
+
+def probe_layers(spec, model_cfg: dict, pool: str):
+    """(layers, feature width) of --layers SPEC, or (None, embed_dim) without it; SystemExit when the spec is wrong or the concatenation
+    is wider than the probe kernels take.  Needs the config alone: it runs before any data or checkpoint is loaded."""
+    from ssrl_vit_mae_jepa_amd.representation import config_depth_dim, parse_layers
+    depth, dim = config_depth_dim(model_cfg)
+    if spec is None:
+        if pool == "cls_mean":
+            raise SystemExit("linear_probe: --pool cls_mean needs --layers")
+        return None, dim
+    try:
+        layers = parse_layers(spec, depth)
+    except ValueError as exc:
+        raise SystemExit(f"linear_probe: {exc}")
+    width = len(layers) * dim * (2 if pool == "cls_mean" else 1)
+    if width > PROBE_MAX_DIM:
+        raise SystemExit(f"linear_probe: --layers {spec} with pool {pool} gives {width} feature columns ({len(layers)} blocks x "
+                         f"{width // len(layers)}); the probe kernels take at most {PROBE_MAX_DIM}")
+    return layers, width
 
 
 def _evaluate(probe: LinearProbe, feats: torch.Tensor, labels: torch.Tensor, batch: int):
@@ -125,6 +155,9 @@ def main(argv=None):
     pool = args.pool or ("mean" if is_ijepa else "cls")
     if is_ijepa and pool == "cls":
         raise SystemExit("linear_probe: I-JEPA encoders see no class token: --pool must be mean or mean_all")
+    if is_ijepa and pool == "cls_mean":
+        raise SystemExit("linear_probe: I-JEPA encoders see no class token: --pool must be mean or mean_all")
+    layers, width = probe_layers(args.layers, model_cfg, pool)   # before any data or checkpoint is loaded
     if args.max_epochs is not None and args.max_epochs < 1:
         raise SystemExit("linear_probe: --max_epochs must be at least 1")
     if args.checkpoint != "random" and not Path(args.checkpoint).exists():
@@ -150,7 +183,10 @@ def main(argv=None):
     precision = cfg.get("engine", {}).get("precision")
     enc = load_eval_encoder(args.checkpoint, model_cfg, encoder=args.encoder, precision=precision, device=dev)
     try:
-        classifier_pool(pool, enc.with_cls)
+        if pool == "cls_mean":
+            classifier_pool("cls", enc.with_cls)   # the same rule: it needs the class token
+        else:
+            classifier_pool(pool, enc.with_cls)
     except ValueError as exc:
         raise SystemExit(f"linear_probe: {exc}")
 
@@ -161,9 +197,11 @@ def main(argv=None):
     if crop:   # the training features are re-extracted per step: only the images and labels are kept, at the stored resolution
         train_images, train_f, train_y = train_b.images[train_b.idx], None, train_b.labels[train_b.idx]
     else:
-        train_images, (train_f, train_y) = None, extract_split_features(enc, train_b, pool=pool, normalize="none")
-    val_f, val_y = extract_split_features(enc, val_b, pool=pool, normalize="none")
-    test_f, test_y = extract_split_features(enc, test_b, pool=pool, normalize="none")
+        train_images, (train_f, train_y) = None, extract_split_features(enc, train_b, pool=pool, normalize="none", layers=layers)
+        train_f = train_f.flatten(1)   # (N, n, W) -> (N, n W) with --layers
+    val_f, val_y = extract_split_features(enc, val_b, pool=pool, normalize="none", layers=layers)
+    test_f, test_y = extract_split_features(enc, test_b, pool=pool, normalize="none", layers=layers)
+    val_f, test_f = val_f.flatten(1), test_f.flatten(1)
     torch.cuda.synchronize()
     extract_s = time.perf_counter() - t0
     n = int(train_y.shape[0])
@@ -171,11 +209,14 @@ def main(argv=None):
         raise SystemExit(f"linear_probe: {n} training and {val_f.shape[0]} validation rows are too few")
     num_classes = int(max(int(train_y.max()), int(val_y.max()), int(test_y.max()))) + 1
 
-    probe = LinearProbe(enc.embed_dim, num_classes, pcfg, seed=seed, device=dev)
+    probe = LinearProbe(enc.embed_dim if layers is None else width, num_classes, pcfg, seed=seed, device=dev)
     start_epoch = 0
     best = dict(val_acc=-1.0, epoch=-1, test_acc=None, test_loss=None)
     if args.resume is not None:
         state = torch.load(args.resume, map_location="cpu", weights_only=False)
+        if list(state.get("layers") or []) != list(layers or []) or (layers is not None and state.get("pool") != pool):
+            raise SystemExit(f"linear_probe: --resume state was trained on layers {state.get('layers')} pool {state.get('pool')}, "
+                             f"this run asks for layers {None if layers is None else list(layers)} pool {pool}")
         probe.load_state_dict(state)
         start_epoch = probe.epoch
         best = dict(state.get("best") or best)   # best.ckpt is replaced only by a better epoch
@@ -198,7 +239,7 @@ def main(argv=None):
             if crop:
                 imgs = train_images[j].contiguous()
                 g = torch.Generator().manual_seed(int(np.random.SeedSequence([seed, epoch, step]).generate_state(1)[0]))
-                feats = _features(enc, augment_to_size(imgs, crop_size, draw_augment_params(imgs.shape[0], imgs.shape[2], g), crop_dtype), pool)
+                feats = _features(enc, augment_to_size(imgs, crop_size, draw_augment_params(imgs.shape[0], imgs.shape[2], g), crop_dtype), pool, layers)
             else:
                 feats = train_f[j]
             loss, correct = probe.step(feats, train_y[j], lr)
@@ -214,18 +255,25 @@ def main(argv=None):
         metrics.write(json.dumps(line) + "\n")
         metrics.flush()
         print(json.dumps(line))
-        ckpt = probe.classifier_checkpoint(enc, model_cfg, pool, epoch=epoch)
-        save(out_dir / "checkpoints" / "last.ckpt", ckpt)
+        # a head on several blocks is no classifier head (the classifier reads the last block alone): no classifier checkpoint then
+        ckpt = probe.classifier_checkpoint(enc, model_cfg, pool, epoch=epoch) if layers is None else None
+        if ckpt is not None:
+            save(out_dir / "checkpoints" / "last.ckpt", ckpt)
         if val_acc > best["val_acc"]:
             test_loss, test_acc = _evaluate(probe, test_f, test_y, batch)
             best = dict(val_acc=val_acc, epoch=epoch, test_acc=test_acc, test_loss=test_loss)
-            save(out_dir / "checkpoints" / "best.ckpt", ckpt)
-        save(out_dir / "checkpoints" / "probe_last.pt", dict(probe.state_dict(), best=best))
+            if ckpt is not None:
+                save(out_dir / "checkpoints" / "best.ckpt", ckpt)
+        extra = {} if layers is None else dict(layers=list(layers), pool=pool)
+        save(out_dir / "checkpoints" / "probe_last.pt", dict(probe.state_dict(), best=best, **extra))
     metrics.close()
-    res = dict(checkpoint=args.checkpoint, kind=enc.kind, encoder=enc.encoder, pool=pool, classifier_pool=classifier_pool(pool, enc.with_cls),
+    res = dict(checkpoint=args.checkpoint, kind=enc.kind, encoder=enc.encoder, pool=pool,
+               classifier_pool=classifier_pool(pool, enc.with_cls) if layers is None else None,
                augment=pcfg["augment"], epochs=end_epoch, train_size=int(n), val_size=int(val_f.shape[0]), test_size=int(test_f.shape[0]),
                best_epoch=best["epoch"], val_acc=best["val_acc"], test_acc=best["test_acc"], test_loss=best["test_loss"], peak_lr=peak,
                extract_s=extract_s)
+    if layers is not None:
+        res["layers"] = list(layers)
     (out_dir / "probe.json").write_text(json.dumps(res) + "\n")
     print(json.dumps(res))
     return res

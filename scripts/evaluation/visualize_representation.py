@@ -16,7 +16,7 @@ import torch
 import yaml
 
 from ssrl_vit_mae_jepa_amd.data import get_test_batches
-from ssrl_vit_mae_jepa_amd.representation import apply_normalization, extract_split_features, load_eval_encoder
+from ssrl_vit_mae_jepa_amd.representation import apply_normalization, config_depth_dim, extract_split_features, load_eval_encoder, parse_layers
 
 try:
     import umap
@@ -79,7 +79,9 @@ def parse_args(argv=None):
     p.add_argument("--config", type=str, default="configs/mae.yaml")
     p.add_argument("--encoder_ckpt", type=str, required=True, help="checkpoint path or 'random'")
     p.add_argument("--method", type=str, choices=["umap", "tsne"], default="umap")
-    p.add_argument("--pool", type=str, choices=["cls", "mean"], default="cls")
+    p.add_argument("--pool", type=str, choices=["cls", "mean", "cls_mean"], default="cls", help="cls_mean = [class token | patch mean], with --layers only")
+    p.add_argument("--layers", type=str, default=None,
+                   help="plot the features after these encoder blocks (last | lastN | each | comma-separated indices; several are concatenated)")
     p.add_argument("--normalize", type=str, choices=["none", "l2", "channel"], default="none")
     p.add_argument("--max_samples", type=int, default=2000)
     p.add_argument("--batch_size", type=int, default=512)
@@ -96,6 +98,14 @@ def main(argv=None):
         raise RuntimeError("UMAP requested but not installed.")
     with open(args.config, "r") as f:
         cfg = yaml.safe_load(f)
+    layers = None
+    if args.layers is not None:
+        try:
+            layers = parse_layers(args.layers, config_depth_dim(cfg["model"])[0])
+        except ValueError as exc:
+            raise SystemExit(f"visualize_representation: {exc}")
+    elif args.pool == "cls_mean":
+        raise SystemExit("visualize_representation: --pool cls_mean needs --layers")
     if not torch.cuda.is_available():
         raise SystemExit("visualize_representation: the MI355X engine has no CPU fallback")
     dev = torch.device("cuda", 0)
@@ -105,7 +115,8 @@ def main(argv=None):
     test_cfg = dict(cfg, test=dict(cfg.get("test", {}), batch_size=args.batch_size))
     batches = get_test_batches(test_cfg, dev, synthetic_images=args.synthetic_images)
     print("Extracting features...")
-    feats, labels = extract_split_features(enc, batches, pool=args.pool, normalize="none", max_samples=args.max_samples)
+    feats, labels = extract_split_features(enc, batches, pool=args.pool, normalize="none", max_samples=args.max_samples, layers=layers)
+    feats = feats.flatten(1)  # (N, n, W) -> (N, n W) with --layers
     feats = apply_normalization(feats.cpu().numpy(), args.normalize)  # the reference normalises on the host, in numpy
     labels = labels.cpu().numpy()
     print("Projecting to 2D...")
@@ -116,6 +127,8 @@ def main(argv=None):
     stem = f"representation_{ckpt_name}_{args.method}_{args.pool}_{args.normalize}"
     if enc.kind == "ijepa":
         stem += f"_{enc.encoder}"
+    if layers is not None:
+        stem += "_blocks" + "-".join(str(l) for l in layers)
     plot_embedding(Z, labels, str(save_dir / f"{stem}.png"), f"{args.method}, pool={args.pool}, norm={args.normalize}", STL10_CLASSES)
     for cls_id in np.unique(labels):
         plot_class_vs_all(Z, labels, cls_id, STL10_CLASSES[cls_id], str(save_dir / f"{stem}_class{cls_id}.png"))

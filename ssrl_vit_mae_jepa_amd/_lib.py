@@ -17,7 +17,7 @@ LIB_PATH = Path(os.environ.get("MAE_HIP_LIB") or _HERE / "lib" / "libmae_hip.so"
 MAE_F32, MAE_BF16, MAE_U8 = 0, 1, 2
 PARAM_TRAINABLE, PARAM_FROZEN, PARAM_UNUSED, PARAM_MATRIX = 1, 2, 4, 8
 LOSS_MSE, LOSS_SMOOTH_L1 = 0, 1
-POOL_CLS, POOL_MEAN, POOL_MEAN_PATCHES = 0, 1, 2
+POOL_CLS, POOL_MEAN, POOL_MEAN_PATCHES, POOL_CLS_MEAN_PATCHES = 0, 1, 2, 3
 FEAT_NONE, FEAT_L2 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL, EPI_GELU_ACT = 0, 1, 2, 3, 4, 5, 6
 AUG_NONE, AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_INVERT, AUG_POSTERIZE, AUG_SOLARIZE, AUG_SOLARIZE_ADD, AUG_COLOR, AUG_CONTRAST, AUG_BRIGHTNESS, \
@@ -112,6 +112,7 @@ SIGNATURES = {
     "mae_engine_refresh_transposed_range": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "mae_engine_features_workspace_bytes": (_i64, [_vp, _i32, _i32]),
     "mae_engine_extract_features": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "mae_engine_extract_layer_features": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _pp(_i32), _i32, _vp, _i64, _vp, _vp]),
     "mae_reconstruct_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "mae_reconstruct_compose": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mae_engine_reconstruct": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
@@ -174,6 +175,7 @@ SIGNATURES = {
     "mae_full_grad_split_partial_floats": (_i64, [_i32, _i32, _i32]),
     "mae_zero_token_rows": (C.c_int, [_i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mae_features_pool": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_features_tap": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "mae_cast": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp]),
     "mae_add_rows_pos": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "mae_add_into": (C.c_int, [_vp, _vp, _i32, _i64, _vp]),

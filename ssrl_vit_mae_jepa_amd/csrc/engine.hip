@@ -247,6 +247,11 @@ struct Ctx {
   void* const* ready = nullptr;  // hipEvent_t per gradient-ready point (entries may be null), or null
   bool fwd_only = false;         // no backward will follow (I-JEPA target encoder): the MLP saves no derivative
   bool skip_final_norm = false;  // forward_encoder_impl stops after the last block: x_mid + branch_b is left for the caller
+  // taps (mae_engine_extract_layer_features alone): right after block tap_layers[i] the tap kernel pools x_mid + branch_b into slice i of
+  // tap_out (batch, tap_n, W), and the encoder stops after the last tapped block
+  const int32_t* tap_layers = nullptr;
+  int tap_n = 0, tap_with_cls = 1, tap_pool = MAE_POOL_CLS, tap_normalize = MAE_FEAT_NONE;
+  float* tap_out = nullptr;
   const float* branch_scale = nullptr;  // drop path (classifier training only): (2 * depth, batch) per-image scales of the encoder's branches
   // row j of the table (row 2i: attention branch of encoder block i, 2i + 1: its MLP branch), or null without a table
   const float* scale_row(int j, int batch) const { return branch_scale ? branch_scale + (int64_t)j * batch : nullptr; }
@@ -261,7 +266,7 @@ struct Ctx {
   template <class T = void> T* buf(int64_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
 
-// the one place a Ctx is built; `ready` / `fwd_only` / `skip_final_norm` are set by the few callers that need them
+// the one place a Ctx is built; `ready` / `fwd_only` / `skip_final_norm` / the taps are set by the few callers that need them
 static Ctx make_ctx(mae_engine* e, const float* params, const void* wcache, float* grads, void* ws, void* stream) {
   return Ctx{e, params, (const char*)wcache, grads, (char*)ws, (hipStream_t)stream, e->act, (int64_t)dtype_size(e->act)};
 }
@@ -426,6 +431,18 @@ static int check_image_dtype(int dt, const char* who) {
   return 0;
 }
 
+// Tap `slot` of the call: block i has just run, so pl.enc[i].x_mid and pl.branch_b hold its residual stream until the next block's fc2
+// rewrites the branch.  The encoder's final norm, as for the last block.  Bytes: the pooled rows read, the slice written.
+static int tap_block(const Ctx& c, const Plan& pl, int i, int slot) {
+  mae_engine* e = c.e; hipStream_t s = c.s;
+  const int T = pl.k, W = features_tap_width(c.tap_pool, e->D);
+  const int lo = c.tap_pool == MAE_POOL_MEAN_PATCHES && c.tap_with_cls ? 1 : 0, hi = c.tap_pool == MAE_POOL_CLS ? 1 : T;
+  RUN(TK_LN_FWD, 0, (double)pl.B * (hi - lo) * e->D * (4 + c.as) + (double)pl.B * W * 4,
+      launch_features_tap(c.buf<float>(pl.enc[i].x_mid), c.buf<>(pl.branch_b), e->act, c.P(e->i_norm_w), c.P(e->i_norm_b), 1e-6f, pl.B, T, e->D,
+                          c.tap_with_cls, c.tap_pool, c.tap_normalize, c.tap_out + (int64_t)slot * W, (int64_t)c.tap_n * W, s));
+  return 0;
+}
+
 static int forward_encoder_impl(const Ctx& c, const Plan& pl, const void* images, int img_dt, float* x_encoded_out) {
   mae_engine* e = c.e; hipStream_t s = c.s;
   const int32_t* keep32 = c.buf<int32_t>(pl.keep32);
@@ -434,10 +451,13 @@ static int forward_encoder_impl(const Ctx& c, const Plan& pl, const void* images
   RUN(TK_DATA, 0, gather_read + pl.Me * e->P * c.as, launch_gather_patches(images, img_dt, keep32, pl.B, pl.k, e->C, e->img, e->p, c.act, c.buf<>(pl.patchA), s));
   MAE_TRY(linear(c, c.buf<>(pl.patchA), e->i_patch_w, e->i_patch_b, pl.Me, e->D, e->P, MAE_EPI_NONE, MAE_F32, c.buf<>(pl.enc_x[0]), nullptr, nullptr));
   RUN(TK_DATA, 0, pl.Me * e->D * 12, launch_assemble_visible(c.buf<float>(pl.enc_x[0]), keep32, c.P(e->i_cls), c.P(e->i_pos), pl.Me, e->D, s));
-  for (int i = 0; i < e->depth; ++i)
+  const int blocks = c.tap_n ? c.tap_layers[c.tap_n - 1] + 1 : e->depth;
+  for (int i = 0, slot = 0; i < blocks; ++i) {
     MAE_TRY(block_forward(c, pl, e->enc[i], pl.enc[i], pl.Me, e->D, e->H, pl.B, pl.k, i ? pl.enc[i - 1].x_mid : 0, i > 0, pl.enc_x[i],
                           i ? c.scale_row(2 * i - 1, pl.B) : nullptr, c.scale_row(2 * i, pl.B)));
-  if (c.skip_final_norm) return 0;
+    if (slot < c.tap_n && c.tap_layers[slot] == i) MAE_TRY(tap_block(c, pl, i, slot++));
+  }
+  if (c.skip_final_norm || c.tap_n) return 0;
   MAE_TRY(ln_fwd(c, c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w),
                  c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, c.act, c.buf<>(pl.enc_norm), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd),
                  c.scale_row(2 * e->depth - 1, pl.B), pl.k));
@@ -1341,6 +1361,39 @@ extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params,
       launch_features_pool(c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), e->act, c.P(e->i_norm_w), c.P(e->i_norm_b), 1e-6f,
                            batch, T, e->D, lo, hi, normalize, feats, s));
   return 0;
+}
+
+// mae_engine_extract_features after the blocks `layers` names: the same forward with a tap list, stopped after the highest tapped block.
+// Tap depth - 1 reads what launch_features_pool reads above, in the same arithmetic order.
+extern "C" int mae_engine_extract_layer_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                                 int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, const int32_t* layers,
+                                                 int32_t num_layers, void* workspace, int64_t workspace_bytes, float* feats, void* stream) {
+  const char* who = "mae_engine_extract_layer_features";
+  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
+  MAE_REQUIRE(images && feats && layers, "%s: null argument", who);
+  if (pool == MAE_POOL_CLS_MEAN_PATCHES)
+    MAE_REQUIRE(with_cls == 1, "%s: pool MAE_POOL_CLS_MEAN_PATCHES needs with_cls = 1 (got %d)", who, with_cls);
+  else
+    MAE_TRY(check_pool(with_cls, pool, true, who));
+  MAE_REQUIRE(e->D % 4 == 0 && e->D <= 1024, "%s: embed_dim = %d must be a multiple of 4 and at most 1024", who, e->D);
+  MAE_REQUIRE(normalize == MAE_FEAT_NONE || normalize == MAE_FEAT_L2, "%s: normalize must be MAE_FEAT_NONE or MAE_FEAT_L2 (got %d)", who, normalize);
+  MAE_TRY(check_image_dtype(image_dtype, who));
+  MAE_REQUIRE(num_layers >= 1 && num_layers <= e->depth, "%s: num_layers = %d outside [1, depth = %d]", who, num_layers, e->depth);
+  for (int i = 0; i < num_layers; ++i) {
+    MAE_REQUIRE(layers[i] >= 0 && layers[i] < e->depth, "%s: layers[%d] = %d outside [0, depth = %d)", who, i, layers[i], e->depth);
+    MAE_REQUIRE(i == 0 || layers[i] > layers[i - 1], "%s: layers must be strictly ascending (layers[%d] = %d after %d)", who, i, layers[i], layers[i - 1]);
+  }
+  MAE_REQUIRE(((uintptr_t)feats & 15) == 0, "%s: feats must be 16-byte aligned", who);
+  const int64_t need = mae_engine_features_workspace_bytes(e, batch, with_cls);
+  MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
+  MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
+  const Plan pl = make_encoder_plan(e, batch, with_cls != 0);
+  MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pl.k > with_cls, "%s: the sequence of %d rows has no patch row", who, pl.k);
+  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  c.fwd_only = true;
+  c.tap_layers = layers; c.tap_n = num_layers; c.tap_with_cls = with_cls; c.tap_pool = pool; c.tap_normalize = normalize; c.tap_out = feats;
+  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
+  return forward_encoder_impl(c, pl, images, image_dtype, nullptr);
 }
 
 // mae_engine_extract_features without the pool: the same encoder forward, then the last residual add and the final LayerNorm in fp32

@@ -154,6 +154,11 @@ int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* d
 // when normalize == MAE_FEAT_L2.  Reads only the pooled rows.
 int launch_features_pool(const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta, float eps, int B, int seq,
                          int D, int row_lo, int row_hi, int normalize, float* out, hipStream_t s);
+// The same step by (with_cls, pool) into out + b * out_stride (floats): one slice of a (B, taps, W) buffer.  W = features_tap_width:
+// D, or 2 D for MAE_POOL_CLS_MEAN_PATCHES = [class row | patch mean].  The pools shared with launch_features_pool give its bits.
+int features_tap_width(int pool, int D);
+int launch_features_tap(const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta, float eps, int B, int seq,
+                        int D, int with_cls, int pool, int normalize, float* out, int64_t out_stride, hipStream_t s);
 // top-k of queries (Q, D) . bank (N, D)^T per query row: similarity descending, bank index ascending; -1 for bad arguments
 int knn_splits(int64_t Q, int64_t N, int k);
 int64_t knn_scratch_bytes(int64_t Q, int64_t N, int D, int k);

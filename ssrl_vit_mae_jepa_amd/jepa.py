@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -237,18 +237,20 @@ class IJEPA(nn.Module):
         return (loss, h, pred) if return_aux else loss
 
     @torch.no_grad()
-    def extract_features(self, images: torch.Tensor, encoder: str = "target", pool: str = "mean", normalize: str = "none") -> torch.Tensor:
+    def extract_features(self, images: torch.Tensor, encoder: str = "target", pool: str = "mean", normalize: str = "none",
+                         layers: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Pooled features of the EMA target encoder (``encoder="target"``, what I-JEPA evaluates) or the context encoder:
         (B, D) fp32 over the patch tokens, the only tokens the I-JEPA encoders were trained on.  pool "mean" (the only one:
-        there is no class token); normalize "none" | "l2"."""
+        there is no class token); normalize "none" | "l2".  layers: as ``MaskedAutoencoder.extract_features`` -- (B, n, D), the
+        blocks' outputs through the encoder's final LayerNorm (the last-n-layers probe of the I-JEPA paper)."""
         if encoder not in ("target", "context"):
             raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
         if pool != "mean":
             raise ValueError(f"I-JEPA encoders see no class token: pool must be 'mean', got {pool!r}")
         net = self.net
         if encoder == "target":
-            return net._extract(images, self.target_arena, self._target_weights(), pool, normalize, with_cls=False)
-        return net._extract(images, net.flat_params, net._weights(), pool, normalize, with_cls=False)
+            return net._extract(images, self.target_arena, self._target_weights(), pool, normalize, with_cls=False, layers=layers)
+        return net._extract(images, net.flat_params, net._weights(), pool, normalize, with_cls=False, layers=layers)
 
     @torch.no_grad()
     def extract_tokens(self, images: torch.Tensor, encoder: str = "target") -> torch.Tensor:

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Any, Dict, List, NamedTuple, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -198,9 +198,10 @@ class _ViT(_Node):
     def forward(self, images: torch.Tensor) -> torch.Tensor:
         return self.forward_features(images)
 
-    def extract_features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none", with_cls: bool = True) -> torch.Tensor:
+    def extract_features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none", with_cls: bool = True,
+                         layers: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Pooled features of the frozen encoder: ``MaskedAutoencoder.extract_features``."""
-        return self._owner().extract_features(images, pool=pool, normalize=normalize, with_cls=with_cls)
+        return self._owner().extract_features(images, pool=pool, normalize=normalize, with_cls=with_cls, layers=layers)
 
     def extract_tokens(self, images: torch.Tensor, with_cls: bool = True, drop_cls: bool = True) -> torch.Tensor:
         """Every token of the frozen encoder: ``MaskedAutoencoder.extract_tokens``."""
@@ -210,6 +211,24 @@ class _ViT(_Node):
 # extract_features pool names: "mean" averages the patch tokens (visualize_representation.py:94), "mean_all" every token (the classifier)
 FEATURE_POOLS = {"cls": _lib.POOL_CLS, "mean": _lib.POOL_MEAN_PATCHES, "mean_all": _lib.POOL_MEAN}
 FEATURE_NORMS = {"none": _lib.FEAT_NONE, "l2": _lib.FEAT_L2}
+# with layers=...: also "cls_mean" = [class token | mean over the patch tokens], twice as wide (DINO's ViT-B linear-probe input)
+LAYER_FEATURE_POOLS = dict(FEATURE_POOLS, cls_mean=_lib.POOL_CLS_MEAN_PATCHES)
+
+
+def resolve_layers(layers: Sequence[int], depth: int) -> Tuple[int, ...]:
+    """0-based block indices of ``extract_features(layers=...)``: negative ones count from the end; the result must be strictly
+    ascending inside [0, depth) -- the order of the slices in the result, and of the blocks in the forward pass."""
+    if isinstance(layers, (str, bytes)) or len(layers) == 0:
+        raise ValueError(f"layers must be a non-empty sequence of block indices, got {layers!r}")
+    out = []
+    for v in layers:
+        i = int(v)
+        if i != v or not -depth <= i < depth:
+            raise ValueError(f"layer {v!r} outside the encoder's {depth} blocks")
+        out.append(i + depth if i < 0 else i)
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"layers must be strictly ascending without repeats, got {list(layers)} (= blocks {out})")
+    return tuple(out)
 
 
 class _Encoder(_Node):
@@ -607,21 +626,32 @@ class MaskedAutoencoder(nn.Module):
         return self._run_encoder(images, idx_keep)
 
     @torch.no_grad()
-    def extract_features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none", with_cls: bool = True) -> torch.Tensor:
+    def extract_features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none", with_cls: bool = True,
+                         layers: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Pooled features of the encoder (scripts/evaluation/visualize_representation.py:87-108): (B, D) fp32, no autograd graph.
         pool "cls" = the class-token row, "mean" = mean over the patch tokens, "mean_all" = mean over every token (the
         classifier's "mean"); normalize "none" | "l2" (f / (||f|| + 1e-8)).  with_cls=False runs the encoder over the patch
-        tokens only, as the I-JEPA encoders see them ("cls" is then an error)."""
-        return self._extract(images, self._arena, self._weights(), pool, normalize, with_cls)
+        tokens only, as the I-JEPA encoders see them ("cls" is then an error).
+
+        layers: block indices (0-based, negative ones from the end, strictly ascending) -> (B, len(layers), W) fp32 from ONE forward
+        pass that stops after the highest block named: slice i is the residual stream after block layers[i] through the encoder's
+        final LayerNorm and the pool (DINO's get_intermediate_layers; ``layers=[-1]`` holds the bits of the plain call).  pool
+        "cls_mean" (only here, only with the class token) = [class token | patch mean], W = 2 D, else W = D.  normalize="l2"
+        normalises every (layer, pool) slice of D values on its own, so the cosine similarity of two flattened (n W) rows is the
+        mean of their per-slice cosines."""
+        return self._extract(images, self._arena, self._weights(), pool, normalize, with_cls, layers)
 
     def _extract(self, images: torch.Tensor, params: torch.Tensor, wcache: Optional[torch.Tensor], pool: str, normalize: str,
-                 with_cls: bool) -> torch.Tensor:
-        if pool not in FEATURE_POOLS:
-            raise ValueError(f"pool must be one of {sorted(FEATURE_POOLS)}, got {pool!r}")
+                 with_cls: bool, layers: Optional[Sequence[int]] = None) -> torch.Tensor:
+        pools = FEATURE_POOLS if layers is None else LAYER_FEATURE_POOLS
+        if pool not in pools:
+            raise ValueError(f"pool must be one of {sorted(pools)}, got {pool!r}" + (" ('cls_mean' needs layers=...)" if pool == "cls_mean" else ""))
         if normalize not in FEATURE_NORMS:
             raise ValueError(f"normalize must be one of {sorted(FEATURE_NORMS)}, got {normalize!r}")
-        if pool == "cls" and not with_cls:
-            raise ValueError("pool='cls' needs the class token (with_cls=True)")
+        if pool in ("cls", "cls_mean") and not with_cls:
+            raise ValueError(f"pool={pool!r} needs the class token (with_cls=True)")
+        if layers is not None:
+            layers = resolve_layers(layers, self._dims["depth"])
         dev = self._require_cuda()
         images = self._check_images(images.to(dev))
         B = images.shape[0]
@@ -634,6 +664,13 @@ class MaskedAutoencoder(nn.Module):
             self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
         self._plan = None
         self._gen_enc += 1; self._gen_dec += 1
+        if layers is not None:
+            n, W = len(layers), self._dims["embed_dim"] * (2 if pool == "cls_mean" else 1)
+            out = torch.empty(B, n, W, dtype=torch.float32, device=dev)
+            check(lib.mae_engine_extract_layer_features(self._engine.handle, _ptr(params), _ptr(wcache), _ptr(images), self._img_dt(images), B,
+                                                        int(bool(with_cls)), pools[pool], FEATURE_NORMS[normalize], (C.c_int32 * n)(*layers), n,
+                                                        _ptr(self._workspace), self._workspace.numel(), _ptr(out), _stream(dev)))
+            return out
         out = torch.empty(B, self._dims["embed_dim"], dtype=torch.float32, device=dev)
         check(lib.mae_engine_extract_features(self._engine.handle, _ptr(params), _ptr(wcache), _ptr(images), self._img_dt(images), B,
                                               int(bool(with_cls)), FEATURE_POOLS[pool], FEATURE_NORMS[normalize], _ptr(self._workspace),

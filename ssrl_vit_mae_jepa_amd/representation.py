@@ -22,6 +22,7 @@ from .mae import _ViT, _stream
 _ptr = _lib.ptr
 
 KNN_MAX_K = 256
+KNN_MAX_DIM = 4096  # columns mae_knn_topk takes
 DEFAULT_KS = (10, 20, 100, 200)
 
 
@@ -113,6 +114,43 @@ def parse_ks(text: Union[str, Iterable[int]]) -> Tuple[int, ...]:
     return tuple(sorted(set(vals)))
 
 
+def config_depth_dim(model_cfg: Dict[str, Any]) -> Tuple[int, int]:
+    """(depth, embed_dim) of the encoder a ``model`` config section builds, with the defaults of ``MaskedAutoencoder``: what the
+    evaluation tools need to check ``--layers`` before anything is loaded."""
+    enc = model_cfg.get("encoder", {}) or {}
+    return int(enc.get("depth", 12)), int(enc.get("embed_dim", 384))
+
+
+def parse_layers(spec: str, depth: int) -> Tuple[int, ...]:
+    """The ``--layers`` argument of the evaluation tools as block indices of an encoder of ``depth`` blocks, sorted:
+    ``"last"`` -> (depth - 1,); ``"lastN"`` -> the last N blocks (``"last4"``: DINO's ViT-S probe); ``"each"`` -> every block (the
+    per-layer curve); ``"2,5,-1"`` -> the blocks listed, negative ones from the end.  An unknown word, an index outside the model,
+    a repeat, or N outside [1, depth] raises ValueError."""
+    text = str(spec).strip().lower()
+    if depth < 1:
+        raise ValueError(f"depth must be positive, got {depth}")
+    if text == "each":
+        return tuple(range(depth))
+    if text.startswith("last"):
+        tail = text[4:]
+        if tail and not tail.isdigit():
+            raise ValueError(f"--layers {spec!r}: expected last, lastN, each or comma-separated block indices")
+        n = int(tail) if tail else 1
+        if not 1 <= n <= depth:
+            raise ValueError(f"--layers {spec!r}: the encoder has {depth} blocks")
+        return tuple(range(depth - n, depth))
+    try:
+        vals = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--layers {spec!r}: expected last, lastN, each or comma-separated block indices") from None
+    if any(not -depth <= v < depth for v in vals):
+        raise ValueError(f"--layers {spec!r}: block index outside the encoder's {depth} blocks")
+    out = sorted(v + depth if v < 0 else v for v in vals)
+    if len(set(out)) != len(out):
+        raise ValueError(f"--layers {spec!r}: a block is named twice")
+    return tuple(out)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # normalisation (scripts/evaluation/visualize_representation.py:99-115)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -163,10 +201,19 @@ class EvalEncoder:
             self.vit._owner().to(device)
         return self
 
-    def features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none") -> torch.Tensor:
+    @property
+    def depth(self) -> int:
+        """Number of encoder blocks: what ``layers`` indexes."""
+        model = self.ijepa.net if self.ijepa is not None else self.vit._owner()
+        return int(model._dims["depth"])
+
+    def features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none", layers: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """(B, D) pooled features of the last block, or with ``layers`` (block indices, ascending) (B, n, W) from one forward pass:
+        see ``MaskedAutoencoder.extract_features``.  normalize="l2" normalises every (layer, pool) slice on its own: the cosine
+        similarity of two flattened rows is then the mean of their per-slice cosines."""
         if self.ijepa is not None:
-            return self.ijepa.extract_features(images, encoder=self.encoder, pool=pool, normalize=normalize)
-        return self.vit.extract_features(images, pool=pool, normalize=normalize, with_cls=self.with_cls)
+            return self.ijepa.extract_features(images, encoder=self.encoder, pool=pool, normalize=normalize, layers=layers)
+        return self.vit.extract_features(images, pool=pool, normalize=normalize, with_cls=self.with_cls, layers=layers)
 
     def tokens(self, images: torch.Tensor, drop_cls: bool = True) -> torch.Tensor:
         """Every token after the final LayerNorm, (B, T, D) fp32: the patch rows, and with ``drop_cls=False`` the class row in front of
@@ -290,11 +337,12 @@ def load_ijepa_encoder(src: Union[str, Path, Dict[str, Any]], model_cfg: Dict[st
 
 @torch.no_grad()
 def extract_split_features(enc: EvalEncoder, batches, pool: str = "cls", normalize: str = "none",
-                           max_samples: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Features (n, D) fp32 and labels (n,) int64 of a ``LabeledBatches`` split, on the device, in the split's order."""
+                           max_samples: Optional[int] = None, layers: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Features (n, D) fp32 -- with ``layers`` (n, len(layers), W), see ``EvalEncoder.features`` -- and labels (n,) int64 of a
+    ``LabeledBatches`` split, on the device, in the split's order."""
     feats, labels, n = [], [], 0
     for imgs, lbls in batches():
-        feats.append(enc.features(imgs, pool=pool, normalize=normalize))
+        feats.append(enc.features(imgs, pool=pool, normalize=normalize, layers=layers))
         labels.append(lbls)
         n += imgs.shape[0]
         if max_samples is not None and n >= max_samples:

@@ -7,6 +7,9 @@
   * mae_knn_topk at (Q, N, D, k) = (8000, 5000, 384, 20 / 200) and (8000, 100000, 384, 20), alternated with torch.mm +
     torch.topk (a measurement-only baseline that materialises Q x N), with the achieved 2QND / t as a share of the
     157.3 TF fp32-MFMA peak.
+  * with --layers "SPEC;SPEC;..." (part `layers`): ViT-S/8 features after encoder blocks (mae_engine_extract_layer_features, one entry
+    per SPEC of representation.parse_layers, e.g. "each;5") alternated with the plain last-block call, and the tap kernel alone
+    (mae_features_tap next to mae_features_pool on the same buffers) with its bytes/s.
 Device events time `--steps` calls after `--warmup` calls; every number is the median of `--repeats` alternated runs.
 
     python tools/representation_bench.py --out profiles/r05_representation_bench.json
@@ -27,7 +30,9 @@ sys.path.insert(0, str(ROOT))
 
 from ssrl_vit_mae_jepa_amd.classifier import ViTClassifierTrainModule, encoder_mae  # noqa: E402
 from ssrl_vit_mae_jepa_amd.jepa import IJEPA  # noqa: E402
-from ssrl_vit_mae_jepa_amd.representation import knn_topk  # noqa: E402
+from ssrl_vit_mae_jepa_amd import _lib  # noqa: E402
+from ssrl_vit_mae_jepa_amd.mae import _ptr, _stream  # noqa: E402
+from ssrl_vit_mae_jepa_amd.representation import knn_topk, parse_layers  # noqa: E402
 
 FP32_MFMA_PEAK_TF = 157.3
 
@@ -100,6 +105,54 @@ def bench_ijepa(B: int, steps: int, warmup: int, repeats: int) -> dict:
     return res
 
 
+def bench_layers(specs, B: int, steps: int, warmup: int, repeats: int) -> dict:
+    """ViT-S/8, mean over the patch tokens: the plain call, one layers=... call per spec, and the pooling kernels alone."""
+    cfg_path = ROOT / "configs" / "vits8_dec192.yaml"
+    mc = model_cfg(cfg_path)
+    dev = torch.device("cuda", 0)
+    mae = encoder_mae(mc).to(dev)
+    depth, D, T = mae._dims["depth"], mae._dims["embed_dim"], mae.sequence_length
+    S = mc["general"]["image_size"]
+    images = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(0))
+    cases = [("extract_mean_patches", lambda: mae.extract_features(images, pool="mean"))]
+    layer_sets = {}
+    for spec in specs:
+        layers = parse_layers(spec, depth)
+        layer_sets[f"layers_{spec}"] = list(layers)
+        cases.append((f"layers_{spec}", lambda layers=layers: mae.extract_features(images, pool="mean", layers=layers)))
+        if mae.encoder.vit.with_cls:
+            cases.append((f"layers_{spec}_cls_mean", lambda layers=layers: mae.extract_features(images, pool="cls_mean", layers=layers)))
+    # the kernels alone, on buffers of the engine's shapes: x_mid fp32, the MLP branch in the activation type
+    bf = mae.engine.precision == "bf16"
+    g = torch.Generator(device=dev).manual_seed(3)
+    x = torch.randn(B, T, D, device=dev, generator=g)
+    br = torch.randn(B, T, D, device=dev, generator=g).to(torch.bfloat16 if bf else torch.float32)
+    gamma, beta = torch.randn(D, device=dev, generator=g), torch.randn(D, device=dev, generator=g)
+    out = torch.empty(B, 12, 2 * D, device=dev)
+    dt, st = (_lib.MAE_BF16 if bf else _lib.MAE_F32), _stream(dev)
+
+    def tap(pool, stride):
+        _lib.check(_lib.lib.mae_features_tap(_ptr(x), _ptr(br), dt, _ptr(gamma), _ptr(beta), 1e-6, B, T, D, 1, pool, 0, _ptr(out), stride, st))
+
+    def pool_kernel():
+        _lib.check(_lib.lib.mae_features_pool(_ptr(x), _ptr(br), dt, _ptr(gamma), _ptr(beta), 1e-6, B, T, D, 1, T, 0, _ptr(out), st))
+
+    cases += [("kernel_features_pool_mean_patches", pool_kernel),
+              ("kernel_features_tap_mean_patches", lambda: tap(_lib.POOL_MEAN_PATCHES, 12 * D)),
+              ("kernel_features_tap_cls_mean", lambda: tap(_lib.POOL_CLS_MEAN_PATCHES, 12 * 2 * D))]
+    ms, runs = alternate(cases, steps, warmup, repeats)
+    act = 2 if bf else 4
+    kernel_bytes = {"kernel_features_pool_mean_patches": B * ((T - 1) * D * (4 + act) + D * 4),
+                    "kernel_features_tap_mean_patches": B * ((T - 1) * D * (4 + act) + D * 4),
+                    "kernel_features_tap_cls_mean": B * (T * D * (4 + act) + 2 * D * 4)}
+    res = {"model": "vits8", "config": str(cfg_path.relative_to(ROOT)), "batch": B, "precision": mae.engine.precision, "pool": "mean",
+           "layers": layer_sets, "ms": ms, "ms_over_plain": {k: v - ms["extract_mean_patches"] for k, v in ms.items() if k.startswith("layers_")},
+           "kernel_bytes": kernel_bytes, "kernel_tb_per_s": {k: b / (ms[k] / 1e3) / 1e12 for k, b in kernel_bytes.items()}, "ms_all": runs}
+    del mae, x, br, out
+    torch.cuda.empty_cache()
+    return res
+
+
 def bench_topk(Q: int, N: int, D: int, k: int, steps: int, warmup: int, repeats: int) -> dict:
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(2)
@@ -126,6 +179,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--parts", default="extract,ijepa,topk")
+    ap.add_argument("--layers", default=None, help='part `layers`: ";"-separated layer specs, e.g. "each;5"')
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -137,6 +191,10 @@ def main(argv=None):
             out["extraction"].append(bench_extraction(name, path, args.batch, args.steps, args.warmup, args.repeats))
     if "ijepa" in parts:
         out["extraction"].append(bench_ijepa(args.batch, args.steps, args.warmup, args.repeats))
+    if "layers" in parts or args.layers:
+        if not args.layers:
+            ap.error("part `layers` needs --layers")
+        out["layers"] = bench_layers([t for t in args.layers.split(";") if t], args.batch, args.steps, args.warmup, args.repeats)
     if "topk" in parts:
         for shape in ((8000, 5000, 384, 20), (8000, 5000, 384, 200), (8000, 100_000, 384, 20)):
             out["topk"].append(bench_topk(*shape, args.steps, args.warmup, args.repeats))
