@@ -514,6 +514,24 @@ int mae_engine_extract_tokens(mae_engine_t* e, const float* params, const void* 
                               int32_t batch, int32_t with_cls, int32_t drop_cls, void* workspace, int64_t workspace_bytes,
                               float* tokens, void* stream);
 
+/* Attention maps of the frozen encoder (additive in ABI v4): ONE forward pass that stops after block
+ * layers[num_layers - 1], then mae_attention_colsum (below) over the blocks' saved qkv.  P_l,h = the attention probabilities of
+ * head h of block l, (T, T), rows = queries.
+ *   query: MAE_ATTN_QUERY_CLS (with_cls = 1 only): the start weight w is the class row e_0, a map is the class token's attention row
+ *          (DINO's maps); MAE_ATTN_QUERY_MEAN: w = 1 / T in every column, a map is the mean attention each token receives.
+ *   layers: HOST array as for mae_engine_extract_layer_features: strictly ascending, each in [0, depth); 1 <= num_layers <= depth.
+ *   maps:    (batch, num_layers, H, T) fp32 or NULL: maps[b][i][h][j] = sum_t w[t] P_layers[i],h[t][j]; every (b, i, h) row sums to 1.
+ *   rollout: (batch, T) fp32 or NULL (not both): row w A_top ... A_0 of attention rollout, A_l = (mean_h P_l,h + I) / 2,
+ *            top = layers[num_layers - 1], down to block 0 whatever else layers names; computed as a chain of vector-matrix steps.
+ * T = N + with_cls must not exceed mae_attention_colsum_max_tokens(head_dim, act dtype); head_dim and the head count within that
+ * call's limits.  maps and rollout 16-byte aligned.  Workspace: mae_engine_attention_workspace_bytes = the features workspace.
+ * Every refusal comes before any launch; results are bit-identical from run to run and an image's do not depend on its batch. */
+enum { MAE_ATTN_QUERY_CLS = 0, MAE_ATTN_QUERY_MEAN = 1 };
+int64_t mae_engine_attention_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls);
+int mae_engine_extract_attention(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                 int32_t batch, int32_t with_cls, int32_t query, const int32_t* layers, int32_t num_layers, float* maps,
+                                 float* rollout, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* MAE reconstruction (additive in ABI v4; scripts/evaluation/visualize_reconstruction.py of the reference, MAEReconstructor):
  * the inverse of mae_patchify_gather, fused with the whole-image error sums.  One pass over the OUTPUT pixels produces up to
  * three results from images (batch, C, S, S) in image_dtype (MAE_F32 normalised | MAE_U8 raw pixels, normalised in the read),
@@ -765,6 +783,22 @@ int mae_attention_fwd(const void* qkv, int32_t batch, int32_t T, int32_t H, int3
                       float* lse, void* stream);
 int mae_attention_bwd(const void* qkv, const void* out, const void* d_out, const float* lse, int32_t batch,
                       int32_t T, int32_t H, int32_t hd, int32_t dtype, void* d_qkv, void* stream);
+
+/* Weighted column sum of the attention probabilities of one block, from its qkv (layout as above; V is not read):
+ *     P_b,h[t][j] = softmax_j(hd^-1/2 q_t . k_j)
+ *     per_head[b * per_head_stride + h * T + j] = sum_t row_weight[b][t] P_b,h[t][j]              (fp32; stride in floats)
+ *     mixed[b][j] = row_weight[b][j] / 2 + (1 / (2 H)) sum_h per_head[b][h][j]                    ((batch, T) fp32: one rollout step)
+ *   Either output may be NULL, not both; each holds the same bits whether or not the other is asked for.  mixed must not overlap
+ *   row_weight.  All arithmetic is fp32: scores by fused multiply-adds over d in index order, the row maximum subtracted before the
+ *   exponential, every row divided by its own sum (no saved log-sum-exp).  A row whose weight is exactly 0 is skipped and its q is
+ *   not read.  No atomics: every sum has an order fixed by the shape, and an image's result does not depend on its batch.
+ *   Limits (checked before the launch; a refused call writes nothing): hd in {16, 24, 32, 48, 64}; 1 <= H <= 16; batch * T < 2^31;
+ *   T <= mae_attention_colsum_max_tokens(hd, dtype) (what the LDS layout of the keys allows: 512 for every supported pair; -1 for an
+ *   unsupported one); qkv, row_weight and mixed 16-byte aligned; per_head a float pointer with per_head_stride >= H * T, so that a
+ *   slice of a (batch, n, H, T) buffer can be written in place whatever H * T is. */
+int32_t mae_attention_colsum_max_tokens(int32_t hd, int32_t dtype);
+int mae_attention_colsum(const void* qkv, int32_t dtype, int32_t batch, int32_t T, int32_t H, int32_t hd, const float* row_weight,
+                         float* per_head, int64_t per_head_stride, float* mixed, void* stream);
 
 /* Token and pixel movement between those pieces, and the losses that read the image.  Index arguments are int32, as the kernels
  * take them; token id 0 is the class token, id t >= 1 is patch t - 1 (row-major over the patch grid).  Unless a function says

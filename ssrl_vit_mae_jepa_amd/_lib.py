@@ -19,6 +19,7 @@ PARAM_TRAINABLE, PARAM_FROZEN, PARAM_UNUSED, PARAM_MATRIX = 1, 2, 4, 8
 LOSS_MSE, LOSS_SMOOTH_L1 = 0, 1
 POOL_CLS, POOL_MEAN, POOL_MEAN_PATCHES, POOL_CLS_MEAN_PATCHES = 0, 1, 2, 3
 FEAT_NONE, FEAT_L2 = 0, 1
+ATTN_QUERY_CLS, ATTN_QUERY_MEAN = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL, EPI_GELU_ACT = 0, 1, 2, 3, 4, 5, 6
 AUG_NONE, AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_INVERT, AUG_POSTERIZE, AUG_SOLARIZE, AUG_SOLARIZE_ADD, AUG_COLOR, AUG_CONTRAST, AUG_BRIGHTNESS, \
     AUG_SHARPNESS, AUG_AFFINE = range(12)
@@ -150,6 +151,8 @@ SIGNATURES = {
     "mae_attn_probe_project_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "mae_engine_tokens_workspace_bytes": (_i64, [_vp, _i32, _i32]),
     "mae_engine_extract_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "mae_engine_attention_workspace_bytes": (_i64, [_vp, _i32, _i32]),
+    "mae_engine_extract_attention": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _pp(_i32), _i32, _vp, _vp, _vp, _i64, _vp]),
     "mae_linear_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mae_linear_wgrad_scratch_bytes": (_i64, [_i64, _i32, _i32]),
     "mae_linear_wgrad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -157,6 +160,8 @@ SIGNATURES = {
     "mae_linear_wgrad_pair": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
     "mae_attention_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mae_attention_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mae_attention_colsum_max_tokens": (_i32, [_i32, _i32]),
+    "mae_attention_colsum": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
     "mae_gather_patches": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mae_assemble_visible": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "mae_visible_grad_split": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),

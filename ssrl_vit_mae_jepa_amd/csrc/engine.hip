@@ -252,6 +252,7 @@ struct Ctx {
   const int32_t* tap_layers = nullptr;
   int tap_n = 0, tap_with_cls = 1, tap_pool = MAE_POOL_CLS, tap_normalize = MAE_FEAT_NONE;
   float* tap_out = nullptr;
+  int stop_after = -1;  // mae_engine_extract_attention alone: the encoder stops after this block, as it does after the last tap
   const float* branch_scale = nullptr;  // drop path (classifier training only): (2 * depth, batch) per-image scales of the encoder's branches
   // row j of the table (row 2i: attention branch of encoder block i, 2i + 1: its MLP branch), or null without a table
   const float* scale_row(int j, int batch) const { return branch_scale ? branch_scale + (int64_t)j * batch : nullptr; }
@@ -266,7 +267,7 @@ struct Ctx {
   template <class T = void> T* buf(int64_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
 
-// the one place a Ctx is built; `ready` / `fwd_only` / `skip_final_norm` / the taps are set by the few callers that need them
+// the one place a Ctx is built; `ready` / `fwd_only` / `skip_final_norm` / the taps / `stop_after` are set by the few callers that need them
 static Ctx make_ctx(mae_engine* e, const float* params, const void* wcache, float* grads, void* ws, void* stream) {
   return Ctx{e, params, (const char*)wcache, grads, (char*)ws, (hipStream_t)stream, e->act, (int64_t)dtype_size(e->act)};
 }
@@ -451,13 +452,13 @@ static int forward_encoder_impl(const Ctx& c, const Plan& pl, const void* images
   RUN(TK_DATA, 0, gather_read + pl.Me * e->P * c.as, launch_gather_patches(images, img_dt, keep32, pl.B, pl.k, e->C, e->img, e->p, c.act, c.buf<>(pl.patchA), s));
   MAE_TRY(linear(c, c.buf<>(pl.patchA), e->i_patch_w, e->i_patch_b, pl.Me, e->D, e->P, MAE_EPI_NONE, MAE_F32, c.buf<>(pl.enc_x[0]), nullptr, nullptr));
   RUN(TK_DATA, 0, pl.Me * e->D * 12, launch_assemble_visible(c.buf<float>(pl.enc_x[0]), keep32, c.P(e->i_cls), c.P(e->i_pos), pl.Me, e->D, s));
-  const int blocks = c.tap_n ? c.tap_layers[c.tap_n - 1] + 1 : e->depth;
+  const int blocks = c.tap_n ? c.tap_layers[c.tap_n - 1] + 1 : c.stop_after >= 0 ? c.stop_after + 1 : e->depth;
   for (int i = 0, slot = 0; i < blocks; ++i) {
     MAE_TRY(block_forward(c, pl, e->enc[i], pl.enc[i], pl.Me, e->D, e->H, pl.B, pl.k, i ? pl.enc[i - 1].x_mid : 0, i > 0, pl.enc_x[i],
                           i ? c.scale_row(2 * i - 1, pl.B) : nullptr, c.scale_row(2 * i, pl.B)));
     if (slot < c.tap_n && c.tap_layers[slot] == i) MAE_TRY(tap_block(c, pl, i, slot++));
   }
-  if (c.skip_final_norm || c.tap_n) return 0;
+  if (c.skip_final_norm || c.tap_n || c.stop_after >= 0) return 0;
   MAE_TRY(ln_fwd(c, c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w),
                  c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, c.act, c.buf<>(pl.enc_norm), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd),
                  c.scale_row(2 * e->depth - 1, pl.B), pl.k));
@@ -1394,6 +1395,77 @@ extern "C" int mae_engine_extract_layer_features(mae_engine_t* e, const float* p
   c.tap_layers = layers; c.tap_n = num_layers; c.tap_with_cls = with_cls; c.tap_pool = pool; c.tap_normalize = normalize; c.tap_out = feats;
   MAE_TRY(keep_every_token(c, pl, with_cls != 0));
   return forward_encoder_impl(c, pl, images, image_dtype, nullptr);
+}
+
+// =====================================================================================================
+// Attention maps.  A forward-only pass keeps every block's qkv in the workspace (pl.enc[i].qkv), so after a forward
+// that stops at the highest block named the maps are column sums of the attention probabilities (k_attnmap.hip) over those buffers:
+// the query's start weight w (the class row, or 1 / T) gives maps[:, i] from block layers[i], and the rollout row is the chain
+// r <- r / 2 + mean_h S_h(r) / 2 from the top block down to block 0.  Two (batch, T) weight rows ping-pong in pl.dres, which only a
+// backward pass uses; the last step writes the caller's buffer.
+// =====================================================================================================
+extern "C" int64_t mae_engine_attention_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls) {
+  return mae_engine_features_workspace_bytes(e, batch, with_cls);
+}
+
+// One colsum launch over block l.  `dense` says whether every row of w may be non-zero (the kernel skips the zero rows of a one-hot
+// start weight).  Flops: the scores and the weighted sum of the rows that run; bytes: K once, those rows of q, w, the outputs.
+static int attention_colsum(const Ctx& c, const Plan& pl, int l, const float* w, bool dense, float* per_head, int64_t stride, float* mixed) {
+  mae_engine* e = c.e; hipStream_t s = c.s;
+  const int T = pl.k, hd = e->D / e->H;
+  const double rows = dense ? T : 1, BH = (double)pl.B * e->H;
+  RUN(TK_ATTN_FWD, BH * rows * T * (2.0 * hd + 6), BH * (T + rows) * hd * c.as + (double)pl.B * T * 4 * (1 + (mixed ? 1 : 0) + (per_head ? e->H : 0)),
+      launch_attention_colsum(c.buf<>(pl.enc[l].qkv), e->act, pl.B, T, e->H, hd, w, per_head, stride, mixed, s));
+  return 0;
+}
+
+extern "C" int mae_engine_extract_attention(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                            int32_t batch, int32_t with_cls, int32_t query, const int32_t* layers, int32_t num_layers,
+                                            float* maps, float* rollout, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "mae_engine_extract_attention";
+  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
+  MAE_REQUIRE(images && layers && (maps || rollout), "%s: null argument (images, layers, or both of maps and rollout)", who);
+  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+  MAE_REQUIRE(query == MAE_ATTN_QUERY_CLS || query == MAE_ATTN_QUERY_MEAN, "%s: query must be MAE_ATTN_QUERY_CLS or MAE_ATTN_QUERY_MEAN (got %d)", who, query);
+  MAE_REQUIRE(query != MAE_ATTN_QUERY_CLS || with_cls == 1, "%s: query MAE_ATTN_QUERY_CLS needs with_cls = 1", who);
+  MAE_TRY(check_image_dtype(image_dtype, who));
+  MAE_REQUIRE(num_layers >= 1 && num_layers <= e->depth, "%s: num_layers = %d outside [1, depth = %d]", who, num_layers, e->depth);
+  for (int i = 0; i < num_layers; ++i) {
+    MAE_REQUIRE(layers[i] >= 0 && layers[i] < e->depth, "%s: layers[%d] = %d outside [0, depth = %d)", who, i, layers[i], e->depth);
+    MAE_REQUIRE(i == 0 || layers[i] > layers[i - 1], "%s: layers must be strictly ascending (layers[%d] = %d after %d)", who, i, layers[i], layers[i - 1]);
+  }
+  MAE_REQUIRE(((uintptr_t)maps & 15) == 0 && ((uintptr_t)rollout & 15) == 0, "%s: maps and rollout must be 16-byte aligned", who);
+  const int64_t need = mae_engine_attention_workspace_bytes(e, batch, with_cls);
+  MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
+  MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
+  const Plan pl = make_encoder_plan(e, batch, with_cls != 0);
+  const int T = pl.k, H = e->H, hd = e->D / H;
+  // the colsum launcher's own limits, so that no forward runs for a call it would refuse
+  const int max_t = attention_colsum_max_tokens(hd, e->act);
+  MAE_REQUIRE(max_t > 0 && H <= 16, "%s: head_dim %d (16, 24, 32, 48, 64) / %d heads (at most 16) unsupported", who, hd, H);
+  MAE_REQUIRE(T >= 1 && T <= max_t, "%s: the sequence of %d tokens is outside the map kernel's [1, %d] at head_dim %d", who, T, max_t, hd);
+  MAE_REQUIRE(pl.Me < (1ll << 31), "%s: batch * T = %lld must stay below 2^31", who, (long long)pl.Me);
+  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  c.fwd_only = true;
+  const int top = layers[num_layers - 1];
+  c.stop_after = top;
+  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
+  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
+  float* r[2] = {c.buf<float>(pl.dres), c.buf<float>(pl.dres) + round_up(pl.Me, 4)};   // plan buffers are at least 256 bytes: both fit
+  hipStream_t s = c.s;
+  RUN(TK_DATA, 0, pl.Me * 4, launch_attention_weight_fill(r[0], batch, T, query == MAE_ATTN_QUERY_CLS ? 0 : -1, s));
+  const bool dense0 = query != MAE_ATTN_QUERY_CLS;
+  const int64_t stride = (int64_t)num_layers * H * T;
+  // the last map is block `top`, the chain's first step: that launch writes both
+  float* first = !rollout ? nullptr : top == 0 ? rollout : r[1];
+  for (int i = 0; i < num_layers; ++i) {
+    float* ph = maps ? maps + (int64_t)i * H * T : nullptr;
+    float* mx = i == num_layers - 1 ? first : nullptr;
+    if (ph || mx) MAE_TRY(attention_colsum(c, pl, layers[i], r[0], dense0, ph, stride, mx));
+  }
+  for (int l = top - 1, cur = 1; rollout && l >= 0; --l, cur ^= 1)
+    MAE_TRY(attention_colsum(c, pl, l, r[cur], true, nullptr, 0, l == 0 ? rollout : r[cur ^ 1]));
+  return 0;
 }
 
 // mae_engine_extract_features without the pool: the same encoder forward, then the last residual add and the final LayerNorm in fp32

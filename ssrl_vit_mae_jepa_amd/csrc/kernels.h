@@ -342,5 +342,13 @@ int launch_linear_wgrad_pair(const void* dY0, const void* A0, int N0, int K0, fl
 int launch_attention_fwd(const void* qkv, int B, int T, int H, int hd, int dt, void* out, float* lse, hipStream_t s);
 int launch_attention_bwd(const void* qkv, const void* out, const void* d_out, const float* lse, int B, int T, int H,
                          int hd, int dt, void* d_qkv, hipStream_t s);
+// Attention maps (k_attnmap.hip) from a block's qkv (B, T, 3, H, hd): per_head + b * per_head_stride + h * T + j = sum_t w[b,t] P_{b,h}[t,j]
+// and / or mixed[b,j] = w[b,j] / 2 + sum_h per_head[b,h,j] / (2 H), one rollout step; fp32, fixed orders, no atomics.  Every limit
+// (T <= attention_colsum_max_tokens, -1 for an unsupported hd / dtype) is checked before the launch.
+int attention_colsum_max_tokens(int hd, int dt);
+int launch_attention_colsum(const void* qkv, int dt, int B, int T, int H, int hd, const float* w, float* per_head, int64_t per_head_stride,
+                            float* mixed, hipStream_t s);
+// w (B, T) = row `row` of the identity in every image, or 1 / T everywhere for row < 0
+int launch_attention_weight_fill(float* w, int B, int T, int row, hipStream_t s);
 
 }  // namespace mae

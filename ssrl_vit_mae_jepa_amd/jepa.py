@@ -264,6 +264,21 @@ class IJEPA(nn.Module):
         return net._extract_tokens(images, net.flat_params, net._weights(), False, False)
 
     @torch.no_grad()
+    def extract_attention(self, images: torch.Tensor, encoder: str = "target", layers: Sequence[int] = (-1,), query: str = "mean",
+                          rollout: bool = False):
+        """Attention maps (B, n, H, N) of the EMA target encoder (``encoder="target"``) or the context encoder over the patch tokens:
+        ``MaskedAutoencoder.extract_attention`` with with_cls=False.  query "mean" (the only one: there is no class token) = the mean
+        attention each patch receives; rollout=True adds the (B, N) rollout of that query."""
+        if encoder not in ("target", "context"):
+            raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
+        if query != "mean":
+            raise ValueError(f"I-JEPA encoders see no class token: query must be 'mean', got {query!r}")
+        net = self.net
+        if encoder == "target":
+            return net._extract_attention(images, self.target_arena, self._target_weights(), layers, query, False, rollout)
+        return net._extract_attention(images, net.flat_params, net._weights(), layers, query, False, rollout)
+
+    @torch.no_grad()
     def target_features(self, images: torch.Tensor, idx_target: torch.Tensor) -> torch.Tensor:
         """layer_norm(target_encoder(images))[target blocks]: (B, nblk, m, D) fp32 (no gradient, nothing else computed)."""
         net = self.net

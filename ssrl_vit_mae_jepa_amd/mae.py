@@ -207,12 +207,19 @@ class _ViT(_Node):
         """Every token of the frozen encoder: ``MaskedAutoencoder.extract_tokens``."""
         return self._owner().extract_tokens(images, with_cls=with_cls, drop_cls=drop_cls)
 
+    def extract_attention(self, images: torch.Tensor, layers: Sequence[int] = (-1,), query: str = "cls", with_cls: bool = True,
+                          rollout: bool = False):
+        """Attention maps of the frozen encoder: ``MaskedAutoencoder.extract_attention``."""
+        return self._owner().extract_attention(images, layers=layers, query=query, with_cls=with_cls, rollout=rollout)
+
 
 # extract_features pool names: "mean" averages the patch tokens (visualize_representation.py:94), "mean_all" every token (the classifier)
 FEATURE_POOLS = {"cls": _lib.POOL_CLS, "mean": _lib.POOL_MEAN_PATCHES, "mean_all": _lib.POOL_MEAN}
 FEATURE_NORMS = {"none": _lib.FEAT_NONE, "l2": _lib.FEAT_L2}
 # with layers=...: also "cls_mean" = [class token | mean over the patch tokens], twice as wide (DINO's ViT-B linear-probe input)
 LAYER_FEATURE_POOLS = dict(FEATURE_POOLS, cls_mean=_lib.POOL_CLS_MEAN_PATCHES)
+# extract_attention queries: "cls" = the class token's attention row, "mean" = the mean attention every token receives
+ATTENTION_QUERIES = {"cls": _lib.ATTN_QUERY_CLS, "mean": _lib.ATTN_QUERY_MEAN}
 
 
 def resolve_layers(layers: Sequence[int], depth: int) -> Tuple[int, ...]:
@@ -676,6 +683,53 @@ class MaskedAutoencoder(nn.Module):
                                               int(bool(with_cls)), FEATURE_POOLS[pool], FEATURE_NORMS[normalize], _ptr(self._workspace),
                                               self._workspace.numel(), _ptr(out), _stream(dev)))
         return out
+
+    @torch.no_grad()
+    def extract_attention(self, images: torch.Tensor, layers: Sequence[int] = (-1,), query: str = "cls", with_cls: bool = True,
+                          rollout: bool = False):
+        """Where the encoder looks: attention maps (B, n, H, T) fp32 of the blocks ``layers`` (as in ``extract_features``), one per
+        head, from ONE forward pass that stops after the highest block named; no autograd graph.  query "cls": the class token's
+        attention row (DINO's maps; needs with_cls=True); "mean": the mean over the queries of the attention each token receives (what
+        an encoder without a class token offers).  Every (image, block, head) row sums to 1 over the T keys, T = N + 1 [cls | patches]
+        or the N patches with with_cls=False.  rollout=True returns (maps, rollout): rollout (B, T) is the query's row of attention
+        rollout (Abnar & Zuidema 2020) from block layers[-1] down to the input, with the head mean and half the identity per block;
+        it sums to 1.  ``representation.attention_grid`` turns either into patch grids."""
+        return self._extract_attention(images, self._arena, self._weights(), layers, query, with_cls, rollout)
+
+    def _extract_attention(self, images: torch.Tensor, params: torch.Tensor, wcache: Optional[torch.Tensor], layers: Sequence[int],
+                           query: str, with_cls: bool, rollout: bool):
+        if query not in ATTENTION_QUERIES:
+            raise ValueError(f"query must be one of {sorted(ATTENTION_QUERIES)}, got {query!r}")
+        with_cls = bool(with_cls)
+        if query == "cls" and not with_cls:
+            raise ValueError("query='cls' needs the class token (with_cls=True)")
+        layers = resolve_layers(layers, self._dims["depth"])
+        H = self._dims["num_heads"]
+        T = self.sequence_length - (0 if with_cls else 1)
+        limit = lib.mae_attention_colsum_max_tokens(self._dims["embed_dim"] // H, self._engine.act)
+        if limit < 0 or H > 16:
+            raise ValueError(f"attention maps need a head width of 16, 24, 32, 48 or 64 and at most 16 heads (got {self._dims['embed_dim'] // H}, {H})")
+        if T > limit:
+            raise ValueError(f"attention maps take sequences of at most {limit} tokens (this encoder has {T})")
+        dev = self._require_cuda()
+        images = self._check_images(images.to(dev))
+        B = images.shape[0]
+        need = lib.mae_engine_attention_workspace_bytes(self._engine.handle, B, int(with_cls))
+        if need < 0:
+            raise ValueError(f"bad batch {B}")
+        # the module's workspace is reused: whatever a pending backward saved in it is gone
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._plan = None
+        self._gen_enc += 1; self._gen_dec += 1
+        n = len(layers)
+        maps = torch.empty(B, n, H, T, dtype=torch.float32, device=dev)
+        roll = torch.empty(B, T, dtype=torch.float32, device=dev) if rollout else None
+        check(lib.mae_engine_extract_attention(self._engine.handle, _ptr(params), _ptr(wcache), _ptr(images), self._img_dt(images), B, int(with_cls),
+                                               ATTENTION_QUERIES[query], (C.c_int32 * n)(*layers), n, _ptr(maps), _ptr(roll),
+                                               _ptr(self._workspace), self._workspace.numel(), _stream(dev)))
+        return (maps, roll) if rollout else maps
 
     @torch.no_grad()
     def extract_tokens(self, images: torch.Tensor, with_cls: bool = True, drop_cls: bool = True) -> torch.Tensor:

@@ -151,6 +151,20 @@ def parse_layers(spec: str, depth: int) -> Tuple[int, ...]:
     return tuple(out)
 
 
+def attention_grid(maps: torch.Tensor, with_cls: bool, grid: int) -> torch.Tensor:
+    """Attention maps or a rollout, (..., T) over the keys, as patch grids (..., grid, grid): the class column (the first, with
+    ``with_cls``) is dropped, the patch columns are renormalised to sum 1 and laid out row-major as the patches are.  A row whose
+    whole mass sits on the class key has no patch map and raises."""
+    n = int(grid) * int(grid)
+    if grid < 1 or maps.dim() < 1 or maps.shape[-1] != n + (1 if with_cls else 0):
+        raise ValueError(f"expected (..., {n + (1 if with_cls else 0)}) keys for a {grid} x {grid} grid (with_cls={bool(with_cls)}), got {tuple(maps.shape)}")
+    patches = maps[..., 1:] if with_cls else maps
+    total = patches.sum(dim=-1, keepdim=True)
+    if not bool((total > 0).all()):
+        raise ValueError("a map puts no attention on the patch keys")
+    return (patches / total).reshape(*maps.shape[:-1], grid, grid)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # normalisation (scripts/evaluation/visualize_representation.py:99-115)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -221,6 +235,14 @@ class EvalEncoder:
         if self.ijepa is not None:
             return self.ijepa.extract_tokens(images, encoder=self.encoder)
         return self.vit.extract_tokens(images, with_cls=self.with_cls, drop_cls=drop_cls)
+
+    def attention(self, images: torch.Tensor, layers: Sequence[int] = (-1,), query: Optional[str] = None, rollout: bool = False):
+        """Attention maps (B, n, H, T) fp32 of the blocks ``layers`` and, with ``rollout``, the (B, T) rollout behind them: see
+        ``MaskedAutoencoder.extract_attention``.  query defaults to "cls" where the encoder has a class token, else "mean"."""
+        query = ("cls" if self.with_cls else "mean") if query is None else query
+        if self.ijepa is not None:
+            return self.ijepa.extract_attention(images, encoder=self.encoder, layers=layers, query=query, rollout=rollout)
+        return self.vit.extract_attention(images, layers=layers, query=query, with_cls=self.with_cls, rollout=rollout)
 
     @property
     def num_heads(self) -> int:

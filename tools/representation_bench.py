@@ -10,6 +10,10 @@
   * with --layers "SPEC;SPEC;..." (part `layers`): ViT-S/8 features after encoder blocks (mae_engine_extract_layer_features, one entry
     per SPEC of representation.parse_layers, e.g. "each;5") alternated with the plain last-block call, and the tap kernel alone
     (mae_features_tap next to mae_features_pool on the same buffers) with its bytes/s.
+  * part `attention`: ViT-S/8 attention maps (mae_engine_extract_attention) of the last block, of every block, and of the last block
+    with rollout, alternated with the plain extract_features call; and the map kernel alone (mae_attention_colsum) with a dense and with
+    a one-hot weight row on a random qkv of the engine's shape, next to the forward attention kernel (mae_attention_fwd) on the same
+    qkv, with its flops/s and bytes/s.
 Device events time `--steps` calls after `--warmup` calls; every number is the median of `--repeats` alternated runs.
 
     python tools/representation_bench.py --out profiles/r05_representation_bench.json
@@ -153,6 +157,53 @@ def bench_layers(specs, B: int, steps: int, warmup: int, repeats: int) -> dict:
     return res
 
 
+def bench_attention(B: int, steps: int, warmup: int, repeats: int) -> dict:
+    """ViT-S/8: extract_attention next to extract_features, and the colsum kernel next to the forward attention kernel."""
+    cfg_path = ROOT / "configs" / "vits8_dec192.yaml"
+    mc = model_cfg(cfg_path)
+    dev = torch.device("cuda", 0)
+    mae = encoder_mae(mc).to(dev)
+    depth, D, H, T = mae._dims["depth"], mae._dims["embed_dim"], mae._dims["num_heads"], mae.sequence_length
+    hd, S = D // H, mc["general"]["image_size"]
+    images = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(0))
+    cases = [("extract_cls", lambda: mae.extract_features(images, pool="cls")),
+             ("attention_last", lambda: mae.extract_attention(images)),
+             ("attention_each", lambda: mae.extract_attention(images, layers=range(depth))),
+             ("attention_last_rollout", lambda: mae.extract_attention(images, rollout=True)),
+             ("attention_last_mean_query", lambda: mae.extract_attention(images, query="mean"))]
+    bf = mae.engine.precision == "bf16"
+    g = torch.Generator(device=dev).manual_seed(3)
+    qkv = torch.randn(B, T, 3 * D, device=dev, generator=g).to(torch.bfloat16 if bf else torch.float32)
+    dense = torch.full((B, T), 1.0 / T, device=dev)
+    onehot = torch.zeros(B, T, device=dev)
+    onehot[:, 0] = 1.0
+    per_head, mixed = torch.empty(B, H, T, device=dev), torch.empty(B, T, device=dev)
+    att, lse = torch.empty(B, T, D, device=dev, dtype=qkv.dtype), torch.empty(B, H, T, device=dev)
+    dt, st = (_lib.MAE_BF16 if bf else _lib.MAE_F32), _stream(dev)
+
+    def colsum(w):
+        _lib.check(_lib.lib.mae_attention_colsum(_ptr(qkv), dt, B, T, H, hd, _ptr(w), _ptr(per_head), H * T, _ptr(mixed), st))
+
+    def attention_fwd():
+        _lib.check(_lib.lib.mae_attention_fwd(_ptr(qkv), B, T, H, hd, dt, _ptr(att), _ptr(lse), st))
+
+    cases += [("kernel_attention_fwd", attention_fwd), ("kernel_colsum_dense", lambda: colsum(dense)), ("kernel_colsum_onehot", lambda: colsum(onehot))]
+    ms, runs = alternate(cases, steps, warmup, repeats)
+    act = 2 if bf else 4
+    out_bytes = B * T * 4 * (2 + H)
+    work = {"kernel_attention_fwd": dict(flops=4.0 * B * H * T * T * hd, bytes=B * T * 4 * D * act + B * H * T * 4),
+            "kernel_colsum_dense": dict(flops=B * H * T * T * (2.0 * hd + 6), bytes=B * 2 * T * D * act + out_bytes),
+            "kernel_colsum_onehot": dict(flops=B * H * T * (2.0 * hd + 6), bytes=B * (T + 1) * D * act + out_bytes)}
+    res = {"model": "vits8", "config": str(cfg_path.relative_to(ROOT)), "batch": B, "precision": mae.engine.precision, "shape": [B, T, H, hd],
+           "ms": ms, "ms_over_extract_cls": {k: v - ms["extract_cls"] for k, v in ms.items() if k.startswith("attention_")},
+           "kernel_over_attention_fwd": {k: ms[k] / ms["kernel_attention_fwd"] for k in work},
+           "kernel_work": work, "kernel_tflops": {k: w["flops"] / (ms[k] / 1e3) / 1e12 for k, w in work.items()},
+           "kernel_tb_per_s": {k: w["bytes"] / (ms[k] / 1e3) / 1e12 for k, w in work.items()}, "ms_all": runs}
+    del mae, qkv, att
+    torch.cuda.empty_cache()
+    return res
+
+
 def bench_topk(Q: int, N: int, D: int, k: int, steps: int, warmup: int, repeats: int) -> dict:
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(2)
@@ -195,6 +246,8 @@ def main(argv=None):
         if not args.layers:
             ap.error("part `layers` needs --layers")
         out["layers"] = bench_layers([t for t in args.layers.split(";") if t], args.batch, args.steps, args.warmup, args.repeats)
+    if "attention" in parts:
+        out["attention"] = bench_attention(args.batch, args.steps, args.warmup, args.repeats)
     if "topk" in parts:
         for shape in ((8000, 5000, 384, 20), (8000, 5000, 384, 200), (8000, 100_000, 384, 20)):
             out["topk"].append(bench_topk(*shape, args.steps, args.warmup, args.repeats))
