@@ -708,6 +708,44 @@ int mae_lars_step(float* params, const float* grads, float* mu, int64_t count, i
 int mae_batchnorm_stats(const float* x, int64_t rows, int32_t dim, float eps, int32_t training, float momentum, float* running_mean,
                         float* running_var, float* mean_out, float* rstd_out, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* The linear-probe sweep (additive in ABI v4; no reference counterpart): the G heads of a learning-rate /
+ * weight-decay grid on the same BatchNorm output in one pass.  BatchNorm1d(affine=False) has no per-head state, so one
+ * mae_batchnorm_fwd serves every head, and the heads are two GEMMs on the exact-fp32 MFMA over the stacked class index (g, c).
+ *
+ * mae_probe_sweep_head: y (rows, dim) fp32; heads = num_heads stacked buffers of HF = round_up(C * dim + C, 4) floats, each
+ *   [W (C, dim) | b (C) | zero padding], the layout mae_classifier_head reads.  Per head g the call is mae_classifier_head on fp32 rows
+ *   with seq_len = 1, MAE_POOL_CLS and grad_scale = 1:
+ *     logits[g][b][c] = sum_d y[b][d] W_g[c][d] + b_g[c];  loss_out[g] = mean_b (logsumexp_c logits - logits[label]);
+ *     correct_out[g] = #{b : argmax_c logits == label} (the first index among equal maxima);
+ *     head_grads[g] = [dW = dlogits^T y | db = sum_b dlogits | zeros], dlogits = (softmax - onehot(label)) / rows.
+ *   A label outside [0, C) is treated as mae_classifier_head's kernel treats it: it is never used as an index, the row's loss and
+ *   its row of dlogits are NaN (so loss_out[g] and head g's gradients are NaN for every head) and the row does not count as correct.
+ *   labels == NULL: logits only (logits is then required; loss_out / correct_out / head_grads are not written).
+ *   head_grads == NULL: the evaluation call, nothing is written there.  logits == NULL: the logits stay in the scratch.
+ *   The bits of head g's logits, loss, correct count and gradients do not depend on num_heads or on g's position in the stack: every
+ *   output element is one fmaf chain whose order is fixed by (rows, dim) alone -- the forward walks dim in the order 0, 4, 1, 5, 2, 6,
+ *   3, 7, 8, 12, ...; the weight gradient walks the rows of min(ceil(rows / 128), 16) batch slices [rows s / S, rows (s + 1) / S) in
+ *   ascending order and the slices are added in order.  No atomics; a call is bit-identical from run to run.
+ *   Limits, checked before any launch (a refused call launches nothing and writes nothing): dim % 4 == 0, 4 <= dim <= 1024;
+ *   2 <= num_classes <= 128; 1 <= num_heads <= 64; rows >= 1, rows * num_heads * num_classes < 2^31; every buffer 16-byte aligned;
+ *   labels come with loss_out and correct_out, head_grads with labels; scratch_bytes >= mae_probe_sweep_scratch_bytes (-1 = outside
+ *   the limits).
+ * mae_lars_step_groups: mae_lars_step on the num_groups <= 64 segments params + g * group_stride (count elements each; count and
+ *   group_stride multiples of 4, group_stride >= count; grads and mu laid out alike) with per-group lr[g] and weight_decay[g].  Both
+ *   are HOST arrays of num_groups floats that are copied into the kernel arguments: nothing is staged on the device and nothing
+ *   synchronises.  Each group gets, bit for bit, what mae_lars_step gives on that segment alone (params, mu and norms: the same device
+ *   code with the segment on blockIdx.y); the elements between the groups are not touched.  norms_out (num_groups, 2) may be NULL.
+ *   scratch_floats >= 4096 * num_groups. */
+int64_t mae_probe_sweep_scratch_bytes(int64_t rows, int32_t dim, int32_t num_classes, int32_t num_heads);
+int mae_probe_sweep_head(const float* y, int64_t rows, int32_t dim, const float* heads, int32_t num_heads, int32_t num_classes,
+                         const int64_t* labels /* may be NULL */, float* logits /* (G, rows, C), may be NULL */, float* loss_out /* G */,
+                         int32_t* correct_out /* G */, float* head_grads /* (G, HF), may be NULL */, void* scratch, int64_t scratch_bytes,
+                         void* stream);
+int mae_lars_step_groups(float* params, const float* grads, float* mu, int32_t num_groups, int64_t group_stride, int64_t count,
+                         int32_t adapt, const float* lr /* HOST, G */, const float* weight_decay /* HOST, G */, float momentum,
+                         float trust_coefficient, float* norms_out /* (G, 2), may be NULL */, float* scratch, int64_t scratch_floats,
+                         void* stream);
+
 /* The attentive probe on cached tokens (additive in ABI v4; no reference counterpart).  x (batch, tokens, dim) fp32 is
  * the frozen encoder's output, heads | dim, hd = dim / heads; q (dim), Wk, Wv (dim, dim), no bias.  Behind BatchNorm1d(affine=False)
  * with statistics mean / rstd (dim) the definition is

@@ -17,6 +17,15 @@ images_per_s), ``checkpoints/{best,last}.ckpt`` (classifier checkpoints with Bat
 state: resume with --resume) and ``probe.json`` (test_acc / test_loss at the best validation epoch).  Every hyper-parameter flag
 overrides its ``probe.*`` YAML key.
 
+``--sweep_lr 0.01,0.03,0.1,0.3,1.0 --sweep_wd 0,0.0005`` (or the top-level YAML block ``probe_sweep: {base_learning_rate: [...],
+weight_decay: [...]}``; a flag overrides its key, a missing axis takes the single ``probe.*`` value, at most 64 heads) trains the
+whole grid of heads in ONE pass (``probe.ProbeSweep``): the features of a step are formed once and shared, every head follows the same
+epochs and schedule shape at its own peak learning rate, and the head with the best validation accuracy wins (ties: the lower
+validation loss, then the lower index).  ``logs/metrics.jsonl`` then holds per-head lists, ``sweep.json`` one row per head (lr, wd, best
+validation accuracy, its epoch, test accuracy / loss at that epoch) and the winner's index, ``probe.json`` the winner's figures plus
+``sweep_index``, ``best.ckpt`` the winner at its best epoch, ``last.ckpt`` the current leader and ``probe_last.pt`` the whole sweep
+(``--resume`` refuses a state whose grid differs).
+
 ``--layers SPEC`` (last | lastN | each | 2,5,-1) probes the concatenated features of those encoder blocks, each through the encoder's final
 LayerNorm (DINO's and I-JEPA's last-n-blocks probe), from one forward pass per batch; ``--pool cls_mean`` then gives [class token |
 patch mean] per block.  The concatenation must fit the probe kernels' 1024 columns (ViT-S: two blocks).  Such a head reads no single
@@ -35,7 +44,8 @@ import torch
 import yaml
 
 from ssrl_vit_mae_jepa_amd.data import STL10_DIR, augment_to_size, draw_augment_params, get_test_batches, get_train_batches, labeled_serving
-from ssrl_vit_mae_jepa_amd.probe import AUGMENTS, PROBE_DEFAULTS, LinearProbe, classifier_pool, parse_probe, probe_lr
+from ssrl_vit_mae_jepa_amd.probe import (AUGMENTS, PROBE_DEFAULTS, LinearProbe, ProbeSweep, classifier_pool, parse_probe, parse_sweep, probe_lr,
+                                         select)
 from ssrl_vit_mae_jepa_amd.training import lr_lambda
 
 HYPER_FLAGS = ("total_epochs", "warmup_epochs", "batch_size", "base_learning_rate", "weight_decay", "momentum", "trust_coefficient", "bn_eps",
@@ -58,6 +68,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_epochs", type=int, default=None, help="stop after this many epochs (the schedule keeps probe.total_epochs)")
     p.add_argument("--output_dir_suffix", type=str, default="linprobe")
     p.add_argument("--resume", type=str, default=None, help="a probe_last.pt to continue from")
+    p.add_argument("--sweep_lr", type=str, default=None,
+                   help="comma-separated base learning rates: train one head per (lr, wd) pair in one pass (overrides probe_sweep.base_learning_rate)")
+    p.add_argument("--sweep_wd", type=str, default=None, help="comma-separated weight decays of the sweep (overrides probe_sweep.weight_decay)")
     for key in HYPER_FLAGS:
         kind = type(PROBE_DEFAULTS[key])
         if key == "augment":
@@ -142,12 +155,117 @@ def _evaluate(probe: LinearProbe, feats: torch.Tensor, labels: torch.Tensor, bat
     return float(loss) / n, int(correct) / n
 
 
+def _evaluate_sweep(sweep: ProbeSweep, feats: torch.Tensor, labels: torch.Tensor, batch: int):
+    """(loss, accuracy) per head over the split: two lists of len(sweep)."""
+    loss = torch.zeros(len(sweep), dtype=torch.float64, device=feats.device)
+    correct = torch.zeros(len(sweep), dtype=torch.int64, device=feats.device)
+    for i in range(0, feats.shape[0], batch):
+        _, l, c = sweep.evaluate(feats[i:i + batch], labels[i:i + batch])
+        loss += l.double() * min(batch, feats.shape[0] - i)
+        correct += c
+    n = feats.shape[0]
+    return (loss / n).tolist(), (correct.double() / n).tolist()
+
+
+def _run_sweep(args, cfg, pcfg, grid, enc, pool, layers, dim, num_classes, seed, data, dev):
+    """The training loop with a grid of heads: the same epochs, batches and schedule shape as the single probe; every step's features
+    are formed once and shared by all heads, validation is evaluated for all heads every epoch and test whenever a head improves."""
+    model_cfg, batch, crop = cfg["model"], pcfg["batch_size"], pcfg["augment"] == "crop"
+    train_images, train_f, train_y = data["train_images"], data["train_f"], data["train_y"]
+    val_f, val_y, test_f, test_y = data["val_f"], data["val_y"], data["test_f"], data["test_y"]
+    n, G = int(train_y.shape[0]), len(grid)
+    sweep = ProbeSweep(dim, num_classes, grid, pcfg, seed=seed, device=dev)
+    start_epoch = 0
+    best = [dict(val_acc=-1.0, val_loss=None, epoch=-1, test_acc=None, test_loss=None) for _ in range(G)]
+    if args.resume is not None:
+        state = torch.load(args.resume, map_location="cpu", weights_only=False)
+        if "grid" not in state:
+            raise SystemExit(f"linear_probe: --resume {args.resume} holds a single probe, this run asks for a sweep of {G} heads")
+        if list(state.get("layers") or []) != list(layers or []) or (layers is not None and state.get("pool") != pool):
+            raise SystemExit(f"linear_probe: --resume state was trained on layers {state.get('layers')} pool {state.get('pool')}, "
+                             f"this run asks for layers {None if layers is None else list(layers)} pool {pool}")
+        try:
+            sweep.load_state_dict(state)
+        except ValueError as exc:
+            raise SystemExit(f"linear_probe: --resume: {exc}")
+        start_epoch = sweep.epoch
+        best = [dict(b) for b in state["best"]]
+    out_dir = Path(cfg.get("logging", {}).get("output_dir_base", "outputs")) / "probe" / args.output_dir_suffix
+    (out_dir / "checkpoints").mkdir(parents=True, exist_ok=True)
+    (out_dir / "logs").mkdir(parents=True, exist_ok=True)
+    axes = {k: list(dict.fromkeys(g[k] for g in grid)) for k in ("base_learning_rate", "weight_decay")}
+    (out_dir / "config.yaml").write_text(yaml.safe_dump(dict(cfg, probe=pcfg, probe_sweep=axes)))
+    end_epoch = pcfg["total_epochs"] if args.max_epochs is None else min(pcfg["total_epochs"], start_epoch + args.max_epochs)
+    winner = lambda: select([b["val_acc"] for b in best], [float("inf") if b["val_loss"] is None else b["val_loss"] for b in best])
+    metrics = (out_dir / "logs" / "metrics.jsonl").open("a" if args.resume else "w")
+    for epoch in range(start_epoch, end_epoch):
+        factor = lr_lambda(epoch, pcfg["warmup_epochs"], pcfg["total_epochs"])
+        loss_sum = torch.zeros(G, dtype=torch.float64, device=dev)
+        correct_sum = torch.zeros(G, dtype=torch.int64, device=dev)
+        rows = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for step, idx in enumerate(epoch_batches(n, batch, seed, epoch)):
+            j = torch.from_numpy(idx).to(dev)
+            if crop:
+                imgs = train_images[j].contiguous()
+                g = torch.Generator().manual_seed(int(np.random.SeedSequence([seed, epoch, step]).generate_state(1)[0]))
+                feats = _features(enc, augment_to_size(imgs, data["crop_size"], draw_augment_params(imgs.shape[0], imgs.shape[2], g), data["crop_dtype"]),
+                                  pool, layers)
+            else:
+                feats = train_f[j]
+            loss, correct = sweep.step(feats, train_y[j], factor)
+            loss_sum += loss.double() * len(idx)
+            correct_sum += correct
+            rows += len(idx)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        sweep.epoch = epoch + 1
+        val_loss, val_acc = _evaluate_sweep(sweep, val_f, val_y, batch)
+        leader = select(val_acc, val_loss)   # this epoch's
+        line = dict(epoch=epoch, train_loss=(loss_sum / max(rows, 1)).tolist(), train_acc=(correct_sum.double() / max(rows, 1)).tolist(),
+                    val_loss=val_loss, val_acc=val_acc, lr=[float(x) for x in sweep.head_lrs(factor)], leader=leader, images_per_s=rows / max(dt, 1e-9))
+        metrics.write(json.dumps(line) + "\n")
+        metrics.flush()
+        print(json.dumps(line))
+        improved = [g for g in range(G) if val_acc[g] > best[g]["val_acc"]]
+        if improved:
+            test_loss, test_acc = _evaluate_sweep(sweep, test_f, test_y, batch)
+            for g in improved:
+                best[g] = dict(val_acc=val_acc[g], val_loss=val_loss[g], epoch=epoch, test_acc=test_acc[g], test_loss=test_loss[g])
+        if layers is None:   # as for the single probe: a head on several blocks is no classifier head
+            save(out_dir / "checkpoints" / "last.ckpt", sweep.export(leader).classifier_checkpoint(enc, model_cfg, pool, epoch=epoch))
+            w = winner()
+            if w in improved:   # the winner's entry is of this epoch (an entry changes only by improving, so no other head can take over)
+                save(out_dir / "checkpoints" / "best.ckpt", sweep.export(w).classifier_checkpoint(enc, model_cfg, pool, epoch=epoch))
+        extra = {} if layers is None else dict(layers=list(layers), pool=pool)
+        save(out_dir / "checkpoints" / "probe_last.pt", dict(sweep.state_dict(), best=best, **extra))
+    metrics.close()
+    w = winner()
+    heads = [dict(index=g, base_learning_rate=grid[g]["base_learning_rate"], weight_decay=grid[g]["weight_decay"],
+                  peak_lr=probe_lr(dict(pcfg, **grid[g])), best_val_acc=best[g]["val_acc"], best_val_loss=best[g]["val_loss"],
+                  best_epoch=best[g]["epoch"], test_acc=best[g]["test_acc"], test_loss=best[g]["test_loss"]) for g in range(G)]
+    (out_dir / "sweep.json").write_text(json.dumps(dict(winner=w, heads=heads)) + "\n")
+    res = dict(checkpoint=args.checkpoint, kind=enc.kind, encoder=enc.encoder, pool=pool,
+               classifier_pool=classifier_pool(pool, enc.with_cls) if layers is None else None,
+               augment=pcfg["augment"], epochs=end_epoch, train_size=n, val_size=int(val_f.shape[0]), test_size=int(test_f.shape[0]),
+               best_epoch=best[w]["epoch"], val_acc=best[w]["val_acc"], test_acc=best[w]["test_acc"], test_loss=best[w]["test_loss"],
+               peak_lr=heads[w]["peak_lr"], extract_s=data["extract_s"], sweep_index=w, sweep_heads=G,
+               base_learning_rate=grid[w]["base_learning_rate"], weight_decay=grid[w]["weight_decay"])
+    if layers is not None:
+        res["layers"] = list(layers)
+    (out_dir / "probe.json").write_text(json.dumps(res) + "\n")
+    print(json.dumps(res))
+    return res
+
+
 def main(argv=None):
     args = parse_args(argv)
     with open(args.config, "r") as f:
         cfg = yaml.safe_load(f)
     try:
         pcfg = probe_config(cfg, args)
+        grid = parse_sweep(cfg.get("probe_sweep"), pcfg, args.sweep_lr, args.sweep_wd)   # None: no sweep asked for
     except ValueError as exc:
         raise SystemExit(f"linear_probe: {exc}")
     model_cfg = cfg["model"]
@@ -208,12 +326,18 @@ def main(argv=None):
     if n < 2 or val_f.shape[0] < 1:
         raise SystemExit(f"linear_probe: {n} training and {val_f.shape[0]} validation rows are too few")
     num_classes = int(max(int(train_y.max()), int(val_y.max()), int(test_y.max()))) + 1
+    if grid is not None:
+        data = dict(train_images=train_images, train_f=train_f, train_y=train_y, val_f=val_f, val_y=val_y, test_f=test_f, test_y=test_y,
+                    crop_size=crop_size, crop_dtype=crop_dtype, extract_s=extract_s)
+        return _run_sweep(args, cfg, pcfg, grid, enc, pool, layers, enc.embed_dim if layers is None else width, num_classes, seed, data, dev)
 
     probe = LinearProbe(enc.embed_dim if layers is None else width, num_classes, pcfg, seed=seed, device=dev)
     start_epoch = 0
     best = dict(val_acc=-1.0, epoch=-1, test_acc=None, test_loss=None)
     if args.resume is not None:
         state = torch.load(args.resume, map_location="cpu", weights_only=False)
+        if "grid" in state:
+            raise SystemExit(f"linear_probe: --resume {args.resume} holds a sweep of {len(state['grid'])} heads; pass its grid (--sweep_lr / --sweep_wd)")
         if list(state.get("layers") or []) != list(layers or []) or (layers is not None and state.get("pool") != pool):
             raise SystemExit(f"linear_probe: --resume state was trained on layers {state.get('layers')} pool {state.get('pool')}, "
                              f"this run asks for layers {None if layers is None else list(layers)} pool {pool}")

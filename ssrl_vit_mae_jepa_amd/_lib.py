@@ -141,6 +141,9 @@ SIGNATURES = {
     "mae_batchnorm_fwd": (C.c_int, [_vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mae_lars_step": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "mae_batchnorm_stats": (C.c_int, [_vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mae_probe_sweep_scratch_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "mae_probe_sweep_head": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mae_lars_step_groups": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _i64, _vp]),
     "mae_attn_pool_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mae_attn_pool_bwd_scratch_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "mae_attn_pool_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),

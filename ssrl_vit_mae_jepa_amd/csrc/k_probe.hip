@@ -16,13 +16,13 @@
 // column exact (every difference is 0, so mean = x[0][c], M2 = 0 and y = 0 bit for bit) and keeps the first sum's terms the size of the
 // spread, not of the mean.  The normalising sweep takes mean from the scratch, never from x, so y may be x itself.
 #include "kernels.h"
+#include "lars_dev.cuh"
 
 namespace mae {
 
 constexpr int BN_MAX_BLOCKS = 1024;  // row slices of the column reductions
 constexpr int BN_MIN_TRIPS = 4;      // trips a block makes at least before another block is opened
 constexpr int BN_NORM_BLOCKS = 256 * 16;
-constexpr int LARS_BLOCKS = 1024;    // stage-1 partials per norm; the scratch holds 2 * LARS_BLOCKS floats + 4
 
 struct BnGeo {
   int d4, rp, grid;
@@ -166,62 +166,23 @@ int launch_batchnorm_stats(const float* x, int64_t rows, int dim, float eps, int
 }
 
 // ---------------------------------------------------------------------------------------------------
-// LARS: the two norms as sumsq_kernel forms them (block_sum_256 per block, a one-block finalize), then one sweep over p / g / mu
+// LARS: the two norms as sumsq_kernel forms them (block_sum_256 per block, a one-block finalize), then one sweep over p / g / mu;
+// the device code is lars_dev.cuh, which mae_lars_step_groups (k_probe_sweep.hip) shares
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) lars_sumsq_kernel(const float* __restrict__ p, const float* __restrict__ g, int64_t n4, float wd,
                                                          float* __restrict__ partial) {
-  __shared__ float red[4];
-  float ap = 0.f, au = 0.f;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    const f32x4 v = load4(p + i * 4);
-    const f32x4 d = load4(g + i * 4) + v * wd;
-    ap += sumsq4(v);
-    au += sumsq4(d);
-  }
-  ap = block_sum_256(ap, red);
-  au = block_sum_256(au, red);
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x] = ap;
-    partial[LARS_BLOCKS + blockIdx.x] = au;
-  }
+  lars_sumsq_block(p, g, n4, wd, partial, blockIdx.x, gridDim.x);
 }
 
-// stats[0] = |p|, stats[1] = |dp|, stats[2] = q
 __global__ void __launch_bounds__(256) lars_finalize_kernel(const float* __restrict__ partial, int nb, float trust, float* __restrict__ stats,
                                                             float* __restrict__ norms_out) {
-  __shared__ float red[4];
-  float ap = 0.f, au = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) {
-    ap += partial[i];
-    au += partial[LARS_BLOCKS + i];
-  }
-  ap = block_sum_256(ap, red);
-  au = block_sum_256(au, red);
-  if (threadIdx.x == 0) {
-    const float pn = sqrtf(ap), un = sqrtf(au);
-    stats[0] = pn;
-    stats[1] = un;
-    stats[2] = (pn > 0.f && un > 0.f) ? trust * pn / un : 1.0f;
-    if (norms_out) {
-      norms_out[0] = pn;
-      norms_out[1] = un;
-    }
-  }
+  lars_finalize_block(partial, nb, trust, stats, norms_out);
 }
 
 template <bool ADAPT>
 __global__ void __launch_bounds__(256) lars_update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mu, int64_t n4,
                                                           float lr, float momentum, float wd, const float* __restrict__ stats) {
-  const float q = ADAPT ? stats[2] : 1.0f;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    f32x4 pp = load4(p + i * 4);
-    f32x4 d = load4(g + i * 4);
-    if (ADAPT) d = (d + pp * wd) * q;
-    const f32x4 m = load4(mu + i * 4) * momentum + d;
-    pp -= m * lr;
-    store4(mu + i * 4, m);
-    store4(p + i * 4, pp);
-  }
+  lars_update_block<ADAPT>(p, g, mu, n4, lr, momentum, wd, stats, blockIdx.x, gridDim.x);
 }
 
 int launch_lars_step(float* p, const float* g, float* mu, int64_t n, int adapt, float lr, float momentum, float wd, float trust,
@@ -232,13 +193,13 @@ int launch_lars_step(float* p, const float* g, float* mu, int64_t n, int adapt, 
   MAE_REQUIRE(aligned16(p) && aligned16(g) && aligned16(mu), "lars: params / grads / mu must be 16-byte aligned");
   const int64_t n4 = n / 4;
   if (adapt || norms_out) {
-    const int grid = (int)std::min<int64_t>(cdiv(n4, 256), LARS_BLOCKS);
+    const int grid = lars_sum_grid(n4);
     hipLaunchKernelGGL(lars_sumsq_kernel, dim3(grid), dim3(256), 0, s, p, g, n4, adapt ? wd : 0.f, scratch);
     MAE_LAUNCH_CHECK();
     hipLaunchKernelGGL(lars_finalize_kernel, dim3(1), dim3(256), 0, s, scratch, grid, trust, scratch + 2 * LARS_BLOCKS, norms_out);
     MAE_LAUNCH_CHECK();
   }
-  const int grid = (int)std::min<int64_t>(cdiv(n4, 256), 256 * 16);
+  const int grid = lars_update_grid(n4);
   with_bool(adapt != 0, [&](auto A) {  // without ADAPT the kernel reads neither wd nor the stats
     hipLaunchKernelGGL((lars_update_kernel<decltype(A)::value>), dim3(grid), dim3(256), 0, s, p, g, mu, n4, lr, momentum, wd, scratch + 2 * LARS_BLOCKS);
   });

@@ -219,6 +219,17 @@ int launch_batchnorm_stats(const float* x, int64_t rows, int dim, float eps, int
 int launch_lars_step(float* p, const float* g, float* mu, int64_t n, int adapt, float lr, float momentum, float wd, float trust,
                      float* norms_out, float* scratch, hipStream_t s);
 
+// ---- k_probe_sweep.hip: G probe heads on the same BatchNorm output in one pass, and LARS over G segments -----------
+// heads (G, HF = round_up(C D + C, 4)): [W (C, D) | b (C) | padding] per head.  logits (G, rows, C), loss_out / correct_out (G),
+// head_grads (G, HF); the bits of head g do not depend on G or on g.  scratch >= probe_sweep_scratch_bytes (-1 = outside the limits)
+int64_t probe_sweep_scratch_bytes(int64_t rows, int dim, int C, int G);
+int launch_probe_sweep_head(const float* y, int64_t rows, int dim, const float* heads, int G, int C, const int64_t* labels, float* logits,
+                            float* loss_out, int32_t* correct_out, float* head_grads, void* scratch, int64_t scratch_bytes, hipStream_t s);
+// launch_lars_step on the G segments p + g stride of n elements each, bit for bit; lr / wd are host arrays of G floats that travel in
+// the kernel arguments.  norms_out (G, 2) may be null.  scratch >= 4096 G floats
+int launch_lars_step_groups(float* p, const float* g, float* mu, int G, int64_t stride, int64_t n, int adapt, const float* lr, const float* wd,
+                            float momentum, float trust, float* norms_out, float* scratch, int64_t scratch_floats, hipStream_t s);
+
 // ---- k_attnpool.hip: the attentive probe's pool over cached tokens and the small products around it -------------
 // x (B, T, D) fp32 tokens, centred on load with mean (D, null = 0); uq (H, D).  ybar[b][h] = sum_t a (x - mean), a = softmax_t of
 // (x - mean) . uq[h]; lse (B, H) = the log of the softmax denominator.  One workgroup per image, online softmax over token chunks

@@ -276,3 +276,217 @@ class LinearProbe:
             raise ValueError(f"mu has {state['mu'].numel()} elements, the probe {self.mu.numel()}")
         self.mu.copy_(state["mu"].to(self.mu.device))
         self.steps, self.epoch = int(state["steps"]), int(state["epoch"])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the sweep: a grid of heads on the same features in one pass
+# ----------------------------------------------------------------------------------------------------------------------
+SWEEP_MAX_HEADS = 64
+SWEEP_AXES = ("base_learning_rate", "weight_decay")
+
+
+def _sweep_axis(name: str, value) -> list:
+    """One axis of the grid: a comma-separated string (a flag), a list (the YAML) or a single number."""
+    if isinstance(value, str):
+        items = [v.strip() for v in value.split(",")]
+        if not value.strip() or any(not v for v in items):
+            raise ValueError(f"probe sweep: {name} must be a comma-separated list of numbers, got {value!r}")
+    elif isinstance(value, (list, tuple)):
+        items = list(value)
+    else:
+        items = [value]
+    if not items:
+        raise ValueError(f"probe sweep: {name} is empty")
+    out = []
+    for v in items:
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            out.append(float(v))
+        except (TypeError, ValueError):
+            raise ValueError(f"probe sweep: {name} holds {v!r}, which is no number") from None
+    for v in out:
+        if not np.isfinite(v) or (v <= 0 if name == "base_learning_rate" else v < 0):
+            raise ValueError(f"probe sweep: {name} = {v} ({'must be > 0' if name == 'base_learning_rate' else 'must be >= 0'})")
+    if len(set(out)) != len(out):
+        raise ValueError(f"probe sweep: {name} repeats a value: {out}")
+    return out
+
+
+def parse_sweep(block: Optional[Dict[str, Any]], cfg: Dict[str, Any], sweep_lr=None, sweep_wd=None) -> Optional[list]:
+    """The grid of a sweep, or None when none is asked for.  ``block`` is the top-level YAML block ``probe_sweep:`` (lists under
+    ``base_learning_rate`` / ``weight_decay``), ``sweep_lr`` / ``sweep_wd`` the flags' comma-separated strings: a flag overrides its
+    key, a missing axis takes the single value of ``cfg`` (a ``parse_probe`` result).  The grid is the product, learning rate
+    outermost: a list of {base_learning_rate, weight_decay}.  More than SWEEP_MAX_HEADS heads are refused by name."""
+    if block is None and sweep_lr is None and sweep_wd is None:
+        return None
+    block = {} if block is None else block
+    if not isinstance(block, dict):
+        raise ValueError(f"probe_sweep must be a mapping, got {block!r}")
+    unknown = set(block) - set(SWEEP_AXES)
+    if unknown:
+        raise ValueError(f"probe_sweep: unknown keys {sorted(unknown)}")
+    given = dict(base_learning_rate=sweep_lr, weight_decay=sweep_wd)
+    axes = {}
+    for name in SWEEP_AXES:
+        value = given[name] if given[name] is not None else block.get(name)
+        axes[name] = _sweep_axis(name, cfg[name] if value is None else value)
+    heads = len(axes["base_learning_rate"]) * len(axes["weight_decay"])
+    if heads > SWEEP_MAX_HEADS:
+        raise ValueError(f"probe sweep: {len(axes['base_learning_rate'])} learning rates x {len(axes['weight_decay'])} weight decays = {heads} heads; "
+                         f"one sweep takes at most {SWEEP_MAX_HEADS}")
+    return [dict(base_learning_rate=lr, weight_decay=wd) for lr in axes["base_learning_rate"] for wd in axes["weight_decay"]]
+
+
+def select(val_acc, val_loss) -> int:
+    """The winner of a sweep: the highest validation accuracy; ties go to the lower validation loss, then to the lower index.
+    A loss that is not finite loses every tie."""
+    if len(val_acc) != len(val_loss) or len(val_acc) == 0:
+        raise ValueError(f"select: {len(val_acc)} accuracies and {len(val_loss)} losses")
+    key = lambda g: (-float(val_acc[g]), float(val_loss[g]) if np.isfinite(float(val_loss[g])) else float("inf"), g)
+    return min(range(len(val_acc)), key=key)
+
+
+class ProbeSweep:
+    """G linear probes that differ in learning rate and weight decay alone, trained on the same features in one pass: one shared
+    BatchNorm (it has no per-head state), a stacked (G, HF) parameter, momentum and gradient buffer, ``mae_probe_sweep_head`` for
+    every head's logits, loss and gradients and ``mae_lars_step_groups`` for every head's update.  ``grid``: a list of
+    {base_learning_rate, weight_decay} (``parse_sweep``); everything else comes from ``cfg``, a ``parse_probe`` result shared by all
+    heads.  Every head starts from the weights ``ProbeHead(seed)`` has."""
+
+    def __init__(self, dim: int, num_classes: int, grid, cfg: Optional[Dict[str, Any]] = None, seed: Optional[int] = 73, device=None):
+        self.cfg = parse_probe(cfg)
+        self.grid = [dict(base_learning_rate=float(g["base_learning_rate"]), weight_decay=float(g["weight_decay"])) for g in grid]
+        if not 1 <= len(self.grid) <= SWEEP_MAX_HEADS:
+            raise ValueError(f"a probe sweep has 1 to {SWEEP_MAX_HEADS} heads, got {len(self.grid)}")
+        if any(not (g["base_learning_rate"] > 0 and g["weight_decay"] >= 0) for g in self.grid):
+            raise ValueError("probe sweep: base_learning_rate > 0 and weight_decay >= 0 in every head")
+        proto = ProbeHead(dim, num_classes, self.cfg["head_init_std"], seed)
+        self.dim, self.num_classes, self.seed = proto.dim, proto.num_classes, seed
+        self.bn = _BatchNormStats(self.dim)
+        self.head_floats = proto.flat.numel()
+        self.flat = proto.flat.detach().clone().unsqueeze(0).repeat(len(self.grid), 1).contiguous()   # (G, HF)
+        self.mu = torch.zeros_like(self.flat)
+        self.grads = torch.zeros_like(self.flat)
+        self.steps = 0
+        self.epoch = 0
+        self._scratch: Dict[str, torch.Tensor] = {}
+        self.last: Dict[str, torch.Tensor] = {}   # y, mean, rstd, logits (G, B, C) of the latest step
+        if device is not None:
+            self.to(device)
+
+    def __len__(self) -> int:
+        return len(self.grid)
+
+    def to(self, device) -> "ProbeSweep":
+        self.bn.to(device)
+        self.flat, self.mu, self.grads = self.flat.to(device), self.mu.to(device), self.grads.to(device)
+        self._scratch.clear()
+        return self
+
+    @property
+    def device(self) -> torch.device:
+        return self.flat.device
+
+    _bytes = LinearProbe._bytes
+    _check_feats = LinearProbe._check_feats
+
+    def _batchnorm(self, feats: torch.Tensor, training: bool) -> torch.Tensor:
+        B, D = feats.shape
+        bn, dev = self.bn, feats.device
+        y = torch.empty_like(feats)
+        need = lib.mae_batchnorm_scratch_bytes(B, D)
+        if need < 0:
+            raise ValueError(f"BatchNorm shape ({B}, {D}) outside the kernel's limits")
+        scratch = self._bytes("bn", need)
+        mean, rstd = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
+        check(lib.mae_batchnorm_fwd(_ptr(feats), B, D, self.cfg["bn_eps"], int(training), self.cfg["bn_momentum"], _ptr(bn.running_mean),
+                                    _ptr(bn.running_var), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(scratch), scratch.numel(), _stream(dev)))
+        self.last.update(y=y, mean=mean, rstd=rstd)
+        return y
+
+    def _heads(self, rows: torch.Tensor, labels: Optional[torch.Tensor], grads: Optional[torch.Tensor], want_logits: bool = True):
+        B, D = rows.shape
+        dev, C, G = rows.device, self.num_classes, len(self.grid)
+        logits = torch.empty(G, B, C, dtype=torch.float32, device=dev) if want_logits or labels is None else None
+        loss = torch.empty(G, dtype=torch.float32, device=dev) if labels is not None else None
+        correct = torch.empty(G, dtype=torch.int32, device=dev) if labels is not None else None
+        need = lib.mae_probe_sweep_scratch_bytes(B, D, C, G)
+        if need < 0:
+            raise ValueError(f"sweep shape (rows {B}, dim {D}, classes {C}, heads {G}) outside the kernel's limits")
+        scratch = self._bytes("head", need)
+        if labels is not None and labels.data_ptr() % 16:   # a slice of a label vector at an odd row: the kernels take 16-byte aligned buffers
+            labels = labels.clone()
+        check(lib.mae_probe_sweep_head(_ptr(rows), B, D, _ptr(self.flat), G, C, _ptr(labels), _ptr(logits), _ptr(loss), _ptr(correct), _ptr(grads),
+                                       _ptr(scratch), scratch.numel(), _stream(dev)))
+        return logits, loss, correct
+
+    def head_lrs(self, lr_factor: float = 1.0) -> np.ndarray:
+        """fp32 learning rate per head: probe_lr(head) * lr_factor, formed in double and rounded once."""
+        bs = int(self.cfg["batch_size"])
+        return np.array([float(g["base_learning_rate"]) * bs / 256.0 * float(lr_factor) for g in self.grid], dtype=np.float64).astype(np.float32)
+
+    # ---- the operations ------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, feats: torch.Tensor, labels: torch.Tensor, lr_factor: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One training step of every head on a batch of at least two rows: (loss (G,) fp32, correct (G,) int32), device tensors, no
+        synchronisation.  One BatchNorm, one sweep head, two grouped LARS calls (W with the trust ratio, then the bias slice)."""
+        feats, labels = self._check_feats(feats, labels)
+        if feats.shape[0] < 2:
+            raise ValueError("a probe step needs at least 2 rows (BatchNorm in training mode)")
+        y = self._batchnorm(feats, True)
+        self.bn.num_batches_tracked += 1
+        logits, loss, correct = self._heads(y, labels, self.grads)
+        self.last["logits"] = logits
+        c, G, HF = self.cfg, len(self.grid), self.head_floats
+        nw = self.num_classes * self.dim
+        dev = feats.device
+        lrs = self.head_lrs(lr_factor)
+        wds = np.array([g["weight_decay"] for g in self.grid], dtype=np.float32)
+        ls = self._bytes("lars", G * LARS_SCRATCH_FLOATS * 4).view(torch.float32)
+        flat, grads, mu = self.flat.view(-1), self.grads.view(-1), self.mu.view(-1)
+        for lo, hi, adapt in ((0, nw, 1), (nw, HF, 0)):   # W with the trust ratio, then the bias slice (padding included)
+            check(lib.mae_lars_step_groups(_ptr(flat[lo:]), _ptr(grads[lo:]), _ptr(mu[lo:]), G, HF, hi - lo, adapt, lrs.ctypes.data, wds.ctypes.data,
+                                           c["momentum"], c["trust_coefficient"], None, _ptr(ls), ls.numel(), _stream(dev)))
+        self.steps += 1
+        return loss, correct
+
+    @torch.no_grad()
+    def evaluate(self, feats: torch.Tensor, labels: Optional[torch.Tensor] = None):
+        """(logits (G, B, C), loss (G,) or None, correct (G,) or None) with the running statistics; changes no state."""
+        feats, labels = self._check_feats(feats, labels)
+        y = self._batchnorm(feats, False)
+        return self._heads(y, labels, None)
+
+    def export(self, g: int) -> LinearProbe:
+        """Head g as a ``LinearProbe`` of its own: its weights, momentum, hyper-parameters and the shared BatchNorm buffers (copies), so
+        ``folded_head`` / ``classifier_checkpoint`` write it as they write any probe."""
+        g = int(g)
+        if not 0 <= g < len(self.grid):
+            raise IndexError(f"head {g} of a sweep of {len(self.grid)}")
+        probe = LinearProbe(self.dim, self.num_classes, dict(self.cfg, **self.grid[g]), seed=self.seed, device=self.device)
+        with torch.no_grad():
+            probe.head.flat.copy_(self.flat[g])
+            probe.mu.copy_(self.mu[g])
+            for k in ("running_mean", "running_var", "num_batches_tracked"):
+                getattr(probe.head.bn, k).copy_(getattr(self.bn, k))
+        probe.steps, probe.epoch = self.steps, self.epoch
+        return probe
+
+    # ---- resume --------------------------------------------------------------------------------------
+    def state_dict(self) -> Dict[str, Any]:
+        out = {"bn." + k: v.detach().cpu().clone() for k, v in self.bn.state_dict().items()}
+        out.update(flat=self.flat.detach().cpu().clone(), mu=self.mu.detach().cpu().clone(), steps=int(self.steps), epoch=int(self.epoch),
+                   cfg=dict(self.cfg), grid=[dict(g) for g in self.grid], dim=self.dim, num_classes=self.num_classes)
+        return out
+
+    @torch.no_grad()
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        if "grid" not in state or [dict(g) for g in state["grid"]] != self.grid:
+            raise ValueError(f"the state's grid {state.get('grid')} differs from this sweep's {self.grid}")
+        if tuple(state["flat"].shape) != tuple(self.flat.shape):
+            raise ValueError(f"the state holds heads of shape {tuple(state['flat'].shape)}, the sweep {tuple(self.flat.shape)}")
+        self.bn.load_state_dict({k[len("bn."):]: v for k, v in state.items() if k.startswith("bn.")}, strict=True)
+        self.flat.copy_(state["flat"].to(self.device))
+        self.mu.copy_(state["mu"].to(self.device))
+        self.steps, self.epoch = int(state["steps"]), int(state["epoch"])
