@@ -838,6 +838,39 @@ int32_t mae_attention_colsum_max_tokens(int32_t hd, int32_t dtype);
 int mae_attention_colsum(const void* qkv, int32_t dtype, int32_t batch, int32_t T, int32_t H, int32_t hd, const float* row_weight,
                          float* per_head, int64_t per_head_stride, float* mixed, void* stream);
 
+/* Exact t-SNE of n feature rows in the plane (additive in ABI v4; no reference counterpart).  Everything is fp32; every
+ * sum has an order fixed by (n, dim) alone and there are no atomics, so a call is bit-identical from run to run; nothing synchronises
+ * with the host and every buffer is the caller's.  Limits, refused by name before any pointer is touched: 8 <= n <= 16384,
+ * 1 <= dim <= 8192, 1 <= perplexity < n - 1.
+ *   mae_tsne_pitch(n)        round_up(n, 4), the row pitch of P in floats (-1 outside the limits).  P is (n, pitch), 16-byte aligned,
+ *                            with zeros in the columns [n, pitch).
+ *   mae_tsne_scratch_bytes   the scratch of mae_tsne_gradient / mae_tsne_step (-1 outside the limits).
+ *   mae_tsne_affinities      d_ij = sum_k (x_ik - x_jk)^2 (the difference form, one fused multiply-add per k in the order of k);
+ *                            per row sklearn's _binary_search_perplexity on d_ij less the row's minimum over j != i: beta from 1,
+ *                            doubled or halved until bracketed, then bisected, at most 100 steps, until |H_i - log(perplexity)| <= 1e-5,
+ *                            H_i = log sum_j e^(-beta d_ij) + beta sum_j d_ij p_j|i over j != i; p_j|i = e^(-beta_i d_ij) / sum;
+ *                            P_ij = (p_j|i + p_i|j) / (2 n), symmetric bit for bit, diagonal 0.  The symmetrisation is a launch of
+ *                            its own, in place.  sqdist (n, n), beta (n) and p_cond (n, n), all unpadded, may each be NULL.
+ *   mae_tsne_gradient        with w_ij = 1 / (1 + |y_i - y_j|^2) (v_rcp_f32): a_i = sum_j p_ij w_ij (y_i - y_j), r_i = sum_j w_ij^2
+ *                            (y_i - y_j), Z = sum_i sum_{j != i} w_ij, grad_i = 4 (alpha a_i - r_i / Z), one pass over P.  kl (one
+ *                            float, may be NULL) = sum_{i != j} p_ij (log p_ij - log w_ij) + log Z with 0 log 0 = 0; P is taken as it
+ *                            is given (alpha is not applied to it).  grad (n, 2) is required.
+ *   mae_tsne_update          sklearn's _gradient_descent step per coordinate, every operation rounded once (no contraction):
+ *                            gains = max(update * grad < 0 ? gains + 0.2f : gains * 0.8f, min_gain);
+ *                            update = momentum * update - learning_rate * (grad * gains);  y = y + update.
+ *   mae_tsne_step            mae_tsne_gradient followed by mae_tsne_update, bit for bit, in two launches instead of three.
+ *   y, update, gains, grad (n, 2) and scratch must be 16-byte aligned. */
+int32_t mae_tsne_pitch(int32_t n);
+int64_t mae_tsne_scratch_bytes(int32_t n, int32_t dim);
+int mae_tsne_affinities(const float* x, int32_t n, int32_t dim, float perplexity, float* P, float* sqdist /* may be NULL */,
+                        float* beta /* may be NULL */, float* p_cond /* may be NULL */, void* stream);
+int mae_tsne_gradient(const float* P, const float* y, int32_t n, float alpha, float* grad, float* kl /* may be NULL */, void* scratch,
+                      int64_t scratch_bytes, void* stream);
+int mae_tsne_update(float* y, float* update, float* gains, const float* grad, int32_t n, float momentum, float learning_rate,
+                    float min_gain, void* stream);
+int mae_tsne_step(const float* P, float* y, float* update, float* gains, int32_t n, float alpha, float momentum, float learning_rate,
+                  float min_gain, float* grad, float* kl /* may be NULL */, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Token and pixel movement between those pieces, and the losses that read the image.  Index arguments are int32, as the kernels
  * take them; token id 0 is the class token, id t >= 1 is patch t - 1 (row-major over the patch grid).  Unless a function says
  * otherwise the ids must lie in [0, seq_len): nothing here range-checks them on the device.  `partial` is scratch of

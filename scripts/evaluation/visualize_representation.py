@@ -2,13 +2,16 @@
 features taken from the engine (``mae_engine_extract_features``) instead of timm ``forward_features`` + host pooling.
 Same flags, the same plots (one all-class plot and one class-vs-all plot per class), plus ``--encoder`` (I-JEPA target /
 context), ``--synthetic_images``, ``--output_dir`` (default assets/visualizations) and ``--save_features`` (an .npz of the
-normalised features and labels).  t-SNE comes from sklearn, the plots from matplotlib; UMAP needs umap-learn.
+normalised features and labels).  t-SNE comes from sklearn, the plots from matplotlib; UMAP needs umap-learn.  ``--method tsne_gpu``
+is the exact t-SNE of ``ssrl_vit_mae_jepa_amd.embedding.DeviceTSNE`` on the MI355X (PCA initialisation, the same perplexity rule, at
+most 16384 samples); it also writes ``<stem>.json`` with the KL trace.
 
     python -m scripts.evaluation.visualize_representation --config configs/mae.yaml --encoder_ckpt outputs/pretrain/mae_pretrain/vit-mae.pt --method tsne
 """
 from __future__ import annotations
 
 import argparse
+import json
 from pathlib import Path
 
 import numpy as np
@@ -25,6 +28,7 @@ try:
 except ImportError:
     HAS_UMAP = False
 
+TSNE_GPU_MAX_SAMPLES = 16384  # embedding.MAX_N: what exact t-SNE on the device admits
 STL10_CLASSES = ["airplane", "bird", "car", "cat", "deer", "dog", "horse", "monkey", "ship", "truck"]
 
 
@@ -40,6 +44,15 @@ def project(features: np.ndarray, method: str = "umap", seed: int = 73) -> np.nd
         print("Running UMAP...")
         return umap.UMAP(n_components=2).fit_transform(features)
     raise ValueError(f"Unknown method: {method}")
+
+
+def project_tsne_gpu(features: np.ndarray, device):
+    """-> (Z (N, 2) numpy, info): DeviceTSNE from pca_init, perplexity by project()'s rule."""
+    from ssrl_vit_mae_jepa_amd.embedding import DeviceTSNE
+    print("Running t-SNE on the device...")
+    tsne = DeviceTSNE(perplexity=min(30.0, max(1.0, (len(features) - 1) / 3)))
+    Z, info = tsne.fit(torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(device))
+    return Z.cpu().numpy(), info
 
 
 def plot_embedding(Z, y, out_path, title_extra, class_names):
@@ -78,7 +91,7 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description="2-D projection of frozen encoder features")
     p.add_argument("--config", type=str, default="configs/mae.yaml")
     p.add_argument("--encoder_ckpt", type=str, required=True, help="checkpoint path or 'random'")
-    p.add_argument("--method", type=str, choices=["umap", "tsne"], default="umap")
+    p.add_argument("--method", type=str, choices=["umap", "tsne", "tsne_gpu"], default="umap")
     p.add_argument("--pool", type=str, choices=["cls", "mean", "cls_mean"], default="cls", help="cls_mean = [class token | patch mean], with --layers only")
     p.add_argument("--layers", type=str, default=None,
                    help="plot the features after these encoder blocks (last | lastN | each | comma-separated indices; several are concatenated)")
@@ -96,6 +109,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.method == "umap" and not HAS_UMAP:
         raise RuntimeError("UMAP requested but not installed.")
+    if args.method == "tsne_gpu" and args.max_samples > TSNE_GPU_MAX_SAMPLES:
+        raise SystemExit(f"visualize_representation: --method tsne_gpu embeds at most {TSNE_GPU_MAX_SAMPLES} samples, --max_samples is {args.max_samples}")
     with open(args.config, "r") as f:
         cfg = yaml.safe_load(f)
     layers = None
@@ -120,7 +135,11 @@ def main(argv=None):
     feats = apply_normalization(feats.cpu().numpy(), args.normalize)  # the reference normalises on the host, in numpy
     labels = labels.cpu().numpy()
     print("Projecting to 2D...")
-    Z = project(feats, method=args.method)
+    info = None
+    if args.method == "tsne_gpu":
+        Z, info = project_tsne_gpu(feats, dev)
+    else:
+        Z = project(feats, method=args.method)
     save_dir = Path(args.output_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
     ckpt_name = "random" if args.encoder_ckpt == "random" else Path(args.encoder_ckpt).parent.parent.stem
@@ -134,6 +153,8 @@ def main(argv=None):
         plot_class_vs_all(Z, labels, cls_id, STL10_CLASSES[cls_id], str(save_dir / f"{stem}_class{cls_id}.png"))
     if args.save_features:
         np.savez(save_dir / f"{stem}.npz", features=feats, labels=labels, projection=Z)
+    if info is not None:
+        (save_dir / f"{stem}.json").write_text(json.dumps(info, indent=1))
     return save_dir, stem
 
 

@@ -165,6 +165,12 @@ SIGNATURES = {
     "mae_attention_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mae_attention_colsum_max_tokens": (_i32, [_i32, _i32]),
     "mae_attention_colsum": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "mae_tsne_pitch": (_i32, [_i32]),
+    "mae_tsne_scratch_bytes": (_i64, [_i32, _i32]),
+    "mae_tsne_affinities": (C.c_int, [_vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "mae_tsne_gradient": (C.c_int, [_vp, _vp, _i32, _f32, _vp, _vp, _vp, _i64, _vp]),
+    "mae_tsne_update": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp]),
+    "mae_tsne_step": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _i64, _vp]),
     "mae_gather_patches": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mae_assemble_visible": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "mae_visible_grad_split": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),

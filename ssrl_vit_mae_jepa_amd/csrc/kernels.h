@@ -230,6 +230,21 @@ int launch_probe_sweep_head(const float* y, int64_t rows, int dim, const float* 
 int launch_lars_step_groups(float* p, const float* g, float* mu, int G, int64_t stride, int64_t n, int adapt, const float* lr, const float* wd,
                             float momentum, float trust, float* norms_out, float* scratch, int64_t scratch_floats, hipStream_t s);
 
+// ---- k_tsne.hip: exact t-SNE in the plane, 8 <= n <= 16384; fp32, fixed orders, no atomics -------------------------
+// P is (n, tsne_pitch(n) = round_up(n, 4)) with zeros in the padding columns; -1 outside the limits
+int tsne_pitch(int n);
+int64_t tsne_scratch_bytes(int n, int dim);   // the gradient's scratch
+// x (n, dim) -> symmetric joint P; sqdist (n, n), beta (n), p_cond (n, n) optional.  The P buffer is the only working space
+int launch_tsne_affinities(const float* x, int n, int dim, float perplexity, float* P, float* sqdist, float* beta, float* p_cond, hipStream_t s);
+// grad (n, 2) = 4 (alpha a - r / Z) in one pass over P; kl (1 float, may be null) = sum p (log p - log w) + log Z
+int launch_tsne_gradient(const float* P, const float* y, int n, float alpha, float* grad, float* kl, void* scratch, int64_t scratch_bytes,
+                         hipStream_t s);
+// sklearn's _gradient_descent step on (y, update, gains), every operation rounded once
+int launch_tsne_update(float* y, float* upd, float* gains, const float* grad, int n, float momentum, float lr, float min_gain, hipStream_t s);
+// both, the step inside the gradient's finalising launch: the bits of launch_tsne_gradient followed by launch_tsne_update
+int launch_tsne_step(const float* P, float* y, float* upd, float* gains, int n, float alpha, float momentum, float lr, float min_gain, float* grad,
+                     float* kl, void* scratch, int64_t scratch_bytes, hipStream_t s);
+
 // ---- k_attnpool.hip: the attentive probe's pool over cached tokens and the small products around it -------------
 // x (B, T, D) fp32 tokens, centred on load with mean (D, null = 0); uq (H, D).  ybar[b][h] = sum_t a (x - mean), a = softmax_t of
 // (x - mean) . uq[h]; lse (B, H) = the log of the softmax denominator.  One workgroup per image, online softmax over token chunks
