@@ -956,8 +956,9 @@ int mae_smooth_l1_loss(const float* pred, const float* target, int64_t n, float 
  *     v = fl32(x_mid + branch);  y[t] = LayerNorm(v[t]; gamma, beta, eps) in fp32 (biased variance, 1 / sqrt(var + eps));
  *     f = sum_{t in [row_lo, row_hi)} y[t] / (row_hi - row_lo);  normalize = MAE_FEAT_L2: out = f / (||f||_2 + 1e-8), else out = f.
  *   One block per image; wave w of four adds rows row_lo + w, row_lo + w + 4, ... and the four sums are added in wave order, so an
- *   image's result does not depend on batch.  Only the pooled rows are read.  Limits: dim as above, 0 <= row_lo < row_hi <= seq_len.
- * mae_features_tap: mae_features_pool by (with_cls, pool) with a row stride on the output: image b's feature goes to
+ *   image's result does not depend on batch.  Only the pooled rows are read.  Limits: dim as above, 0 <= row_lo < row_hi <= seq_len;
+ *   out 4-byte aligned.
+ * mae_features_tap: the same kernel by (with_cls, pool) with a row stride on the output: image b's feature goes to
  *     out + b * out_row_stride (floats).  Rows pooled: MAE_POOL_CLS row 0; MAE_POOL_MEAN every row; MAE_POOL_MEAN_PATCHES rows
  *     [with_cls, seq_len); each with mae_features_pool's arithmetic order, so the slice holds its bits.  MAE_POOL_CLS_MEAN_PATCHES:
  *     W = 2 dim, out[0, dim) = the MAE_POOL_CLS result, out[dim, 2 dim) = the MAE_POOL_MEAN_PATCHES result, bit for bit, from one

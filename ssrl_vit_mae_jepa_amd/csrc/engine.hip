@@ -246,13 +246,14 @@ struct Ctx {
   int64_t as;
   void* const* ready = nullptr;  // hipEvent_t per gradient-ready point (entries may be null), or null
   bool fwd_only = false;         // no backward will follow (I-JEPA target encoder): the MLP saves no derivative
-  bool skip_final_norm = false;  // forward_encoder_impl stops after the last block: x_mid + branch_b is left for the caller
-  // taps (mae_engine_extract_layer_features alone): right after block tap_layers[i] the tap kernel pools x_mid + branch_b into slice i of
-  // tap_out (batch, tap_n, W), and the encoder stops after the last tapped block
+  // the frozen read-outs: -1 runs every block and the final norm; >= 0 runs blocks 0 .. last_block and returns before the norm, so
+  // that x_mid + branch_b of that block is left for the caller
+  int last_block = -1;
+  // taps (the pooled features alone): right after block tap_layers[i] the feature kernel pools x_mid + branch_b into slice i of
+  // tap_out (batch, tap_n, W); last_block = tap_layers[tap_n - 1]
   const int32_t* tap_layers = nullptr;
   int tap_n = 0, tap_with_cls = 1, tap_pool = MAE_POOL_CLS, tap_normalize = MAE_FEAT_NONE;
   float* tap_out = nullptr;
-  int stop_after = -1;  // mae_engine_extract_attention alone: the encoder stops after this block, as it does after the last tap
   const float* branch_scale = nullptr;  // drop path (classifier training only): (2 * depth, batch) per-image scales of the encoder's branches
   // row j of the table (row 2i: attention branch of encoder block i, 2i + 1: its MLP branch), or null without a table
   const float* scale_row(int j, int batch) const { return branch_scale ? branch_scale + (int64_t)j * batch : nullptr; }
@@ -267,7 +268,7 @@ struct Ctx {
   template <class T = void> T* buf(int64_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
 
-// the one place a Ctx is built; `ready` / `fwd_only` / `skip_final_norm` / the taps / `stop_after` are set by the few callers that need them
+// the one place a Ctx is built; `ready` / `fwd_only` / `last_block` / the taps are set by the few callers that need them
 static Ctx make_ctx(mae_engine* e, const float* params, const void* wcache, float* grads, void* ws, void* stream) {
   return Ctx{e, params, (const char*)wcache, grads, (char*)ws, (hipStream_t)stream, e->act, (int64_t)dtype_size(e->act)};
 }
@@ -452,13 +453,13 @@ static int forward_encoder_impl(const Ctx& c, const Plan& pl, const void* images
   RUN(TK_DATA, 0, gather_read + pl.Me * e->P * c.as, launch_gather_patches(images, img_dt, keep32, pl.B, pl.k, e->C, e->img, e->p, c.act, c.buf<>(pl.patchA), s));
   MAE_TRY(linear(c, c.buf<>(pl.patchA), e->i_patch_w, e->i_patch_b, pl.Me, e->D, e->P, MAE_EPI_NONE, MAE_F32, c.buf<>(pl.enc_x[0]), nullptr, nullptr));
   RUN(TK_DATA, 0, pl.Me * e->D * 12, launch_assemble_visible(c.buf<float>(pl.enc_x[0]), keep32, c.P(e->i_cls), c.P(e->i_pos), pl.Me, e->D, s));
-  const int blocks = c.tap_n ? c.tap_layers[c.tap_n - 1] + 1 : c.stop_after >= 0 ? c.stop_after + 1 : e->depth;
+  const int blocks = c.last_block >= 0 ? c.last_block + 1 : e->depth;
   for (int i = 0, slot = 0; i < blocks; ++i) {
     MAE_TRY(block_forward(c, pl, e->enc[i], pl.enc[i], pl.Me, e->D, e->H, pl.B, pl.k, i ? pl.enc[i - 1].x_mid : 0, i > 0, pl.enc_x[i],
                           i ? c.scale_row(2 * i - 1, pl.B) : nullptr, c.scale_row(2 * i, pl.B)));
     if (slot < c.tap_n && c.tap_layers[slot] == i) MAE_TRY(tap_block(c, pl, i, slot++));
   }
-  if (c.skip_final_norm || c.tap_n || c.stop_after >= 0) return 0;
+  if (c.last_block >= 0) return 0;
   MAE_TRY(ln_fwd(c, c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), c.buf<float>(pl.enc_x[e->depth]), nullptr, c.P(e->i_norm_w),
                  c.P(e->i_norm_b), 1e-6f, pl.Me, e->D, c.act, c.buf<>(pl.enc_norm), c.buf<float>(pl.enc_mean), c.buf<float>(pl.enc_rstd),
                  c.scale_row(2 * e->depth - 1, pl.B), pl.k));
@@ -1328,73 +1329,88 @@ extern "C" int mae_engine_classifier_loss_and_grads_sd(mae_engine_t* e, const fl
 // =====================================================================================================
 // Frozen-encoder features (scripts/evaluation/visualize_representation.py:87-108): the encoder over [cls | patches] or the
 // patches alone, forward only, with a token-sized decoder stub (the I-JEPA target phase's plan).  The encoder stops before
-// its final LayerNorm; k_representation.hip does that add + LayerNorm (fp32) + pool + L2 and writes only (batch, D).
+// its final LayerNorm; k_representation.hip does that add + LayerNorm (fp32) + pool + L2 after each block asked for and writes only
+// (batch, blocks, W).  The attention maps and the token rows below are read-outs of the same forward.
 // =====================================================================================================
 extern "C" int64_t mae_engine_features_workspace_bytes(const mae_engine_t* e, int32_t batch, int32_t with_cls) {
-  if (!e || batch <= 0 || (with_cls != 0 && with_cls != 1) || e->D % 4 != 0 || e->D > 1024) return -1;  // the pool kernel's width limit
+  if (!e || batch <= 0 || (with_cls != 0 && with_cls != 1) || e->D % 4 != 0 || e->D > 1024) return -1;  // the feature kernel's width limit
   if (!batch_in_bound(e, batch)) return -1;
   return make_encoder_plan(e, batch, with_cls != 0).total;
 }
 
-extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
-                                           int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, void* workspace,
-                                           int64_t workspace_bytes, float* feats, void* stream) {
-  const char* who = "mae_engine_extract_features";
+// What the four frozen read-outs share, all of it before any launch: the common rules, the images, the plan over every token of every
+// image with its workspace size, and a forward-only Ctx.  The entry adds its own rules, then calls run_frozen_forward.
+static int begin_frozen_forward(mae_engine* e, const float* params, const void* wcache, const void* images, int image_dtype, int batch,
+                                int with_cls, void* workspace, int64_t workspace_bytes, void* stream, const char* who, Plan* pl, Ctx* c) {
   MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
-  MAE_REQUIRE(images && feats, "%s: null argument", who);
-  MAE_TRY(check_pool(with_cls, pool, true, who));
-  MAE_REQUIRE(e->D % 4 == 0 && e->D <= 1024, "%s: embed_dim = %d must be a multiple of 4 and at most 1024", who, e->D);
-  MAE_REQUIRE(normalize == MAE_FEAT_NONE || normalize == MAE_FEAT_L2, "%s: normalize must be MAE_FEAT_NONE or MAE_FEAT_L2 (got %d)", who, normalize);
+  MAE_REQUIRE(images, "%s: null argument", who);
+  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
   MAE_TRY(check_image_dtype(image_dtype, who));
-  const int64_t need = mae_engine_features_workspace_bytes(e, batch, with_cls);
-  MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
-  MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
-  const Plan pl = make_encoder_plan(e, batch, with_cls != 0);
-  const int T = pl.k;
-  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
-  hipStream_t s = c.s;
-  c.fwd_only = true;
-  c.skip_final_norm = true;
-  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
-  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
-  const int lo = pool == MAE_POOL_MEAN_PATCHES && with_cls ? 1 : 0, hi = pool == MAE_POOL_CLS ? 1 : T;
-  RUN(TK_LN_FWD, 0, (double)batch * (hi - lo) * e->D * (4 + c.as) + (double)batch * e->D * 4,
-      launch_features_pool(c.buf<float>(pl.enc[e->depth - 1].x_mid), c.buf<>(pl.branch_b), e->act, c.P(e->i_norm_w), c.P(e->i_norm_b), 1e-6f,
-                           batch, T, e->D, lo, hi, normalize, feats, s));
+  MAE_REQUIRE(batch > 0, "%s: batch %d out of range", who, batch);
+  *pl = make_encoder_plan(e, batch, with_cls != 0);
+  MAE_REQUIRE(workspace_bytes >= pl->total, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)pl->total);
+  *c = make_ctx(e, params, wcache, nullptr, workspace, stream);
+  c->fwd_only = true;
   return 0;
 }
 
-// mae_engine_extract_features after the blocks `layers` names: the same forward with a tap list, stopped after the highest tapped block.
-// Tap depth - 1 reads what launch_features_pool reads above, in the same arithmetic order.
-extern "C" int mae_engine_extract_layer_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
-                                                 int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, const int32_t* layers,
-                                                 int32_t num_layers, void* workspace, int64_t workspace_bytes, float* feats, void* stream) {
-  const char* who = "mae_engine_extract_layer_features";
-  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
-  MAE_REQUIRE(images && feats && layers, "%s: null argument", who);
-  if (pool == MAE_POOL_CLS_MEAN_PATCHES)
+// The encoder over every token, through block c.last_block: x_mid + branch_b of that block is what the entry reads next.
+static int run_frozen_forward(const Ctx& c, const Plan& pl, const void* images, int image_dtype, int with_cls) {
+  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
+  return forward_encoder_impl(c, pl, images, image_dtype, nullptr);
+}
+
+static int check_layers(const mae_engine* e, const int32_t* layers, int n, const char* who) {
+  MAE_REQUIRE(n >= 1 && n <= e->depth, "%s: num_layers = %d outside [1, depth = %d]", who, n, e->depth);
+  for (int i = 0; i < n; ++i) {
+    MAE_REQUIRE(layers[i] >= 0 && layers[i] < e->depth, "%s: layers[%d] = %d outside [0, depth = %d)", who, i, layers[i], e->depth);
+    MAE_REQUIRE(i == 0 || layers[i] > layers[i - 1], "%s: layers must be strictly ascending (layers[%d] = %d after %d)", who, i, layers[i], layers[i - 1]);
+  }
+  return 0;
+}
+
+// Both feature calls: the forward with a tap list, stopped after the highest tapped block.  The plain call (`plain`, no list) taps the
+// last block alone, keeps to the three single pools and takes any 4-byte aligned feats; the 16-byte rule is the layer call's alone.
+static int extract_features_impl(mae_engine* e, const float* params, const void* wcache, const void* images, int image_dtype, int batch,
+                                 int with_cls, int pool, int normalize, bool plain, const int32_t* layers, int num_layers, void* workspace,
+                                 int64_t workspace_bytes, float* feats, void* stream, const char* who) {
+  Plan pl;
+  Ctx c{};
+  MAE_TRY(begin_frozen_forward(e, params, wcache, images, image_dtype, batch, with_cls, workspace, workspace_bytes, stream, who, &pl, &c));
+  MAE_REQUIRE(feats && (plain || layers), "%s: null argument", who);
+  if (!plain && pool == MAE_POOL_CLS_MEAN_PATCHES)
     MAE_REQUIRE(with_cls == 1, "%s: pool MAE_POOL_CLS_MEAN_PATCHES needs with_cls = 1 (got %d)", who, with_cls);
   else
     MAE_TRY(check_pool(with_cls, pool, true, who));
   MAE_REQUIRE(e->D % 4 == 0 && e->D <= 1024, "%s: embed_dim = %d must be a multiple of 4 and at most 1024", who, e->D);
   MAE_REQUIRE(normalize == MAE_FEAT_NONE || normalize == MAE_FEAT_L2, "%s: normalize must be MAE_FEAT_NONE or MAE_FEAT_L2 (got %d)", who, normalize);
-  MAE_TRY(check_image_dtype(image_dtype, who));
-  MAE_REQUIRE(num_layers >= 1 && num_layers <= e->depth, "%s: num_layers = %d outside [1, depth = %d]", who, num_layers, e->depth);
-  for (int i = 0; i < num_layers; ++i) {
-    MAE_REQUIRE(layers[i] >= 0 && layers[i] < e->depth, "%s: layers[%d] = %d outside [0, depth = %d)", who, i, layers[i], e->depth);
-    MAE_REQUIRE(i == 0 || layers[i] > layers[i - 1], "%s: layers must be strictly ascending (layers[%d] = %d after %d)", who, i, layers[i], layers[i - 1]);
+  const int32_t last = e->depth - 1;
+  if (plain) {
+    layers = &last;
+    num_layers = 1;
+  } else {
+    MAE_TRY(check_layers(e, layers, num_layers, who));
+    MAE_REQUIRE(((uintptr_t)feats & 15) == 0, "%s: feats must be 16-byte aligned", who);
   }
-  MAE_REQUIRE(((uintptr_t)feats & 15) == 0, "%s: feats must be 16-byte aligned", who);
-  const int64_t need = mae_engine_features_workspace_bytes(e, batch, with_cls);
-  MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
-  MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
-  const Plan pl = make_encoder_plan(e, batch, with_cls != 0);
   MAE_REQUIRE(pool == MAE_POOL_CLS || pool == MAE_POOL_MEAN || pl.k > with_cls, "%s: the sequence of %d rows has no patch row", who, pl.k);
-  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
-  c.fwd_only = true;
   c.tap_layers = layers; c.tap_n = num_layers; c.tap_with_cls = with_cls; c.tap_pool = pool; c.tap_normalize = normalize; c.tap_out = feats;
-  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
-  return forward_encoder_impl(c, pl, images, image_dtype, nullptr);
+  c.last_block = layers[num_layers - 1];
+  return run_frozen_forward(c, pl, images, image_dtype, with_cls);
+}
+
+extern "C" int mae_engine_extract_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                           int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, void* workspace,
+                                           int64_t workspace_bytes, float* feats, void* stream) {
+  return extract_features_impl(e, params, wcache, images, image_dtype, batch, with_cls, pool, normalize, true, nullptr, 0, workspace, workspace_bytes,
+                               feats, stream, "mae_engine_extract_features");
+}
+
+// mae_engine_extract_features after the blocks `layers` names, with the fourth pool [class row | patch mean]
+extern "C" int mae_engine_extract_layer_features(mae_engine_t* e, const float* params, const void* wcache, const void* images, int32_t image_dtype,
+                                                 int32_t batch, int32_t with_cls, int32_t pool, int32_t normalize, const int32_t* layers,
+                                                 int32_t num_layers, void* workspace, int64_t workspace_bytes, float* feats, void* stream) {
+  return extract_features_impl(e, params, wcache, images, image_dtype, batch, with_cls, pool, normalize, false, layers, num_layers, workspace,
+                               workspace_bytes, feats, stream, "mae_engine_extract_layer_features");
 }
 
 // =====================================================================================================
@@ -1423,34 +1439,22 @@ extern "C" int mae_engine_extract_attention(mae_engine_t* e, const float* params
                                             int32_t batch, int32_t with_cls, int32_t query, const int32_t* layers, int32_t num_layers,
                                             float* maps, float* rollout, void* workspace, int64_t workspace_bytes, void* stream) {
   const char* who = "mae_engine_extract_attention";
-  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
-  MAE_REQUIRE(images && layers && (maps || rollout), "%s: null argument (images, layers, or both of maps and rollout)", who);
-  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+  Plan pl;
+  Ctx c{};
+  MAE_TRY(begin_frozen_forward(e, params, wcache, images, image_dtype, batch, with_cls, workspace, workspace_bytes, stream, who, &pl, &c));
+  MAE_REQUIRE(layers && (maps || rollout), "%s: null argument (images, layers, or both of maps and rollout)", who);
   MAE_REQUIRE(query == MAE_ATTN_QUERY_CLS || query == MAE_ATTN_QUERY_MEAN, "%s: query must be MAE_ATTN_QUERY_CLS or MAE_ATTN_QUERY_MEAN (got %d)", who, query);
   MAE_REQUIRE(query != MAE_ATTN_QUERY_CLS || with_cls == 1, "%s: query MAE_ATTN_QUERY_CLS needs with_cls = 1", who);
-  MAE_TRY(check_image_dtype(image_dtype, who));
-  MAE_REQUIRE(num_layers >= 1 && num_layers <= e->depth, "%s: num_layers = %d outside [1, depth = %d]", who, num_layers, e->depth);
-  for (int i = 0; i < num_layers; ++i) {
-    MAE_REQUIRE(layers[i] >= 0 && layers[i] < e->depth, "%s: layers[%d] = %d outside [0, depth = %d)", who, i, layers[i], e->depth);
-    MAE_REQUIRE(i == 0 || layers[i] > layers[i - 1], "%s: layers must be strictly ascending (layers[%d] = %d after %d)", who, i, layers[i], layers[i - 1]);
-  }
+  MAE_TRY(check_layers(e, layers, num_layers, who));
   MAE_REQUIRE(((uintptr_t)maps & 15) == 0 && ((uintptr_t)rollout & 15) == 0, "%s: maps and rollout must be 16-byte aligned", who);
-  const int64_t need = mae_engine_attention_workspace_bytes(e, batch, with_cls);
-  MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
-  MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
-  const Plan pl = make_encoder_plan(e, batch, with_cls != 0);
   const int T = pl.k, H = e->H, hd = e->D / H;
   // the colsum launcher's own limits, so that no forward runs for a call it would refuse
   const int max_t = attention_colsum_max_tokens(hd, e->act);
   MAE_REQUIRE(max_t > 0 && H <= 16, "%s: head_dim %d (16, 24, 32, 48, 64) / %d heads (at most 16) unsupported", who, hd, H);
   MAE_REQUIRE(T >= 1 && T <= max_t, "%s: the sequence of %d tokens is outside the map kernel's [1, %d] at head_dim %d", who, T, max_t, hd);
   MAE_REQUIRE(pl.Me < (1ll << 31), "%s: batch * T = %lld must stay below 2^31", who, (long long)pl.Me);
-  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
-  c.fwd_only = true;
-  const int top = layers[num_layers - 1];
-  c.stop_after = top;
-  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
-  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
+  const int top = c.last_block = layers[num_layers - 1];
+  MAE_TRY(run_frozen_forward(c, pl, images, image_dtype, with_cls));
   float* r[2] = {c.buf<float>(pl.dres), c.buf<float>(pl.dres) + round_up(pl.Me, 4)};   // plan buffers are at least 256 bytes: both fit
   hipStream_t s = c.s;
   RUN(TK_DATA, 0, pl.Me * 4, launch_attention_weight_fill(r[0], batch, T, query == MAE_ATTN_QUERY_CLS ? 0 : -1, s));
@@ -1480,24 +1484,17 @@ extern "C" int mae_engine_extract_tokens(mae_engine_t* e, const float* params, c
                                          int32_t batch, int32_t with_cls, int32_t drop_cls, void* workspace, int64_t workspace_bytes,
                                          float* tokens, void* stream) {
   const char* who = "mae_engine_extract_tokens";
-  MAE_TRY(check_common(e, params, wcache, batch, workspace, who));
-  MAE_REQUIRE(images && tokens, "%s: null argument", who);
-  MAE_REQUIRE(with_cls == 0 || with_cls == 1, "%s: with_cls must be 0 or 1 (got %d)", who, with_cls);
+  Plan pl;
+  Ctx c{};
+  MAE_TRY(begin_frozen_forward(e, params, wcache, images, image_dtype, batch, with_cls, workspace, workspace_bytes, stream, who, &pl, &c));
+  MAE_REQUIRE(tokens, "%s: null argument", who);
   MAE_REQUIRE(drop_cls == 0 || (drop_cls == 1 && with_cls == 1), "%s: drop_cls = %d needs a sequence with a class row (with_cls = 1)", who, drop_cls);
   MAE_REQUIRE(e->D % 4 == 0 && e->D <= 1024, "%s: embed_dim = %d must be a multiple of 4 and at most 1024", who, e->D);
-  MAE_TRY(check_image_dtype(image_dtype, who));
-  const int64_t need = mae_engine_tokens_workspace_bytes(e, batch, with_cls);
-  MAE_REQUIRE(need > 0, "%s: batch %d out of range", who, batch);
-  MAE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)need);
-  const Plan pl = make_encoder_plan(e, batch, with_cls != 0);
   const int T = pl.k, T_out = T - drop_cls;
   MAE_REQUIRE(T_out >= 1, "%s: no token row is left", who);
-  Ctx c = make_ctx(e, params, wcache, nullptr, workspace, stream);
   hipStream_t s = c.s;
-  c.fwd_only = true;
-  c.skip_final_norm = true;
-  MAE_TRY(keep_every_token(c, pl, with_cls != 0));
-  MAE_TRY(forward_encoder_impl(c, pl, images, image_dtype, nullptr));
+  c.last_block = e->depth - 1;
+  MAE_TRY(run_frozen_forward(c, pl, images, image_dtype, with_cls));
   const void* branch = c.buf<>(pl.branch_b);
   if (e->act != MAE_F32) {
     MAE_TRY(launch_cast(branch, e->act, c.buf<>(pl.dres), MAE_F32, pl.Me * e->D, s));

@@ -2,9 +2,9 @@
 // Reference: scripts/evaluation/visualize_representation.py:87-150 (forward_features -> pool -> optional normalisation);
 // the k-NN probe has no reference code (DINO's weighted k-NN: cosine similarity, k = 20, T = 0.07; spec in DESIGN.md 11).
 //
-// (1) features_pool_kernel: the encoder's last residual add, its final LayerNorm in fp32, the pool and the optional L2 step,
-//     one block per image, writing (B, D) fp32 only.  features_tap_kernel: the same step after any encoder block, into one
-//     slice of a (B, taps, W) buffer, with the extra pool [class row | patch mean]; bit-equal on the pools they share.
+// (1) features_kernel: the residual add after any encoder block, the encoder's final LayerNorm in fp32, the pool and the optional
+//     L2 step, one block per image, writing fp32 only: (B, D), or one slice of a (B, taps, W) buffer, where the pool
+//     [class row | patch mean] has W = 2 D.
 // (2) knn_search_kernel: fused similarity + per-query running top-k.  Query tiles of 32 x bank splits; each chunk of 128
 //     bank rows is one 32x32 tile per wave on the fp32-input MFMA (exact fp32, a fixed fmaf order per pair, so the value
 //     of a pair depends on the two rows alone), staged in LDS, then merged into the running lists behind a threshold test.
@@ -16,100 +16,25 @@
 namespace mae {
 
 // ---------------------------------------------------------------------------------------------------
-// (1) final add + LayerNorm + pool + L2
+// (1) add + LayerNorm + pool + L2 of the residual stream after an encoder block, into out + b * out_stride: (B, D), or one
+// slice of a (B, taps, W) buffer; the pool [class row | patch mean] (W = 2 D) comes from one pass over the rows.
 // ---------------------------------------------------------------------------------------------------
-// Wave w normalises rows row_lo + w, row_lo + w + 4, ... of the image (lane owns columns 4 * (lane + 64 i)) and keeps its
-// own running sum; the four wave sums are added in wave order.  Fixed order everywhere, no atomics.
-template <class T>
-__global__ void __launch_bounds__(256) features_pool_kernel(const float* __restrict__ x_mid, const T* __restrict__ branch,
-                                                            const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                            int seq, int D, int row_lo, int row_hi, int normalize, float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float part[4][1024];
-  __shared__ float red[4];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int D4 = D / 4;
-  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-  f32x4 acc[4] = {z, z, z, z};
-  for (int j = row_lo + wave; j < row_hi; j += 4) {
-    const int64_t r = ((int64_t)b * seq + j) * D;
-    f32x4 v[4];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane + 64 * i;
-      v[i] = c < D4 ? load4(x_mid + r + 4 * c) + load4(branch + r + 4 * c) : z;
-      s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (lane + 64 * i < D4) {
-        const f32x4 d = v[i] - mean;
-        q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-      }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane + 64 * i;
-      if (c < D4) acc[i] += (v[i] - mean) * rstd * load4(gamma + 4 * c) + load4(beta + 4 * c);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = lane + 64 * i;
-    if (c < D4) *reinterpret_cast<f32x4*>(&part[wave][4 * c]) = acc[i];
-  }
-  __syncthreads();
-  f32x4 f = z;
-  if (t < D4) {
-    f = *reinterpret_cast<const f32x4*>(&part[0][4 * t]);
-    for (int w = 1; w < 4; ++w) f += *reinterpret_cast<const f32x4*>(&part[w][4 * t]);
-    f = f / (float)(row_hi - row_lo);
-  }
-  if (normalize == MAE_FEAT_L2) {  // f / (||f||_2 + 1e-8)
-    const float ss = block_sum_256((f[0] * f[0] + f[1] * f[1]) + (f[2] * f[2] + f[3] * f[3]), red);
-    f = f / (sqrtf(ss) + 1e-8f);
-  }
-  if (t < D4) store4(out + (int64_t)b * D + 4 * t, f);
-}
-
-int launch_features_pool(const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta, float eps, int B, int seq,
-                         int D, int row_lo, int row_hi, int normalize, float* out, hipStream_t s) {
-  MAE_REQUIRE(x_mid && branch && gamma && beta && out && B > 0 && seq > 0, "features_pool: bad arguments");
-  MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "features_pool: D = %d must be a multiple of 4 in [4, 1024]", D);
-  MAE_REQUIRE(row_lo >= 0 && row_lo < row_hi && row_hi <= seq, "features_pool: rows [%d, %d) outside the sequence of %d", row_lo, row_hi, seq);
-  MAE_REQUIRE(branch_dt == MAE_F32 || branch_dt == MAE_BF16, "features_pool: branch dtype must be MAE_F32 or MAE_BF16 (got %d)", branch_dt);
-  if (branch_dt == MAE_BF16)
-    hipLaunchKernelGGL(features_pool_kernel<bf16>, dim3(B), dim3(256), 0, s, x_mid, (const bf16*)branch, gamma, beta, eps, seq, D, row_lo, row_hi, normalize, out);
-  else
-    hipLaunchKernelGGL(features_pool_kernel<float>, dim3(B), dim3(256), 0, s, x_mid, (const float*)branch, gamma, beta, eps, seq, D, row_lo, row_hi, normalize, out);
-  MAE_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// (1b) the same step after any encoder block (a "tap"): add + LayerNorm + pool + L2 into slice `b * out_stride` of a
-// (B, taps, W) buffer, plus the pool [class row | patch mean] (W = 2 D) from one pass over the rows.
-// ---------------------------------------------------------------------------------------------------
-// The build contracts a * b + c wherever it finds one (-ffp-contract=fast), and which products of a sum of squares it contracts depends
-// on the code around them: in features_pool_kernel the row's squares (d * d) stay plain products (packed multiplies, then additions),
-// LayerNorm's scale and shift is one fused multiply-add, and the L2 sum is fma(f0, f0, f1 * f1) + fma(f2, f2, f3 * f3).  The tap kernel
-// must give that kernel's bits, so it spells the same roundings out: fmaf where that kernel fuses, tap_product where it does not.
-__device__ __forceinline__ float tap_product(float a, float b) {
+// The roundings are fixed in the text, because under -ffp-contract=fast the build would pick which a * b + c to fuse from the code
+// around it (and pragmas or *_rn intrinsics do not stop it).  Fused (fmaf): LayerNorm's scale and shift, and the L2 sum
+// fma(f0, f0, f1 * f1) + fma(f2, f2, f3 * f3).  Not fused (unfused_mul): the row's squares (d * d), and the inner products of the L2 sum.
+__device__ __forceinline__ float unfused_mul(float a, float b) {
   float p = a * b;
   asm("" : "+v"(p));  // emits nothing; the product is opaque to the contraction of the addition that follows
   return p;
 }
-__device__ __forceinline__ float tap_sumsq4(f32x4 f) {  // the L2 term of one thread
-  return __builtin_fmaf(f[0], f[0], tap_product(f[1], f[1])) + __builtin_fmaf(f[2], f[2], tap_product(f[3], f[3]));
+__device__ __forceinline__ float l2_sumsq4(f32x4 f) {  // the L2 term of one thread
+  return __builtin_fmaf(f[0], f[0], unfused_mul(f[1], f[1])) + __builtin_fmaf(f[2], f[2], unfused_mul(f[3], f[3]));
 }
 
-// One row of features_pool_kernel's loop, rounding for rounding: the three pools it shares with that kernel give the same bits.
+// One row: a wave normalises it (lane owns columns 4 * (lane + 64 i)) and adds it to the wave's running sum.
 template <class T>
-__device__ __forceinline__ void tap_add_row(const float* __restrict__ x_mid, const T* __restrict__ branch, const float* __restrict__ gamma,
-                                            const float* __restrict__ beta, float eps, int64_t r, int D, int D4, int lane, f32x4 (&acc)[4]) {
+__device__ __forceinline__ void features_add_row(const float* __restrict__ x_mid, const T* __restrict__ branch, const float* __restrict__ gamma,
+                                                 const float* __restrict__ beta, float eps, int64_t r, int D, int D4, int lane, f32x4 (&acc)[4]) {
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
   f32x4 v[4];
   float s = 0.f;
@@ -125,7 +50,7 @@ __device__ __forceinline__ void tap_add_row(const float* __restrict__ x_mid, con
   for (int i = 0; i < 4; ++i) {
     if (lane + 64 * i < D4) {
       const f32x4 d = v[i] - mean;
-      q += (tap_product(d[0], d[0]) + tap_product(d[1], d[1])) + (tap_product(d[2], d[2]) + tap_product(d[3], d[3]));
+      q += (unfused_mul(d[0], d[0]) + unfused_mul(d[1], d[1])) + (unfused_mul(d[2], d[2]) + unfused_mul(d[3], d[3]));
     }
   }
   const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
@@ -140,15 +65,16 @@ __device__ __forceinline__ void tap_add_row(const float* __restrict__ x_mid, con
   }
 }
 
-// Rows [row_lo, row_hi) are pooled as in features_pool_kernel (wave w: rows row_lo + w, row_lo + w + 4, ...; wave sums added in wave
-// order).  cls_row (MAE_POOL_CLS_MEAN_PATCHES, row_lo = 1): wave 0 also takes row 0 into an accumulator of its own; the row goes to
-// out[0, D), the patch mean to out[D, 2D), each L2-normalised on its own.  A lone row needs no wave sum and no division: with the
-// accumulator started at +0, acc + 0 + 0 + 0 and acc / 1 return acc's bits, so out[0, D) is what MAE_POOL_CLS gives.
+// Rows [row_lo, row_hi) of the image are pooled: wave w takes rows row_lo + w, row_lo + w + 4, ... into its own running sum, and the
+// four wave sums are added in wave order.  Fixed order everywhere, no atomics.  cls_row (MAE_POOL_CLS_MEAN_PATCHES, row_lo = 1): wave 0
+// also takes row 0 into an accumulator of its own; the row goes to out[0, D), the patch mean to out[D, 2D), each L2-normalised on its
+// own.  A lone row needs no wave sum and no division: with the accumulator started at +0, acc + 0 + 0 + 0 and acc / 1 return acc's
+// bits, so out[0, D) is what MAE_POOL_CLS gives.
 template <class T>
-__global__ void __launch_bounds__(256) features_tap_kernel(const float* __restrict__ x_mid, const T* __restrict__ branch,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                           int seq, int D, int row_lo, int row_hi, int cls_row, int normalize,
-                                                           float* __restrict__ out, int64_t out_stride) {
+__global__ void __launch_bounds__(256) features_kernel(const float* __restrict__ x_mid, const T* __restrict__ branch,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                       int seq, int D, int row_lo, int row_hi, int cls_row, int normalize,
+                                                       float* __restrict__ out, int64_t out_stride) {
   __shared__ __attribute__((aligned(16))) float part[4][1024];
   __shared__ __attribute__((aligned(16))) float part_cls[1024];
   __shared__ float red[4];
@@ -158,14 +84,14 @@ __global__ void __launch_bounds__(256) features_tap_kernel(const float* __restri
   f32x4 acc[4] = {z, z, z, z};
   if (cls_row && wave == 0) {
     f32x4 acc_cls[4] = {z, z, z, z};
-    tap_add_row(x_mid, branch, gamma, beta, eps, (int64_t)b * seq * D, D, D4, lane, acc_cls);
+    features_add_row(x_mid, branch, gamma, beta, eps, (int64_t)b * seq * D, D, D4, lane, acc_cls);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int c = lane + 64 * i;
       if (c < D4) *reinterpret_cast<f32x4*>(&part_cls[4 * c]) = acc_cls[i];
     }
   }
-  for (int j = row_lo + wave; j < row_hi; j += 4) tap_add_row(x_mid, branch, gamma, beta, eps, ((int64_t)b * seq + j) * D, D, D4, lane, acc);
+  for (int j = row_lo + wave; j < row_hi; j += 4) features_add_row(x_mid, branch, gamma, beta, eps, ((int64_t)b * seq + j) * D, D, D4, lane, acc);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = lane + 64 * i;
@@ -179,7 +105,7 @@ __global__ void __launch_bounds__(256) features_tap_kernel(const float* __restri
     f = f / (float)(row_hi - row_lo);
   }
   if (normalize == MAE_FEAT_L2) {  // f / (||f||_2 + 1e-8)
-    const float ss = block_sum_256(tap_sumsq4(f), red);
+    const float ss = block_sum_256(l2_sumsq4(f), red);
     f = f / (sqrtf(ss) + 1e-8f);
   }
   float* o = out + (int64_t)b * out_stride;
@@ -188,7 +114,7 @@ __global__ void __launch_bounds__(256) features_tap_kernel(const float* __restri
   f32x4 g = z;
   if (t < D4) g = *reinterpret_cast<const f32x4*>(&part_cls[4 * t]);
   if (normalize == MAE_FEAT_L2) {  // block_sum_256 opens with a barrier: every read of red above is over before it is rewritten
-    const float ss = block_sum_256(tap_sumsq4(g), red);
+    const float ss = block_sum_256(l2_sumsq4(g), red);
     g = g / (sqrtf(ss) + 1e-8f);
   }
   if (t < D4) store4(o + 4 * t, g);
@@ -196,31 +122,38 @@ __global__ void __launch_bounds__(256) features_tap_kernel(const float* __restri
 
 int features_tap_width(int pool, int D) { return pool == MAE_POOL_CLS_MEAN_PATCHES ? 2 * D : D; }
 
-int launch_features_tap(const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta, float eps, int B, int seq,
-                        int D, int with_cls, int pool, int normalize, float* out, int64_t out_stride, hipStream_t s) {
-  const char* who = "mae_features_tap";
+// The one launch of features_kernel and the rules every caller shares; `who` names the C entry in the messages.
+static int launch_features(const char* who, const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta,
+                           float eps, int B, int seq, int D, int row_lo, int row_hi, int cls_row, int normalize, float* out,
+                           int64_t out_stride, hipStream_t s) {
   MAE_REQUIRE(x_mid && branch && gamma && beta && out, "%s: null argument", who);
   MAE_REQUIRE(B > 0 && seq > 0, "%s: batch = %d and seq_len = %d must be positive", who, B, seq);
   MAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "%s: dim = %d must be a multiple of 4 in [4, 1024]", who, D);
-  MAE_REQUIRE(branch_dt == MAE_F32 || branch_dt == MAE_BF16, "%s: branch_dtype must be MAE_F32 or MAE_BF16 (got %d)", who, branch_dt);
+  MAE_REQUIRE(branch_dt == MAE_F32 || branch_dt == MAE_BF16, "%s: branch_dtype = %d, but the branch dtype must be MAE_F32 or MAE_BF16", who, branch_dt);
   MAE_REQUIRE(normalize == MAE_FEAT_NONE || normalize == MAE_FEAT_L2, "%s: normalize must be MAE_FEAT_NONE or MAE_FEAT_L2 (got %d)", who, normalize);
+  MAE_REQUIRE(row_lo >= 0 && row_lo < row_hi && row_hi <= seq, "%s: rows [%d, %d) outside the sequence of %d", who, row_lo, row_hi, seq);
+  if (branch_dt == MAE_BF16)
+    hipLaunchKernelGGL(features_kernel<bf16>, dim3(B), dim3(256), 0, s, x_mid, (const bf16*)branch, gamma, beta, eps, seq, D, row_lo, row_hi, cls_row,
+                       normalize, out, out_stride);
+  else
+    hipLaunchKernelGGL(features_kernel<float>, dim3(B), dim3(256), 0, s, x_mid, (const float*)branch, gamma, beta, eps, seq, D, row_lo, row_hi, cls_row,
+                       normalize, out, out_stride);
+  MAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_features_tap(const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta, float eps, int B, int seq,
+                        int D, int with_cls, int pool, int normalize, float* out, int64_t out_stride, hipStream_t s) {
+  const char* who = "mae_features_tap";
   const bool both = pool == MAE_POOL_CLS_MEAN_PATCHES;
   if (both) MAE_REQUIRE(with_cls == 1, "%s: pool MAE_POOL_CLS_MEAN_PATCHES needs with_cls = 1 (got %d)", who, with_cls);
   else MAE_TRY(check_pool(with_cls, pool, true, who));
   const int lo = (both || pool == MAE_POOL_MEAN_PATCHES) && with_cls ? 1 : 0, hi = pool == MAE_POOL_CLS ? 1 : seq;
-  MAE_REQUIRE(lo < hi, "%s: seq_len = %d leaves no patch row behind the class row (pool %d needs seq_len >= 2)", who, seq, pool);
+  MAE_REQUIRE(seq <= 0 || lo < hi, "%s: seq_len = %d leaves no patch row behind the class row (pool %d needs seq_len >= 2)", who, seq, pool);
   const int W = features_tap_width(pool, D);
   MAE_REQUIRE(out_stride >= W && out_stride % 4 == 0, "%s: out_row_stride = %lld must be a multiple of 4 and at least the width %d", who,
               (long long)out_stride, W);
-  MAE_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out must be 16-byte aligned", who);
-  if (branch_dt == MAE_BF16)
-    hipLaunchKernelGGL(features_tap_kernel<bf16>, dim3(B), dim3(256), 0, s, x_mid, (const bf16*)branch, gamma, beta, eps, seq, D, lo, hi, (int)both,
-                       normalize, out, out_stride);
-  else
-    hipLaunchKernelGGL(features_tap_kernel<float>, dim3(B), dim3(256), 0, s, x_mid, (const float*)branch, gamma, beta, eps, seq, D, lo, hi, (int)both,
-                       normalize, out, out_stride);
-  MAE_LAUNCH_CHECK();
-  return 0;
+  return launch_features(who, x_mid, branch, branch_dt, gamma, beta, eps, B, seq, D, lo, hi, (int)both, normalize, out, out_stride, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -464,19 +397,18 @@ int launch_knn_vote(const float* sim, const int64_t* idx, int64_t Q, int k_strid
 
 }  // namespace mae
 
-// single-kernel entry (parity tests): the pooling kernel of mae_engine_extract_features on caller buffers, see mae_hip.h
+// single-kernel entries (parity tests): features_kernel on caller buffers, by row range or by (with_cls, pool); see mae_hip.h
 extern "C" int mae_features_pool(const float* x_mid, const void* branch, int32_t branch_dtype, const float* gamma, const float* beta, float eps,
                                  int32_t batch, int32_t seq_len, int32_t dim, int32_t row_lo, int32_t row_hi, int32_t normalize, float* out,
                                  void* stream) {
-  MAE_REQUIRE(normalize == MAE_FEAT_NONE || normalize == MAE_FEAT_L2, "mae_features_pool: normalize must be MAE_FEAT_NONE or MAE_FEAT_L2 (got %d)", normalize);
-  return mae::launch_features_pool(x_mid, branch, branch_dtype, gamma, beta, eps, batch, seq_len, dim, row_lo, row_hi, normalize, out,
-                                   (hipStream_t)stream);
+  return mae::launch_features("mae_features_pool", x_mid, branch, branch_dtype, gamma, beta, eps, batch, seq_len, dim, row_lo, row_hi, 0, normalize, out,
+                              dim, (hipStream_t)stream);
 }
 
-// single-kernel entry (parity tests): the tap kernel of mae_engine_extract_layer_features on caller buffers, see mae_hip.h
 extern "C" int mae_features_tap(const float* x_mid, const void* branch, int32_t branch_dtype, const float* gamma, const float* beta, float eps,
                                 int32_t batch, int32_t seq_len, int32_t dim, int32_t with_cls, int32_t pool, int32_t normalize, float* out,
                                 int64_t out_row_stride, void* stream) {
+  MAE_REQUIRE(((uintptr_t)out & 15) == 0, "mae_features_tap: out must be 16-byte aligned");
   return mae::launch_features_tap(x_mid, branch, branch_dtype, gamma, beta, eps, batch, seq_len, dim, with_cls, pool, normalize, out,
                                   out_row_stride, (hipStream_t)stream);
 }

@@ -150,12 +150,9 @@ int launch_full_grad_split(const float* dx, int B, int L, int D, int dt, void* d
                            hipStream_t s);
 
 // ---- k_representation.hip: frozen-encoder features and the k-NN probe -----------------------------------------------------
-// out[b] (fp32, D) = pool over rows [row_lo, row_hi) of LN(x_mid + branch) of image b (seq rows each), then f / (||f|| + 1e-8)
-// when normalize == MAE_FEAT_L2.  Reads only the pooled rows.
-int launch_features_pool(const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta, float eps, int B, int seq,
-                         int D, int row_lo, int row_hi, int normalize, float* out, hipStream_t s);
-// The same step by (with_cls, pool) into out + b * out_stride (floats): one slice of a (B, taps, W) buffer.  W = features_tap_width:
-// D, or 2 D for MAE_POOL_CLS_MEAN_PATCHES = [class row | patch mean].  The pools shared with launch_features_pool give its bits.
+// out + b * out_stride (fp32, W floats) = the pool (with_cls, pool) names over the rows of LN(x_mid + branch) of image b (seq rows each),
+// then f / (||f|| + 1e-8) when normalize == MAE_FEAT_L2: (B, D), or one slice of a (B, taps, W) buffer.  W = features_tap_width: D, or
+// 2 D for MAE_POOL_CLS_MEAN_PATCHES = [class row | patch mean].  Reads only the pooled rows; out needs 4-byte alignment only.
 int features_tap_width(int pool, int D);
 int launch_features_tap(const float* x_mid, const void* branch, int branch_dt, const float* gamma, const float* beta, float eps, int B, int seq,
                         int D, int with_cls, int pool, int normalize, float* out, int64_t out_stride, hipStream_t s);

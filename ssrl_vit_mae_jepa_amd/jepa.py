@@ -236,6 +236,14 @@ class IJEPA(nn.Module):
             _ptr(ws), ws.numel(), _ptr(net.flat_grads), _ptr(loss, torch.float32), _ptr(h), _ptr(pred), evs, n_ev, _stream(dev)))
         return (loss, h, pred) if return_aux else loss
 
+    def _encoder_arena(self, encoder: str) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """(params, wcache) of the encoder a read-out names: the EMA target's arena or the context encoder's."""
+        if encoder == "target":
+            return self.target_arena, self._target_weights()
+        if encoder == "context":
+            return self.net.flat_params, self.net._weights()
+        raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
+
     @torch.no_grad()
     def extract_features(self, images: torch.Tensor, encoder: str = "target", pool: str = "mean", normalize: str = "none",
                          layers: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -243,25 +251,17 @@ class IJEPA(nn.Module):
         (B, D) fp32 over the patch tokens, the only tokens the I-JEPA encoders were trained on.  pool "mean" (the only one:
         there is no class token); normalize "none" | "l2".  layers: as ``MaskedAutoencoder.extract_features`` -- (B, n, D), the
         blocks' outputs through the encoder's final LayerNorm (the last-n-layers probe of the I-JEPA paper)."""
-        if encoder not in ("target", "context"):
-            raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
         if pool != "mean":
             raise ValueError(f"I-JEPA encoders see no class token: pool must be 'mean', got {pool!r}")
-        net = self.net
-        if encoder == "target":
-            return net._extract(images, self.target_arena, self._target_weights(), pool, normalize, with_cls=False, layers=layers)
-        return net._extract(images, net.flat_params, net._weights(), pool, normalize, with_cls=False, layers=layers)
+        params, wcache = self._encoder_arena(encoder)
+        return self.net._extract(images, params, wcache, pool, normalize, with_cls=False, layers=layers)
 
     @torch.no_grad()
     def extract_tokens(self, images: torch.Tensor, encoder: str = "target") -> torch.Tensor:
         """The patch tokens of the EMA target encoder (``encoder="target"``) or the context encoder after the final LayerNorm:
         (B, N, D) fp32 -- ``extract_features`` without the pool."""
-        if encoder not in ("target", "context"):
-            raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
-        net = self.net
-        if encoder == "target":
-            return net._extract_tokens(images, self.target_arena, self._target_weights(), False, False)
-        return net._extract_tokens(images, net.flat_params, net._weights(), False, False)
+        params, wcache = self._encoder_arena(encoder)
+        return self.net._extract_tokens(images, params, wcache, False, False)
 
     @torch.no_grad()
     def extract_attention(self, images: torch.Tensor, encoder: str = "target", layers: Sequence[int] = (-1,), query: str = "mean",
@@ -269,14 +269,10 @@ class IJEPA(nn.Module):
         """Attention maps (B, n, H, N) of the EMA target encoder (``encoder="target"``) or the context encoder over the patch tokens:
         ``MaskedAutoencoder.extract_attention`` with with_cls=False.  query "mean" (the only one: there is no class token) = the mean
         attention each patch receives; rollout=True adds the (B, N) rollout of that query."""
-        if encoder not in ("target", "context"):
-            raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
         if query != "mean":
             raise ValueError(f"I-JEPA encoders see no class token: query must be 'mean', got {query!r}")
-        net = self.net
-        if encoder == "target":
-            return net._extract_attention(images, self.target_arena, self._target_weights(), layers, query, False, rollout)
-        return net._extract_attention(images, net.flat_params, net._weights(), layers, query, False, rollout)
+        params, wcache = self._encoder_arena(encoder)
+        return self.net._extract_attention(images, params, wcache, layers, query, False, rollout)
 
     @torch.no_grad()
     def target_features(self, images: torch.Tensor, idx_target: torch.Tensor) -> torch.Tensor:

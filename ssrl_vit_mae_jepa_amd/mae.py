@@ -632,6 +632,23 @@ class MaskedAutoencoder(nn.Module):
             return _EncoderFunction.apply(self, images, idx_keep, *self._enc_params)
         return self._run_encoder(images, idx_keep)
 
+    def _frozen_workspace(self, images: torch.Tensor, with_cls: bool, bytes_fn) -> Tuple[torch.device, torch.Tensor, int]:
+        """The step every frozen read-out opens with, after its own argument checks: the images on the device and the module's
+        workspace grown to what ``bytes_fn`` asks for -> (device, images, batch)."""
+        dev = self._require_cuda()
+        images = self._check_images(images.to(dev))
+        B = images.shape[0]
+        need = bytes_fn(self._engine.handle, B, int(bool(with_cls)))
+        if need < 0:
+            raise ValueError(f"bad batch {B}")
+        # the module's workspace is reused: whatever a pending backward saved in it is gone
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._plan = None
+        self._gen_enc += 1; self._gen_dec += 1
+        return dev, images, B
+
     @torch.no_grad()
     def extract_features(self, images: torch.Tensor, pool: str = "cls", normalize: str = "none", with_cls: bool = True,
                          layers: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -659,18 +676,7 @@ class MaskedAutoencoder(nn.Module):
             raise ValueError(f"pool={pool!r} needs the class token (with_cls=True)")
         if layers is not None:
             layers = resolve_layers(layers, self._dims["depth"])
-        dev = self._require_cuda()
-        images = self._check_images(images.to(dev))
-        B = images.shape[0]
-        need = lib.mae_engine_features_workspace_bytes(self._engine.handle, B, int(bool(with_cls)))
-        if need < 0:
-            raise ValueError(f"bad batch {B}")
-        # the module's workspace is reused: whatever a pending backward saved in it is gone
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-        self._plan = None
-        self._gen_enc += 1; self._gen_dec += 1
+        dev, images, B = self._frozen_workspace(images, with_cls, lib.mae_engine_features_workspace_bytes)
         if layers is not None:
             n, W = len(layers), self._dims["embed_dim"] * (2 if pool == "cls_mean" else 1)
             out = torch.empty(B, n, W, dtype=torch.float32, device=dev)
@@ -711,18 +717,7 @@ class MaskedAutoencoder(nn.Module):
             raise ValueError(f"attention maps need a head width of 16, 24, 32, 48 or 64 and at most 16 heads (got {self._dims['embed_dim'] // H}, {H})")
         if T > limit:
             raise ValueError(f"attention maps take sequences of at most {limit} tokens (this encoder has {T})")
-        dev = self._require_cuda()
-        images = self._check_images(images.to(dev))
-        B = images.shape[0]
-        need = lib.mae_engine_attention_workspace_bytes(self._engine.handle, B, int(with_cls))
-        if need < 0:
-            raise ValueError(f"bad batch {B}")
-        # the module's workspace is reused: whatever a pending backward saved in it is gone
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-        self._plan = None
-        self._gen_enc += 1; self._gen_dec += 1
+        dev, images, B = self._frozen_workspace(images, with_cls, lib.mae_engine_attention_workspace_bytes)
         n = len(layers)
         maps = torch.empty(B, n, H, T, dtype=torch.float32, device=dev)
         roll = torch.empty(B, T, dtype=torch.float32, device=dev) if rollout else None
@@ -739,19 +734,9 @@ class MaskedAutoencoder(nn.Module):
         return self._extract_tokens(images, self._arena, self._weights(), with_cls, drop_cls)
 
     def _extract_tokens(self, images: torch.Tensor, params: torch.Tensor, wcache: Optional[torch.Tensor], with_cls: bool, drop_cls: bool) -> torch.Tensor:
-        dev = self._require_cuda()
-        images = self._check_images(images.to(dev))
-        B = images.shape[0]
         with_cls = bool(with_cls)
         drop = with_cls and bool(drop_cls)
-        need = lib.mae_engine_tokens_workspace_bytes(self._engine.handle, B, int(with_cls))
-        if need < 0:
-            raise ValueError(f"bad batch {B}")
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-        self._plan = None
-        self._gen_enc += 1; self._gen_dec += 1
+        dev, images, B = self._frozen_workspace(images, with_cls, lib.mae_engine_tokens_workspace_bytes)
         T = self.sequence_length - (0 if with_cls and not drop else 1)
         out = torch.empty(B, T, self._dims["embed_dim"], dtype=torch.float32, device=dev)
         check(lib.mae_engine_extract_tokens(self._engine.handle, _ptr(params), _ptr(wcache), _ptr(images), self._img_dt(images), B, int(with_cls),

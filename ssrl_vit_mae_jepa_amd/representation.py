@@ -289,6 +289,23 @@ def _general(model_cfg: Dict[str, Any], precision: Optional[str]) -> Dict[str, A
     return cfg
 
 
+def _open_checkpoint(src: Union[str, Path, Dict[str, Any]]) -> Tuple[Any, Dict[str, Any], str]:
+    """(checkpoint, state dict, layout) of a path, a loaded checkpoint or a state dict."""
+    ckpt = torch.load(src, map_location="cpu", weights_only=False) if isinstance(src, (str, Path)) else src
+    state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
+    return ckpt, state, checkpoint_layout(state)
+
+
+def _ijepa_model(cfg: Dict[str, Any], state: Dict[str, Any]):
+    """The ``IJEPA`` model an ``ijepa_ckpt`` state dict loads into; model.predictor in the config fixes the arena layout."""
+    from .jepa import IJEPAPretrainModule
+    if "predictor" not in cfg:
+        raise ValueError("an I-JEPA checkpoint needs model.predictor in the config")
+    module = IJEPAPretrainModule(cfg, {})
+    module.load_checkpoint_dict({"state_dict": state})
+    return module.model
+
+
 def load_eval_encoder(src: Union[str, Path, Dict[str, Any]], model_cfg: Dict[str, Any], encoder: str = "target",
                       precision: Optional[str] = None, device=None) -> EvalEncoder:
     """The frozen encoder of a checkpoint (a path, a loaded checkpoint or a state dict), or ``"random"`` for the randomly
@@ -301,16 +318,9 @@ def load_eval_encoder(src: Union[str, Path, Dict[str, Any]], model_cfg: Dict[str
     if isinstance(src, str) and src == "random":
         out = EvalEncoder("random", "random", "vit", vit=build_baseline_encoder(cfg, seed=73))
         return out.to(device) if device is not None else out
-    ckpt = torch.load(src, map_location="cpu", weights_only=False) if isinstance(src, (str, Path)) else src
-    state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
-    layout = checkpoint_layout(state)
+    ckpt, state, layout = _open_checkpoint(src)
     if layout == "ijepa_ckpt":
-        from .jepa import IJEPAPretrainModule
-        if "predictor" not in cfg:
-            raise ValueError("an I-JEPA checkpoint needs model.predictor in the config")
-        module = IJEPAPretrainModule(cfg, {})
-        module.load_checkpoint_dict({"state_dict": state})
-        out = EvalEncoder("ijepa", layout, encoder, ijepa=module.model)
+        out = EvalEncoder("ijepa", layout, encoder, ijepa=_ijepa_model(cfg, state))
     else:
         vit = encoder_mae(cfg).encoder.vit
         if layout == "ijepa_pt":
@@ -336,17 +346,10 @@ def load_ijepa_encoder(src: Union[str, Path, Dict[str, Any]], model_cfg: Dict[st
     if encoder not in ("target", "context"):
         raise ValueError(f"encoder must be 'target' or 'context', got {encoder!r}")
     cfg = _general(model_cfg, precision)
-    ckpt = torch.load(src, map_location="cpu", weights_only=False) if isinstance(src, (str, Path)) else src
-    state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
-    layout = checkpoint_layout(state)
+    _, state, layout = _open_checkpoint(src)
     if layout == "ijepa_ckpt":
-        from .jepa import IJEPAPretrainModule
-        if "predictor" not in cfg:
-            raise ValueError("an I-JEPA checkpoint needs model.predictor in the config")
-        module = IJEPAPretrainModule(cfg, {})
-        module.load_checkpoint_dict({"state_dict": state})
-        source = module.model.target_state_dict() if encoder == "target" else module.model.net.state_dict()
-        prefix = "encoder.vit."
+        model = _ijepa_model(cfg, state)
+        source, prefix = model.target_state_dict() if encoder == "target" else model.net.state_dict(), "encoder.vit."
     elif layout == "ijepa_pt":
         source, prefix = state, "target_encoder.vit." if encoder == "target" else "encoder.vit."
     else:
@@ -357,36 +360,31 @@ def load_ijepa_encoder(src: Union[str, Path, Dict[str, Any]], model_cfg: Dict[st
     return vit
 
 
+def _collect_split(batches, fn, max_samples: Optional[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fn(images) of every batch of a ``LabeledBatches`` split and its labels (n,) int64, on the device, in the split's order."""
+    outs, labels, n = [], [], 0
+    for imgs, lbls in batches():
+        outs.append(fn(imgs))
+        labels.append(lbls)
+        n += imgs.shape[0]
+        if max_samples is not None and n >= max_samples:
+            break
+    x, y = torch.cat(outs), torch.cat(labels)
+    if max_samples is not None:
+        x, y = x[:max_samples], y[:max_samples]
+    return x, y
+
+
 @torch.no_grad()
 def extract_split_features(enc: EvalEncoder, batches, pool: str = "cls", normalize: str = "none",
                            max_samples: Optional[int] = None, layers: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Features (n, D) fp32 -- with ``layers`` (n, len(layers), W), see ``EvalEncoder.features`` -- and labels (n,) int64 of a
     ``LabeledBatches`` split, on the device, in the split's order."""
-    feats, labels, n = [], [], 0
-    for imgs, lbls in batches():
-        feats.append(enc.features(imgs, pool=pool, normalize=normalize, layers=layers))
-        labels.append(lbls)
-        n += imgs.shape[0]
-        if max_samples is not None and n >= max_samples:
-            break
-    f, y = torch.cat(feats), torch.cat(labels)
-    if max_samples is not None:
-        f, y = f[:max_samples], y[:max_samples]
-    return f, y
+    return _collect_split(batches, lambda imgs: enc.features(imgs, pool=pool, normalize=normalize, layers=layers), max_samples)
 
 
 @torch.no_grad()
 def extract_split_tokens(enc: EvalEncoder, batches, drop_cls: bool = True, max_samples: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Tokens (n, T, D) fp32 and labels (n,) int64 of a ``LabeledBatches`` split, on the device, in the split's order: the cache an
     attentive probe trains on (n T D 4 bytes: 442 MB for 2000 ViT-S/8 images)."""
-    toks, labels, n = [], [], 0
-    for imgs, lbls in batches():
-        toks.append(enc.tokens(imgs, drop_cls=drop_cls))
-        labels.append(lbls)
-        n += imgs.shape[0]
-        if max_samples is not None and n >= max_samples:
-            break
-    t, y = torch.cat(toks), torch.cat(labels)
-    if max_samples is not None:
-        t, y = t[:max_samples], y[:max_samples]
-    return t, y
+    return _collect_split(batches, lambda imgs: enc.tokens(imgs, drop_cls=drop_cls), max_samples)

@@ -344,7 +344,7 @@ def pool_inits(c: PoolCase) -> dict:
 
 
 def pool_geo(D: int) -> ln_ref.Geo:
-    """The LayerNorm geometry of features_pool_kernel for ln_ref.fwd_bounds: a wave per row, four vectors per lane."""
+    """The LayerNorm geometry of features_kernel for ln_ref.fwd_bounds: a wave per row, four vectors per lane."""
     return ln_ref.Geo(rows=1, dim=D, lpr=64, nv=4, rpw=1, fwd_grid=1, bwd_grid=1, fwd_trips=1, bwd_trips=1, lds_floats=0, sp_blocks=0, sp_strided=0)
 
 

@@ -97,6 +97,29 @@ def test_subsets_and_early_exit(dev, precision):
     mae.engine.timers_enable(False)
 
 
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_block_0_alone_is_slice_0_of_every_block(dev, precision):
+    """The earliest stop: maps and features for layers=[0] hold the bits of slice 0 of the call for every block, from one block's launches."""
+    mae = build(dev, precision)
+    imgs = images_of(CFG, 3, True).to(dev)
+    for query, with_cls in QUERIES:
+        each = mae.extract_attention(imgs, layers=range(DEPTH), query=query, with_cls=with_cls)
+        first = mae.extract_attention(imgs, layers=[0], query=query, with_cls=with_cls)
+        assert first.shape == (3, 1, H, each.shape[-1]) and torch.equal(bits(first[:, 0]), bits(each[:, 0])), (query, with_cls)
+    for pool, norm in (("mean", "l2"), ("cls_mean", "none")):
+        each = mae.extract_features(imgs, pool=pool, normalize=norm, layers=range(DEPTH))
+        first = mae.extract_features(imgs, pool=pool, normalize=norm, layers=[0])
+        assert first.shape == (3, 1, each.shape[-1]) and torch.equal(bits(first[:, 0]), bits(each[:, 0])), (pool, norm)
+    mae.engine.timers_enable(True)
+    for call, attn in ((lambda: mae.extract_attention(imgs, layers=[0]), 1 + 1), (lambda: mae.extract_features(imgs, layers=[0]), 1)):
+        mae.engine.timers_reset()
+        call()
+        torch.cuda.synchronize()
+        t = mae.engine.timers_read()
+        assert t["attention_fwd"]["launches"] == attn and t["linear_nt"]["launches"] == 1 + 4, t   # the patch embedding and one block
+    mae.engine.timers_enable(False)
+
+
 # ------------------------------------------------------------------------------------------------------------------ 5
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_maps_and_rollout_match_the_oracle_walk(dev, precision):

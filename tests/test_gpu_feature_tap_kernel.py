@@ -1,7 +1,7 @@
-"""features_tap_kernel (k_representation.hip) through mae_features_tap against mae_features_pool and tests/engine_kernels_ref.py (-m gpu).
+"""features_kernel (k_representation.hip) through mae_features_tap against mae_features_pool and tests/engine_kernels_ref.py (-m gpu).
 
-The tap kernel is features_pool_kernel with a row stride on its output and a fourth pool, so its reference is that kernel's own
-output: every case of engine_kernels_ref.pool_cases() is written into slot 1 of a NaN-filled (B, 3, D + 4) buffer and must hold
+Both entries launch the one kernel: mae_features_tap picks the rows by (with_cls, pool), adds a row stride on the output and a fourth
+pool, so its reference is mae_features_pool's own output: every case of engine_kernels_ref.pool_cases() is written into slot 1 of a NaN-filled (B, 3, D + 4) buffer and must hold
 mae_features_pool's bits, stay inside expect_pool's bound, and leave slots 0 and 2 and the 4 padding columns NaN.  A case whose rows
 [lo, hi) are not a pool of the whole sequence (the class row, the patch rows, every row) runs image by image on the view of those
 rows as a patch-only sequence: mae_features_pool's result for an image does not depend on its batch (test_gpu_engine_kernels.py).
@@ -151,6 +151,24 @@ def test_image_does_not_depend_on_the_batch(dev, cid, pool):
         torch.cuda.synchronize()
         assert torch.equal(bits(one[0]), bits(whole[b])), f"image {b} alone differs from image {b} of {c.B}"
         assert torch.isnan(one[1]).all()
+
+
+@pytest.mark.parametrize("shape", [(5, 8), (2, 1024)], ids=lambda g: "s{}D{}".format(*g))
+def test_features_pool_takes_a_4_byte_aligned_out(dev, shape):
+    """mae_features_pool's out may start at any float (the 16-byte rule is mae_features_tap's): one float into a NaN-filled buffer,
+    at the narrowest and the widest row of the lane partition, it writes the aligned call's bits and nothing around them."""
+    s = stream(dev)
+    for c in (c for c in EXTRA.values() if (c.seq, c.D) == shape):
+        t = {k: up(v, dev) for k, v in R.gen_pool(c).items()}
+        for lo, hi in ((0, 1), (1, c.seq), (0, c.seq)):
+            want = pool_out(c, t, lo, hi, s, dev)
+            buf = torch.full((c.B * c.D + 8,), float("nan"), device=dev)
+            assert buf.data_ptr() % 16 == 0
+            check(lib.mae_features_pool(_ptr(t["x"]), _ptr(t["branch"]), DT[c.dtype], _ptr(t["gamma"]), _ptr(t["beta"]), R.EPS, c.B, c.seq, c.D, lo, hi,
+                                        int(c.l2), _ptr(buf[1:]), s))
+            torch.cuda.synchronize()
+            assert torch.equal(bits(buf[1:1 + c.B * c.D]), bits(want).view(-1)), (c.id, lo, hi)
+            assert torch.isnan(buf[:1]).all() and torch.isnan(buf[1 + c.B * c.D:]).all(), (c.id, lo, hi)
 
 
 def test_refused_call_writes_nothing(dev):

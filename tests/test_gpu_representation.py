@@ -115,6 +115,30 @@ def test_extraction_is_deterministic_and_guards_backward(dev):
         out.sum().backward()
 
 
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_plain_call_takes_a_4_byte_aligned_feats(dev, precision):
+    """mae_engine_extract_features writes wherever a float may start: feats one float into a NaN-filled buffer gives the bits of the
+    aligned call and leaves the floats around the written range NaN.  (The 16-byte rule belongs to the layer call alone.)"""
+    from ssrl_vit_mae_jepa_amd._lib import check, lib
+    from ssrl_vit_mae_jepa_amd.mae import FEATURE_NORMS, FEATURE_POOLS, _ptr, _stream
+    mae, _ = build_mae(dev, precision)
+    B, D = 3, MICRO.embed_dim
+    imgs = images_of(MICRO, B, True).to(dev)
+    need = lib.mae_engine_features_workspace_bytes(mae.engine.handle, B, 1)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    for pool in ("cls", "mean"):
+        for norm in ("none", "l2"):
+            want = mae.extract_features(imgs, pool=pool, normalize=norm)
+            buf = torch.full((B * D + 8,), float("nan"), device=dev)
+            assert buf.data_ptr() % 16 == 0
+            check(lib.mae_engine_extract_features(mae.engine.handle, _ptr(mae.flat_params), _ptr(mae._weights()), _ptr(imgs), mae._img_dt(imgs), B, 1,
+                                                  FEATURE_POOLS[pool], FEATURE_NORMS[norm], _ptr(ws), need, _ptr(buf[1:]), _stream(dev)))
+            torch.cuda.synchronize()
+            got = buf[1:1 + B * D].view(B, D)
+            assert torch.equal(got.view(torch.int32), want.view(torch.int32)), (pool, norm)
+            assert torch.isnan(buf[:1]).all() and torch.isnan(buf[1 + B * D:]).all(), (pool, norm)
+
+
 def test_classifier_rejects_mean_patches_pool(dev):
     from ssrl_vit_mae_jepa_amd import _lib
     from ssrl_vit_mae_jepa_amd._lib import lib

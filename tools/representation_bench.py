@@ -8,8 +8,8 @@
     torch.topk (a measurement-only baseline that materialises Q x N), with the achieved 2QND / t as a share of the
     157.3 TF fp32-MFMA peak.
   * with --layers "SPEC;SPEC;..." (part `layers`): ViT-S/8 features after encoder blocks (mae_engine_extract_layer_features, one entry
-    per SPEC of representation.parse_layers, e.g. "each;5") alternated with the plain last-block call, and the tap kernel alone
-    (mae_features_tap next to mae_features_pool on the same buffers) with its bytes/s.
+    per SPEC of representation.parse_layers, e.g. "each;5") alternated with the plain last-block call, and the feature kernel alone
+    (through mae_features_tap and through mae_features_pool on the same buffers) with its bytes/s.
   * part `attention`: ViT-S/8 attention maps (mae_engine_extract_attention) of the last block, of every block, and of the last block
     with rollout, alternated with the plain extract_features call; and the map kernel alone (mae_attention_colsum) with a dense and with
     a one-hot weight row on a random qkv of the engine's shape, next to the forward attention kernel (mae_attention_fwd) on the same
