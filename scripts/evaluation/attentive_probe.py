@@ -19,21 +19,20 @@ from __future__ import annotations
 
 import argparse
 import json
-import os
 import time
 from pathlib import Path
 
-import numpy as np
 import torch
 import yaml
 
+from scripts.evaluation import _probe_cli as C
+from scripts.evaluation._probe_cli import epoch_batches, save   # every batch is kept: one image is enough for a step
 from ssrl_vit_mae_jepa_amd.attentive import ATTENTIVE_DEFAULTS, TOKEN_SETS, AttentiveProbe, attentive_lr, parse_attentive_probe
-from ssrl_vit_mae_jepa_amd.data import STL10_DIR, get_test_batches, get_train_batches
+from ssrl_vit_mae_jepa_amd.data import STL10_DIR
 from ssrl_vit_mae_jepa_amd.training import lr_lambda
 
 HYPER_FLAGS = ("total_epochs", "warmup_epochs", "batch_size", "base_learning_rate", "weight_decay", "heads", "tokens", "bn_eps", "bn_momentum",
                "init_std", "head_init_std")
-EXTRACT_BATCH = 500   # images per encoder call while extracting
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -63,43 +62,7 @@ def parse_args(argv=None):
 
 def probe_config(cfg: dict, args) -> dict:
     """``attentive_probe:`` of the YAML with every given flag on top, checked; missing keys fall back to ATTENTIVE_DEFAULTS."""
-    block = dict(cfg.get("attentive_probe") or {})
-    for key in HYPER_FLAGS:
-        if getattr(args, key, None) is not None:
-            block[key] = getattr(args, key)
-    return parse_attentive_probe(block)
-
-
-def require_data(synthetic_images) -> None:
-    if synthetic_images is not None:
-        return
-    missing = [n for n in ("train_X.bin", "train_y.bin", "test_X.bin", "test_y.bin") if not (STL10_DIR / n).exists()]
-    if missing:
-        raise SystemExit(f"attentive_probe: the labeled STL-10 files ({STL10_DIR}/train_*.bin, test_*.bin) are missing; "
-                         "pass --synthetic_images N to run on synthetic images")
-
-
-def epoch_batches(n: int, batch: int, seed: int, epoch: int):
-    """Index arrays of the epoch's batches: a permutation of n drawn from (seed, epoch), cut into batches (the last may be short)."""
-    order = np.random.default_rng([int(seed), int(epoch)]).permutation(n)
-    return [order[i:i + batch] for i in range(0, n, batch)]
-
-
-def save(path: Path, obj) -> None:
-    tmp = path.with_suffix(path.suffix + ".tmp")
-    torch.save(obj, tmp)
-    os.replace(tmp, path)
-
-
-def _evaluate(probe: AttentiveProbe, tokens: torch.Tensor, labels: torch.Tensor, batch: int):
-    loss = torch.zeros((), dtype=torch.float64, device=tokens.device)
-    correct = torch.zeros((), dtype=torch.int64, device=tokens.device)
-    for i in range(0, tokens.shape[0], batch):
-        _, l, c = probe.evaluate(tokens[i:i + batch], labels[i:i + batch])
-        loss += l[0].double() * min(batch, tokens.shape[0] - i)
-        correct += c[0]
-    n = tokens.shape[0]
-    return float(loss) / n, int(correct) / n
+    return parse_attentive_probe(C.merge_flags(cfg.get("attentive_probe"), args, HYPER_FLAGS))
 
 
 def main(argv=None):
@@ -111,27 +74,13 @@ def main(argv=None):
     except ValueError as exc:
         raise SystemExit(f"attentive_probe: {exc}")
     model_cfg = cfg["model"]
-    if args.max_epochs is not None and args.max_epochs < 1:
-        raise SystemExit("attentive_probe: --max_epochs must be at least 1")
-    if args.checkpoint != "random" and not Path(args.checkpoint).exists():
-        raise SystemExit(f"attentive_probe: checkpoint {args.checkpoint} not found")
-    if args.resume is not None and not Path(args.resume).exists():
-        raise SystemExit(f"attentive_probe: --resume {args.resume} not found")
-    require_data(args.synthetic_images)
-    if not torch.cuda.is_available():
-        raise SystemExit("attentive_probe: the MI355X engine has no CPU fallback")
+    C.check_args("attentive_probe", args, STL10_DIR)
     from ssrl_vit_mae_jepa_amd.representation import extract_split_tokens, load_eval_encoder
     dev = torch.device("cuda", 0)
     seed = int(cfg.get("seed", 73))
     batch = pcfg["batch_size"]
 
-    train_cfg = dict(cfg.get("train") or {}, batch_size=EXTRACT_BATCH)
-    if args.samples_per_class is not None:
-        train_cfg["samples_per_class"] = int(args.samples_per_class)
-    data_cfg = dict(cfg, train=train_cfg, test=dict(cfg.get("test") or {}, batch_size=EXTRACT_BATCH))
-    train_b, val_b = get_train_batches(data_cfg, dev, synthetic_images=args.synthetic_images)
-    train_b.shuffle = False   # the cache keeps the split's order; the probe shuffles the cached images itself
-    test_b = get_test_batches(data_cfg, dev, synthetic_images=None if args.synthetic_images is None else max(1, args.synthetic_images * 2 // 5))
+    _, train_b, val_b, test_b = C.labeled_batches(cfg, args, dev)
 
     precision = cfg.get("engine", {}).get("precision")
     enc = load_eval_encoder(args.checkpoint, model_cfg, encoder=args.encoder, precision=precision, device=dev)
@@ -157,7 +106,10 @@ def main(argv=None):
     best = dict(val_acc=-1.0, epoch=-1, test_acc=None, test_loss=None)
     if args.resume is not None:
         state = torch.load(args.resume, map_location="cpu", weights_only=False)
-        probe.load_state_dict(state["probe"])
+        try:
+            probe.load_state_dict(state["probe"])
+        except ValueError as exc:
+            raise SystemExit(f"attentive_probe: --resume: {exc}")
         start_epoch = probe.epoch
         best = dict(state.get("best") or best)   # attnprobe_best.pt is replaced only by a better epoch
     out_dir = Path(args.output_dir) if args.output_dir else Path(cfg.get("logging", {}).get("output_dir_base", "outputs")) / "attnprobe" / args.output_dir_suffix
@@ -168,25 +120,14 @@ def main(argv=None):
     metrics = (out_dir / "metrics.jsonl").open("a" if args.resume else "w")
     for epoch in range(start_epoch, end_epoch):
         lr = peak * lr_lambda(epoch, pcfg["warmup_epochs"], pcfg["total_epochs"])
-        loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
-        correct_sum = torch.zeros((), dtype=torch.int64, device=dev)
-        rows = 0
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for idx in epoch_batches(n, batch, seed, epoch):
-            j = torch.from_numpy(idx).to(dev)
-            loss, correct = probe.step(train_t[j], train_y[j], lr)
-            loss_sum += loss[0].double() * len(idx)
-            correct_sum += correct[0]
-            rows += len(idx)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
+        loss_sum, correct_sum, rows, dt = C.run_steps(epoch_batches(n, batch, seed, epoch), lambda i, j: (train_t[j], train_y[j]),
+                                                      lambda t, y: probe.step(t, y, lr), dev)
         probe.epoch = epoch + 1
-        val_loss, val_acc = _evaluate(probe, val_t, val_y, batch)
+        (val_loss,), (val_acc,) = C.evaluate_split(probe, val_t, val_y, batch)
         line = dict(epoch=epoch, train_loss=float(loss_sum) / max(rows, 1), train_acc=int(correct_sum) / max(rows, 1), val_loss=val_loss,
                     val_acc=val_acc, lr=lr, images_per_s=rows / max(dt, 1e-9))
         if val_acc > best["val_acc"]:
-            test_loss, test_acc = _evaluate(probe, test_t, test_y, batch)
+            (test_loss,), (test_acc,) = C.evaluate_split(probe, test_t, test_y, batch)
             best = dict(val_acc=val_acc, epoch=epoch, test_acc=test_acc, test_loss=test_loss)
             save(out_dir / "attnprobe_best.pt", dict(probe=probe.state_dict(), best=best, epoch=epoch + 1))
         line["test_acc"] = best["test_acc"]

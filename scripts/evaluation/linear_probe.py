@@ -35,7 +35,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import os
 import time
 from pathlib import Path
 
@@ -43,14 +42,15 @@ import numpy as np
 import torch
 import yaml
 
-from ssrl_vit_mae_jepa_amd.data import STL10_DIR, augment_to_size, draw_augment_params, get_test_batches, get_train_batches, labeled_serving
+from scripts.evaluation import _probe_cli as C
+from scripts.evaluation._probe_cli import EXTRACT_BATCH, save
+from ssrl_vit_mae_jepa_amd.data import STL10_DIR, augment_to_size, draw_augment_params, labeled_serving
 from ssrl_vit_mae_jepa_amd.probe import (AUGMENTS, PROBE_DEFAULTS, LinearProbe, ProbeSweep, classifier_pool, parse_probe, parse_sweep, probe_lr,
                                          select)
 from ssrl_vit_mae_jepa_amd.training import lr_lambda
 
 HYPER_FLAGS = ("total_epochs", "warmup_epochs", "batch_size", "base_learning_rate", "weight_decay", "momentum", "trust_coefficient", "bn_eps",
                "bn_momentum", "head_init_std", "augment")
-EXTRACT_BATCH = 500   # images per encoder call while extracting
 PROBE_MAX_DIM = 1024  # columns the probe kernels take (probe.ProbeHead)
 
 
@@ -86,37 +86,12 @@ def parse_args(argv=None):
 
 def probe_config(cfg: dict, args) -> dict:
     """``probe:`` of the YAML with every given flag on top, checked."""
-    block = dict(cfg.get("probe") or {})
-    for key in HYPER_FLAGS:
-        if getattr(args, key, None) is not None:
-            block[key] = getattr(args, key)
-    return parse_probe(block)
-
-
-def require_data(synthetic_images) -> None:
-    if synthetic_images is not None:
-        return
-    missing = [n for n in ("train_X.bin", "train_y.bin", "test_X.bin", "test_y.bin") if not (STL10_DIR / n).exists()]
-    if missing:
-        raise SystemExit(f"linear_probe: the labeled STL-10 files ({STL10_DIR}/train_*.bin, test_*.bin) are missing; "
-                         "pass --synthetic_images N to run on synthetic images")
-
-
-def epoch_order(n: int, seed: int, epoch: int) -> np.ndarray:
-    """The epoch's shuffle: a permutation of n drawn from (seed, epoch)."""
-    return np.random.default_rng([int(seed), int(epoch)]).permutation(n)
+    return parse_probe(C.merge_flags(cfg.get("probe"), args, HYPER_FLAGS))
 
 
 def epoch_batches(n: int, batch: int, seed: int, epoch: int):
-    """Index arrays of the epoch's batches; the last partial batch is used only if it has at least 2 rows."""
-    order = epoch_order(n, seed, epoch)
-    return [order[i:i + batch] for i in range(0, n, batch) if len(order[i:i + batch]) >= 2]
-
-
-def save(path: Path, obj) -> None:
-    tmp = path.with_suffix(path.suffix + ".tmp")
-    torch.save(obj, tmp)
-    os.replace(tmp, path)
+    """Index arrays of the epoch's batches; the last partial batch is used only if it has at least 2 rows (BatchNorm needs two)."""
+    return C.epoch_batches(n, batch, seed, epoch, min_rows=2)
 
 
 def _features(enc, images: torch.Tensor, pool: str, layers=None) -> torch.Tensor:
@@ -144,121 +119,6 @@ def probe_layers(spec, model_cfg: dict, pool: str):
     return layers, width
 
 
-def _evaluate(probe: LinearProbe, feats: torch.Tensor, labels: torch.Tensor, batch: int):
-    loss = torch.zeros((), dtype=torch.float64, device=feats.device)
-    correct = torch.zeros((), dtype=torch.int64, device=feats.device)
-    for i in range(0, feats.shape[0], batch):
-        _, l, c = probe.evaluate(feats[i:i + batch], labels[i:i + batch])
-        loss += l[0].double() * min(batch, feats.shape[0] - i)
-        correct += c[0]
-    n = feats.shape[0]
-    return float(loss) / n, int(correct) / n
-
-
-def _evaluate_sweep(sweep: ProbeSweep, feats: torch.Tensor, labels: torch.Tensor, batch: int):
-    """(loss, accuracy) per head over the split: two lists of len(sweep)."""
-    loss = torch.zeros(len(sweep), dtype=torch.float64, device=feats.device)
-    correct = torch.zeros(len(sweep), dtype=torch.int64, device=feats.device)
-    for i in range(0, feats.shape[0], batch):
-        _, l, c = sweep.evaluate(feats[i:i + batch], labels[i:i + batch])
-        loss += l.double() * min(batch, feats.shape[0] - i)
-        correct += c
-    n = feats.shape[0]
-    return (loss / n).tolist(), (correct.double() / n).tolist()
-
-
-def _run_sweep(args, cfg, pcfg, grid, enc, pool, layers, dim, num_classes, seed, data, dev):
-    """The training loop with a grid of heads: the same epochs, batches and schedule shape as the single probe; every step's features
-    are formed once and shared by all heads, validation is evaluated for all heads every epoch and test whenever a head improves."""
-    model_cfg, batch, crop = cfg["model"], pcfg["batch_size"], pcfg["augment"] == "crop"
-    train_images, train_f, train_y = data["train_images"], data["train_f"], data["train_y"]
-    val_f, val_y, test_f, test_y = data["val_f"], data["val_y"], data["test_f"], data["test_y"]
-    n, G = int(train_y.shape[0]), len(grid)
-    sweep = ProbeSweep(dim, num_classes, grid, pcfg, seed=seed, device=dev)
-    start_epoch = 0
-    best = [dict(val_acc=-1.0, val_loss=None, epoch=-1, test_acc=None, test_loss=None) for _ in range(G)]
-    if args.resume is not None:
-        state = torch.load(args.resume, map_location="cpu", weights_only=False)
-        if "grid" not in state:
-            raise SystemExit(f"linear_probe: --resume {args.resume} holds a single probe, this run asks for a sweep of {G} heads")
-        if list(state.get("layers") or []) != list(layers or []) or (layers is not None and state.get("pool") != pool):
-            raise SystemExit(f"linear_probe: --resume state was trained on layers {state.get('layers')} pool {state.get('pool')}, "
-                             f"this run asks for layers {None if layers is None else list(layers)} pool {pool}")
-        try:
-            sweep.load_state_dict(state)
-        except ValueError as exc:
-            raise SystemExit(f"linear_probe: --resume: {exc}")
-        start_epoch = sweep.epoch
-        best = [dict(b) for b in state["best"]]
-    out_dir = Path(cfg.get("logging", {}).get("output_dir_base", "outputs")) / "probe" / args.output_dir_suffix
-    (out_dir / "checkpoints").mkdir(parents=True, exist_ok=True)
-    (out_dir / "logs").mkdir(parents=True, exist_ok=True)
-    axes = {k: list(dict.fromkeys(g[k] for g in grid)) for k in ("base_learning_rate", "weight_decay")}
-    (out_dir / "config.yaml").write_text(yaml.safe_dump(dict(cfg, probe=pcfg, probe_sweep=axes)))
-    end_epoch = pcfg["total_epochs"] if args.max_epochs is None else min(pcfg["total_epochs"], start_epoch + args.max_epochs)
-    winner = lambda: select([b["val_acc"] for b in best], [float("inf") if b["val_loss"] is None else b["val_loss"] for b in best])
-    metrics = (out_dir / "logs" / "metrics.jsonl").open("a" if args.resume else "w")
-    for epoch in range(start_epoch, end_epoch):
-        factor = lr_lambda(epoch, pcfg["warmup_epochs"], pcfg["total_epochs"])
-        loss_sum = torch.zeros(G, dtype=torch.float64, device=dev)
-        correct_sum = torch.zeros(G, dtype=torch.int64, device=dev)
-        rows = 0
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for step, idx in enumerate(epoch_batches(n, batch, seed, epoch)):
-            j = torch.from_numpy(idx).to(dev)
-            if crop:
-                imgs = train_images[j].contiguous()
-                g = torch.Generator().manual_seed(int(np.random.SeedSequence([seed, epoch, step]).generate_state(1)[0]))
-                feats = _features(enc, augment_to_size(imgs, data["crop_size"], draw_augment_params(imgs.shape[0], imgs.shape[2], g), data["crop_dtype"]),
-                                  pool, layers)
-            else:
-                feats = train_f[j]
-            loss, correct = sweep.step(feats, train_y[j], factor)
-            loss_sum += loss.double() * len(idx)
-            correct_sum += correct
-            rows += len(idx)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        sweep.epoch = epoch + 1
-        val_loss, val_acc = _evaluate_sweep(sweep, val_f, val_y, batch)
-        leader = select(val_acc, val_loss)   # this epoch's
-        line = dict(epoch=epoch, train_loss=(loss_sum / max(rows, 1)).tolist(), train_acc=(correct_sum.double() / max(rows, 1)).tolist(),
-                    val_loss=val_loss, val_acc=val_acc, lr=[float(x) for x in sweep.head_lrs(factor)], leader=leader, images_per_s=rows / max(dt, 1e-9))
-        metrics.write(json.dumps(line) + "\n")
-        metrics.flush()
-        print(json.dumps(line))
-        improved = [g for g in range(G) if val_acc[g] > best[g]["val_acc"]]
-        if improved:
-            test_loss, test_acc = _evaluate_sweep(sweep, test_f, test_y, batch)
-            for g in improved:
-                best[g] = dict(val_acc=val_acc[g], val_loss=val_loss[g], epoch=epoch, test_acc=test_acc[g], test_loss=test_loss[g])
-        if layers is None:   # as for the single probe: a head on several blocks is no classifier head
-            save(out_dir / "checkpoints" / "last.ckpt", sweep.export(leader).classifier_checkpoint(enc, model_cfg, pool, epoch=epoch))
-            w = winner()
-            if w in improved:   # the winner's entry is of this epoch (an entry changes only by improving, so no other head can take over)
-                save(out_dir / "checkpoints" / "best.ckpt", sweep.export(w).classifier_checkpoint(enc, model_cfg, pool, epoch=epoch))
-        extra = {} if layers is None else dict(layers=list(layers), pool=pool)
-        save(out_dir / "checkpoints" / "probe_last.pt", dict(sweep.state_dict(), best=best, **extra))
-    metrics.close()
-    w = winner()
-    heads = [dict(index=g, base_learning_rate=grid[g]["base_learning_rate"], weight_decay=grid[g]["weight_decay"],
-                  peak_lr=probe_lr(dict(pcfg, **grid[g])), best_val_acc=best[g]["val_acc"], best_val_loss=best[g]["val_loss"],
-                  best_epoch=best[g]["epoch"], test_acc=best[g]["test_acc"], test_loss=best[g]["test_loss"]) for g in range(G)]
-    (out_dir / "sweep.json").write_text(json.dumps(dict(winner=w, heads=heads)) + "\n")
-    res = dict(checkpoint=args.checkpoint, kind=enc.kind, encoder=enc.encoder, pool=pool,
-               classifier_pool=classifier_pool(pool, enc.with_cls) if layers is None else None,
-               augment=pcfg["augment"], epochs=end_epoch, train_size=n, val_size=int(val_f.shape[0]), test_size=int(test_f.shape[0]),
-               best_epoch=best[w]["epoch"], val_acc=best[w]["val_acc"], test_acc=best[w]["test_acc"], test_loss=best[w]["test_loss"],
-               peak_lr=heads[w]["peak_lr"], extract_s=data["extract_s"], sweep_index=w, sweep_heads=G,
-               base_learning_rate=grid[w]["base_learning_rate"], weight_decay=grid[w]["weight_decay"])
-    if layers is not None:
-        res["layers"] = list(layers)
-    (out_dir / "probe.json").write_text(json.dumps(res) + "\n")
-    print(json.dumps(res))
-    return res
-
-
 def main(argv=None):
     args = parse_args(argv)
     with open(args.config, "r") as f:
@@ -271,40 +131,20 @@ def main(argv=None):
     model_cfg = cfg["model"]
     is_ijepa = "predictor" in model_cfg
     pool = args.pool or ("mean" if is_ijepa else "cls")
-    if is_ijepa and pool == "cls":
-        raise SystemExit("linear_probe: I-JEPA encoders see no class token: --pool must be mean or mean_all")
-    if is_ijepa and pool == "cls_mean":
+    if is_ijepa and pool in ("cls", "cls_mean"):
         raise SystemExit("linear_probe: I-JEPA encoders see no class token: --pool must be mean or mean_all")
     layers, width = probe_layers(args.layers, model_cfg, pool)   # before any data or checkpoint is loaded
-    if args.max_epochs is not None and args.max_epochs < 1:
-        raise SystemExit("linear_probe: --max_epochs must be at least 1")
-    if args.checkpoint != "random" and not Path(args.checkpoint).exists():
-        raise SystemExit(f"linear_probe: checkpoint {args.checkpoint} not found")
-    if args.resume is not None and not Path(args.resume).exists():
-        raise SystemExit(f"linear_probe: --resume {args.resume} not found")
-    require_data(args.synthetic_images)
-    if not torch.cuda.is_available():
-        raise SystemExit("linear_probe: the MI355X engine has no CPU fallback")
+    C.check_args("linear_probe", args, STL10_DIR)
     from ssrl_vit_mae_jepa_amd.representation import extract_split_features, load_eval_encoder
     dev = torch.device("cuda", 0)
     seed = int(cfg.get("seed", 73))
     batch = pcfg["batch_size"]
-
-    train_cfg = dict(cfg.get("train") or {}, batch_size=EXTRACT_BATCH)
-    if args.samples_per_class is not None:
-        train_cfg["samples_per_class"] = int(args.samples_per_class)
-    data_cfg = dict(cfg, train=train_cfg, test=dict(cfg.get("test") or {}, batch_size=EXTRACT_BATCH))
-    train_b, val_b = get_train_batches(data_cfg, dev, synthetic_images=args.synthetic_images)
-    train_b.shuffle = False   # the cache keeps the split's order; the probe shuffles the cached rows itself
-    test_b = get_test_batches(data_cfg, dev, synthetic_images=None if args.synthetic_images is None else max(1, args.synthetic_images * 2 // 5))
+    data_cfg, train_b, val_b, test_b = C.labeled_batches(cfg, args, dev)
 
     precision = cfg.get("engine", {}).get("precision")
     enc = load_eval_encoder(args.checkpoint, model_cfg, encoder=args.encoder, precision=precision, device=dev)
     try:
-        if pool == "cls_mean":
-            classifier_pool("cls", enc.with_cls)   # the same rule: it needs the class token
-        else:
-            classifier_pool(pool, enc.with_cls)
+        classifier_pool("cls" if pool == "cls_mean" else pool, enc.with_cls)   # cls_mean follows the rule of cls: it needs the class token
     except ValueError as exc:
         raise SystemExit(f"linear_probe: {exc}")
 
@@ -326,76 +166,93 @@ def main(argv=None):
     if n < 2 or val_f.shape[0] < 1:
         raise SystemExit(f"linear_probe: {n} training and {val_f.shape[0]} validation rows are too few")
     num_classes = int(max(int(train_y.max()), int(val_y.max()), int(test_y.max()))) + 1
-    if grid is not None:
-        data = dict(train_images=train_images, train_f=train_f, train_y=train_y, val_f=val_f, val_y=val_y, test_f=test_f, test_y=test_y,
-                    crop_size=crop_size, crop_dtype=crop_dtype, extract_s=extract_s)
-        return _run_sweep(args, cfg, pcfg, grid, enc, pool, layers, enc.embed_dim if layers is None else width, num_classes, seed, data, dev)
 
-    probe = LinearProbe(enc.embed_dim if layers is None else width, num_classes, pcfg, seed=seed, device=dev)
+    # One loop for the probe and the sweep, on per-head lists throughout (a single probe is one head).  The two differ in the object
+    # built, in what step() is handed, in the resume refusals and in what is written: lists and the sweep's extra keys with a grid,
+    # scalars without.
+    sweep = grid is not None
+    heads = [dict(pcfg, **g) for g in grid] if sweep else [pcfg]   # every head's hyper-parameters
+    G, peaks = len(heads), [probe_lr(h) for h in heads]
+    dim = enc.embed_dim if layers is None else width
+    probe = ProbeSweep(dim, num_classes, grid, pcfg, seed=seed, device=dev) if sweep else LinearProbe(dim, num_classes, pcfg, seed=seed, device=dev)
+    written = (lambda v: v) if sweep else (lambda v: v[0])
     start_epoch = 0
-    best = dict(val_acc=-1.0, epoch=-1, test_acc=None, test_loss=None)
+    best = [dict(val_acc=-1.0, val_loss=None, epoch=-1, test_acc=None, test_loss=None) for _ in range(G)]
     if args.resume is not None:
         state = torch.load(args.resume, map_location="cpu", weights_only=False)
-        if "grid" in state:
+        if sweep and "grid" not in state:
+            raise SystemExit(f"linear_probe: --resume {args.resume} holds a single probe, this run asks for a sweep of {G} heads")
+        if not sweep and "grid" in state:
             raise SystemExit(f"linear_probe: --resume {args.resume} holds a sweep of {len(state['grid'])} heads; pass its grid (--sweep_lr / --sweep_wd)")
         if list(state.get("layers") or []) != list(layers or []) or (layers is not None and state.get("pool") != pool):
             raise SystemExit(f"linear_probe: --resume state was trained on layers {state.get('layers')} pool {state.get('pool')}, "
                              f"this run asks for layers {None if layers is None else list(layers)} pool {pool}")
-        probe.load_state_dict(state)
+        try:
+            probe.load_state_dict(state)
+        except ValueError as exc:
+            raise SystemExit(f"linear_probe: --resume: {exc}")
         start_epoch = probe.epoch
-        best = dict(state.get("best") or best)   # best.ckpt is replaced only by a better epoch
+        best = [dict(b) for b in state["best"]] if sweep else [dict(state.get("best") or best[0])]   # best.ckpt is replaced only by a better epoch
     out_dir = Path(cfg.get("logging", {}).get("output_dir_base", "outputs")) / "probe" / args.output_dir_suffix
     (out_dir / "checkpoints").mkdir(parents=True, exist_ok=True)
     (out_dir / "logs").mkdir(parents=True, exist_ok=True)
-    (out_dir / "config.yaml").write_text(yaml.safe_dump(dict(cfg, probe=pcfg)))
-    peak = probe_lr(pcfg)
+    axes = {k: list(dict.fromkeys(g[k] for g in grid)) for k in ("base_learning_rate", "weight_decay")} if sweep else None
+    (out_dir / "config.yaml").write_text(yaml.safe_dump(dict(cfg, probe=pcfg, probe_sweep=axes) if sweep else dict(cfg, probe=pcfg)))
     end_epoch = pcfg["total_epochs"] if args.max_epochs is None else min(pcfg["total_epochs"], start_epoch + args.max_epochs)
+    winner = lambda: select([b["val_acc"] for b in best], [float("inf") if b.get("val_loss") is None else b["val_loss"] for b in best])
+    as_probe = lambda g: probe.export(g) if sweep else probe   # head g as a LinearProbe, for its classifier checkpoint
+    written_best = lambda: best if sweep else {k: v for k, v in best[0].items() if k != "val_loss"}   # the single probe's entry has no val_loss
     metrics = (out_dir / "logs" / "metrics.jsonl").open("a" if args.resume else "w")
     for epoch in range(start_epoch, end_epoch):
-        lr = peak * lr_lambda(epoch, pcfg["warmup_epochs"], pcfg["total_epochs"])
-        loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
-        correct_sum = torch.zeros((), dtype=torch.int64, device=dev)
-        rows = 0
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for step, idx in enumerate(epoch_batches(n, batch, seed, epoch)):
-            j = torch.from_numpy(idx).to(dev)
-            if crop:
-                imgs = train_images[j].contiguous()
-                g = torch.Generator().manual_seed(int(np.random.SeedSequence([seed, epoch, step]).generate_state(1)[0]))
-                feats = _features(enc, augment_to_size(imgs, crop_size, draw_augment_params(imgs.shape[0], imgs.shape[2], g), crop_dtype), pool, layers)
-            else:
-                feats = train_f[j]
-            loss, correct = probe.step(feats, train_y[j], lr)
-            loss_sum += loss[0].double() * len(idx)
-            correct_sum += correct[0]
-            rows += len(idx)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
+        factor = lr_lambda(epoch, pcfg["warmup_epochs"], pcfg["total_epochs"])
+        lr = factor if sweep else peaks[0] * factor   # ProbeSweep.step scales every head's own peak itself; LinearProbe.step takes the rate
+
+        def gather(step, j):   # the batch's features: cached, or re-extracted from a fresh crop of its images
+            if not crop:
+                return train_f[j], train_y[j]
+            imgs = train_images[j].contiguous()
+            g = torch.Generator().manual_seed(int(np.random.SeedSequence([seed, epoch, step]).generate_state(1)[0]))
+            return _features(enc, augment_to_size(imgs, crop_size, draw_augment_params(imgs.shape[0], imgs.shape[2], g), crop_dtype), pool, layers), train_y[j]
+
+        loss_sum, correct_sum, rows, dt = C.run_steps(epoch_batches(n, batch, seed, epoch), gather, lambda f, y: probe.step(f, y, lr), dev)
         probe.epoch = epoch + 1
-        val_loss, val_acc = _evaluate(probe, val_f, val_y, batch)
-        line = dict(epoch=epoch, train_loss=float(loss_sum) / max(rows, 1), train_acc=int(correct_sum) / max(rows, 1), val_loss=val_loss,
-                    val_acc=val_acc, lr=lr, images_per_s=rows / max(dt, 1e-9))
+        val_loss, val_acc = C.evaluate_split(probe, val_f, val_y, batch)
+        leader = select(val_acc, val_loss)   # this epoch's
+        line = dict(epoch=epoch, train_loss=written([v / max(rows, 1) for v in loss_sum.tolist()]),
+                    train_acc=written([v / max(rows, 1) for v in correct_sum.tolist()]), val_loss=written(val_loss), val_acc=written(val_acc),
+                    lr=[float(x) for x in probe.head_lrs(factor)] if sweep else lr)
+        if sweep:
+            line["leader"] = leader
+        line["images_per_s"] = rows / max(dt, 1e-9)
         metrics.write(json.dumps(line) + "\n")
         metrics.flush()
         print(json.dumps(line))
-        # a head on several blocks is no classifier head (the classifier reads the last block alone): no classifier checkpoint then
-        ckpt = probe.classifier_checkpoint(enc, model_cfg, pool, epoch=epoch) if layers is None else None
-        if ckpt is not None:
+        improved = [g for g in range(G) if val_acc[g] > best[g]["val_acc"]]
+        if improved:   # the test split is evaluated whenever a head improves
+            test_loss, test_acc = C.evaluate_split(probe, test_f, test_y, batch)
+            for g in improved:
+                best[g] = dict(val_acc=val_acc[g], val_loss=val_loss[g], epoch=epoch, test_acc=test_acc[g], test_loss=test_loss[g])
+        if layers is None:   # a head on several blocks is no classifier head (the classifier reads the last block alone): no classifier checkpoint then
+            ckpt = as_probe(leader).classifier_checkpoint(enc, model_cfg, pool, epoch=epoch)
             save(out_dir / "checkpoints" / "last.ckpt", ckpt)
-        if val_acc > best["val_acc"]:
-            test_loss, test_acc = _evaluate(probe, test_f, test_y, batch)
-            best = dict(val_acc=val_acc, epoch=epoch, test_acc=test_acc, test_loss=test_loss)
-            if ckpt is not None:
-                save(out_dir / "checkpoints" / "best.ckpt", ckpt)
+            w = winner()
+            if w in improved:   # the winner's entry is of this epoch (an entry changes only by improving, so no other head can take over)
+                save(out_dir / "checkpoints" / "best.ckpt", ckpt if w == leader else as_probe(w).classifier_checkpoint(enc, model_cfg, pool, epoch=epoch))
         extra = {} if layers is None else dict(layers=list(layers), pool=pool)
-        save(out_dir / "checkpoints" / "probe_last.pt", dict(probe.state_dict(), best=best, **extra))
+        save(out_dir / "checkpoints" / "probe_last.pt", dict(probe.state_dict(), best=written_best(), **extra))
     metrics.close()
+    w = winner()
     res = dict(checkpoint=args.checkpoint, kind=enc.kind, encoder=enc.encoder, pool=pool,
                classifier_pool=classifier_pool(pool, enc.with_cls) if layers is None else None,
-               augment=pcfg["augment"], epochs=end_epoch, train_size=int(n), val_size=int(val_f.shape[0]), test_size=int(test_f.shape[0]),
-               best_epoch=best["epoch"], val_acc=best["val_acc"], test_acc=best["test_acc"], test_loss=best["test_loss"], peak_lr=peak,
-               extract_s=extract_s)
+               augment=pcfg["augment"], epochs=end_epoch, train_size=n, val_size=int(val_f.shape[0]), test_size=int(test_f.shape[0]),
+               best_epoch=best[w]["epoch"], val_acc=best[w]["val_acc"], test_acc=best[w]["test_acc"], test_loss=best[w]["test_loss"],
+               peak_lr=peaks[w], extract_s=extract_s)
+    if sweep:
+        table = [dict(index=g, base_learning_rate=grid[g]["base_learning_rate"], weight_decay=grid[g]["weight_decay"], peak_lr=peaks[g],
+                      best_val_acc=best[g]["val_acc"], best_val_loss=best[g]["val_loss"], best_epoch=best[g]["epoch"], test_acc=best[g]["test_acc"],
+                      test_loss=best[g]["test_loss"]) for g in range(G)]
+        (out_dir / "sweep.json").write_text(json.dumps(dict(winner=w, heads=table)) + "\n")
+        res.update(sweep_index=w, sweep_heads=G, base_learning_rate=grid[w]["base_learning_rate"], weight_decay=grid[w]["weight_decay"])
     if layers is not None:
         res["layers"] = list(layers)
     (out_dir / "probe.json").write_text(json.dumps(res) + "\n")

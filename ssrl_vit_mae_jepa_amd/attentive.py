@@ -20,10 +20,10 @@ from typing import Any, Dict, Optional, Tuple
 
 import torch
 
-from . import _lib
 from ._lib import check, lib
 from .classifier import MAX_CLASSES, _pad4, _trunc_normal
 from .mae import Engine, _ptr, _stream
+from .probe import _Probe, parse_block, probe_lr
 
 ATTENTIVE_DEFAULTS: Dict[str, Any] = {
     "total_epochs": 90, "warmup_epochs": 10, "batch_size": 256, "base_learning_rate": 1e-3, "weight_decay": 0.05, "heads": None,
@@ -36,20 +36,8 @@ MAX_HEADS = 16
 def parse_attentive_probe(block: Optional[Dict[str, Any]]) -> Dict[str, Any]:
     """The YAML block ``attentive_probe:`` checked and completed with ``ATTENTIVE_DEFAULTS``; an unknown key is refused by name.
     ``heads: null`` means the encoder's head count (the caller fills it in)."""
-    block = block or {}
-    if not isinstance(block, dict):
-        raise ValueError(f"attentive_probe must be a mapping, got {block!r}")
-    unknown = set(block) - set(ATTENTIVE_DEFAULTS)
-    if unknown:
-        raise ValueError(f"attentive_probe: unknown keys {sorted(unknown)}")
-    out = dict(ATTENTIVE_DEFAULTS)
-    for k, v in block.items():
-        if v is not None:
-            out[k] = v
-    for k in ("total_epochs", "warmup_epochs", "batch_size"):
-        out[k] = int(out[k])
-    for k in ("base_learning_rate", "weight_decay", "bn_eps", "bn_momentum", "init_std", "head_init_std", "beta1", "beta2", "adam_eps"):
-        out[k] = float(out[k])
+    out = parse_block(block, ATTENTIVE_DEFAULTS, "attentive_probe", ("total_epochs", "warmup_epochs", "batch_size"),
+                      ("base_learning_rate", "weight_decay", "bn_eps", "bn_momentum", "init_std", "head_init_std", "beta1", "beta2", "adam_eps"))
     if out["heads"] is not None:
         out["heads"] = int(out["heads"])
         if not 1 <= out["heads"] <= MAX_HEADS:
@@ -65,9 +53,7 @@ def parse_attentive_probe(block: Optional[Dict[str, Any]]) -> Dict[str, Any]:
     return out
 
 
-def attentive_lr(cfg: Dict[str, Any]) -> float:
-    """The peak learning rate: base_learning_rate * batch_size / 256."""
-    return float(cfg["base_learning_rate"]) * int(cfg["batch_size"]) / 256.0
+attentive_lr = probe_lr   # the peak learning rate: base_learning_rate * batch_size / 256
 
 
 def layout(dim: int, num_classes: int) -> Dict[str, Tuple[int, int]]:
@@ -93,7 +79,7 @@ def _opt_engine() -> Engine:
     return _OPT_ENGINE
 
 
-class AttentiveProbe:
+class AttentiveProbe(_Probe):
     """The probe's state (one flat fp32 parameter buffer, the BatchNorm running statistics, the AdamW moments, gradient and scratch
     buffers) and its operations.  ``cfg``: a ``parse_attentive_probe`` result (or a subset of its keys); tokens are (B, T, dim) fp32 on
     the device."""
@@ -159,68 +145,26 @@ class AttentiveProbe:
     def device(self) -> torch.device:
         return self.flat.device
 
-    # ---- buffers -------------------------------------------------------------------------------------------------
-    def _bytes(self, key: str, need: int) -> torch.Tensor:
-        buf = self._scratch.get(key)
-        if buf is None or buf.numel() < need or buf.device != self.device:
-            buf = self._scratch[key] = torch.empty(max(int(need), 16), dtype=torch.uint8, device=self.device)
-        return buf
-
-    def _f32(self, key: str, *shape: int) -> torch.Tensor:
-        n = 1
-        for s in shape:
-            n *= int(s)
-        return self._bytes(key, 4 * n)[:4 * n].view(torch.float32).view(*shape)
-
-    def _check_tokens(self, tokens: torch.Tensor, labels: Optional[torch.Tensor]):
-        if not tokens.is_cuda:
-            raise RuntimeError("the attentive probe's kernels run on the MI355X only (move the tokens to cuda)")
-        if self.device != tokens.device:
-            raise RuntimeError("AttentiveProbe: move the probe to the tokens' device with .to(device)")
-        if tokens.dim() != 3 or tokens.shape[2] != self.dim:
-            raise ValueError(f"tokens must be (B, T, {self.dim}), got {tuple(tokens.shape)}")
-        tokens = tokens.to(dtype=torch.float32).contiguous()
-        if labels is not None:
-            labels = labels.to(device=tokens.device, dtype=torch.int64).contiguous().view(-1)
-            if labels.numel() != tokens.shape[0]:
-                raise ValueError(f"{labels.numel()} labels for {tokens.shape[0]} images")
-        return tokens, labels
+    _INPUT = ("the attentive probe's", "AttentiveProbe", "tokens", ("B", "T"), "images")
 
     # ---- the forward pass ----------------------------------------------------------------------------------------
     def _statistics(self, tokens: torch.Tensor, training: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-        B, T, D = tokens.shape
-        rows = B * T
-        need = lib.mae_batchnorm_scratch_bytes(rows, D)
-        if need < 0:
-            raise ValueError(f"BatchNorm shape ({rows}, {D}) outside the kernel's limits")
-        scratch = self._bytes("bn", need)
+        D = tokens.shape[2]
         mean, rstd = self._f32("mean", D), self._f32("rstd", D)
-        check(lib.mae_batchnorm_stats(_ptr(tokens), rows, D, self.cfg["bn_eps"], int(training), self.cfg["bn_momentum"], _ptr(self.running_mean),
-                                      _ptr(self.running_var), _ptr(mean), _ptr(rstd), _ptr(scratch), scratch.numel(), _stream(tokens.device)))
+        self._batchnorm(tokens, self.running_mean, self.running_var, training, mean, rstd)
         return mean, rstd
 
     def _forward(self, tokens: torch.Tensor, labels: Optional[torch.Tensor], training: bool):
         B, T, D = tokens.shape
-        H, C, dev = self.heads, self.num_classes, tokens.device
-        s = _stream(dev)
+        H, s = self.heads, _stream(tokens.device)
         mean, rstd = self._statistics(tokens, training)
         uq, ybar, lse, p = self._f32("uq", H, D), self._f32("ybar", B, H, D), self._f32("lse", B, H), self._f32("p", B, D)
         check(lib.mae_attn_probe_fold(_ptr(self.q), _ptr(self.wk), _ptr(rstd), D, H, _ptr(uq), s))
         check(lib.mae_attn_pool_fwd(_ptr(tokens), _ptr(mean), _ptr(uq), B, T, D, H, _ptr(ybar), _ptr(lse), s))
         check(lib.mae_attn_probe_project(_ptr(ybar), _ptr(rstd), _ptr(self.wv), B, D, H, _ptr(p), s))
-        logits = torch.empty(B, C, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev) if labels is not None else None
-        correct = torch.empty(1, dtype=torch.int32, device=dev) if labels is not None else None
         dp = self._f32("dp", B, D) if training else None
-        need = lib.mae_classifier_head_scratch_bytes(B, C, D)
-        if need < 0:
-            raise ValueError(f"head shape (batch {B}, classes {C}, dim {D}) outside the kernel's limits")
-        scratch = self._bytes("head", need + 256)
-        off = (-scratch.data_ptr()) % 256
-        scratch = scratch[off:off + need]
         head_grads = self.grads[self.layout["w"][0]:] if training else None
-        check(lib.mae_classifier_head(_ptr(p), _lib.MAE_F32, B, 1, D, _lib.POOL_CLS, _ptr(self.head_flat), C, _ptr(labels), 1.0, _ptr(logits),
-                                      _ptr(loss), _ptr(correct), _ptr(head_grads), _ptr(dp), _ptr(scratch), need, s))
+        logits, loss, correct = self._classifier_head(p, self.head_flat, labels, head_grads, dp)
         self.last = dict(mean=mean, rstd=rstd, uq=uq, ybar=ybar, lse=lse, p=p, logits=logits)
         return logits, loss, correct, dp
 
@@ -229,7 +173,7 @@ class AttentiveProbe:
     def loss_and_grads(self, tokens: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Forward in training mode (batch statistics, the running buffers updated) and backward into ``grads``; no optimizer step.
         (loss (1,) fp32, correct (1,) int32), device tensors."""
-        tokens, labels = self._check_tokens(tokens, labels)
+        tokens, labels = self._check(tokens, labels)
         B, T, D = tokens.shape
         if B * T < 2:
             raise ValueError("a probe step needs at least 2 token rows (BatchNorm in training mode)")
@@ -271,7 +215,7 @@ class AttentiveProbe:
     @torch.no_grad()
     def evaluate(self, tokens: torch.Tensor, labels: Optional[torch.Tensor] = None):
         """(logits, loss or None, correct or None) with the running statistics; changes no state."""
-        tokens, labels = self._check_tokens(tokens, labels)
+        tokens, labels = self._check(tokens, labels)
         logits, loss, correct, _ = self._forward(tokens, labels, False)
         return logits, loss, correct
 

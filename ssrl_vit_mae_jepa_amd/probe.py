@@ -37,22 +37,28 @@ AUGMENTS = ("none", "crop")
 LARS_SCRATCH_FLOATS = 4096
 
 
-def parse_probe(block: Optional[Dict[str, Any]]) -> Dict[str, Any]:
-    """The YAML block ``probe:`` checked and completed with ``PROBE_DEFAULTS``; an unknown key is refused by name."""
+def parse_block(block: Optional[Dict[str, Any]], defaults: Dict[str, Any], name: str, int_keys, float_keys) -> Dict[str, Any]:
+    """The YAML block ``name:`` completed with ``defaults``: it must be a mapping, an unknown key is refused by name, a ``None`` value
+    keeps its default, and ``int_keys`` / ``float_keys`` are cast.  The range checks are the caller's."""
     block = block or {}
     if not isinstance(block, dict):
-        raise ValueError(f"probe must be a mapping, got {block!r}")
-    unknown = set(block) - set(PROBE_DEFAULTS)
+        raise ValueError(f"{name} must be a mapping, got {block!r}")
+    unknown = set(block) - set(defaults)
     if unknown:
-        raise ValueError(f"probe: unknown keys {sorted(unknown)}")
-    out = dict(PROBE_DEFAULTS)
-    for k, v in block.items():
-        if v is not None:
-            out[k] = v
-    for k in ("total_epochs", "warmup_epochs", "batch_size"):
+        raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+    out = dict(defaults)
+    out.update({k: v for k, v in block.items() if v is not None})
+    for k in int_keys:
         out[k] = int(out[k])
-    for k in ("base_learning_rate", "weight_decay", "momentum", "trust_coefficient", "bn_eps", "bn_momentum", "head_init_std"):
+    for k in float_keys:
         out[k] = float(out[k])
+    return out
+
+
+def parse_probe(block: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+    """The YAML block ``probe:`` checked and completed with ``PROBE_DEFAULTS``; an unknown key is refused by name."""
+    out = parse_block(block, PROBE_DEFAULTS, "probe", ("total_epochs", "warmup_epochs", "batch_size"),
+                      ("base_learning_rate", "weight_decay", "momentum", "trust_coefficient", "bn_eps", "bn_momentum", "head_init_std"))
     if out["augment"] not in AUGMENTS:
         raise ValueError(f"probe.augment must be one of {list(AUGMENTS)}, got {out['augment']!r}")
     if out["total_epochs"] < 1 or out["warmup_epochs"] < 0 or out["batch_size"] < 2:
@@ -134,7 +140,88 @@ def _encoder_state(encoder) -> Tuple[Dict[str, torch.Tensor], bool]:
     return {k[len(pfx):]: v for k, v in src.items() if k.startswith(pfx)}, False
 
 
-class LinearProbe:
+class _Probe:
+    """What ``LinearProbe``, ``ProbeSweep`` and ``attentive.AttentiveProbe`` share: the scratch pool, the check of a batch and the
+    BatchNorm and classifier-head calls.  A subclass has ``device``, ``dim``, ``num_classes``, ``cfg`` (bn_eps, bn_momentum) and a
+    ``_scratch`` dict that ``to()`` clears."""
+
+    # whose kernels, the class the device message names, the input's word, its leading axes, what a label belongs to
+    _INPUT = ("the probe's", "LinearProbe", "features", ("B",), "feature rows")
+
+    def _bytes(self, key: str, need: int) -> torch.Tensor:
+        """The pool's buffer ``key`` with at least ``need`` bytes: it only grows, so a smaller call reuses the larger buffer."""
+        buf = self._scratch.get(key)
+        if buf is None or buf.numel() < need or buf.device != self.device:
+            buf = self._scratch[key] = torch.empty(max(int(need), 16), dtype=torch.uint8, device=self.device)
+        return buf
+
+    def _f32(self, key: str, *shape: int) -> torch.Tensor:
+        n = 1
+        for s in shape:
+            n *= int(s)
+        return self._bytes(key, 4 * n)[:4 * n].view(torch.float32).view(*shape)
+
+    def _check(self, x: torch.Tensor, labels: Optional[torch.Tensor]):
+        """(x fp32 contiguous, labels int64 flat or None) of a batch on the probe's device, one label per leading row."""
+        whose, cls, word, lead, rows = self._INPUT
+        if not x.is_cuda:
+            raise RuntimeError(f"{whose} kernels run on the MI355X only (move the {word} to cuda)")
+        if self.device != x.device:
+            raise RuntimeError(f"{cls}: move the probe to the {word}' device with .to(device)")
+        if x.dim() != len(lead) + 1 or x.shape[-1] != self.dim:
+            raise ValueError(f"{word} must be ({', '.join(lead)}, {self.dim}), got {tuple(x.shape)}")
+        x = x.to(dtype=torch.float32).contiguous()
+        if labels is not None:
+            labels = labels.to(device=x.device, dtype=torch.int64).contiguous().view(-1)
+            if labels.numel() != x.shape[0]:
+                raise ValueError(f"{labels.numel()} labels for {x.shape[0]} {rows}")
+        return x, labels
+
+    def _batchnorm(self, x: torch.Tensor, running_mean, running_var, training: bool, mean, rstd, y=None) -> None:
+        """BatchNorm over all rows of ``x`` (every axis but the last) on the given running buffers: ``mean`` and ``rstd`` always, the
+        normalised rows too where ``y`` is given (``mae_batchnorm_fwd``, else ``mae_batchnorm_stats``)."""
+        D = x.shape[-1]
+        rows = x.numel() // D
+        need = lib.mae_batchnorm_scratch_bytes(rows, D)
+        if need < 0:
+            raise ValueError(f"BatchNorm shape ({rows}, {D}) outside the kernel's limits")
+        scratch = self._bytes("bn", need)
+        head = (_ptr(x), rows, D, self.cfg["bn_eps"], int(training), self.cfg["bn_momentum"], _ptr(running_mean), _ptr(running_var))
+        tail = (_ptr(mean), _ptr(rstd), _ptr(scratch), scratch.numel(), _stream(x.device))
+        check(lib.mae_batchnorm_stats(*head, *tail) if y is None else lib.mae_batchnorm_fwd(*head, _ptr(y), *tail))
+
+    def _classifier_head(self, rows: torch.Tensor, flat: torch.Tensor, labels: Optional[torch.Tensor], grads=None, d_feats=None):
+        """``mae_classifier_head`` on (B, D) fp32 rows (seq_len 1, the class-row pool) with the flat W-then-b head ``flat``: (logits,
+        loss or None, correct or None); ``grads`` takes dW then db, ``d_feats`` the gradient of the rows."""
+        B, D = rows.shape
+        dev, C = rows.device, self.num_classes
+        logits = torch.empty(B, C, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev) if labels is not None else None
+        correct = torch.empty(1, dtype=torch.int32, device=dev) if labels is not None else None
+        need = lib.mae_classifier_head_scratch_bytes(B, C, D)
+        if need < 0:
+            raise ValueError(f"head shape (batch {B}, classes {C}, dim {D}) outside the kernel's limits")
+        scratch = self._bytes("head", need + 256)
+        off = (-scratch.data_ptr()) % 256
+        scratch = scratch[off:off + need]
+        check(lib.mae_classifier_head(_ptr(rows), _lib.MAE_F32, B, 1, D, _lib.POOL_CLS, _ptr(flat), C, _ptr(labels), 1.0, _ptr(logits),
+                                      _ptr(loss), _ptr(correct), _ptr(grads), _ptr(d_feats), _ptr(scratch), need, _stream(dev)))
+        return logits, loss, correct
+
+
+class _FeatureProbe(_Probe):
+    """A probe on (B, dim) feature rows behind one BatchNorm, ``self.bn``."""
+
+    def _normalise(self, feats: torch.Tensor, training: bool) -> torch.Tensor:
+        D, dev = feats.shape[1], feats.device
+        y = torch.empty_like(feats)   # the cached features are read again next epoch: never in place here
+        mean, rstd = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
+        self._batchnorm(feats, self.bn.running_mean, self.bn.running_var, training, mean, rstd, y)
+        self.last.update(y=y, mean=mean, rstd=rstd)
+        return y
+
+
+class LinearProbe(_FeatureProbe):
     """The probe's state (a ``ProbeHead``, the LARS momentum buffer, the gradient and scratch buffers) and its three operations.
     ``cfg``: a ``parse_probe`` result (or a subset of its keys); features are (B, dim) fp32 rows on the device."""
 
@@ -162,66 +249,21 @@ class LinearProbe:
     def device(self) -> torch.device:
         return self.head.flat.device
 
-    # ---- buffers -----------------------------------------------------------------------------------
-    def _bytes(self, key: str, need: int) -> torch.Tensor:
-        buf = self._scratch.get(key)
-        if buf is None or buf.numel() < need or buf.device != self.device:
-            buf = self._scratch[key] = torch.empty(max(int(need), 16), dtype=torch.uint8, device=self.device)
-        return buf
-
-    def _check_feats(self, feats: torch.Tensor, labels: Optional[torch.Tensor]):
-        if not feats.is_cuda:
-            raise RuntimeError("the probe's kernels run on the MI355X only (move the features to cuda)")
-        if self.device != feats.device:
-            raise RuntimeError("LinearProbe: move the probe to the features' device with .to(device)")
-        if feats.dim() != 2 or feats.shape[1] != self.dim:
-            raise ValueError(f"features must be (B, {self.dim}), got {tuple(feats.shape)}")
-        feats = feats.to(dtype=torch.float32).contiguous()
-        if labels is not None:
-            labels = labels.to(device=feats.device, dtype=torch.int64).contiguous().view(-1)
-            if labels.numel() != feats.shape[0]:
-                raise ValueError(f"{labels.numel()} labels for {feats.shape[0]} feature rows")
-        return feats, labels
-
-    def _batchnorm(self, feats: torch.Tensor, training: bool) -> torch.Tensor:
-        B, D = feats.shape
-        bn, dev = self.head.bn, feats.device
-        y = torch.empty_like(feats)   # the cached features are read again next epoch: never in place here
-        need = lib.mae_batchnorm_scratch_bytes(B, D)
-        if need < 0:
-            raise ValueError(f"BatchNorm shape ({B}, {D}) outside the kernel's limits")
-        scratch = self._bytes("bn", need)
-        mean, rstd = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
-        check(lib.mae_batchnorm_fwd(_ptr(feats), B, D, self.cfg["bn_eps"], int(training), self.cfg["bn_momentum"], _ptr(bn.running_mean),
-                                    _ptr(bn.running_var), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(scratch), scratch.numel(), _stream(dev)))
-        self.last.update(y=y, mean=mean, rstd=rstd)
-        return y
-
-    def _head(self, rows: torch.Tensor, flat: torch.Tensor, labels: Optional[torch.Tensor], grads: Optional[torch.Tensor]):
-        B, D = rows.shape
-        dev, C = rows.device, self.num_classes
-        logits = torch.empty(B, C, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev) if labels is not None else None
-        correct = torch.empty(1, dtype=torch.int32, device=dev) if labels is not None else None
-        need = lib.mae_classifier_head_scratch_bytes(B, C, D)
-        scratch = self._bytes("head", need + 256)
-        off = (-scratch.data_ptr()) % 256
-        scratch = scratch[off:off + need]
-        check(lib.mae_classifier_head(_ptr(rows), _lib.MAE_F32, B, 1, D, _lib.POOL_CLS, _ptr(flat), C, _ptr(labels), 1.0, _ptr(logits),
-                                      _ptr(loss), _ptr(correct), _ptr(grads), None, _ptr(scratch), need, _stream(dev)))
-        return logits, loss, correct
+    @property
+    def bn(self) -> _BatchNormStats:
+        return self.head.bn
 
     # ---- the three operations ------------------------------------------------------------------------
     @torch.no_grad()
     def step(self, feats: torch.Tensor, labels: torch.Tensor, lr: float) -> Tuple[torch.Tensor, torch.Tensor]:
         """One training step on a batch of at least two rows: (loss (1,) fp32, correct (1,) int32), device tensors, no synchronisation."""
-        feats, labels = self._check_feats(feats, labels)
+        feats, labels = self._check(feats, labels)
         if feats.shape[0] < 2:
             raise ValueError("a probe step needs at least 2 rows (BatchNorm in training mode)")
-        y = self._batchnorm(feats, True)
-        self.head.bn.num_batches_tracked += 1
+        y = self._normalise(feats, True)
+        self.bn.num_batches_tracked += 1
         flat = self.head.flat
-        logits, loss, correct = self._head(y, flat, labels, self.grads)
+        logits, loss, correct = self._classifier_head(y, flat, labels, self.grads)
         self.last["logits"] = logits
         c = self.cfg
         nw = self.num_classes * self.dim
@@ -236,9 +278,8 @@ class LinearProbe:
     @torch.no_grad()
     def evaluate(self, feats: torch.Tensor, labels: Optional[torch.Tensor] = None):
         """(logits, loss or None, correct or None) with the running statistics; changes no state."""
-        feats, labels = self._check_feats(feats, labels)
-        y = self._batchnorm(feats, False)
-        return self._head(y, self.head.flat, labels, None)
+        feats, labels = self._check(feats, labels)
+        return self._classifier_head(self._normalise(feats, False), self.head.flat, labels)
 
     def folded_head(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(W' (C, D), b' (C,)) fp32 on the host: BatchNorm's evaluation form folded into the linear layer, computed in float64 and
@@ -347,7 +388,7 @@ def select(val_acc, val_loss) -> int:
     return min(range(len(val_acc)), key=key)
 
 
-class ProbeSweep:
+class ProbeSweep(_FeatureProbe):
     """G linear probes that differ in learning rate and weight decay alone, trained on the same features in one pass: one shared
     BatchNorm (it has no per-head state), a stacked (G, HF) parameter, momentum and gradient buffer, ``mae_probe_sweep_head`` for
     every head's logits, loss and gradients and ``mae_lars_step_groups`` for every head's update.  ``grid``: a list of
@@ -388,23 +429,6 @@ class ProbeSweep:
     def device(self) -> torch.device:
         return self.flat.device
 
-    _bytes = LinearProbe._bytes
-    _check_feats = LinearProbe._check_feats
-
-    def _batchnorm(self, feats: torch.Tensor, training: bool) -> torch.Tensor:
-        B, D = feats.shape
-        bn, dev = self.bn, feats.device
-        y = torch.empty_like(feats)
-        need = lib.mae_batchnorm_scratch_bytes(B, D)
-        if need < 0:
-            raise ValueError(f"BatchNorm shape ({B}, {D}) outside the kernel's limits")
-        scratch = self._bytes("bn", need)
-        mean, rstd = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
-        check(lib.mae_batchnorm_fwd(_ptr(feats), B, D, self.cfg["bn_eps"], int(training), self.cfg["bn_momentum"], _ptr(bn.running_mean),
-                                    _ptr(bn.running_var), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(scratch), scratch.numel(), _stream(dev)))
-        self.last.update(y=y, mean=mean, rstd=rstd)
-        return y
-
     def _heads(self, rows: torch.Tensor, labels: Optional[torch.Tensor], grads: Optional[torch.Tensor], want_logits: bool = True):
         B, D = rows.shape
         dev, C, G = rows.device, self.num_classes, len(self.grid)
@@ -431,10 +455,10 @@ class ProbeSweep:
     def step(self, feats: torch.Tensor, labels: torch.Tensor, lr_factor: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
         """One training step of every head on a batch of at least two rows: (loss (G,) fp32, correct (G,) int32), device tensors, no
         synchronisation.  One BatchNorm, one sweep head, two grouped LARS calls (W with the trust ratio, then the bias slice)."""
-        feats, labels = self._check_feats(feats, labels)
+        feats, labels = self._check(feats, labels)
         if feats.shape[0] < 2:
             raise ValueError("a probe step needs at least 2 rows (BatchNorm in training mode)")
-        y = self._batchnorm(feats, True)
+        y = self._normalise(feats, True)
         self.bn.num_batches_tracked += 1
         logits, loss, correct = self._heads(y, labels, self.grads)
         self.last["logits"] = logits
@@ -454,9 +478,8 @@ class ProbeSweep:
     @torch.no_grad()
     def evaluate(self, feats: torch.Tensor, labels: Optional[torch.Tensor] = None):
         """(logits (G, B, C), loss (G,) or None, correct (G,) or None) with the running statistics; changes no state."""
-        feats, labels = self._check_feats(feats, labels)
-        y = self._batchnorm(feats, False)
-        return self._heads(y, labels, None)
+        feats, labels = self._check(feats, labels)
+        return self._heads(self._normalise(feats, False), labels, None)
 
     def export(self, g: int) -> LinearProbe:
         """Head g as a ``LinearProbe`` of its own: its weights, momentum, hyper-parameters and the shared BatchNorm buffers (copies), so

@@ -258,7 +258,7 @@ def test_cli_refuses_65_heads_before_loading_data(dev, tmp_path, monkeypatch):
     from pathlib import Path
     from scripts.evaluation import linear_probe
     root = Path(__file__).resolve().parents[1]
-    monkeypatch.setattr(linear_probe, "get_train_batches", lambda *a, **k: (_ for _ in ()).throw(AssertionError("data was loaded")))
+    monkeypatch.setattr(linear_probe.C, "get_train_batches", lambda *a, **k: (_ for _ in ()).throw(AssertionError("data was loaded")))
     lrs = ",".join(str(0.01 * (i + 1)) for i in range(13))
     with pytest.raises(SystemExit) as e:
         linear_probe.main(["--config", str(root / "configs" / "vits8_dec192_linprobe.yaml"), "--checkpoint", "random", "--synthetic_images", "200",

@@ -164,8 +164,8 @@ def test_linear_probe_width_check_fires_before_data_is_loaded(tmp_path, monkeypa
 
     def no_data(*a, **k):
         raise AssertionError("data was loaded before the width check")
-    monkeypatch.setattr(linear_probe, "require_data", no_data)
-    monkeypatch.setattr(linear_probe, "get_train_batches", no_data)
+    monkeypatch.setattr(linear_probe.C, "require_data", no_data)
+    monkeypatch.setattr(linear_probe.C, "get_train_batches", no_data)
     with pytest.raises(SystemExit, match="1024"):       # ViT-S last-4: 1536 columns
         linear_probe.main(["--config", str(path), "--checkpoint", "random", "--layers", "last4", "--synthetic_images", "50"])
     with pytest.raises(SystemExit, match="1024"):       # [cls | mean] of two blocks: 1536 columns

@@ -61,7 +61,7 @@ def test_cli_grid_and_early_exit(tmp_path, monkeypatch):
     assert len(parse_sweep(None, L.probe_config({}, args), args.sweep_lr, args.sweep_wd)) == 4
     # more than 64 heads: the named error, before any data is loaded or the device is asked for
     monkeypatch.setattr(torch.cuda, "is_available", lambda: (_ for _ in ()).throw(AssertionError("device work was reached")))
-    monkeypatch.setattr(L, "get_train_batches", lambda *a, **k: (_ for _ in ()).throw(AssertionError("data was loaded")))
+    monkeypatch.setattr(L.C, "get_train_batches", lambda *a, **k: (_ for _ in ()).throw(AssertionError("data was loaded")))
     lrs = ",".join(str(0.01 * (i + 1)) for i in range(13))
     with pytest.raises(SystemExit) as e:
         L.main(["--config", CFG, "--checkpoint", "random", "--synthetic_images", "64", "--sweep_lr", lrs, "--sweep_wd", "0,0.1,0.2,0.3,0.4"])
