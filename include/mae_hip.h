@@ -871,6 +871,39 @@ int mae_tsne_update(float* y, float* update, float* gains, const float* grad, in
 int mae_tsne_step(const float* P, float* y, float* update, float* gains, int32_t n, float alpha, float momentum, float learning_rate,
                   float min_gain, float* grad, float* kl /* may be NULL */, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* UMAP of n feature rows in the plane (McInnes et al.; umap-learn 0.5's defaults; additive in ABI v4; no reference counterpart;
+ * DESIGN.md 11.4).  Everything is fp32; every sum has an order fixed by the shapes alone and there are no atomics, so a call is
+ * bit-identical from run to run; nothing synchronises with the host and every buffer is the caller's.  Limits, refused by name before
+ * any pointer is touched: 8 <= n <= 16384, 1 <= dim <= 8192, 2 <= n_neighbors <= 64, n_neighbors < n, 1 <= rate <= 16, 0 <= t < 2^24.
+ *   mae_umap_scratch_bytes   the scratch of mae_umap_fuzzy_knn: the (n, round_up(n, 4)) squared distances and two rows (-1 outside the
+ *                            limits).  16-byte aligned.
+ *   mae_umap_fuzzy_knn       d_ij = sqrt(sum_c (x_ic - x_jc)^2): the difference form of mae_tsne_affinities (one fused multiply-add per
+ *                            column in column order), then one correctly rounded square root.  Row i of knn_idx / knn_dist (n, k) holds
+ *                            the k smallest d_ij, the point itself included, by distance ascending, then index ascending.
+ *                            rho_i = the first entry > 0 (0 if none).  sigma_i by umap-learn's smooth_knn_dist: lo = 0, hi = inf,
+ *                            mid = 1; at most 64 steps; psum = sum_{r = 1 .. k - 1} e^(-(max(d_ir - rho_i, 0) / mid)); stop when
+ *                            |psum - log2 k| < 1e-5; psum above: hi = mid, mid = (lo + hi) / 2; else lo = mid, and mid doubles while
+ *                            hi = inf, else mid = (lo + hi) / 2.  Floor: sigma_i >= 1e-3 x the row's mean distance when rho_i > 0, else
+ *                            >= 1e-3 x the mean of all n k distances (the rows' sums added in a fixed order).  memb (n, k) = 0 for the
+ *                            point itself, 1 if d - rho <= 0 or sigma = 0, else e^(-((d - rho) / sigma)).  Exponentials by v_exp_f32.
+ *   mae_umap_epoch           epoch t of the synchronous layout over a CSR graph of E directed edges: row_ptr (n + 1), col / eps / next
+ *                            (E); row_ptr ascending from 0, the caller's word is taken for it; a column outside [0, n) is clamped.
+ *                            Edge e of row i fires iff next[e] <= t.  A firing edge adds to row i, from y_in alone,
+ *                              2 clip(c (y_i - y_j)),  j = col[e],  c = -2 a b d2^(b - 1) / (a d2^b + 1),  d2 = |y_i - y_j|^2, and for
+ *                              s = 0 .. rate - 1:  clip(c (y_i - y_k)),  c = 2 gamma b / ((0.001 + d2) (a d2^b + 1)),  d2 = |y_i - y_k|^2,
+ *                            clip per coordinate to [-4, 4]; a term with d2 = 0, or with k = i, is 0.  The negative sample is
+ *                              k = (uint64(h) * n) >> 32,  h = mix(mix(seed, t), 16 e + s),  mix(s, i) = fmix32(fmix32(i + 0x9E3779B9) ^ s)
+ *                            in uint32 arithmetic, fmix32 murmur3's finaliser (h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13;
+ *                            h *= 0xC2B2AE35; h ^= h >> 16), e the edge's index in col.  16 e + s < 2^25 for E <= 2 n k <= 2^21: the key
+ *                            never wraps.  y_out[i] = fma(alpha, sum_i, y_in[i]) for every row; next[e] += eps[e] (one fp32 add) on the
+ *                            edges that fired.  The sum's order depends on the row's degree and the rate alone.  y_in is not written
+ *                            and must not be y_out; y_in and y_out (n, 2) 16-byte aligned. */
+int64_t mae_umap_scratch_bytes(int32_t n, int32_t dim, int32_t n_neighbors);
+int mae_umap_fuzzy_knn(const float* x, int32_t n, int32_t dim, int32_t n_neighbors, int32_t* knn_idx, float* knn_dist, float* memb,
+                       float* rho, float* sigma, void* scratch, int64_t scratch_bytes, void* stream);
+int mae_umap_epoch(const float* y_in, float* y_out, const int32_t* row_ptr, const int32_t* col, const float* eps, float* next,
+                   int32_t n, float a, float b, float gamma, float alpha, int32_t t, int32_t rate, uint32_t seed, void* stream);
+
 /* Token and pixel movement between those pieces, and the losses that read the image.  Index arguments are int32, as the kernels
  * take them; token id 0 is the class token, id t >= 1 is patch t - 1 (row-major over the patch grid).  Unless a function says
  * otherwise the ids must lie in [0, seq_len): nothing here range-checks them on the device.  `partial` is scratch of

@@ -4,7 +4,8 @@ Same flags, the same plots (one all-class plot and one class-vs-all plot per cla
 context), ``--synthetic_images``, ``--output_dir`` (default assets/visualizations) and ``--save_features`` (an .npz of the
 normalised features and labels).  t-SNE comes from sklearn, the plots from matplotlib; UMAP needs umap-learn.  ``--method tsne_gpu``
 is the exact t-SNE of ``ssrl_vit_mae_jepa_amd.embedding.DeviceTSNE`` on the MI355X (PCA initialisation, the same perplexity rule, at
-most 16384 samples); it also writes ``<stem>.json`` with the KL trace.
+most 16384 samples); it also writes ``<stem>.json`` with the KL trace.  ``--method umap_gpu`` is ``embedding.DeviceUMAP`` (umap-learn's
+defaults, exact neighbours, a deterministic layout; at most 16384 samples) and writes ``<stem>.json`` with its parameters.
 
     python -m scripts.evaluation.visualize_representation --config configs/mae.yaml --encoder_ckpt outputs/pretrain/mae_pretrain/vit-mae.pt --method tsne
 """
@@ -28,7 +29,7 @@ try:
 except ImportError:
     HAS_UMAP = False
 
-TSNE_GPU_MAX_SAMPLES = 16384  # embedding.MAX_N: what exact t-SNE on the device admits
+TSNE_GPU_MAX_SAMPLES = 16384  # embedding.MAX_N: what exact t-SNE and UMAP on the device admit
 STL10_CLASSES = ["airplane", "bird", "car", "cat", "deer", "dog", "horse", "monkey", "ship", "truck"]
 
 
@@ -52,6 +53,14 @@ def project_tsne_gpu(features: np.ndarray, device):
     print("Running t-SNE on the device...")
     tsne = DeviceTSNE(perplexity=min(30.0, max(1.0, (len(features) - 1) / 3)))
     Z, info = tsne.fit(torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(device))
+    return Z.cpu().numpy(), info
+
+
+def project_umap_gpu(features: np.ndarray, device, seed: int = 73):
+    """-> (Z (N, 2) numpy, info): DeviceUMAP with umap-learn's defaults from umap_init."""
+    from ssrl_vit_mae_jepa_amd.embedding import DeviceUMAP
+    print("Running UMAP on the device...")
+    Z, info = DeviceUMAP(seed=seed).fit(torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(device))
     return Z.cpu().numpy(), info
 
 
@@ -91,7 +100,7 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description="2-D projection of frozen encoder features")
     p.add_argument("--config", type=str, default="configs/mae.yaml")
     p.add_argument("--encoder_ckpt", type=str, required=True, help="checkpoint path or 'random'")
-    p.add_argument("--method", type=str, choices=["umap", "tsne", "tsne_gpu"], default="umap")
+    p.add_argument("--method", type=str, choices=["umap", "tsne", "tsne_gpu", "umap_gpu"], default="umap")
     p.add_argument("--pool", type=str, choices=["cls", "mean", "cls_mean"], default="cls", help="cls_mean = [class token | patch mean], with --layers only")
     p.add_argument("--layers", type=str, default=None,
                    help="plot the features after these encoder blocks (last | lastN | each | comma-separated indices; several are concatenated)")
@@ -109,8 +118,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.method == "umap" and not HAS_UMAP:
         raise RuntimeError("UMAP requested but not installed.")
-    if args.method == "tsne_gpu" and args.max_samples > TSNE_GPU_MAX_SAMPLES:
-        raise SystemExit(f"visualize_representation: --method tsne_gpu embeds at most {TSNE_GPU_MAX_SAMPLES} samples, --max_samples is {args.max_samples}")
+    if args.method in ("tsne_gpu", "umap_gpu") and args.max_samples > TSNE_GPU_MAX_SAMPLES:
+        raise SystemExit(f"visualize_representation: --method {args.method} embeds at most {TSNE_GPU_MAX_SAMPLES} samples, --max_samples is {args.max_samples}")
     with open(args.config, "r") as f:
         cfg = yaml.safe_load(f)
     layers = None
@@ -138,6 +147,8 @@ def main(argv=None):
     info = None
     if args.method == "tsne_gpu":
         Z, info = project_tsne_gpu(feats, dev)
+    elif args.method == "umap_gpu":
+        Z, info = project_umap_gpu(feats, dev)
     else:
         Z = project(feats, method=args.method)
     save_dir = Path(args.output_dir)

@@ -171,6 +171,9 @@ SIGNATURES = {
     "mae_tsne_gradient": (C.c_int, [_vp, _vp, _i32, _f32, _vp, _vp, _vp, _i64, _vp]),
     "mae_tsne_update": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp]),
     "mae_tsne_step": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _i64, _vp]),
+    "mae_umap_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "mae_umap_fuzzy_knn": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mae_umap_epoch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _i32, _i32, C.c_uint32, _vp]),
     "mae_gather_patches": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mae_assemble_visible": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "mae_visible_grad_split": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),

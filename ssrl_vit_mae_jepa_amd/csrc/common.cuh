@@ -125,6 +125,14 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// ---- counter-based generator (k_augment.hip's erase noise, k_umap.hip's negative samples) ------
+// murmur3's finaliser, and word i of the stream `seed`: mix(s, i) = fmix32(fmix32(i + 0x9E3779B9) ^ s), all in uint32
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+__device__ __forceinline__ uint32_t aug_mix(uint32_t seed, uint32_t i) { return fmix32(fmix32(i + 0x9E3779B9u) ^ seed); }
+
 // exact (erf) GELU and its derivative: torch.nn.GELU() default
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_erf_grad(float x) {

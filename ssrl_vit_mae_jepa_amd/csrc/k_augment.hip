@@ -47,11 +47,7 @@ __device__ __forceinline__ unsigned aug_blend(int d, int v, float alpha, bool un
 // ImageMode L of an RGB pixel
 __device__ __forceinline__ int aug_lum(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
 
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return h;
-}
-__device__ __forceinline__ uint32_t aug_mix(uint32_t seed, uint32_t i) { return fmix32(fmix32(i + 0x9E3779B9u) ^ seed); }
+// fmix32 / aug_mix: common.cuh (shared with k_umap.hip)
 __device__ __forceinline__ float aug_noise(uint32_t seed, uint32_t e) {
   const uint32_t w0 = aug_mix(seed, 2u * e), w1 = aug_mix(seed, 2u * e + 1u);
   const float u1 = (float)((w0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(w1 >> 8) * 0x1p-24f;

@@ -29,13 +29,11 @@
 // its columns, then the xor butterfly.  tsne_finalize_kernel adds the n row sums z_i in a fixed order (thread t: t, t + 256, ...;
 // butterfly; waves in order -- every workgroup does the same sum and gets the same Z), forms grad = 4 (alpha a - r / Z) and, in
 // mae_tsne_step, applies the descent step in the same launch: two launches per iteration.
-#include "kernels.h"
+#include "sqdist_dev.cuh"
 
 namespace mae {
 
 constexpr int TS_MIN_N = 8, TS_MAX_N = 16384, TS_MAX_DIM = 8192;
-constexpr int TS_THREADS = 256;
-constexpr int TS_TILE = 64, TS_KC = 16, TS_KS = TS_TILE + 4;   // sqdist: tile edge, staged columns, k-major row stride
 constexpr int TS_ROWS = 4;                                     // gradient: rows of a wave
 constexpr int TS_MAX_STEPS = 100;
 constexpr float TS_TOL = 1e-5f;
@@ -49,52 +47,7 @@ int64_t tsne_scratch_bytes(int n, int dim) {
 }
 
 // ---- affinities ----------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(TS_THREADS) tsne_sqdist_kernel(const float* __restrict__ x, int n, int dim, float* __restrict__ P, int pitch,
-                                                                 float* __restrict__ sqdist) {
-  __shared__ __attribute__((aligned(16))) float As[TS_KC * TS_KS], Bs[TS_KC * TS_KS];
-  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-  const int i0 = blockIdx.y * TS_TILE, j0 = blockIdx.x * TS_TILE;
-  float acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
-  const int kk = t & 15, r0 = t >> 4;   // staging: 16 consecutive columns of one row per 16 lanes
-  for (int k0 = 0; k0 < dim; k0 += TS_KC) {
-    __syncthreads();   // the previous chunk has been read
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int r = r0 + 16 * p, k = k0 + kk;
-      const int ri = i0 + r, rj = j0 + r;
-      As[kk * TS_KS + r] = (ri < n && k < dim) ? x[(int64_t)ri * dim + k] : 0.f;   // zeros past n and past dim: a difference of 0
-      Bs[kk * TS_KS + r] = (rj < n && k < dim) ? x[(int64_t)rj * dim + k] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < TS_KC; ++k) {
-      const f32x4 a = load4(As + k * TS_KS + 4 * ty), b = load4(Bs + k * TS_KS + 4 * tx);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const float df = a[u] - b[v];
-          acc[u][v] = fmaf(df, df, acc[u][v]);
-        }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int i = i0 + 4 * ty + u;
-    if (i >= n) continue;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int j = j0 + 4 * tx + v;
-      if (j >= n) continue;
-      P[(int64_t)i * pitch + j] = acc[u][v];
-      if (sqdist) sqdist[(int64_t)i * n + j] = acc[u][v];
-    }
-  }
-}
+// tsne_sqdist_kernel: sqdist_dev.cuh (shared with k_umap.hip)
 
 // (a, b) summed over the 256 threads; red = 8 floats of LDS; the same bits in every thread
 __device__ __forceinline__ void block_sum2_256(float& a, float& b, float* red) {

@@ -242,6 +242,15 @@ int launch_tsne_update(float* y, float* upd, float* gains, const float* grad, in
 int launch_tsne_step(const float* P, float* y, float* upd, float* gains, int n, float alpha, float momentum, float lr, float min_gain, float* grad,
                      float* kl, void* scratch, int64_t scratch_bytes, hipStream_t s);
 
+// ---- k_umap.hip: UMAP in the plane, 8 <= n <= 16384, 2 <= k <= 64, k < n; fp32, fixed orders, no atomics -------------
+int64_t umap_scratch_bytes(int n, int dim, int k);   // the squared distances and two rows of floats; -1 outside the limits
+// x (n, dim) -> the k nearest rows of every row (itself included) by (distance, index), umap-learn's rho, sigma and memberships
+int launch_umap_fuzzy_knn(const float* x, int n, int dim, int k, int32_t* knn_idx, float* knn_dist, float* memb, float* rho, float* sigma, void* scratch,
+                          int64_t scratch_bytes, hipStream_t s);
+// one synchronous layout epoch over the CSR graph (row_ptr, col, eps, next): y_out from y_in, next += eps on the edges that fired
+int launch_umap_epoch(const float* y_in, float* y_out, const int32_t* row_ptr, const int32_t* col, const float* eps, float* next, int n, float a, float b,
+                      float gamma, float alpha, int t, int rate, uint32_t seed, hipStream_t s);
+
 // ---- k_attnpool.hip: the attentive probe's pool over cached tokens and the small products around it -------------
 // x (B, T, D) fp32 tokens, centred on load with mean (D, null = 0); uq (H, D).  ybar[b][h] = sum_t a (x - mean), a = softmax_t of
 // (x - mean) . uq[h]; lse (B, H) = the log of the softmax denominator.  One workgroup per image, online softmax over token chunks
